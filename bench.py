@@ -10,6 +10,11 @@ random-init weights, inputs resident in HBM.  Graphs are independent: by default
 N ranks by the fitted step cost (strong scaling, the figure SURVEY.md 8(d) and the ">= 6x at 8 GPUs" target refer to; `--weak` gives every rank
 its own 128-graph batch instead), no collective inside the loop; the only collective is the final gather of `pred` over RCCL,
 exercised after the timed region.  Prints ONE JSON line on rank 0.
+
+A plain run sets up, warms up, times exactly --steps steps (one block), writes the outputs of its last step if --dump-outputs is
+given, and prints the headline line.  `--full` adds everything else it measures: --repeats blocks (default 3, median reported) with
+HIP events on the triplet / knn-node launches in the last one, the rooflines, the measured MFMA peak, the weak-scaling figure (N > 1),
+BASELINE's other single-GPU configurations and the CPU baseline.
 """
 import argparse
 import json
@@ -393,19 +398,46 @@ def _traffic_record(kernel_prefix):
     return rec.get('hbm_bytes_per_launch'), src
 
 
+def dump_outputs(out_dir, res, gathered=None, max_bytes=64 * 2 ** 20):
+    """What the caller of the timed path receives from its last step, as float32 .npy files: `pred` of finish_sampling (node logits
+    [N,12], x0 coordinates [N,3], bond logits [E,6]) and, on one GPU, the state the step drew (the last trajectory frame: atom types
+    one-hot [N,12], coordinates [N,3], bond types one-hot [E,6]).  N > 1: the gathered `pred` of all ranks, in global graph order.
+    Above `max_bytes` in all (batches far larger than the headline's), every array keeps the same fixed, seeded sample of its rows."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    pred = gathered if gathered is not None else res['pred']
+    arrays = {'pred_node_logits': pred[0], 'pred_pos': pred[1], 'pred_bond_logits': pred[2]}
+    if gathered is None and res['traj'][0] is not None:
+        arrays.update(state_node_types=res['traj'][0][res['last_frame']], state_pos=res['traj'][1][res['last_frame']],
+                      state_bond_types=res['traj'][2][res['last_frame']])
+    total, budget = sum(a.numel() * 4 for a in arrays.values()), max_bytes - 256 * len(arrays)      # (.npy headers: 128 B each)
+    for name, a in arrays.items():
+        a = a.detach().float().cpu()
+        if total > budget:
+            keep = int(a.size(0) * budget / total)
+            a = a[torch.randperm(a.size(0), generator=torch.Generator().manual_seed(0))[:keep].sort().values]
+        np.save(os.path.join(out_dir, name + '.npy'), a.numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=40)
     ap.add_argument('--warmup', type=int, default=5)
-    ap.add_argument('--repeats', type=int, default=3, help='timed blocks of --steps steps each; the median block is reported')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beside the headline: repeated blocks, rooflines, measured MFMA peak, weak scaling (N > 1), '
+                         'BASELINE configs[1] / [3] / [4] and the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last step computed as DIR/<name>.npy (float32)')
+    ap.add_argument('--repeats', type=int, default=None,
+                    help='timed blocks of --steps steps each; the median block is reported (default 1; 3 with --full)')
     ap.add_argument('--graphs', type=int, default=128)
     ap.add_argument('--fixed-shape', action='store_true', help='n=40, p=107 for every graph (closed-form counts)')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-secondary', action='store_true', help='skip BASELINE configs[1] / [3] / [4] after the timed region (they run at N = 1 in a full default-style run only)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baseline')
+    ap.add_argument('--no-secondary', action='store_true', help='--full without BASELINE configs[1] / [3] / [4] after the timed region (they run at N = 1 only)')
     ap.add_argument('--weak', action='store_true',
                     help='weak scaling only: --graphs graphs PER GPU (default: strong scaling, SURVEY.md 8d: ONE batch of '
-                         '--graphs graphs partitioned over the ranks by the fitted step cost; a weak-scaling figure is added for N > 1)')
+                         '--graphs graphs partitioned over the ranks by the fitted step cost; --full adds a weak-scaling figure for N > 1)')
     ap.add_argument('--strong', action='store_true', help='(default) kept for compatibility')
     ap.add_argument('--train', action='store_true',
                     help='BASELINE config 5 instead: one compute_loss forward + backward + Adam step on 256 synthetic pairs '
@@ -438,7 +470,8 @@ def main():
     from phoregen_amd.weights import init_deterministic_
 
     model = init_deterministic_(PhoreDiff(default_model_config(), 'zinc_300'), 0).eval().to(dev)
-    K, W, R = args.steps, args.warmup, max(args.repeats, 1)
+    K, W = args.steps, args.warmup
+    R = max(args.repeats if args.repeats is not None else (3 if args.full else 1), 1)
     T = model.num_timesteps
 
     def barrier():
@@ -454,7 +487,7 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
-    def run(work, gids, time_triplet):
+    def run(work, gids, headline, time_triplet):
         """W warm-up steps, then R blocks of exactly K steps, each bracketed by barrier + synchronize; per-block wall time
         is the MAX over ranks.  Returns (block times [R], triplet launch durations, final result dict)."""
         n_total = min(W + 32 + R * K, max(T, W + R * K))       # room for up to 32 more untimed steps (grid tuning of small batches, below)
@@ -466,7 +499,7 @@ def main():
         # (small batches choose their persistent triplet grid inside begin_sampling since round 6 -- Engine.calibrate_tri_grid -- so the loop
         #  below runs a fixed launch list; nothing of the choice falls into the timed region)
         extra = 0
-        if time_triplet:                       # (the headline run; the weak-scaling figure below reports its own)
+        if headline:                           # (the weak-scaling figure below reports its own)
             run.warmup_steps = W + extra
         times, tri, knn = [], [], []
         i = W + extra
@@ -487,13 +520,16 @@ def main():
                 tri += st.eng.kernel_ms('triplet')
                 knn += st.eng.kernel_ms('knn_node')
                 st.eng.timers = None
+        if headline:
+            run.tri_grid = st.eng.prog_fwd[st.eng.tri_calls[0]][1][-1]._obj.tri_grid or 256      # persistent triplet workgroups in use (small batches: tuned online)
         if time_triplet:
             run.knn_ms, run.knn_mfma = knn, knn_node_mfma(st.eng)
             run.exec_flops = executed_flops(st.eng)
             run.tri_launches = len(st.eng.tri_calls)
-            run.tri_grid = st.eng.prog_fwd[st.eng.tri_calls[0]][1][-1]._obj.tri_grid or 256      # persistent triplet workgroups in use (small batches: tuned online)
             run.knn_launches = 1 if any(a[1]._obj.mode == 0 and a[1]._obj.n_seg2 > 0 for f, a, l in st.eng.prog_fwd if l >= 0 and f is st.eng.lib.pg_seg_attn) else 2
-        return times, tri, model.finish_sampling(st)
+        res = model.finish_sampling(st)
+        res['last_frame'] = i                  # (the trajectory frame the last timed step wrote)
+        return times, tri, res
 
     # ---- strong scaling (headline): ONE batch of --graphs graphs, partitioned over the ranks by phoregen_amd.parallel.graph_cost ----
     full = ligphore_workload(args.graphs, seed=1234, fixed_shape=args.fixed_shape)
@@ -506,35 +542,30 @@ def main():
         work = subset_workload(full, mine) if world > 1 else full
         total_graphs = args.graphs
     counts = algorithmic_counts(work['num_atoms'], work['n_phore'])
-    times, tri_ms, res = run(work, mine, time_triplet=True)
+    times, tri_ms, res = run(work, mine, headline=True, time_triplet=args.full)
     order = sorted(range(R), key=lambda r: times[r])
     dt = times[order[R // 2]]                              # median block
 
     # the one collective of the path: re-assemble `pred` of all ranks (phoregen_amd/parallel.py), after the timed loop
-    gather_ms = None
+    gather_ms = gathered = None
     if world > 1:
         tg = time.perf_counter()
-        gather_predictions(res['pred'], work['num_atoms'], mine)
+        gathered, _ = gather_predictions(res['pred'], work['num_atoms'], mine)
         torch.cuda.synchronize()
         gather_ms = (time.perf_counter() - tg) * 1e3
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, res, gathered)
 
     # ---- secondary figure for N > 1: weak scaling, --graphs graphs per GPU ----
     weak = None
-    if world > 1 and not args.weak:
+    if world > 1 and not args.weak and args.full:
         wwork = ligphore_workload(args.graphs, seed=1234 + rank, fixed_shape=args.fixed_shape)
-        wt, _, _ = run(wwork, torch.arange(args.graphs) + rank * args.graphs, time_triplet=False)
+        wt, _, _ = run(wwork, torch.arange(args.graphs) + rank * args.graphs, headline=False, time_triplet=False)
         wdt = sorted(wt)[R // 2]
         weak = {'graphs_per_gpu': args.graphs, 'ms_per_step': wdt / K * 1e3, 'graph_steps_per_sec': K * world * args.graphs / wdt,
                 'batch_steps_per_sec': world * K / wdt}
 
     if rank == 0:
-        peak_tf = 157.3                      # fp32 MFMA dense peak, MI355X_MICROARCH.md "Chip-level parameters"
-        tri_avg_ms = sum(tri_ms) / max(len(tri_ms), 1)
-        exec_tf = counts['flops_triplet_executed'] / (tri_avg_ms * 1e-3) / 1e12 if tri_ms else None
-        alg_tf = counts['flops_triplet_kernel'] / (tri_avg_ms * 1e-3) / 1e12 if tri_ms else None
-        traffic, traffic_src = _traffic_record('pg::triplet')
-        meas_tf = measured_mfma_peak(dev)
-        mfma_only_tf = counts['flops_triplet_mfma'] / (tri_avg_ms * 1e-3) / 1e12 if tri_ms else None
         scale = 1.0 if not args.weak else float(world)
         line = {
             'metric': 'denoise-steps/sec (batch=128, ~40-atom graphs)', 'value': scale * K / dt, 'unit': 'steps/s',
@@ -551,6 +582,17 @@ def main():
             'repeats': R, 'repeats_ms_per_step': [t / K * 1e3 for t in times], 'statistic': 'median block of `repeats` blocks of `steps` steps',
             'graph_steps_per_sec': K * total_graphs / dt,
             'ranks': world, 'distinct_devices': min(world, n_dev), 'dist_backend': backend,
+            'final_gather_ms': gather_ms,
+        }
+    if rank == 0 and args.full:
+        peak_tf = 157.3                      # nominal dense fp32 MFMA peak of the MI355X
+        tri_avg_ms = sum(tri_ms) / max(len(tri_ms), 1)
+        exec_tf = counts['flops_triplet_executed'] / (tri_avg_ms * 1e-3) / 1e12 if tri_ms else None
+        alg_tf = counts['flops_triplet_kernel'] / (tri_avg_ms * 1e-3) / 1e12 if tri_ms else None
+        traffic, traffic_src = _traffic_record('pg::triplet')
+        meas_tf = measured_mfma_peak(dev)
+        mfma_only_tf = counts['flops_triplet_mfma'] / (tri_avg_ms * 1e-3) / 1e12 if tri_ms else None
+        line.update({
             'roofline': {'kernel': 'triplet kernel (pg_seg_attn PG_SEG_TRIPLET = BondUpdateLayer, 6 sub-layers/step' + (': each as two launches, ligands of up to 50 atoms on the 3-tile instance and the larger ones beside them on another lane; a launch = the pair' if getattr(run, 'tri_launches', 6) > 6 else '') + '), rank 0',
                          'bound': 'mfma', 'achieved': exec_tf, 'peak': peak_tf, 'unit': 'TFLOP/s',
                          'frac': (exec_tf / peak_tf) if exec_tf else None, 'traffic': traffic, 'traffic_source': traffic_src,
@@ -594,8 +636,7 @@ def main():
                               'note': 'rank-0 share of the batch; survey_mfma_frac uses SURVEY 8d FLOPs (unfolded form) and is not a '
                                       'utilisation; the step is fp32-issue-bound, not HBM-bound (AI ~ 3000 FLOP/B)'},
             'weak_scaling': weak,
-            'final_gather_ms': gather_ms,
-        }
+        })
         # the other single-GPU configurations of BASELINE.json, after the timed region (N = 1, full runs only: the quick runs of tools/ pass
         # --no-cpu-baseline or another --graphs)
         if world == 1 and not (args.no_secondary or args.no_cpu_baseline or args.weak) and args.graphs == 128:
@@ -606,6 +647,7 @@ def main():
             line['cpu_baseline'] = cpu_baseline(full)      # final barrier below)
         else:
             line['cpu_baseline'] = None
+    if rank == 0:
         print(json.dumps(line))
     if world > 1:
         dist.barrier()                  # (rank 0 times the CPU baseline after the timed region; the others wait here)

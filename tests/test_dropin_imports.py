@@ -1,14 +1,12 @@
 """The `dropin/` alias packages: the reference's own import lines must resolve to phoregen_amd with ONE sys.path entry
 (SURVEY.md 8(b) "Import surface the callers use").  Runs in a fresh interpreter so that this test session's own `models` /
-`utils` imports cannot leak in.  With /root/reference present (build container only) the actual import blocks of
-sample_all.py and run/run.py are executed unedited; on the GPU box only the alias-side assertions run."""
+`utils` imports cannot leak in.  The second test puts a stand-in reference checkout, written at test time, behind the aliases."""
 import os
 import subprocess
 import sys
 import textwrap
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REFERENCE = os.environ.get('PHOREGEN_REFERENCE', '/root/reference')
 
 
 def _run(code, extra_path=()):
@@ -41,25 +39,45 @@ def test_alias_packages_resolve_to_phoregen_amd():
     assert out.strip().endswith('ok')
 
 
-def test_reference_scripts_import_unchanged():
-    import pytest
-    if not os.path.isdir(os.path.join(REFERENCE, 'models')):
-        pytest.skip('reference checkout not present (GPU box)')
+# A stand-in for a reference checkout placed behind the alias packages: the reference's own `models` package (which the alias must
+# shadow), `utils/misc.py` and `utils/sample_utils.py` (reference-owned modules the extended `utils` package path must still find),
+# and a `run` package.  Written at test time, so the test needs nothing outside the repository.
+_STANDIN_CHECKOUT = {
+    'models/__init__.py': '',
+    'models/diffusion.py': 'class PhoreDiff:  # the alias must win over this one\n    pass\n',
+    'models/model_utils.py': 'class EMA:  # the alias must win over this one\n    pass\n',
+    'utils/__init__.py': '',
+    'utils/misc.py': 'def seed_all(seed):\n    return seed\n',
+    'utils/sample_utils.py': 'class MolReconsError(Exception):\n    pass\n\n\ndef reconstruct_from_generated_with_edges(*args, **kwargs):\n'
+                             '    raise MolReconsError()\n',
+    'run/__init__.py': '',
+}
+
+
+def test_reference_scripts_import_unchanged(tmp_path):
+    """A caller's imports resolve with the alias packages first on sys.path and a reference checkout behind them: `models` and
+    `utils.sample_utils` are phoregen_amd's, every other `utils.*` module is the checkout's own, and the molecule reconstruction
+    (`MolReconsError`, `reconstruct_from_generated_with_edges`) is handed through to the checkout's `utils/sample_utils.py`."""
+    checkout = tmp_path / 'reference'
+    for rel, text in _STANDIN_CHECKOUT.items():
+        (checkout / rel).parent.mkdir(parents=True, exist_ok=True)
+        (checkout / rel).write_text(text)
     standins = os.path.join(ROOT, 'oracle', 'standins')       # the third-party wheels this image lacks (test infrastructure)
     out = _run(f'''
-        import ast
-        def import_block(path, last_line):
-            src = open(path).read()
-            tree = ast.parse(src)
-            keep = [n for n in tree.body if isinstance(n, (ast.Import, ast.ImportFrom)) and n.lineno <= last_line]
-            exec(compile(ast.Module(body=keep, type_ignores=[]), path, 'exec'), globals())
-        import_block({os.path.join(REFERENCE, 'sample_all.py')!r}, 12)          # sample_all.py:1-12, unedited
+        from torch_geometric.loader import DataLoader, DataListLoader
+        from torch_geometric.data import Batch
+        from utils.misc import *
+        from models.diffusion import PhoreDiff
+        from utils.sample_utils import unbatch_data, decode_data, reconstruct_from_generated_with_edges, MolReconsError
         assert PhoreDiff.__module__ == 'phoregen_amd.models.diffusion', PhoreDiff.__module__
         assert unbatch_data.__module__ == 'phoregen_amd.utils.sample_utils' and decode_data.__module__ == unbatch_data.__module__
-        assert seed_all.__module__ == 'utils.misc' and 'reference' in sys.modules['utils.misc'].__file__   # the reference's own file
-        import_block({os.path.join(REFERENCE, 'run', 'run.py')!r}, 13)           # run/run.py:1-13
+        assert seed_all.__module__ == 'utils.misc' and sys.modules['utils.misc'].__file__.startswith({str(checkout)!r})   # the checkout's own file
+        from models.model_utils import EMA
+        import run
         assert EMA.__module__ == 'phoregen_amd.models.model_utils'
+        assert run.__file__.startswith({str(checkout)!r})
         assert MolReconsError.__module__ in ('utils._reference_sample_utils', 'utils.sample_utils')
+        assert reconstruct_from_generated_with_edges.__module__ == 'utils._reference_sample_utils'
         print('ok')
-    ''', extra_path=(REFERENCE, standins))
+    ''', extra_path=(str(checkout), standins))
     assert out.strip().endswith('ok')

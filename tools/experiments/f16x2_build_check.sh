@@ -12,8 +12,8 @@ for rep in 1 2; do
 done
 for g in 128 16; do
   echo "== sampler step, $g graphs (bench.py --no-cpu-baseline): product, f16x2 =="
-  python3 bench.py --graphs $g --no-cpu-baseline 2>/dev/null | grep -o '"ms_per_step": [0-9.]*\|"avg_launch_ms": [0-9.]*' | tr '\n' ' '; echo
-  env $X python3 bench.py --graphs $g --no-cpu-baseline 2>/dev/null | grep -o '"ms_per_step": [0-9.]*\|"avg_launch_ms": [0-9.]*' | tr '\n' ' '; echo
+  python3 bench.py --full --graphs $g --no-cpu-baseline 2>/dev/null | grep -o '"ms_per_step": [0-9.]*\|"avg_launch_ms": [0-9.]*' | tr '\n' ' '; echo
+  env $X python3 bench.py --full --graphs $g --no-cpu-baseline 2>/dev/null | grep -o '"ms_per_step": [0-9.]*\|"avg_launch_ms": [0-9.]*' | tr '\n' ' '; echo
 done
 rm -f gpurun_out/parity_ratios.jsonl
 echo "== f16x2 build: forward / sampler parity tests against the reference goldens and the oracle =="
