@@ -181,7 +181,12 @@ __global__ __launch_bounds__(THREADS, FUSED ? 1 : 3) void node_attn_kernel(PgTop
           bool valid = k < n_rows;
           int src = 0, crow = 0;
           if constexpr (KNN) {
-            if (valid) { src = p.nbr[(size_t)seg * p.knn_k + k]; crow = src; }
+            // every load of the knn rows is unconditional: an invalid row reads neighbour slot 0 / context row 0 (both exist), and
+            // its values are selected away or cannot reach a valid row (below).  A load under a lane condition is a branch of its
+            // own, and the compiler waits for each such load right where it is used (vmcnt(0)): one round trip per load
+            src = p.nbr[(size_t)seg * p.knn_k + (valid ? k : 0)];
+            src = valid ? src : 0;
+            crow = src;
           } else {
             valid = valid && k != li;
             if (valid) { src = lig0 + k; crow = eid_g[k * n + li]; }
@@ -190,20 +195,26 @@ __global__ __launch_bounds__(THREADS, FUSED ? 1 : 3) void node_attn_kernel(PgTop
             // 48 features of row k for f = 4 step + g (packing._knn_feat); f = 47 carries the target's constant Cdst
             float d = 0.f, dots[3] = {0.f, 0.f, 0.f};
             bool src_lig = false;
-            if (valid) {
+            {
               float xs[3], ns[3];
 #pragma unroll
               for (int c = 0; c < 3; ++c) { xs[c] = p.x[src * 3 + c]; ns[c] = p.nrm[src * 3 + c]; }
+              const bool is_lig = t.ctx_is_lig[src] != 0;
               const float r0 = xd[0] - xs[0], r1 = xd[1] - xs[1], r2 = xd[2] - xs[2];
-              d = sqrtf(r0 * r0 + r1 * r1 + r2 * r2);
-              dots[0] = ns[0] * nd[0] + ns[1] * nd[1] + ns[2] * nd[2];
-              dots[1] = -(ns[0] * r0 + ns[1] * r1 + ns[2] * r2);
-              dots[2] = -(nd[0] * r0 + nd[1] * r1 + nd[2] * r2);
-              src_lig = t.ctx_is_lig[src] != 0;
+              const float dd = sqrtf(r0 * r0 + r1 * r1 + r2 * r2);
+              const float d0 = ns[0] * nd[0] + ns[1] * nd[1] + ns[2] * nd[2];
+              const float d1 = -(ns[0] * r0 + ns[1] * r1 + ns[2] * r2);
+              const float d2 = -(nd[0] * r0 + nd[1] * r1 + nd[2] * r2);
+              d = valid ? dd : 0.f;
+              dots[0] = valid ? d0 : 0.f;
+              dots[1] = valid ? d1 : 0.f;
+              dots[2] = valid ? d2 : 0.f;
+              src_lig = valid && is_lig;
             }
 #pragma unroll
             for (int st = 0; st < 5; ++st) {
-              const float sv = valid ? smear(d, 4 * st + g) : 0.f;
+              const float se = smear(d, 4 * st + g);       // (unconditional: its offset-table read is then not a branch)
+              const float sv = valid ? se : 0.f;
               feat[tile][st] = src_lig ? sv : 0.f;
               feat[tile][5 + st] = src_lig ? 0.f : sv;
             }
@@ -219,8 +230,14 @@ __global__ __launch_bounds__(THREADS, FUSED ? 1 : 3) void node_attn_kernel(PgTop
 #pragma unroll
             for (int tq = 0; tq < 8; ++tq) {
               f4 c = {0.f, 0.f, 0.f, 0.f};
-              if (valid) c = *reinterpret_cast<const f4*>(pk + 16 * tq);
-              if constexpr (!KNN) c += *reinterpret_cast<const f4*>(ckp + 16 * tq + 4 * g);
+              if constexpr (KNN) {
+                // an invalid row keeps context row 0 here: the key path is row-local (the feature MFMAs, the LayerNorm over the
+                // channels of row m, the logit MFMAs) and its logit is replaced by NA_NEG below, so nothing of it reaches a valid row
+                c = *reinterpret_cast<const f4*>(pk + 16 * tq);
+              } else {
+                if (valid) c = *reinterpret_cast<const f4*>(pk + 16 * tq);
+                c += *reinterpret_cast<const f4*>(ckp + 16 * tq + 4 * g);
+              }
               hid[tq] = c;
             }
           }
@@ -232,7 +249,7 @@ __global__ __launch_bounds__(THREADS, FUSED ? 1 : 3) void node_attn_kernel(PgTop
 #pragma unroll
               for (int tq = 0; tq < 8; ++tq) {
                 float w = wf_k[(st * 8 + tq) * 64 + lw];
-                if (st == 11) w = g == 3 ? ckp[16 * tq + m] : w;
+                if (st == 11) { const float cd = ckp[16 * tq + m]; w = g == 3 ? cd : w; }
                 hid[tq] = mfma16(w, feat[tile][st], hid[tq]);
               }
           }
@@ -260,8 +277,14 @@ __global__ __launch_bounds__(THREADS, FUSED ? 1 : 3) void node_attn_kernel(PgTop
 #pragma unroll
             for (int tq = 0; tq < 8; ++tq) {
               f4 c = {0.f, 0.f, 0.f, 0.f};
-              if (valid) c = *reinterpret_cast<const f4*>(pk + 16 * tq);
-              if constexpr (!KNN) c += *reinterpret_cast<const f4*>(cvp + 16 * tq + 4 * g);
+              if constexpr (KNN) {
+                const f4 v = *reinterpret_cast<const f4*>(pk + 16 * tq);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) c[r] = valid ? v[r] : 0.f;
+              } else {
+                if (valid) c = *reinterpret_cast<const f4*>(pk + 16 * tq);
+                c += *reinterpret_cast<const f4*>(cvp + 16 * tq + 4 * g);
+              }
               hx[tq] = c;
             }
 #pragma unroll
@@ -272,7 +295,7 @@ __global__ __launch_bounds__(THREADS, FUSED ? 1 : 3) void node_attn_kernel(PgTop
 #pragma unroll
                 for (int tq = 0; tq < 8; ++tq) {
                   float w = wf_v[(st * 8 + tq) * 64 + lw];
-                  if (st == 11) w = g == 3 ? cvp[16 * tq + m] : w;
+                  if (st == 11) { const float cd = cvp[16 * tq + m]; w = g == 3 ? cd : w; }
                   hx[tq] = mfma16(w, feat[tile][st], hx[tq]);
                 }
             }
@@ -388,10 +411,20 @@ __global__ __launch_bounds__(THREADS, FUSED ? 1 : 3) void node_attn_kernel(PgTop
             const int kr = tile * 16 + 4 * g + r;
             const bool vr = kr < n_rows && (KNN || kr != li);
             int crow = 0;
-            if (vr) crow = KNN ? p.nbr[(size_t)seg * p.knn_k + kr] : eid_g[kr * n + li];
+            if constexpr (KNN) {                     // (unconditional loads, as in pass A)
+              crow = p.nbr[(size_t)seg * p.knn_k + (vr ? kr : 0)];
+              crow = vr ? crow : 0;
+            } else {
+              if (vr) crow = eid_g[kr * n + li];
+            }
             const float* pv = p.Csrc_v + (size_t)crow * p.ld_csrc + m;
 #pragma unroll
-            for (int tq = 0; tq < 8; ++tq) hv[tq][r] = vr ? pv[16 * tq] : 0.f;
+            for (int tq = 0; tq < 8; ++tq) {
+              // KNN: an invalid row keeps context row 0.  Every step of the value path is row-local up to the S^T chain, where
+              // row r enters multiplied by aw[r] = (0 x gate) x rsq, a zero whose sign does not depend on the row's finite values
+              if constexpr (KNN) hv[tq][r] = pv[16 * tq];
+              else hv[tq][r] = vr ? pv[16 * tq] : 0.f;
+            }
           }
           if constexpr (!KNN) {
 #pragma unroll
@@ -405,7 +438,7 @@ __global__ __launch_bounds__(THREADS, FUSED ? 1 : 3) void node_attn_kernel(PgTop
 #pragma unroll
               for (int tq = 0; tq < 8; ++tq) {
                 float w = wf_v[(st * 8 + tq) * 64 + lw];
-                if (st == 11) w = g == 3 ? cvp[16 * tq + m] : w;
+                if (st == 11) { const float cd = cvp[16 * tq + m]; w = g == 3 ? cd : w; }
                 hv[tq] = mfma16(feat[tile][st], w, hv[tq]);
               }
           }
