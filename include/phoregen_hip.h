@@ -84,7 +84,7 @@ int pg_selftest_mfma(int* d_result, void* stream);
  * key = seed (lo, hi), counter = (element index lo, hi, step, stream_id). */
 int pg_selftest_philox(const uint32_t* ctr_key, int n, uint32_t* out, void* stream);
 /* test hook (returns the old setting): bit 0 routes the node-target modes of pg_seg_attn through the generic one-pass kernel,
- * bit 1 keeps PG_SEG_TRIPLET on the gather kernel (csrc/triplet.hip) even when the staged one (csrc/triplet2.hip) applies,
+ * bit 1 no longer has an effect (it selected a triplet kernel that has since been removed),
  * bit 2 runs the staged kernel with 8 instead of 12 waves per workgroup (tuning) */
 int pg_debug_force_generic_seg(int mask);
 

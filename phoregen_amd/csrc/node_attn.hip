@@ -1,5 +1,5 @@
 // Node-target attention sub-layers (knn edges / bond edges, node update / position update) in the two-pass,
-// low-register form of triplet.hip: one wave per target node,
+// low-register form of triplet2.hip: one wave per target node,
 //   pass A  K path for every row tile -> logits (and, for the position update, the per-head value scalars);
 //   exact softmax over the stored logits (base 2; queries carry log2(e)/sqrt(8));
 //   pass B  V path -> S^T[c,h] (node update) or the weighted sum of relative positions (position update).

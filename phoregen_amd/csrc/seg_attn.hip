@@ -17,7 +17,6 @@
 
 namespace pg {
 
-int launch_triplet(const PgTopo* t, const PgSegAttn* p, hipStream_t st);     // triplet.hip
 int launch_triplet_staged(const PgTopo* t, const PgSegAttn* p, hipStream_t st);   // triplet2.hip (-1: not applicable)
 int launch_node_attn(const PgTopo* t, const PgSegAttn* p, hipStream_t st);   // node_attn.hip (-1: shape not covered)
 bool node_attn_fused_request(const PgSegAttn* p);                            // node_attn.hip
@@ -648,15 +647,12 @@ extern "C" int pg_seg_attn(const PgTopo* t, const PgSegAttn* p, void* stream) {
     case PG_SEG_KNN_POS: return launch_seg<PG_SEG_KNN_POS>(t, p, st);
     case PG_SEG_BOND_NODE: return launch_seg<PG_SEG_BOND_NODE>(t, p, st);
     case PG_SEG_BOND_POS: return launch_seg<PG_SEG_BOND_POS>(t, p, st);
-    case PG_SEG_TRIPLET:
-      if (!(g_force_generic & 2)) {        // source-atom rows staged in LDS (sampling form, target-major bond order)
-        const int rc = launch_triplet_staged(t, p, st);
-        if (rc >= 0) return rc;
-      }
-      // the occupancy-tuned kernel holds the logits of <= 5 row tiles in registers (ligands of <= 80 atoms)
-      // S / swn output (training): the tuned kernel when the query-side inputs are given too, else the generic form
-      return (t->max_nlig <= 80 && (!p->S || (p->q && p->W2k_l && p->G))) ? launch_triplet(t, p, st)
-                                                                        : launch_seg<PG_SEG_TRIPLET>(t, p, st);
+    case PG_SEG_TRIPLET: {
+      // source-atom rows staged in LDS (sampling and training forms, target-major bond order); without the plan's queue, or for
+      // ligands of more than 81 atoms, the generic form
+      const int rc = launch_triplet_staged(t, p, st);
+      return rc >= 0 ? rc : launch_seg<PG_SEG_TRIPLET>(t, p, st);
+    }
     case PG_SEG_PHORE: return launch_seg<PG_SEG_PHORE>(t, p, st);
   }
   set_error("pg_seg_attn: unknown mode %d", p->mode);

@@ -51,7 +51,7 @@ struct RowGeo {
 };
 
 // sin(x) or cos(x) for 0 <= x <= ~10 (angular code arguments are bounded by 3 pi): k = rint(x * 2/pi), two-constant
-// Cody-Waite reduction, degree-9 / degree-8 polynomials on [-pi/4, pi/4], quadrant select (csrc/triplet.hip uses the same)
+// Cody-Waite reduction, degree-9 / degree-8 polynomials on [-pi/4, pi/4], quadrant select (csrc/triplet2.hip uses the same)
 __device__ __forceinline__ float sincos_bounded(float arg, bool want_cos) {
   const float kf = rintf(arg * 0.63661977236758134308f);
   float r = fmaf(-kf, 1.57079637050628662109375f, arg);

@@ -12,7 +12,8 @@
 // LDS: lane-fixed W2k (64 KB, query fold), feature weights (12 KB), biases, the ligand's coordinates, 80 staged rows (81 KB).
 // The value unfold streams W2v through L2 (64 KB per segment, software-prefetched in batches of 16 float4 per lane): the two
 // 64 KB weight tables and the staged rows do not fit the 160 KB together, and the unfold has no data it must wait for.
-// Per-segment arithmetic is that of triplet.hip (two passes, folded LayerNorm, base-2 softmax); the per-segment constant
+// Per-segment arithmetic: two passes over a segment's row tiles (K path -> logits of every row -> exact softmax -> V path, so the
+// folded-key operand U and the value accumulator S^T are never live together), folded LayerNorm, base-2 softmax; the per-segment constant
 // Q = Wg2 . smear(d_ji) comes in as a row of Cdst (a [n_bond,20]x[20,256] GEMM per layer) and reaches the MFMA through the
 // spare feature column.
 // Lane l = (g = l>>4, m = l&15); 16x16x4 maps as in seg_attn.hip.
@@ -60,7 +61,8 @@ __device__ __forceinline__ float t2_from_lane(float v, int src_lane) {
   return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(src_lane << 2, __builtin_bit_cast(int, v)));
 }
 
-// sin(w*theta) or cos(w*theta) for 0 <= arg <= ~10 (same reduction + polynomials as triplet.hip)
+// sin(w*theta) or cos(w*theta) for 0 <= arg <= ~10: k = rint(arg * 2/pi), r = arg - k*pi/2 (two constants),
+// sin/cos polynomials on [-pi/4, pi/4], quadrant select; cos(x) = sin-quadrant shifted by one (exact)
 __device__ __forceinline__ float t2_sincos(float arg, bool want_cos) {
   const float kf = rintf(arg * 0.63661977236758134308f);
   float r = fmaf(-kf, 1.57079637050628662109375f, arg);

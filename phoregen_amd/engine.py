@@ -44,20 +44,6 @@ def _f(*shape, device, zero=False):
     return (torch.zeros if zero else torch.empty)(*shape, dtype=torch.float32, device=device)
 
 
-class _TorchPoint:
-    """torch.cuda.Event behind the two calls of hip.OrderPoint."""
-    __slots__ = ('ev',)
-
-    def __init__(self):
-        self.ev = torch.cuda.Event()
-
-    def record(self, stream):
-        self.ev.record(stream)
-
-    def wait(self, stream):
-        stream.wait_event(self.ev)
-
-
 class _Tap:
     """A launch-list entry that is not a kernel launch: 'order' (records / waits of order points between the lanes), 'event' (a timing
     event when Engine.timers is set) or 'mark' (clones of tensors when Engine.debug is set)."""
@@ -87,43 +73,25 @@ class Engine:
         # switch them with options.override(...), the ambient environment only counts under PHOREGEN_DEBUG=1)
         o = options.snapshot()
         self.multi_stream = o['streams']
-        self.staged_triplet = o['tri_staged']          # csrc/triplet2.hip (False: the gather kernel)
-        self.fused_node = o['node_fused']              # node attention folds / unfolds in-kernel
-        self.group_knn = o['knn_group']                # neighbour slots partitioned by source kind
-        self.merge_knn_lists = o['knn_merge'] != 'never'      # ligand + pharmacophore targets of a knn sub-layer in one launch
-        self.merge_knn_always = o['knn_merge'] == 'always'    # ... also below the batch size where it pays (tests)
         # the next layer's first-layer blocks, triplet queries and bond-node rows (everything in front of its triplet kernel that does
         # not depend on the new coordinates) run on lane 2 during this layer's position updates
         self.layer_ahead = o['layer_ahead']
-        # cross-lane order points without the host-visibility fence of a default event (hip.OrderPoint; tools/micro/stream_packets.py)
-        self.order_points = o['order_points'] and not o['graph']
         self.tri_split, self.tri_split_from = o['tri_split'], o['tri_split_from']
         self.tri_overlap = o['tri_overlap']
         self.chain_q_from = o['chain_q_from']
         self.tune_grid = o['tune_grid']
         self.tuned_tri_grid = None
         self.geom_split = o['geom_split'] == 'always' or (o['geom_split'] == 'auto' and self.plan.n_bond < o['geom_split_below'])
-        # (hipGraph capture of the v2 launch list segfaults inside the runtime -- lanes 2 / 3 wait on lane 1 there while lane 1 waits on
-        #  lane 3; the replay variant, off by default and measured slower, keeps the previous list)
-        self.ahead_v2 = (o['ahead_v2'] == 'always' or (o['ahead_v2'] == 'auto' and self.plan.n_bond < o['ahead_v2_below'])) and not o['graph']
+        self.ahead_v2 = o['ahead_v2'] == 'always' or (o['ahead_v2'] == 'auto' and self.plan.n_bond < o['ahead_v2_below'])
         self.step_ahead = o['step_ahead']
-        self.head_early = o['sa_head_early']
         self.pos_tiled, self.pos_tiled_below = o['pos_tiled'], o['pos_tiled_below']
         self.tri_grid = o['tri_grid']                  # persistent triplet workgroups (-1: by batch size)
-        # apply_dx + bond smearing + direction vectors as one launch on lane 0: small batches (measured, same box: 16 graphs 3.52 -> 3.40 ms
-        # per step, 32 graphs 5.69 -> 5.43; 128 graphs 20.20 -> 20.28: there the three launches hide beside the first-layer GEMM)
-        self.fused_geom = o['fused_geom'] in ('always', 'auto')
-        # hipGraph replay of the forward launch list.  Off by default: measured on MI355X it buys nothing, a step
-        # is bound by the ~225 dependent kernels themselves, not by their launches (tools/bench_graph.py: B=1 3.19 -> 2.95,
-        # B=10 3.89 -> 4.07, B=30 5.33 -> 5.92 ms/step; identical results)
-        self.graph_mode = '1' if o['graph'] else '0'
-        self._graph = None
         self._lane = 0
         self._n_points = 0       # order points of this engine's launch lists
         self._points = {}        # ... their events in the Python runner (created at first use)
         # the launch lists run inside the library (pg_program_run: ONE foreign call per forward) unless a debug / timing / trace tap is
-        # active, the order points are torch events, or the list is being captured into a hipGraph
-        self.c_program = o['c_program'] and (self.order_points or not self.multi_stream)
+        # active
+        self.c_program = o['c_program']
         self._compiled = {}
         self._side = None
         self.stream_set = 0      # (experiments: a second set of side lanes)
@@ -185,14 +153,9 @@ class Engine:
         assert len(args) + 1 == len(fn.argtypes), (fn.__name__, len(args) + 1, len(fn.argtypes))
         prog.append((fn, args, self._lane if self.multi_stream else 0))
 
-    def _point(self):
-        """A new cross-lane order point: the library's device-scope event, or a torch event (option `order_points` off; hipGraph capture)."""
-        if self.order_points:
-            return hip.OrderPoint()
-        return _TorchPoint()
-
     # Entries of a launch list that are not kernel launches are `_Tap` records (plain data: a launch list holds no reference to its
-    # Engine, so an Engine is freed by reference counting alone).  Order points are numbered per Engine (`_n_points`); the Python
+    # Engine, so an Engine is freed by reference counting alone).  Order points are device-scope HIP events without the host-visibility
+    # fence of a default event (hip.OrderPoint; tools/micro/stream_packets.py), numbered per Engine (`_n_points`); the Python
     # runner creates the event of a point at its first record and re-records it every step (a wait refers to the record that precedes
     # it, so re-use across steps is safe), the C runner (pg_program_*) owns one event per point.
     def _new_point(self):
@@ -252,7 +215,7 @@ class Engine:
             for what, pt, lane in tap.ops:
                 ev = self._points.get(pt)
                 if ev is None:
-                    ev = self._points[pt] = self._point()
+                    ev = self._points[pt] = hip.OrderPoint()
                 if what == 'record':
                     ev.record(streams[lane])
                 else:
@@ -315,12 +278,13 @@ class Engine:
             self._query_gemm(prog, a, Y, col0, h_dst_lists, buf)
         knn = mode in (hip.SEG_KNN_NODE, hip.SEG_KNN_POS)
         pos = mode in (hip.SEG_KNN_POS, hip.SEG_BOND_POS)
-        fused = self.fused_node and mode != hip.SEG_PHORE      # in-kernel query fold / value unfold (csrc/node_attn.hip)
+        # in-kernel query fold / value unfold (csrc/node_attn.hip); the pharmacophore encoder folds and unfolds in launches of their own
+        fused = mode != hip.SEG_PHORE
         # fused knn form with two target lists (ligand + pharmacophore targets, different feature weights): ONE launch, the
         # persistent workgroups split between the lists in proportion to their sizes (PgSegAttn.seg_ids2)
         # (at every size since round 4: with the node chain on 32 ... 96 CUs beside the triplet kernel, two launches of 50 + 85 workgroups
         #  take three rounds where the merged one takes two -- 8 graphs 2.29 -> 2.04 ms per step, 16 graphs 3.05 -> 3.02, 24+ as before)
-        merged = fused and knn and len(h_dst_lists) == 2 and self.merge_knn_lists and all(n > 0 for _, n, _ in h_dst_lists)
+        merged = knn and len(h_dst_lists) == 2 and all(n > 0 for _, n, _ in h_dst_lists)
         lists = [h_dst_lists[0]] if merged else h_dst_lists
         for seg_ids, n_seg, is_lig in lists:
             if not fused:
@@ -342,7 +306,7 @@ class Engine:
                 # small batches: a node's row tiles over several waves (csrc/node_attn.hip, bit-identical): the launch is bound by the
                 # dependent chain inside the wave that owns a node, not by the chip
                 tiled = self.pos_tiled == 'always' or (self.pos_tiled == 'auto' and n_seg <= self.pos_tiled_below)
-                if fused and tiled:
+                if tiled:
                     kw.update(pos_tiled=1)
             else:
                 kw.update(S=wS, swn=wsw)
@@ -467,8 +431,7 @@ class Engine:
 
     def pipelined_programs(self):
         """(prog_step, prog_ahead) of the pipelined sampler step, or None when this engine's schedule has no layer-ahead form."""
-        if not (self.step_ahead and self.multi_stream and self.layer_ahead and self.fused_geom and self.staged_triplet and self.plan.n_tri_iters
-                and self.order_points):
+        if not (self.step_ahead and self.multi_stream and self.layer_ahead and self.plan.n_tri_iters):
             return None
         if self.prog_step is None:
             tri_calls, self.tri_calls = self.tri_calls, []
@@ -506,11 +469,11 @@ class Engine:
                    g['W0'].data_ptr(), g['b0'].data_ptr(), g['g'].data_ptr(), g['b'].data_ptr(), g['W3'].data_ptr(),
                    C.c_float(g['b3']), w.ew.data_ptr())
         self._mark(prog, 'graph', w.nbr, w.deg, w.ew, lane=1)
-        if self.group_knn:      # ligand-source rows first: uniform row tiles skip the other kind's distance columns (node_attn.hip)
-            self._call(prog, lib.pg_knn_group_by_kind, t, self.k, w.nbr.data_ptr(), w.deg.data_ptr(), w.ew.data_ptr())
+        # ligand-source rows first: uniform row tiles skip the other kind's distance columns (node_attn.hip)
+        self._call(prog, lib.pg_knn_group_by_kind, t, self.k, w.nbr.data_ptr(), w.deg.data_ptr(), w.ew.data_ptr())
         self._lane = 0
         cur = 0
-        staged = bool(p.n_tri_iters and self.staged_triplet)
+        staged = bool(p.n_tri_iters)       # the staged triplet kernel (csrc/triplet2.hip) has a queue: ligands of up to 81 atoms
         n_layers = len(pk.layers)
         # next layer's x-independent products inside this layer's position phase: measured (same box, alternating runs) 16 graphs
         # 3.93 -> 3.83 ms, 32 graphs 5.94 -> 5.67, 64 graphs 10.55 -> 10.36, 128 graphs 20.12 -> 20.17 (the triplet kernel then
@@ -534,7 +497,7 @@ class Engine:
         # default once, before the sampler loop, and keep the fastest (`calibrate_tri_grid`; the result does not depend on the grid: the queue
         # hands out the same segments)
         self._tune = None
-        if (self.tune_grid and self.tri_grid < 0 and self.multi_stream and staged and 0 < tri_grid <= 224 and not self.graph_mode == '1'):
+        if (self.tune_grid and self.tri_grid < 0 and self.multi_stream and staged and 0 < tri_grid <= 224):
             self._tune = dict(cands=[g for g in (tri_grid, tri_grid + 32, tri_grid - 32) if 128 <= g <= 256])
 
         if v2 and w.Y1b is None:
@@ -543,7 +506,7 @@ class Engine:
         # chain (x', bond smearing), on lane 1 for the node chain (its own copy of x', direction vectors) -- so that neither chain waits
         # for a launch on the other's lane: each waits for the other's position update only.  The two copies of x' are the same
         # expression of the same operands.
-        split = v2 and self.fused_geom and self.geom_split
+        split = v2 and self.geom_split
         if split and getattr(w, 'x_node', None) is None:
             w.x_node = [torch.empty_like(x[0]), torch.empty_like(x[0])]
             w.dxe2 = torch.zeros_like(w.dxe)
@@ -551,7 +514,7 @@ class Engine:
         first_layer_gemm = lambda L_, h_in, Y1_: self._first_layer_gemm(prog, L_, h_in, Y1_)
         triplet_queries = lambda L_, hb_in, Y1_: self._triplet_queries(prog, L_, hb_in, Y1_)
         bond_node_rows = lambda L_, hb_in, Y1_: self._bond_node_rows(prog, L_, hb_in, Y1_)
-        assert not step_ahead or (ahead and self.fused_geom and staged)
+        assert not step_ahead or (ahead and staged)
 
         for li, L in enumerate(pk.layers):
             nxt = 1 - cur
@@ -563,22 +526,11 @@ class Engine:
             dxe = w.dxe2 if (split and li % 2) else w.dxe           # (alternating: lane 1 writes the next while lane 0's closing launch may read this one)
             pre = ahead and (li > 0 or step_ahead)      # Y1, the triplet queries and the bond-node rows of this layer were launched by the previous one
             pre0 = step_ahead and li == 0                # ... layer 0 of a pipelined step: by `prog_ahead` at the end of the previous STEP (lanes 2 / 3)
-            if self.fused_geom:
-                # direction vectors and bond-length smearing of this layer came with the previous layer's coordinate update (ONE
-                # launch on lane 0, pg_layer_geom); layer 0 forms them from the embedded coordinates the same way
-                if li == 0:
-                    self._call(prog, lib.pg_layer_geom, t, xc.data_ptr(), None, None, w.nrm_phore_ctx.data_ptr(), None,
-                               w.nrm.data_ptr(), w.G.data_ptr())
-            else:
-                # direction vectors (read by the knn attention, lane 1) and bond-length smearing (read by the P product on lane 0 and
-                # the Q rows on lane 2) depend on x only: they run beside the first-layer GEMM instead of in front of it
-                self._fork(prog, (1, 3))
-                self._lane = 1
-                self._call(prog, lib.pg_lig_normals, t, xc.data_ptr(), w.phore_norm.data_ptr(), p.phore2ctx.data_ptr(),
-                           w.nrm.data_ptr())
-                self._lane = 3
-                self._call(prog, lib.pg_bond_smear, t, xc.data_ptr(), w.G.data_ptr())
-                self._lane = 0
+            # direction vectors and bond-length smearing of this layer came with the previous layer's coordinate update (ONE launch on
+            # lane 0, pg_layer_geom); layer 0 forms them from the embedded coordinates the same way
+            if li == 0:
+                self._call(prog, lib.pg_layer_geom, t, xc.data_ptr(), None, None, w.nrm_phore_ctx.data_ptr(), None,
+                           w.nrm.data_ptr(), w.G.data_ptr())
             if (pre and not v2) or pre0:
                 # lane 2 carried this layer's first-layer blocks and triplet queries through the previous layer's position updates
                 # (pipelined step, layer 0: through the end of the previous step)
@@ -588,7 +540,7 @@ class Engine:
             if li == 0 and pre_join:
                 self._join(prog, pre_join)
             # (v2 from layer 1 on: lanes 2 / 3 have nothing in the first half of the layer, only the node chain's lane is released here)
-            q_side = staged and not (chain_q and self.fused_geom)       # the Q rows on lane 2: it reads this layer's smearing (lane 0)
+            q_side = staged and not chain_q        # the Q rows on lane 2: it reads this layer's smearing (lane 0)
             if pre and split and not pre0:         # (split: lane 1 went on behind its own closing launch)
                 if q_side:
                     self._fork(prog, (2,))
@@ -596,10 +548,8 @@ class Engine:
                 self._fork(prog, ((1, 2) if q_side else (1,)) if (pre and v2) else (1, 2, 3))
             # (v2: this layer's first-layer blocks came from lane 1 behind the previous layer's Y2, which lane 0 has joined since; the
             #  triplet queries on lane 2 are waited for in front of the triplet kernel, not in front of P)
-            if not self.fused_geom:
-                self._sync(prog, 0, (3,))              # the smearing (alone on lane 3 so far) is read by P on lane 0
-                self._sync(prog, 2, (3,))              # ... and by the Q rows on lane 2; the queries on lane 3 do not wait for it
             last = heads is not None and li == n_layers - 1
+            early = step_ahead and last            # the node head of a pipelined step right behind the last lin_node (it needs h' only)
             # Launch order of a layer.  Lane 0 carries the bond chain (P -> triplet -> bond position update), lane 1 the node
             # chain (knn attention -> lin_node -> second first-layer GEMM -> knn position update), lane 2 the Q rows and the
             # bond-node attention, lane 3 the triplet queries: nothing on lane 1 waits for the triplet kernel, and lane 0 picks
@@ -607,14 +557,14 @@ class Engine:
             # ---- bond update over triplets, its operands (:285)
             # P[k->j] = W.[h_bond | G] + (source half)[k] + (target half)[j].  Every row of the block a segment j->i reads has the
             # same target j, so in the staged form that half rides on the segment's own row Q[j->i] instead (one gathered operand
-            # per product; the gather kernel builds Q in-kernel and keeps it on P)
+            # per product); without a staged queue P carries both halves and the generic kernel runs
             self._lane = 0
             self._gemm(prog, hbc, 128, L.TB.W_hbg, w.P, E, 256, X2=w.G, K2=20,
                        add1=Y1c[:, 10 * 128:12 * 128], idx1=p.bond_src,
                        **({} if staged else dict(add2=Y1c[:, 12 * 128:14 * 128], idx2=p.bond_dst)))
             # the per-segment constant of the triplet MLPs as rows: Wg2 . smear(d_ji) + (target half)[j].  Small batches: behind P on
             # lane 0 (a 25 us product costs less there than the two cross-lane hops around it on a side lane)
-            q_lane = 0 if (chain_q and self.fused_geom) else 2
+            q_lane = 0 if chain_q else 2
             self._lane = q_lane
             if staged:
                 self._gemm(prog, w.G, 20, L.TB.W_g2, w.Qd, E, 256, add1=Y1c[:, 12 * 128:14 * 128], idx1=p.bond_src)
@@ -669,8 +619,8 @@ class Engine:
             # ---- node update over bond edges (:284)                                   [lane 2]
             # (the sub-layer reads no coordinates: from layer 1 on a small batch has launched it during the previous layer's position
             #  updates, see below)
-            self._lane = 3 if v2 else 2            # (v2: lane 1 then never waits on lane 2, so lane 2 may wait on lane 1 -- the other
-            if not pre:                            #  order of the two edges breaks hipGraph capture)
+            self._lane = 3 if v2 else 2            # (v2: lane 3, so that lin_node on lane 1 waits on lane 3 and never on lane 2)
+            if not pre:
                 bond_node_rows(L, hbc, Y1c)
                 self._node_attention(prog, hip.SEG_BOND_NODE, L.NB, Y1c, 5 * 128, xc, lig, out=w.aggB, csrc=w.CsB2, buf=1)
                 if v2:
@@ -697,7 +647,7 @@ class Engine:
             self._gemm(prog, w.aggE, 128, L.W_lin2[:, :128], w.lin_tmp, n, 128, bias=L.b_lin, add1=hc)
             self._gemm(prog, w.aggB, 128, L.W_lin2[:, 128:], hn, n, 128, add1=w.lin_tmp)
             self._mark(prog, f'A{li}', w.aggE, w.aggB, lane=1)      # (the next layer's bond-node attention may overwrite aggB from here on)
-            if step_ahead and self.head_early and li == n_layers - 1 and heads is not None:
+            if early:
                 hn_done = self._record(prog, 1)        # h' of the last layer: the node head's only input
             # ---- position updates from h', h_bond' and the OLD geometry (:291-296)
             # knn-pos k/v source halves for every node (cols 256:512); target halves, queries and the bond-pos blocks
@@ -719,14 +669,12 @@ class Engine:
                 y1_done = self._record(prog, 1)
             # the bond position update's query MLP runs beside its edge product / the knn position update, not in front of the
             # attention on lane 0: lane 3 is free after the triplet queries (last layer: lane 2, in front of the node head --
-            # forked from lane 0, which has just seen h' and Y2: a lane-2-waits-lane-1 edge after lane 1 waited on lane 2 crashes
-            # hipGraph capture, PG_GRAPH=1)
+            # forked from lane 0, which has just seen h' and Y2)
             qlane = 2 if last else 3
             # (releasing lanes 2 / 3 in FRONT of lane 0's wait above -- they need nothing of lane 1 -- measured slower: 16 graphs 3.10 vs 3.05 ms)
-            early = step_ahead and last and self.head_early
             if early:
                 # pipelined step: the node head (and behind it the node posterior and the next step's products) needs h' only -- it does not
-                # wait for the triplet kernel (this lane-2-waits-lane-1 edge is what the hipGraph capture of the plain list cannot have)
+                # wait for the triplet kernel
                 self._wait(prog, 2, hn_done)
                 self._lane = 2
                 heads[1](hn)
@@ -780,17 +728,15 @@ class Engine:
             if split and more:
                 bp_done = self._record(prog, 0)
             self._join(prog, (1,))
-            if self.fused_geom:      # x' = x + dx, and from x' the next layer's smearing + direction vectors (last layer: the update alone)
-                self._call(prog, lib.pg_layer_geom, t, xc.data_ptr(), dxe.data_ptr(), w.dxb.data_ptr(), w.nrm_phore_ctx.data_ptr(),
-                           xn.data_ptr(), w.nrm.data_ptr() if (more and not split) else None, w.G.data_ptr() if more else None)
-                if split and more:
-                    self._lane = 1
-                    self._wait(prog, 1, bp_done)
-                    self._call(prog, lib.pg_layer_geom, t, xc1.data_ptr(), dxe.data_ptr(), w.dxb.data_ptr(), w.nrm_phore_ctx.data_ptr(),
-                               w.x_node[nxt].data_ptr(), w.nrm.data_ptr(), None)
-                    self._lane = 0
-            else:
-                self._call(prog, lib.pg_apply_dx, t, xc.data_ptr(), dxe.data_ptr(), w.dxb.data_ptr(), xn.data_ptr())
+            # x' = x + dx, and from x' the next layer's smearing + direction vectors (last layer: the update alone)
+            self._call(prog, lib.pg_layer_geom, t, xc.data_ptr(), dxe.data_ptr(), w.dxb.data_ptr(), w.nrm_phore_ctx.data_ptr(),
+                       xn.data_ptr(), w.nrm.data_ptr() if (more and not split) else None, w.G.data_ptr() if more else None)
+            if split and more:
+                self._lane = 1
+                self._wait(prog, 1, bp_done)
+                self._call(prog, lib.pg_layer_geom, t, xc1.data_ptr(), dxe.data_ptr(), w.dxb.data_ptr(), w.nrm_phore_ctx.data_ptr(),
+                           w.x_node[nxt].data_ptr(), w.nrm.data_ptr(), None)
+                self._lane = 0
             self._mark(prog, f'L{li}', hn, hbn, xn, dxe, w.dxb, hbc)
             cur = nxt
         if heads is not None and step_ahead:
@@ -822,7 +768,7 @@ class Engine:
         sp = [st.cuda_stream for st in streams]
         if self.trace is not None:
             return self._run_traced(prog, streams, sp)
-        if compiled and self.c_program and self.timers is None and self.debug is None and not torch.cuda.is_current_stream_capturing():
+        if compiled and self.c_program and self.timers is None and self.debug is None:
             ent = self._compiled.get(id(prog))
             if ent is None or ent[0] is not prog:
                 ent = self._compiled[id(prog)] = (prog, self._compile(prog))
@@ -863,18 +809,6 @@ class Engine:
         w.in_h_edge.copy_(h_edge_pert)
         w.in_t.copy_(time_step)
         return self.forward_inplace()
-
-    def _graph_wanted(self):
-        return self.graph_mode == '1' and self.timers is None and self.debug is None
-
-    def _capture(self):
-        """Capture the (static) forward launch list, side-stream forks / joins included, into one hipGraph."""
-        self._run(self.prog_fwd)              # eager once: lazy kernel attributes, side streams
-        torch.cuda.synchronize()
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            self._run(self.prog_fwd)
-        self._graph = g
 
     TUNE_REPS = 6          # timing marks per candidate grid (five timed steps between them, behind one settling step)
 
@@ -964,12 +898,7 @@ class Engine:
 
     def forward_inplace(self):
         w = self.ws
-        if self._graph_wanted():
-            if self._graph is None:
-                self._capture()
-            self._graph.replay()
-        else:
-            self._run(self.prog_fwd)
+        self._run(self.prog_fwd)
         x0 = torch.index_select(w.x[self.final_idx], 0, self.plan.lig2ctx_long)
         return w.out_v, x0, w.out_bond
 

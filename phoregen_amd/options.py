@@ -3,17 +3,14 @@
 The values in `DEFAULTS` are the product.  They change in two ways only: `options.override(...)` (a context manager; the tests and
 the measurement tools use it), or -- with `PHOREGEN_DEBUG=1` in the environment, for profiling a stock `bench.py` run from a shell
 script -- through the `PG_*` variables listed in `_ENV`.  Without `PHOREGEN_DEBUG=1` the ambient environment cannot change which
-kernels a model runs.  None of the variants routes around the HIP library.
+kernels a model runs.  None of the variants routes around the HIP library.  A variant stays here only while a test or a tool compares
+the product against it (the one-stream list, the Python walk of the launch list, the size-dependent schedule placements, the training forms).
 """
 import contextlib
 import os
 
 DEFAULTS = dict(
     streams=True,         # four lanes (HIP streams) per layer; False: one stream
-    tri_staged=True,      # csrc/triplet2.hip (False: the gather kernel, triplet.hip)
-    node_fused=True,      # node attention folds the query / unfolds the value in-kernel
-    knn_group=True,       # neighbour slots partitioned by source kind
-    knn_merge='auto',     # ligand + pharmacophore targets of a knn sub-layer in one launch ('auto' = 'always' since round 4), 'never' = two launches
     layer_ahead=True,     # small batches: the next layer's x-independent products inside this layer's position phase
     ahead_v2='auto',      # next layer's Y1 on the node chain's lane behind Y2, P waits for it alone, layer 0's bond-node attention on lane 3:
                           # 'auto' = small batches (8 / 16 / 32 graphs - 3 % / - 3.5 % / - 1 %; 64 / 128 graphs + 0.4 % / + 1.7 %), 'never', 'always'
@@ -23,9 +20,7 @@ DEFAULTS = dict(
     step_ahead=True,      # the sampler loop as a software pipeline over reverse steps: the categorical posteriors behind their heads on the side
                           # lanes, the NEXT step's feature embedding and layer 0's coordinate-free products (first-layer blocks, queries, bond-node
                           # sub-layer) behind them, beside the last layer's position phase / the Gaussian posterior (`Engine.pipelined_programs`)
-    sa_head_early=True,   # ... the node head of a pipelined step right behind the last lin_node (it needs h' only), not behind the triplet kernel
     c_program=True,       # a forward = ONE call into the library (pg_program_run walks the launch list); False: the list is walked from Python
-    order_points=True,    # cross-lane order points as device-scope HIP events (pg_order_point_*); False: torch.cuda.Event()
     geom_split='auto',    # ahead_v2: the layer's closing launch (pg_layer_geom) once per chain, on the chain's own lane: 'auto' = batches
                           # whose node chain is the longer one (4 / 8 graphs 2.29 -> 2.22 / 2.38 -> 2.30 ms; 12 graphs equal; 16 / 32 graphs + 1 %)
     geom_split_below=16000,   # ... 'auto': fewer bond edges than this
@@ -37,9 +32,6 @@ DEFAULTS = dict(
     tri_overlap=3,        # the side lane the larger ligands' launch runs on, BESIDE the other one (disjoint ligands; both queues drain into the
                           # same workgroup slots, one tail instead of two); 0 = behind it on lane 0; < 0: that lane, launched second
     tri_grid=-1,          # persistent workgroups of the staged triplet kernel (-1: by batch size)
-    graph=False,          # hipGraph replay of the forward launch list
-    fused_geom='auto',    # coordinate update + bond smearing + direction vectors as one launch on the bond chain's lane (pg_layer_geom):
-                          # 'auto' = 'always' (round 4: it pays at every batch size), 'never' = three launches on three lanes
     dgrad_mm=True,        # training: input gradients through the library GEMM
     rows_sum=True,        # training: pg_bond_rows_sum instead of atomic index_add_
     tri_onepass=True,     # training: one-pass triplet / node adjoints fed by the forward's softmax weights
@@ -59,10 +51,9 @@ DEFAULTS = dict(
 _tri = lambda v: {'0': 'never', '1': 'auto', '2': 'always'}[v]
 _flag = lambda v: v != '0'
 _ENV = {
-    'PG_STREAMS': ('streams', _flag), 'PG_TRI_STAGED': ('tri_staged', _flag),
-    'PG_NODE_FUSED': ('node_fused', _flag), 'PG_KNN_GROUP': ('knn_group', _flag), 'PG_KNN_MERGE': ('knn_merge', _tri),
-    'PG_LAYER_AHEAD': ('layer_ahead', _flag), 'PG_AHEAD_V2': ('ahead_v2', _tri), 'PG_AHEAD_V2_BELOW': ('ahead_v2_below', int), 'PG_TRI_GRID': ('tri_grid', int), 'PG_POS_TILED': ('pos_tiled', _tri), 'PG_POS_TILED_BELOW': ('pos_tiled_below', int), 'PG_GRAPH': ('graph', _flag), 'PG_ORDER_POINTS': ('order_points', _flag), 'PG_C_PROGRAM': ('c_program', _flag), 'PG_STEP_AHEAD': ('step_ahead', _flag), 'PG_CHAIN_Q_FROM': ('chain_q_from', int), 'PG_TRI_SPLIT': ('tri_split', _flag), 'PG_TUNE_GRID': ('tune_grid', _flag), 'PG_GEOM_SPLIT': ('geom_split', _tri),
-    'PG_FUSED_GEOM': ('fused_geom', _tri), 'PG_DGRAD_MM': ('dgrad_mm', _flag),
+    'PG_STREAMS': ('streams', _flag),
+    'PG_LAYER_AHEAD': ('layer_ahead', _flag), 'PG_AHEAD_V2': ('ahead_v2', _tri), 'PG_AHEAD_V2_BELOW': ('ahead_v2_below', int), 'PG_TRI_GRID': ('tri_grid', int), 'PG_POS_TILED': ('pos_tiled', _tri), 'PG_POS_TILED_BELOW': ('pos_tiled_below', int), 'PG_C_PROGRAM': ('c_program', _flag), 'PG_STEP_AHEAD': ('step_ahead', _flag), 'PG_CHAIN_Q_FROM': ('chain_q_from', int), 'PG_TRI_SPLIT': ('tri_split', _flag), 'PG_TUNE_GRID': ('tune_grid', _flag), 'PG_GEOM_SPLIT': ('geom_split', _tri),
+    'PG_DGRAD_MM': ('dgrad_mm', _flag),
     'PG_ROWS_SUM': ('rows_sum', _flag), 'PG_TRI_ONEPASS': ('tri_onepass', _flag), 'PG_WIDE_GEMM': ('wide_gemm', _flag), 'PG_BWD_GRID': ('bwd_grid', int), 'PG_BWD_SPLIT': ('bwd_split', lambda v: {'0': 'none', '1': 'knn', '2': 'all'}[v]), 'PG_BWD_ATOM_SORT': ('bwd_atom_sort', _flag),
     'PG_TRI_BWD_FORM': ('tri_bwd_form', int), 'PG_TRI_BWD_GRID': ('tri_bwd_grid', int), 'PG_PH_ONEPASS': ('ph_onepass', _flag),
 }

@@ -975,9 +975,9 @@ def test_layer_geom_equals_the_three_launches_it_replaces():
                              G.data_ptr(), s) != 0
 
 
-def test_engine_variants_agree(model):
+def test_remaining_engine_variants_agree(model):
     """The measurement switches of the engine must not change results beyond fp32 summation order: one stream vs four lanes
-    (bit-identical: same kernels, same order per kernel), node attention with separate fold / unfold launches, the gather triplet
+    (bit-identical: same kernels, same order per kernel), the schedule's size-dependent placements, the one-pass generic segment
     kernel, the tiled GEMM kernel instead of the streaming one."""
     import os
     from phoregen_amd import hip
@@ -998,15 +998,10 @@ def test_engine_variants_agree(model):
     base = run()
     serial = run(streams=False)
     assert all(torch.equal(a, b) for a, b in zip(base, serial))
-    replay = run(graph=True)                   # hipGraph capture of the four-lane launch list
-    assert all(torch.equal(a, b) for a, b in zip(base, replay))
     with torch.no_grad():                             # the four-lane launch list is race-free: repeated runs give the same bits
         for _ in range(6):
             again = [o.cpu() for o in model(**dev_inp)[:3]]
             assert all(torch.equal(a, b) for a, b in zip(base, again))
-    # the coordinate-only kernels as three launches on three lanes (pg_apply_dx, pg_bond_smear, pg_lig_normals) instead of pg_layer_geom
-    assert all(torch.equal(a, b) for a, b in zip(base, run(fused_geom='never')))
-    assert all(torch.equal(a, b) for a, b in zip(base, run(fused_geom='never', streams=False)))
     # position-update attention with a node's row tiles over several waves (small batches) or one wave per node: same bits
     assert all(torch.equal(a, b) for a, b in zip(base, run(pos_tiled='never')))
     assert all(torch.equal(a, b) for a, b in zip(base, run(pos_tiled='always')))
@@ -1017,24 +1012,17 @@ def test_engine_variants_agree(model):
     assert all(torch.equal(a, b) for a, b in zip(base, run(ahead_v2='always', geom_split='never')))
     # the triplet kernel as ONE launch instantiated for the batch's largest ligand instead of two launches by row tiles (same segments, same arithmetic)
     assert all(torch.equal(a, b) for a, b in zip(base, run(tri_split=False)))
-    # cross-lane order points as torch events (with the host-visibility fence) instead of the library's fence-free ones
-    assert all(torch.equal(a, b) for a, b in zip(base, run(order_points=False)))
     layer_by_layer = run(layer_ahead=False)     # without the next layer's products launched one layer ahead (12 graphs: it is on): same kernels, same bits
     assert all(torch.equal(a, b) for a, b in zip(base, layer_by_layer))
     for grid in (0, 96, 200):                   # persistent triplet workgroups (small batches leave CUs to the side lanes):
         assert all(torch.equal(a, b) for a, b in zip(base, run(tri_grid=grid)))     # the queue hands out the same segments
-    two_launches = run(knn_merge='never')         # ligand / pharmacophore targets of a knn sub-layer as two launches ...
-    one_launch = run(knn_merge='always')           # ... or as one launch with the workgroups split between the lists (the default only
-    assert all(torch.equal(a, b) for a, b in zip(base, two_launches))     # from ~60 graphs up): same bits per node either way
-    assert all(torch.equal(a, b) for a, b in zip(base, one_launch))
-    old_dbg = hip.lib().pg_debug_force_generic_seg(1)  # the one-pass fallback takes a two-list call list after list
+    old_dbg = hip.lib().pg_debug_force_generic_seg(1)  # the one-pass fallback takes the merged two-list knn call list after list
     try:
-        generic_two_lists = run(knn_merge='always')
+        generic_two_lists = run()
     finally:
         hip.lib().pg_debug_force_generic_seg(old_dbg)
     assert max(rel_err(a, b) for a, b in zip(generic_two_lists, base)) <= 2e-5
-    for variant in (run(node_fused=False), run(tri_staged=False), run(gemm_mode=0)):
-        assert max(rel_err(a, b) for a, b in zip(variant, base)) <= 2e-5
+    assert max(rel_err(a, b) for a, b in zip(run(gemm_mode=0), base)) <= 2e-5
 
 
 def test_full_size_e3_equivariance(model):

@@ -586,9 +586,9 @@ def test_triplet_queues_by_row_tiles_cover_the_single_queue():
     assert plan_of([20, 33, 50]).tri_split is None and plan_of([51, 60]).tri_split is None
 
 
-def test_option_switches_are_consistent(monkeypatch):
+def test_option_switches_are_consistent_and_refuse_unknown_names(monkeypatch):
     """phoregen_amd.options: every PG_* variable names a real option and converts; the environment counts only under PHOREGEN_DEBUG=1;
-    override() nests and restores."""
+    override() nests and restores, and refuses a name that is not a switch (a removed one included)."""
     from phoregen_amd import options
     for var, (key, conv) in options._ENV.items():
         assert key in options.DEFAULTS, (var, key)
@@ -597,13 +597,16 @@ def test_option_switches_are_consistent(monkeypatch):
     assert options.get('tri_grid') == options.DEFAULTS['tri_grid']          # ambient environment: ignored
     monkeypatch.setenv('PHOREGEN_DEBUG', '1')
     assert options.get('tri_grid') == 96
-    with options.override(tri_grid=128, knn_merge='never'):
-        assert options.get('tri_grid') == 128 and options.get('knn_merge') == 'never'
+    with options.override(tri_grid=128, pos_tiled='never'):
+        assert options.get('tri_grid') == 128 and options.get('pos_tiled') == 'never'
         with options.override(tri_grid=64):
-            assert options.get('tri_grid') == 64 and options.get('knn_merge') == 'never'
+            assert options.get('tri_grid') == 64 and options.get('pos_tiled') == 'never'
         assert options.get('tri_grid') == 128
-    assert options.get('tri_grid') == 96 and options.get('knn_merge') == options.DEFAULTS['knn_merge']
+    assert options.get('tri_grid') == 96 and options.get('pos_tiled') == options.DEFAULTS['pos_tiled']
     assert set(options.snapshot()) == set(options.DEFAULTS)
+    with pytest.raises(KeyError):
+        with options.override(tri_staged=False):
+            pass
 
 
 

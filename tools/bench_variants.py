@@ -1,5 +1,5 @@
 """ms per sampler step for several batch sizes and engine variants in ONE process (same box, alternating runs).
-usage: bench_variants.py 16,32,128 "base" "fused_geom=False" "tri_grid=224,knn_merge='always'" ...   (options.override keywords)"""
+usage: bench_variants.py 16,32,128 "base" "ahead_v2='never'" "tri_grid=224,pos_tiled='always'" ...   (options.override keywords)"""
 import sys, time, torch
 import os
 _ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, _ROOT)

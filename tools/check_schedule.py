@@ -139,14 +139,8 @@ def access_of(name, args, buf):
         rd(a[1]), rd(a[2]), rd(a[3]), wr(a[11])
     elif name == 'pg_knn_group_by_kind':
         rd(a[2]), wr(a[2]), rd(a[3]), rd(a[4]), wr(a[4])
-    elif name == 'pg_lig_normals':
-        rd(a[1]), rd(a[2]), wr(a[4])
-    elif name == 'pg_bond_smear':
-        rd(a[1]), wr(a[2])
     elif name == 'pg_layer_geom':
         rd(a[1]), rd(a[2]), rd(a[3]), rd(a[4]), wr(a[5]), wr(a[6]), wr(a[7])
-    elif name == 'pg_apply_dx':
-        rd(a[1]), rd(a[2]), rd(a[3]), wr(a[4])
     elif name == 'pg_attn_fold_query':
         rd(a[0]), wr(a[5])
     elif name == 'pg_attn_unfold_value':

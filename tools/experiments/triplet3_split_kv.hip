@@ -18,7 +18,7 @@
 // Price: alpha makes a round trip through memory (256 B per (tile, register) and segment, written and read coalesced, non-temporal)
 // and the V pass recomputes the 11 angular features of a row.
 //
-// Lane l = (g = l>>4, m = l&15); 16x16x4 maps as in seg_attn.hip.  Per-segment arithmetic is that of triplet2.hip / triplet.hip.
+// Lane l = (g = l>>4, m = l&15); 16x16x4 maps as in seg_attn.hip.  Per-segment arithmetic is that of triplet2.hip.
 #include "common.h"
 #include "../../include/phoregen_hip.h"
 
@@ -47,7 +47,7 @@ __device__ __forceinline__ float t3_from_lane(float v, int src_lane) {
   return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(src_lane << 2, __builtin_bit_cast(int, v)));
 }
 
-// sin and cos of one argument (0 <= arg <= ~4) from ONE range reduction (same constants / polynomials as triplet.hip)
+// sin and cos of one argument (0 <= arg <= ~4) from ONE range reduction (same constants / polynomials as triplet2.hip)
 __device__ __forceinline__ void t3_sincos_pair(float arg, float& sn, float& cs) {
   const float kf = rintf(arg * 0.63661977236758134308f);
   float r = fmaf(-kf, 1.57079637050628662109375f, arg);
