@@ -323,6 +323,40 @@ int pg_posterior_position_ctx(const float* x_t, const float* x0_ctx, const int* 
                               int n_rows, const int* graph_row0, const int* graph_key, const float* center, float* x_prev,
                               float* traj_out, float* x_ctx_next, float* x0_out, void* stream);
 
+/* Fragment-conditioned sampling (beyond the reference): the three posterior entry points above with the fixed rows of a fragment
+ * replaced in the same launch.  frag_cls [n_rows]: the fixed class of a row, -1 = free (free rows: exactly the plain entry point's
+ * results).  A fixed row is redrawn at level lvl = time_step - 1 from the forward process: types by Gumbel-argmax over
+ * log q_mats[lvl][v0,:] (floored at -32; log_vt_out = that log-distribution), coordinates sqrt_ab[lvl] * x0f + sqrt_1mab[lvl] * eps;
+ * at time_step 0 the fragment itself (class v0, log-state 0 / -32; coordinates x0f).  Noise: the same Philox and the same counters
+ * as the posterior, with stream id frag_stream_id and counter step lvl (the replacement uses Philox even when `uniform` / `eps`
+ * are given).  x0f [n_rows,3]: fragment coordinates minus the graph's centre; sqrt_ab / sqrt_1mab [T]. */
+int pg_posterior_categorical_frag(const float* logits, const float* log_vt_in, const int* row_graph,
+                                  const int64_t* time_step, const float* q_mats, const float* q_onestep_T,
+                                  int n_rows, int K, const float* uniform, uint64_t seed, uint32_t stream_id,
+                                  uint32_t step, const int* graph_row0, const int* graph_key, float* log_vt_out,
+                                  float* onehot_out, float* traj_out, const int* frag_cls, uint32_t frag_stream_id, void* stream);
+int pg_posterior_position_frag(const float* x_t, const float* x0, const int* row_graph, const int64_t* time_step,
+                               const float* coef_x0, const float* coef_xt, const float* std_, const float* energy_grad,
+                               const float* eps, uint64_t seed, uint32_t stream_id, uint32_t step, int n_rows,
+                               const int* graph_row0, const int* graph_key, const float* center, float* x_prev, float* traj_out,
+                               const int* frag_cls, const float* x0f, const float* sqrt_ab, const float* sqrt_1mab,
+                               uint32_t frag_stream_id, void* stream);
+int pg_posterior_position_ctx_frag(const float* x_t, const float* x0_ctx, const int* lig2ctx, const int* row_graph,
+                                   const int64_t* time_step, const float* coef_x0, const float* coef_xt, const float* std_,
+                                   const float* energy_grad, const float* eps, uint64_t seed, uint32_t stream_id, uint32_t step,
+                                   int n_rows, const int* graph_row0, const int* graph_key, const float* center, float* x_prev,
+                                   float* traj_out, float* x_ctx_next, float* x0_out, const int* frag_cls, const float* x0f,
+                                   const float* sqrt_ab, const float* sqrt_1mab, uint32_t frag_stream_id, void* stream);
+/* The replacement alone at one level (-1 = the fragment itself) for every fixed node row (one-hot type, log-state, coordinates) and
+ * fixed bond row (one-hot type, log-state), with the counters of the posteriors above (graph_row0 = g_lig_off / g_bond_off, may be
+ * NULL: flat counters).  Free rows and NULL outputs are not written.  The sampler's initial state (level T - 1). */
+int pg_fragment_noise(int level, uint64_t seed, int n_lig, int n_bond, const int* node_cls, const int* edge_cls,
+                      const float* x0f, const int* lig_graph, const int* bond_graph, const int* g_lig_off,
+                      const int* g_bond_off, const int* graph_key, const float* q_node, const float* q_edge,
+                      const float* sqrt_ab, const float* sqrt_1mab, uint32_t node_stream_id, uint32_t edge_stream_id,
+                      uint32_t pos_stream_id, float* h_node, float* log_node, float* h_edge, float* log_edge,
+                      float* x_out, void* stream);
+
 /* closed-form guidance gradient (models/diffusion.py:476-502, utils/sample_utils.py:135-165).  phore_center [B,3]: per
  * graph the mean position of its non-EX pharmacophore nodes.  Both energies are means over the graphs of the batch;
  * mean_over_graphs = that divisor (<= 0: this batch's n_graphs; a shard of a larger logical batch passes the full count). */

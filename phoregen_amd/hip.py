@@ -125,6 +125,18 @@ _PROTOS = {
                                         C.c_uint32, C.c_uint32, C.c_int, c_ip, c_ip, c_fp, c_fp, c_fp, C.c_void_p]),
     'pg_posterior_position_ctx': (C.c_int, [c_fp, c_fp, c_ip, c_ip, c_ip, c_fp, c_fp, c_fp, c_fp, c_fp, C.c_uint64,
                                             C.c_uint32, C.c_uint32, C.c_int, c_ip, c_ip, c_fp, c_fp, c_fp, c_fp, c_fp, C.c_void_p]),
+    'pg_posterior_categorical_frag': (C.c_int, [c_fp, c_fp, c_ip, c_ip, c_fp, c_fp, C.c_int, C.c_int, c_fp, C.c_uint64,
+                                                C.c_uint32, C.c_uint32, c_ip, c_ip, c_fp, c_fp, c_fp, c_ip, C.c_uint32,
+                                                C.c_void_p]),
+    'pg_posterior_position_frag': (C.c_int, [c_fp, c_fp, c_ip, c_ip, c_fp, c_fp, c_fp, c_fp, c_fp, C.c_uint64, C.c_uint32,
+                                             C.c_uint32, C.c_int, c_ip, c_ip, c_fp, c_fp, c_fp, c_ip, c_fp, c_fp, c_fp,
+                                             C.c_uint32, C.c_void_p]),
+    'pg_posterior_position_ctx_frag': (C.c_int, [c_fp, c_fp, c_ip, c_ip, c_ip, c_fp, c_fp, c_fp, c_fp, c_fp, C.c_uint64,
+                                                 C.c_uint32, C.c_uint32, C.c_int, c_ip, c_ip, c_fp, c_fp, c_fp, c_fp, c_fp, c_ip,
+                                                 c_fp, c_fp, c_fp, C.c_uint32, C.c_void_p]),
+    'pg_fragment_noise': (C.c_int, [C.c_int, C.c_uint64, C.c_int, C.c_int, c_ip, c_ip, c_fp, c_ip, c_ip, c_ip, c_ip, c_ip,
+                                    c_fp, c_fp, c_fp, c_fp, C.c_uint32, C.c_uint32, C.c_uint32, c_fp, c_fp, c_fp, c_fp, c_fp,
+                                    C.c_void_p]),
     'pg_gemm_wgrad': (C.c_int, [c_fp, C.c_int, c_fp, C.c_int, C.c_int, C.c_int, C.c_int, c_fp, C.c_int, c_fp, C.c_void_p]),
     'pg_ln_relu': (C.c_int, [c_fp, C.c_int, c_fp, c_fp, C.c_int, c_fp, C.c_int, C.c_void_p]),
     'pg_ln_relu_bwd': (C.c_int, [c_fp, C.c_int, c_fp, c_fp, c_fp, C.c_int, C.c_int, c_fp, C.c_int, c_fp, c_fp,

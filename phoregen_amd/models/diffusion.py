@@ -20,6 +20,7 @@ from .common import GaussianSmearing, ShiftedSoftplus, TimeGaussianSmearing, get
 from .transition import ContigousTransition, GeneralCategoricalTransition
 from .. import hip
 from ..engine import Engine
+from ..fragment import STREAM_EDGE, STREAM_NODE, STREAM_POS, as_fragment, fragment_atom_counts, fragment_layout
 from ..packing import ModelPack
 from ..plan import BatchPlan, make_edge_data
 from ..utils.sample_utils import sample_from_interval
@@ -64,6 +65,19 @@ class _LazyFloats(dict):
 
     def __repr__(self):
         return repr(dict(self.items()))
+
+
+def _posterior_cat(lib, frag_cls, frag_stream, args, stream, what):
+    """pg_posterior_categorical, or its fragment form when the batch carries a fragment (frag_cls [rows] int32, -1 = free)."""
+    if frag_cls is None:
+        hip.check(lib.pg_posterior_categorical(*args, stream), what)
+    else:
+        hip.check(lib.pg_posterior_categorical_frag(*args, frag_cls.data_ptr(), frag_stream, stream), what)
+
+
+def _frag_pos_args(frag, pk):
+    """the trailing arguments of pg_posterior_position(_ctx)_frag"""
+    return (frag.node_cls.data_ptr(), frag.x0f.data_ptr(), pk.frag_tab[0].data_ptr(), pk.frag_tab[1].data_ptr(), STREAM_POS)
 
 
 class PhoreDiff(nn.Module):
@@ -322,7 +336,7 @@ class PhoreDiff(nn.Module):
     # ------------------------------------------------------------------ sampler (diffusion.py:390-525)
     @torch.no_grad()
     def sample(self, data, n_graphs, device, pos_guidance_opt=None, sample_mode='uniform', normal_scale=4.0,
-               rng='device', seed=None, num_atoms=None, return_traj=True, **kwargs):
+               rng='device', seed=None, num_atoms=None, return_traj=True, fragment=None, **kwargs):
         """Reference contract: returns {'pred': [logits_node, x0 + center, logits_edge],
         'traj': [node, pos, edge], 'lig_info': [num_atoms, batch, edge_index, edge_batch]}.
 
@@ -331,8 +345,16 @@ class PhoreDiff(nn.Module):
                       per call (so consecutive calls differ and `seed_all(seed)` still controls the whole run).
         rng='cpu'   : noise is drawn from torch's default CPU generator in the reference's order, shape and dtype
                        and uploaded -> same seeds give the reference CPU path's draws.
-        num_atoms   : optional LongTensor [n_graphs] overriding the atom-count draw (tests / benchmarks)."""
+        num_atoms   : optional LongTensor [n_graphs] overriding the atom-count draw (tests / benchmarks).
+        fragment    : optional fragment (phoregen_amd.fragment.Fragment or its dict) kept in every graph as its first n_f atoms and
+                      generated around (beyond the reference; DESIGN.md "Fragment-conditioned sampling").  Drawn atom counts are
+                      raised to n_f + 1; an explicit `num_atoms` below n_f is a ValueError.  Device RNG only."""
         ph = data['phore']
+        fragment = as_fragment(fragment)
+        if fragment is not None and rng != 'device':
+            raise NotImplementedError("phoregen_amd: fragment-conditioned sampling runs with rng='device' only (rng='cpu' replays the "
+                                      'reference, which has no fragment mode)')
+        explicit_counts = num_atoms is not None
         if seed is None:
             # a fresh key per call, drawn from torch's default generator: repeated sample() calls (sample_all.py's while loop)
             # get different noise like the reference's global-RNG draws do, and `seed_all(seed)` still makes a run reproducible.
@@ -340,18 +362,20 @@ class PhoreDiff(nn.Module):
             seed = int(torch.randint(0, 2 ** 62, (1,)).item()) if rng == 'device' else 0
         if num_atoms is None:
             num_atoms = self.sample_nodes(data, n_graphs, device, sample_mode, normal_scale)
+        num_atoms = fragment_atom_counts(num_atoms, fragment, explicit_counts)
         p = ph.x.size(0)
         batch_phore = torch.repeat_interleave(torch.arange(n_graphs), p)
         center = data.center.to(self._device()).float()
         return self.sample_batch(ph.x.repeat(n_graphs, 1), ph.pos.repeat(n_graphs, 1), ph.norm.repeat(n_graphs, 1),
                                  batch_phore, num_atoms, center.unsqueeze(0).expand(n_graphs, 3),
                                  pos_guidance_opt=pos_guidance_opt, rng=rng, seed=seed, return_traj=return_traj,
-                                 guidance_center=ph.pos[ph.x[:, self.ex_col] != 1].mean(0), **kwargs)
+                                 guidance_center=ph.pos[ph.x[:, self.ex_col] != 1].mean(0),
+                                 fragments=None if fragment is None else [fragment] * n_graphs, **kwargs)
 
     @torch.no_grad()
     def sample_batch(self, h_phore, pos_phore, phore_norm, batch_phore, num_atoms, centers, pos_guidance_opt=None,
                      rng='device', seed=0, return_traj=True, guidance_center=None, num_steps=None, on_step=None,
-                     graph_ids=None, guidance_batch=None, pipeline=True):
+                     graph_ids=None, guidance_batch=None, pipeline=True, fragments=None):
         """Sampler over a batch of (possibly different) pharmacophores: the multi-pharmacophore entry point
         the reference lacks.  `centers` [B,3] are added back to coordinates as the reference does.
         pipeline (device RNG, no `on_step`): the loop runs as a software pipeline over the reverse steps (`_reverse_step_pipelined`:
@@ -361,10 +385,14 @@ class PhoreDiff(nn.Module):
         guidance_center [3] or [B,3]: target of the `center_prox` energy (default: per graph, the mean of its non-EX
             pharmacophore nodes, diffusion.py:489-491).
         guidance_batch: the number of graphs the guidance energies average over (default B, the reference's behaviour; a
-            shard of a larger logical batch passes the full batch size so that it reproduces the unsharded run)."""
+            shard of a larger logical batch passes the full batch size so that it reproduces the unsharded run).
+        fragments [B] (device RNG): per graph a fragment (phoregen_amd.fragment.Fragment or its dict) or None; a fragment occupies
+            the first n_f atoms of its graph, whose fixed rows are replaced after every step (DESIGN.md "Fragment-conditioned
+            sampling").  The result then has a 'fragment' key: {'node_fixed': bool [N], 'edge_fixed': bool [E]}."""
         st = self.begin_sampling(h_phore, pos_phore, phore_norm, batch_phore, num_atoms, centers, rng=rng, seed=seed,
                                  return_traj=return_traj, num_steps=num_steps, guidance_center=guidance_center,
-                                 graph_ids=graph_ids, guidance_batch=guidance_batch, pipeline=pipeline and on_step is None)
+                                 graph_ids=graph_ids, guidance_batch=guidance_batch, pipeline=pipeline and on_step is None,
+                                 fragments=fragments)
         T = self.num_timesteps
         for i, step in enumerate(range(T)[::-1][:st.n_steps]):
             self.reverse_step(st, i, step, pos_guidance_opt)
@@ -376,9 +404,14 @@ class PhoreDiff(nn.Module):
     @torch.no_grad()
     @_on_model_device
     def begin_sampling(self, h_phore, pos_phore, phore_norm, batch_phore, num_atoms, centers, rng='device', seed=0,
-                       return_traj=True, num_steps=None, guidance_center=None, graph_ids=None, guidance_batch=None, pipeline=False):
+                       return_traj=True, num_steps=None, guidance_center=None, graph_ids=None, guidance_batch=None, pipeline=False,
+                       fragments=None):
         """pipeline=True: `reverse_step` must then be called for consecutive steps with nothing written to the carried state in
-        between (the next step's features are embedded at the end of the step before it); the teacher-forced tests leave it off."""
+        between (the next step's features are embedded at the end of the step before it); the teacher-forced tests leave it off.
+        fragments: see `sample_batch` (device RNG only)."""
+        if fragments is not None and rng != 'device' and any(f is not None for f in fragments):
+            raise NotImplementedError("phoregen_amd: fragment-conditioned sampling runs with rng='device' only (rng='cpu' replays the "
+                                      'reference, which has no fragment mode)')
         dev = self._device()
         lib = hip.lib()
         B = int(num_atoms.numel())
@@ -406,6 +439,11 @@ class PhoreDiff(nn.Module):
         st.center_rows = st.centers[plan.batch_node]                                     # [N,3]
         st.graph_key = (torch.arange(B) if graph_ids is None else graph_ids.detach().cpu()).to(torch.int32).to(dev)
         st.guidance_batch = int(guidance_batch) if guidance_batch else B
+        # fragment-conditioned sampling: per-row tables, uploaded once (None: no graph carries a fragment -> today's kernels)
+        st.frag = None
+        if fragments is not None:
+            lay = fragment_layout(num_atoms, fragments, centers, edge_index)
+            st.frag = lay.to(dev) if lay is not None else None
 
         # ---- init state (diffusion.py:406-408, transition.py:65-69,331-339) ----
         lp_n = torch.log(torch.from_numpy(self.node_transition.init_prob) + self.node_transition.eps).clamp_min(-32.)
@@ -446,6 +484,15 @@ class PhoreDiff(nn.Module):
 
         st.log_node = [torch.log(h_node.clamp(min=1e-30)), torch.empty(N, 12, device=dev)]   # common.py:398-402
         st.log_edge = [torch.log(h_edge.clamp(min=1e-30)), torch.empty(E, 6, device=dev)]
+        if st.frag is not None:
+            # fixed rows: the forward-process draw at level T - 1 (types, carried log-state, coordinates in the model frame)
+            f, ft = st.frag, pk.frag_tab
+            hip.check(lib.pg_fragment_noise(
+                self.num_timesteps - 1, seed, N, E, f.node_cls.data_ptr(), f.edge_cls.data_ptr(), f.x0f.data_ptr(),
+                plan.lig_graph.data_ptr(), plan.bond_graph.data_ptr(), plan.g_lig_off.data_ptr(), plan.g_bond_off.data_ptr(),
+                st.graph_key.data_ptr(), pk.node_tab[0].data_ptr(), pk.edge_tab[0].data_ptr(), ft[0].data_ptr(), ft[1].data_ptr(),
+                STREAM_NODE, STREAM_EDGE, STREAM_POS, h_node.data_ptr(), st.log_node[0].data_ptr(), h_edge.data_ptr(),
+                st.log_edge[0].data_ptr(), pos.data_ptr(), hip.stream_ptr()), 'fragment init')
         st.cur = 0
         w.in_h_node.copy_(h_node), w.in_pos.copy_(pos), w.in_h_edge.copy_(h_edge)
         st.node_traj = st.pos_traj = st.edge_traj = None
@@ -516,16 +563,17 @@ class PhoreDiff(nn.Module):
         elif st.cpu:                                                 # Appendix B item 5: rand, rand, then randn
             un, ue = torch.rand(N, 12).to(dev), torch.rand(E, 6).to(dev)
         cur = st.cur
-        hip.check(lib.pg_posterior_categorical(
+        frag = getattr(st, 'frag', None)
+        _posterior_cat(lib, frag and frag.node_cls, STREAM_NODE, (
             w.out_v.data_ptr(), st.log_node[cur].data_ptr(), plan.lig_graph.data_ptr(), w.in_t.data_ptr(),
             pk.node_tab[0].data_ptr(), pk.node_tab[1].data_ptr(), N, 12, hip.ptr(un), st.seed, 0, step,
             plan.g_lig_off.data_ptr(), st.graph_key.data_ptr(),
-            st.log_node[1 - cur].data_ptr(), w.in_h_node.data_ptr(), tp(st.node_traj), s), 'posterior(node)')
-        hip.check(lib.pg_posterior_categorical(
+            st.log_node[1 - cur].data_ptr(), w.in_h_node.data_ptr(), tp(st.node_traj)), s, 'posterior(node)')
+        _posterior_cat(lib, frag and frag.edge_cls, STREAM_EDGE, (
             w.out_bond.data_ptr(), st.log_edge[cur].data_ptr(), plan.bond_graph.data_ptr(), w.in_t.data_ptr(),
             pk.edge_tab[0].data_ptr(), pk.edge_tab[1].data_ptr(), E, 6, hip.ptr(ue), st.seed, 1, step,
             plan.g_bond_off.data_ptr(), st.graph_key.data_ptr(),
-            st.log_edge[1 - cur].data_ptr(), w.in_h_edge.data_ptr(), tp(st.edge_traj), s), 'posterior(edge)')
+            st.log_edge[1 - cur].data_ptr(), w.in_h_edge.data_ptr(), tp(st.edge_traj)), s, 'posterior(edge)')
         grad = None
         if pos_guidance_opt:                                         # diffusion.py:476-502
             grad = st.grad
@@ -543,12 +591,15 @@ class PhoreDiff(nn.Module):
                 grad += st.gtmp
         if draws is None and st.cpu:
             eps = torch.randn(N, 3).to(dev)
-        hip.check(lib.pg_posterior_position(
-            w.in_pos.data_ptr(), st.x0.data_ptr(), plan.lig_graph.data_ptr(), w.in_t.data_ptr(),
-            pk.pos_tab[0].data_ptr(), pk.pos_tab[1].data_ptr(), pk.pos_tab[2].data_ptr(), hip.ptr(grad), hip.ptr(eps),
-            st.seed, 2, step, N, plan.g_lig_off.data_ptr(), st.graph_key.data_ptr(),
-            st.centers.data_ptr() if st.return_traj else None,
-            w.in_pos.data_ptr(), tp(st.pos_traj), s), 'posterior(pos)')          # in place: x_t -> x_{t-1}
+        args = (w.in_pos.data_ptr(), st.x0.data_ptr(), plan.lig_graph.data_ptr(), w.in_t.data_ptr(),
+                pk.pos_tab[0].data_ptr(), pk.pos_tab[1].data_ptr(), pk.pos_tab[2].data_ptr(), hip.ptr(grad), hip.ptr(eps),
+                st.seed, 2, step, N, plan.g_lig_off.data_ptr(), st.graph_key.data_ptr(),
+                st.centers.data_ptr() if st.return_traj else None,
+                w.in_pos.data_ptr(), tp(st.pos_traj))                                # in place: x_t -> x_{t-1}
+        if frag is None:
+            hip.check(lib.pg_posterior_position(*args, s), 'posterior(pos)')
+        else:
+            hip.check(lib.pg_posterior_position_frag(*args, *_frag_pos_args(frag, pk), s), 'posterior(pos)')
         st.cur = 1 - cur
 
     def _reverse_step_pipelined(self, st, i, step, pos_guidance_opt=None):
@@ -578,16 +629,17 @@ class PhoreDiff(nn.Module):
         tb = st.t_table.data_ptr() + step * st.t_table.stride(0) * 8        # the [B] row `step` of the table: no fill launch
         _, x0_ctx, _ = eng.step_forward()
         cur = st.cur
-        hip.check(lib.pg_posterior_categorical(
+        frag = getattr(st, 'frag', None)
+        _posterior_cat(lib, frag and frag.node_cls, STREAM_NODE, (
             w.out_v.data_ptr(), st.log_node[cur].data_ptr(), plan.lig_graph.data_ptr(), tb,
             pk.node_tab[0].data_ptr(), pk.node_tab[1].data_ptr(), N, 12, None, st.seed, 0, step,
             plan.g_lig_off.data_ptr(), st.graph_key.data_ptr(),
-            st.log_node[1 - cur].data_ptr(), w.in_h_node.data_ptr(), tp(st.node_traj), s2.cuda_stream), 'posterior(node)')
-        hip.check(lib.pg_posterior_categorical(
+            st.log_node[1 - cur].data_ptr(), w.in_h_node.data_ptr(), tp(st.node_traj)), s2.cuda_stream, 'posterior(node)')
+        _posterior_cat(lib, frag and frag.edge_cls, STREAM_EDGE, (
             w.out_bond.data_ptr(), st.log_edge[cur].data_ptr(), plan.bond_graph.data_ptr(), tb,
             pk.edge_tab[0].data_ptr(), pk.edge_tab[1].data_ptr(), E, 6, None, st.seed, 1, step,
             plan.g_bond_off.data_ptr(), st.graph_key.data_ptr(),
-            st.log_edge[1 - cur].data_ptr(), w.in_h_edge.data_ptr(), tp(st.edge_traj), s3.cuda_stream), 'posterior(edge)')
+            st.log_edge[1 - cur].data_ptr(), w.in_h_edge.data_ptr(), tp(st.edge_traj)), s3.cuda_stream, 'posterior(edge)')
         last = step == 0 or i + 1 >= st.n_steps
         if pos_guidance_opt:
             # the guidance below (lane 0, on the way to the next step's coordinates) reads the bond types just drawn: it waits for THIS point
@@ -615,12 +667,15 @@ class PhoreDiff(nn.Module):
                     int(not atom), hip.ptr(st.gc), st.guidance_batch, st.cnt_ws.data_ptr(), st.mean_ws.data_ptr(),
                     st.gtmp.data_ptr(), s), 'guidance')
                 grad += st.gtmp
-        hip.check(lib.pg_posterior_position_ctx(
-            w.in_pos.data_ptr(), x0_ctx.data_ptr(), plan.lig2ctx.data_ptr(), plan.lig_graph.data_ptr(), tb,
-            pk.pos_tab[0].data_ptr(), pk.pos_tab[1].data_ptr(), pk.pos_tab[2].data_ptr(), hip.ptr(grad), None,
-            st.seed, 2, step, N, plan.g_lig_off.data_ptr(), st.graph_key.data_ptr(),
-            st.centers.data_ptr() if st.return_traj else None,
-            w.in_pos.data_ptr(), tp(st.pos_traj), w.x[0].data_ptr(), st.x0_buf.data_ptr(), s), 'posterior(pos)')
+        args = (w.in_pos.data_ptr(), x0_ctx.data_ptr(), plan.lig2ctx.data_ptr(), plan.lig_graph.data_ptr(), tb,
+                pk.pos_tab[0].data_ptr(), pk.pos_tab[1].data_ptr(), pk.pos_tab[2].data_ptr(), hip.ptr(grad), None,
+                st.seed, 2, step, N, plan.g_lig_off.data_ptr(), st.graph_key.data_ptr(),
+                st.centers.data_ptr() if st.return_traj else None,
+                w.in_pos.data_ptr(), tp(st.pos_traj), w.x[0].data_ptr(), st.x0_buf.data_ptr())
+        if frag is None:
+            hip.check(lib.pg_posterior_position_ctx(*args, s), 'posterior(pos)')
+        else:
+            hip.check(lib.pg_posterior_position_ctx_frag(*args, *_frag_pos_args(frag, pk), s), 'posterior(pos)')
         st.x0 = st.x0_buf
         st.cur = 1 - cur
         st.next_step = step - 1
@@ -632,6 +687,16 @@ class PhoreDiff(nn.Module):
         w, plan = st.eng.ws, st.plan
         if getattr(st, 'pipelined', False):
             st.eng.join_lanes((2, 3))              # (out_v / out_bond / the discrete trajectories are completed on the side lanes)
-        return {'pred': [w.out_v.clone(), st.x0 + st.center_rows, w.out_bond.clone()],
-                'traj': [st.node_traj, st.pos_traj, st.edge_traj],
-                'lig_info': [st.num_atoms.to(self._device()), plan.batch_node, plan.edge_index, plan.batch_edge]}
+        res = {'pred': [w.out_v.clone(), st.x0 + st.center_rows, w.out_bond.clone()],
+               'traj': [st.node_traj, st.pos_traj, st.edge_traj],
+               'lig_info': [st.num_atoms.to(self._device()), plan.batch_node, plan.edge_index, plan.batch_edge]}
+        f = getattr(st, 'frag', None)
+        if f is not None:
+            # fixed rows: the fragment verbatim -- its world coordinates as given, logits 0 at the fixed class and -32 elsewhere
+            nf, ef = f.node_fixed, f.edge_fixed
+            pin = lambda cls, K: F.one_hot(cls.long().clamp(min=0), K).float() * 32. - 32.
+            res['pred'][0] = torch.where(nf.unsqueeze(-1), pin(f.node_cls, 12), res['pred'][0])
+            res['pred'][1] = torch.where(nf.unsqueeze(-1), f.pos, res['pred'][1])
+            res['pred'][2] = torch.where(ef.unsqueeze(-1), pin(f.edge_cls, 6), res['pred'][2])
+            res['fragment'] = {'node_fixed': nf, 'edge_fixed': ef}
+        return res

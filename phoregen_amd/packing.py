@@ -343,3 +343,6 @@ class ModelPack:
         self.pos_tab = tuple(c(f'pos_transition.{n}') for n in ('coef_x0', 'coef_xt', 'std'))
         self.node_tab = (c('node_transition.q_mats'), c('node_transition.transpopse_q_onestep_mats'))
         self.edge_tab = (c('edge_transition.q_mats'), c('edge_transition.transpopse_q_onestep_mats'))
+        # fragment-conditioned sampling: the forward-process scales sqrt(ab[t]), sqrt(1 - ab[t]) of the replacement draw (fp32 [T])
+        ab = sd['pos_transition.alphas_bar'].double()
+        self.frag_tab = (ab.sqrt().float().contiguous(), (1. - ab).sqrt().float().contiguous())

@@ -17,6 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from phoregen_amd.config import default_model_config, load_config  # noqa: E402
 from phoregen_amd.data import parse_phore_file  # noqa: E402
+from phoregen_amd.fragment import load_fragment_json  # noqa: E402
 from phoregen_amd.models.diffusion import PhoreDiff  # noqa: E402
 from phoregen_amd.utils.sample_utils import decode_batch  # noqa: E402
 from phoregen_amd.weights import init_deterministic_  # noqa: E402
@@ -35,6 +36,9 @@ def main():
     ap.add_argument('--normal_scale', type=float, default=4.0)
     ap.add_argument('--seed', type=int, default=2032)
     ap.add_argument('--rng', type=str, default='device', choices=['device', 'cpu'])
+    ap.add_argument('--fragment', type=str, default=None,
+                    help="JSON file {'element' | 'type', 'pos', 'bonds'}: a fragment kept as the first atoms of every molecule "
+                         '(world coordinates of the .phore frame; device RNG only)')
     args = ap.parse_args()
     torch.manual_seed(args.seed)
     cfg = default_model_config()
@@ -52,13 +56,14 @@ def main():
     model = model.eval().to('cuda')
     os.makedirs(args.outdir, exist_ok=True)
     files = json.load(open(args.phore_file_list))
+    fragment = load_fragment_json(args.fragment) if args.fragment else None
     for f in files:
         data = parse_phore_file(f).to('cuda')
         done, t0 = [], time.time()
         while len(done) < args.num_samples:
             n = min(args.batch_size, args.num_samples - len(done))
             res = model.sample(data, n, 'cuda', pos_guidance_opt=args.pos_guidance_opt, sample_mode=args.sample_nodes_mode,
-                               normal_scale=args.normal_scale, rng=args.rng, return_traj=False)
+                               normal_scale=args.normal_scale, rng=args.rng, return_traj=False, fragment=fragment)
             # sample_all.py:104-116 (`.cpu()` of everything, unbatch_data, decode_data) in one pass: argmax on the device,
             # one copy of the compact arrays
             done += decode_batch(res, include_bond=True)
