@@ -434,6 +434,33 @@ int pg_attn_fold_wgrad(const float* X, int ldx, const float* T, int n, const int
 int pg_attn_unfold_bias_grad(const float* gout, int ldg, const float* swn, const float* b2v, int n, const int* ids,
                              float* gswn /*[.,16]*/, float* gb2v /*[128]*/, void* stream);
 
+/* ---- from sampler output to molecules (phoregen_amd/molecule.py; rule of utils/sample_utils.py:96-132, sample_all.py:79-175) ----
+ * Screens F frames of a batch of B graphs, one wave per (frame, graph): atom class = argmax of 12 scores (class 11 = masked atom,
+ * dropped; kept atoms are numbered in order), bond order of the pair a < b = argmax of 6 scores (1..4 bonds, 4 = aromatic; 0 and 5 no
+ * bond; a bond with a dropped end is dropped), per kept atom degree and valence2 = sum of 2 x order (aromatic = 3), connected
+ * components of the kept atoms (label = smallest local atom index of the component), and a status word.  First maximum wins (a NaN
+ * score counts as the largest, as torch.argmax has it).  Only the FIRST half of a graph's bond rows is read: rows [0, n(n-1)/2) of a
+ * graph with n atoms are the pairs a < b in row-major order (phoregen_amd/plan.py make_edge_data); g_bond_off counts both halves.
+ * Scores are logits or one-hots, fp32, rows contiguous: frame f of node_scores starts at node_scores + f * node_fs ELEMENTS (likewise
+ * edge_scores / pos; F = 1 with stride 0 for a single prediction).  node_scores and node_fs 16-byte, edge_scores and edge_fs 8-byte
+ * aligned.  max_valence2 [11]: twice the largest explicit valence per atom class (one more is allowed to an atom with an aromatic bond).
+ * max_n = the largest atom count of the batch: above PG_MOL_MAX_ATOMS the call returns an error before anything is launched.
+ * Every element of every output is written (nothing needs zeroing); integer work only, so results are exact.
+ *   status [F][B], counts [F][B][4] = kept atoms, bonds, components, atoms of the largest component
+ *   cls [F][n_lig] (-1 = dropped), compact [F][n_lig] (-1 = dropped), valence2 [F][n_lig] (saturates at 255), comp [F][n_lig] (-1 = dropped)
+ *   order [F][n_bond / 2] (0..4; the rows of graph g start at g_bond_off[g] / 2) */
+#define PG_MOL_MAX_ATOMS 128
+#define PG_MOL_NO_ATOMS 1            /* failures: nothing kept ...                                             */
+#define PG_MOL_DISCONNECTED 2        /* ... more than one component ...                                        */
+#define PG_MOL_VALENCE 4             /* ... an atom above its largest valence ...                              */
+#define PG_MOL_NONFINITE 8           /* ... a kept atom with a non-finite coordinate                           */
+#define PG_MOL_HAD_MASKED_ATOM 16    /* informational: an atom of class 11 was dropped                         */
+#define PG_MOL_HAD_ABSORBING_BOND 32 /* informational: a first-half bond row of class 5                        */
+int pg_mol_screen(const float* node_scores, int64_t node_fs, const float* edge_scores, int64_t edge_fs, const float* pos,
+                  int64_t pos_fs, const int* g_lig_off /*[B+1]*/, const int* g_bond_off /*[B+1]*/, int B, int F, int n_lig,
+                  int n_bond, int max_n, const uint8_t* max_valence2 /*[11]*/, int* status, int* counts, int8_t* cls,
+                  int16_t* compact, uint8_t* valence2, int16_t* comp, int8_t* order, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

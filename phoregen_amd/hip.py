@@ -79,6 +79,7 @@ SEG_KNN_NODE, SEG_KNN_POS, SEG_BOND_NODE, SEG_BOND_POS, SEG_TRIPLET, SEG_PHORE =
 ACT_NONE, ACT_SSP, ACT_RELU = 0, 1, 2
 
 ABI_VERSION = 11
+PG_MOL_MAX_ATOMS = 128          # include/phoregen_hip.h (the library refuses a larger graph before it launches anything)
 _lib = None
 
 _PROTOS = {
@@ -146,6 +147,8 @@ _PROTOS = {
     'pg_attn_fold_wgrad': (C.c_int, [c_fp, C.c_int, c_fp, C.c_int, c_ip, c_fp, C.c_void_p]),
     'pg_guidance_grad': (C.c_int, [C.POINTER(PgTopo), c_fp, c_fp, c_ip, c_ip, C.c_int, C.c_float, C.c_float,
                                    C.c_int, c_fp, C.c_int, c_fp, c_fp, c_fp, C.c_void_p]),
+    'pg_mol_screen': (C.c_int, [c_fp, C.c_int64, c_fp, C.c_int64, c_fp, C.c_int64, c_ip, c_ip, C.c_int, C.c_int, C.c_int, C.c_int,
+                                C.c_int, c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, C.c_void_p]),
 }
 
 EXPORTS = tuple(_PROTOS)

@@ -4,6 +4,10 @@ RDKit/OpenBabel post-processing is out of scope): .phore files -> PhoreDiff.samp
 element / position / bond arrays (.pt), the input of the reference's reconstruct_from_generated_with_edges.
 
   python tools/sample_cli.py --phore_file_list files.json --num_samples 100 --batch_size 30 --outdir results/x
+
+--valid_only keeps sampling until --num_samples molecules have passed the device-side screen (one connected molecule, no atom
+above its largest valence; phoregen_amd/molecule.py) and prints sample_all.py's `Finished n | Failed m` line; --sdf writes one V2000
+.sdf per molecule as sample_all.py names them, <outdir>/sdf_results/{pidx}_{name}_{i}.sdf.  Without them nothing changes.
 """
 import argparse
 import json
@@ -19,6 +23,7 @@ from phoregen_amd.config import default_model_config, load_config  # noqa: E402
 from phoregen_amd.data import parse_phore_file  # noqa: E402
 from phoregen_amd.fragment import load_fragment_json  # noqa: E402
 from phoregen_amd.models.diffusion import PhoreDiff  # noqa: E402
+from phoregen_amd.molecule import STATUS_NONFINITE, assemble, sample_valid, write_sdf  # noqa: E402
 from phoregen_amd.utils.sample_utils import decode_batch  # noqa: E402
 from phoregen_amd.weights import init_deterministic_  # noqa: E402
 
@@ -39,6 +44,9 @@ def main():
     ap.add_argument('--fragment', type=str, default=None,
                     help="JSON file {'element' | 'type', 'pos', 'bonds'}: a fragment kept as the first atoms of every molecule "
                          '(world coordinates of the .phore frame; device RNG only)')
+    ap.add_argument('--valid_only', action='store_true',
+                    help='sample until num_samples molecules have passed the screen (give up after 3 * num_samples failures)')
+    ap.add_argument('--sdf', action='store_true', help='write one .sdf per molecule under <outdir>/sdf_results/')
     args = ap.parse_args()
     torch.manual_seed(args.seed)
     cfg = default_model_config()
@@ -57,17 +65,33 @@ def main():
     os.makedirs(args.outdir, exist_ok=True)
     files = json.load(open(args.phore_file_list))
     fragment = load_fragment_json(args.fragment) if args.fragment else None
-    for f in files:
+    for pidx, f in enumerate(files):
         data = parse_phore_file(f).to('cuda')
         done, t0 = [], time.time()
-        while len(done) < args.num_samples:
+        kw = dict(pos_guidance_opt=args.pos_guidance_opt, sample_mode=args.sample_nodes_mode, normal_scale=args.normal_scale,
+                  rng=args.rng, fragment=fragment)
+        if args.valid_only:
+            # sample_all.py:79-84,172: top up until num_samples molecules have passed
+            out = sample_valid(model, data, args.num_samples, batch_size=args.batch_size, **kw)
+            done = out['finished']
+            print(f"Finished {len(done)} | Failed {len(out['failed'])}")
+        while len(done) < args.num_samples and not args.valid_only:
             n = min(args.batch_size, args.num_samples - len(done))
-            res = model.sample(data, n, 'cuda', pos_guidance_opt=args.pos_guidance_opt, sample_mode=args.sample_nodes_mode,
-                               normal_scale=args.normal_scale, rng=args.rng, return_traj=False, fragment=fragment)
+            res = model.sample(data, n, 'cuda', return_traj=False, **kw)
             # sample_all.py:104-116 (`.cpu()` of everything, unbatch_data, decode_data) in one pass: argmax on the device,
-            # one copy of the compact arrays
-            done += decode_batch(res, include_bond=True)
+            # one copy of the compact arrays (with --sdf: the a < b bonds and the screen's verdict with them)
+            done += assemble(res) if args.sdf else decode_batch(res, include_bond=True)
         torch.save(done, os.path.join(args.outdir, data.name + '.pt'))
+        if args.sdf:
+            sdf_dir = os.path.join(args.outdir, 'sdf_results')
+            os.makedirs(sdf_dir, exist_ok=True)
+            n_sdf = 0
+            for i, m in enumerate(done):
+                if m['status'] & STATUS_NONFINITE or m['bond_type'].numel() > 999:      # non-finite coordinates / more bonds than a V2000 block counts
+                    continue
+                write_sdf(os.path.join(sdf_dir, f'{pidx}_{data.name}_{i}.sdf'), [m], names=[f'{data.name}_{i}'])
+                n_sdf += 1
+            print(f'{data.name}: {n_sdf} .sdf files in {sdf_dir}')
         print(f'{data.name}: {len(done)} samples in {time.time() - t0:.1f} s')
 
 
