@@ -461,6 +461,18 @@ int pg_mol_screen(const float* node_scores, int64_t node_fs, const float* edge_s
                   int n_bond, int max_n, const uint8_t* max_valence2 /*[11]*/, int* status, int* counts, int8_t* cls,
                   int16_t* compact, uint8_t* valence2, int16_t* comp, int8_t* order, void* stream);
 
+/* Identity keys of the molecules the screen decoded, one wave per (frame, graph).  Reads the screen's outputs cls [F][n_lig] and
+ * order [F][n_bond / 2] (frames are dense: frame f starts at f * n_lig / f * n_bond / 2) with the same offsets; an atom is kept if
+ * its class is 0..10, a pair row is a bond if its order is 1..4 and both ends are kept.  key [F][B]: a 64-bit value that does not
+ * depend on the numbering of the atoms (dropped atoms, their place in the row order, absorbing rows and the reversed half of the bond
+ * rows have no influence); equal keys are necessary, not sufficient, for equal molecules.  colour [F][n_lig] (may be NULL): the final
+ * refinement colour of every kept atom, 0 for a dropped one.  Definition (initial colour from class, valence2, degree and aromatic
+ * bond count; three rounds over all atom pairs with hop distance and bond order; wrapping 64-bit sums): DESIGN.md 2.9.  A graph
+ * without a kept atom has the key 0xE220A8397B1DCDAF.  max_n above PG_MOL_MAX_ATOMS or a negative size: error before anything is
+ * launched, outputs untouched.  Every element of both outputs is written; integer work only, so results are exact. */
+int pg_mol_key(const int8_t* cls, const int8_t* order, const int* g_lig_off /*[B+1]*/, const int* g_bond_off /*[B+1]*/, int B, int F,
+               int n_lig, int n_bond, int max_n, int64_t* key, int64_t* colour, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -4,7 +4,12 @@
 of sample_all.py needs: is this ONE molecule, and can these atoms carry these bonds.  `assemble` turns the final prediction into
 per-molecule arrays with `decode_data`'s keys, `mol_block` / `write_sdf` write them as V2000 mol blocks, `sample_valid` is the loop
 that samples until enough molecules have passed.  No RDKit, no OpenBabel: `valid` is necessary, not sufficient, for the reference's
-`Chem.SanitizeMol` (DESIGN.md "From sampler output to molecules")."""
+`Chem.SanitizeMol` (DESIGN.md "From sampler output to molecules").
+
+Identity: `molecule_keys` gives every decoded molecule a 64-bit key that does not depend on the numbering of its atoms
+(csrc/mol_key.hip; the definition is in DESIGN.md 2.9 "Identity"), `same_molecule` decides exactly whether two assembled molecules
+have the same atoms and bonds, `unique_molecules` / `duplicate_groups` / `sample_valid(unique=True)` use the two.  Equal keys are
+necessary, not sufficient, for equal molecules; this is not SMILES."""
 from dataclasses import dataclass
 
 import numpy as np
@@ -33,6 +38,16 @@ MAX_VALENCE = {5: 3, 6: 4, 7: 4, 8: 2, 9: 1, 14: 4, 15: 7, 16: 6, 17: 1, 35: 1, 
 assert list(MAX_VALENCE) == ATOM_TYPES
 ELEMENT_SYMBOL = {5: 'B', 6: 'C', 7: 'N', 8: 'O', 9: 'F', 14: 'Si', 15: 'P', 16: 'S', 17: 'Cl', 35: 'Br', 53: 'I'}
 MAX_ATOMS = hip.PG_MOL_MAX_ATOMS
+
+# The identity key (DESIGN.md 2.9 "Identity"): constants of the splitmix64 step `mix`, the refinement rounds, the pair word of two
+# atoms without a path between them, and the key of a graph without a kept atom, mix(0).  The kernel and the tests' restatement
+# share these names and nothing else.
+KEY_MIX_GAMMA, KEY_MIX_M1, KEY_MIX_M2 = 0x9E3779B97F4A7C15, 0xBF58476D1CE4E5B9, 0x94D049BB133111EB
+KEY_MIX_SHIFTS = (30, 27, 31)
+KEY_ROUNDS = 3
+KEY_NO_PATH = 255
+KEY_EMPTY = 0xE220A8397B1DCDAF
+_M64 = (1 << 64) - 1
 
 _max_valence2 = {}               # device -> uint8 [11], twice MAX_VALENCE in class order
 
@@ -112,6 +127,41 @@ def screen(results, frames='final'):
     return Screen(valid=(out['status'] & FAIL_MASK) == 0, lig_off=lig_off, bond_off=bond_off, num_atoms=num_atoms, **out)
 
 
+@dataclass
+class MolKeys:
+    """Device tensors of one `molecule_keys` call.  The int64 values are 64-bit patterns: read them as unsigned (`& 2**64 - 1`)."""
+    key: torch.Tensor            # int64 [F, B]   identity key of the decoded molecule (KEY_EMPTY where no atom was kept)
+    colour: torch.Tensor         # int64 [F, N]   final refinement colour of a kept atom, 0 = dropped
+
+
+@torch.no_grad()
+def molecule_keys(sc):
+    """Identity keys of every (frame, graph) of a `Screen`, on its device, in one launch (pg_mol_key).  The key depends on the kept
+    atoms' elements and the bonds' orders alone (4 = aromatic is its own label), not on the numbering of the atoms, coordinates,
+    dropped atoms or absorbing rows.  Equal keys are NECESSARY, not sufficient, for equal molecules: `same_molecule` decides."""
+    dev = sc.cls.device
+    if dev.type != 'cuda':
+        raise RuntimeError('phoregen_amd.molecule.molecule_keys: the key is a HIP kernel and the screen lives on %s; there is no CPU '
+                           'fallback' % dev)
+    F, B = sc.status.shape
+    with torch.cuda.device(dev):
+        lib = hip.lib()
+        key = torch.empty(F, B, dtype=torch.int64, device=dev)
+        colour = torch.empty(F, sc.cls.size(1), dtype=torch.int64, device=dev)
+        _launch_key(lib, sc.cls, sc.order, sc.lig_off, sc.bond_off, B, F, max(sc.num_atoms, default=0), key, colour)
+    return MolKeys(key=key, colour=colour)
+
+
+def _launch_key(lib, cls, order, lig_off, bond_off, B, F, max_n, key, colour):
+    """pg_mol_key on the current stream; `colour` may be None.  A graph above MAX_ATOMS is the library's error: nothing is launched
+    and the outputs are not written."""
+    for t, dt in ((cls, torch.int8), (order, torch.int8), (lig_off, torch.int32), (bond_off, torch.int32)):
+        if t.dtype != dt or not t.is_contiguous() or t.device != cls.device:
+            raise ValueError('phoregen_amd.molecule.molecule_keys: cls / order must be contiguous int8, the offsets int32, on one device')
+    hip.check(lib.pg_mol_key(cls.data_ptr(), order.data_ptr(), lig_off.data_ptr(), bond_off.data_ptr(), B, F, cls.size(-1),
+                             2 * order.size(-1), max_n, key.data_ptr(), hip.ptr(colour), hip.stream_ptr()), 'pg_mol_key')
+
+
 def _launch(lib, node, node_fs, edge, edge_fs, pos, pos_fs, lig_off, bond_off, B, F, N, E, max_n, out):
     """pg_mol_screen on the current stream.  A graph above MAX_ATOMS is the library's error (RuntimeError with its message): nothing
     is launched and `out` is not written."""
@@ -135,18 +185,24 @@ def _pairs(n):
 
 
 @torch.no_grad()
-def assemble(results):
+def assemble(results, keys=False):
     """The final prediction as one dict per graph with `decode_data`'s keys and meaning -- 'element' (atomic numbers), 'atom_pos'
     (kept atoms, the tensor's own fp32 values), 'bond_index' [2, n_b] (indices among the kept atoms) and 'bond_type' [n_b] for
     a < b only, in row order -- plus 'status', 'valid', 'n_components' and 'valence' (per kept atom, halves allowed).  The screen runs
-    on the device; ONE device-to-host copy brings the compact arrays over, the split by offsets is on the host."""
+    on the device; ONE device-to-host copy brings the compact arrays over, the split by offsets is on the host.
+    keys=True: every dict also has 'key' (the identity key of `molecule_keys` as an unsigned Python int) and 'atom_colour' (uint64
+    per kept atom); they ride in the same copy."""
     sc = screen(results, 'final')
     parts = [sc.status[0], sc.counts[0], results['pred'][1], sc.compact[0], sc.cls[0], sc.valence2[0], sc.order[0]]
+    dtypes = [np.int32, np.int32, np.float32, np.int16, np.int8, np.uint8, np.int8]
+    if keys:                                                           # (64-bit parts first: every part stays aligned in the blob)
+        mk = molecule_keys(sc)
+        parts, dtypes = [mk.key[0], mk.colour[0]] + parts, [np.uint64, np.uint64] + dtypes
     sizes = [p.numel() * p.element_size() for p in parts]
     blob = torch.cat([p.reshape(-1).view(torch.uint8) for p in parts]).cpu().numpy()
     cut = np.cumsum([0] + sizes)
-    status, counts, pos, compact, cls, valence2, order = (
-        blob[cut[i]:cut[i + 1]].view(dt) for i, dt in enumerate((np.int32, np.int32, np.float32, np.int16, np.int8, np.uint8, np.int8)))
+    views = [blob[cut[i]:cut[i + 1]].view(dt) for i, dt in enumerate(dtypes)]
+    status, counts, pos, compact, cls, valence2, order = views[-7:]
     counts, pos = counts.reshape(-1, 4), pos.reshape(-1, 3)
     mols, n0, h0 = [], 0, 0
     for g, n in enumerate(sc.num_atoms):
@@ -162,6 +218,8 @@ def assemble(results):
                      'bond_type': torch.from_numpy(o[nz].astype(np.int64)),
                      'status': int(status[g]), 'valid': (int(status[g]) & FAIL_MASK) == 0, 'n_components': int(counts[g, 2]),
                      'valence': valence2[n0:n0 + n][keep].astype(np.float64) / 2.0})
+        if keys:
+            mols[-1]['key'], mols[-1]['atom_colour'] = int(views[0][g]), views[1][n0:n0 + n][keep].copy()
         n0, h0 = n0 + n, h0 + h
     return mols
 
@@ -187,30 +245,175 @@ def mol_block(mol, name=''):
 
 
 def write_sdf(path, mols, names=None):
-    """An SDF file: one mol block per molecule, each closed by a '$$$$' line."""
+    """An SDF file: one mol block per molecule, each closed by a '$$$$' line.  A molecule that carries 'key' (assemble(keys=True))
+    gets one data item `> <PHOREGEN_KEY>` with the key as 16 hex digits between its block and the '$$$$'."""
     names = names if names is not None else [''] * len(mols)
     if len(names) != len(mols):
         raise ValueError(f'write_sdf: {len(mols)} molecules, {len(names)} names')
     with open(path, 'w') as fh:
         for m, nm in zip(mols, names):
             fh.write(mol_block(m, nm))
+            if 'key' in m:
+                fh.write('> <PHOREGEN_KEY>\n%016x\n\n' % (int(m['key']) & _M64))
             fh.write('$$$$\n')
 
 
+# ---- identity: exact comparison and grouping of assembled molecules ---------------------------------------------------------
+
+def _mol_graph(m):
+    """Adjacency {neighbour: order} per atom, the atoms' exact local signatures and the colours handed in (all equal if absent)."""
+    n = len(m['element'])
+    bi, bt = np.asarray(m['bond_index']).reshape(2, -1), np.asarray(m['bond_type']).reshape(-1)
+    adj = [{} for _ in range(n)]
+    for a, b, t in zip(bi[0].tolist(), bi[1].tolist(), bt.tolist()):
+        adj[a][b] = adj[b][a] = int(t)
+    own = [(int(z), tuple(sorted(nb.values()))) for z, nb in zip(m['element'], adj)]
+    col = m.get('atom_colour')
+    col = [0] * n if col is None else [int(c) & _M64 for c in np.asarray(col).reshape(-1).tolist()]
+    if len(col) != n:
+        raise ValueError(f"same_molecule: {n} atoms, {len(col)} entries in 'atom_colour'")
+    # what an atom sees of itself and of its neighbours is the same in any numbering, so it may always restrict the candidates
+    sig = [(own[i], tuple(sorted((t, own[j]) for j, t in adj[i].items())), col[i]) for i in range(n)]
+    return adj, sig
+
+
+def _components(adj):
+    """Connected components as lists of atoms in breadth-first order: every atom but the first has an earlier neighbour."""
+    seen, comps = [False] * len(adj), []
+    for s in range(len(adj)):
+        if seen[s]:
+            continue
+        seen[s], comp = True, [s]
+        for u in comp:                                                 # (grows while it is walked)
+            for v in sorted(adj[u]):
+                if not seen[v]:
+                    seen[v] = True
+                    comp.append(v)
+        comps.append(comp)
+    return comps
+
+
+def _component_matches(c1, adj1, sig1, c2, adj2, sig2):
+    """Is there a bijection of the atoms of c1 onto those of c2 that keeps signatures and bond orders?  Backtracking in the
+    breadth-first order of c1: an atom's image is looked for among the neighbours of its first mapped neighbour's image."""
+    if len(c1) != len(c2) or sorted(sig1[i] for i in c1) != sorted(sig2[j] for j in c2):
+        return False
+    place = {a: k for k, a in enumerate(c1)}
+    earlier = [[(b, t) for b, t in adj1[a].items() if place[b] < k] for k, a in enumerate(c1)]
+    image, used = {}, set()
+
+    def extend(k):
+        if k == len(c1):
+            return True
+        a = c1[k]
+        cands = adj2[image[earlier[k][0][0]]] if earlier[k] else c2
+        for x in cands:
+            if x in used or sig2[x] != sig1[a] or any(adj2[x].get(image[b]) != t for b, t in earlier[k]):
+                continue
+            # (bonds of x that a lacks need no check: signatures hold the degree, so both components have as many bonds, and once
+            # every atom is placed every bond of c1 has its own bond of c2)
+            image[a] = x
+            used.add(x)
+            if extend(k + 1):
+                return True
+            del image[a]
+            used.discard(x)
+        return False
+
+    return extend(0)
+
+
+def same_molecule(m1, m2):
+    """Exact: do two assembled molecules have the same atoms and bonds up to a renumbering of the atoms (elements and bond orders as
+    labels, 4 = aromatic its own label; coordinates play no part)?  'atom_colour', where both carry it, only narrows the search: with
+    any colours, all equal included, the answer is the same, as long as equal molecules were coloured by the same rule."""
+    if len(m1['element']) != len(m2['element']) or np.asarray(m1['bond_type']).size != np.asarray(m2['bond_type']).size:
+        return False
+    if ('atom_colour' in m1) != ('atom_colour' in m2):                  # colours of one side only say nothing: drop them
+        m1, m2 = ({k: v for k, v in m.items() if k != 'atom_colour'} for m in (m1, m2))
+    (adj1, sig1), (adj2, sig2) = _mol_graph(m1), _mol_graph(m2)
+    if sorted(sig1) != sorted(sig2):
+        return False
+    comps1, comps2 = _components(adj1), _components(adj2)
+    if len(comps1) != len(comps2):
+        return False
+    # components pair off greedily: being the same component is an equivalence, so any partner of that kind will do
+    free = list(comps2)
+    for c1 in comps1:
+        hit = next((k for k, c2 in enumerate(free) if _component_matches(c1, adj1, sig1, c2, adj2, sig2)), None)
+        if hit is None:
+            return False
+        free.pop(hit)
+    return True
+
+
+def unique_molecules(mols):
+    """The partition of assembled molecules into classes of `same_molecule`: (representatives, class_of) with the first member of
+    every class as its representative, in order of appearance, and class_of[i] the index into `representatives` of mols[i].
+    If every molecule carries 'key', a molecule is only compared inside its key's group (equal molecules have equal keys); the
+    answer is exact either way."""
+    reps, class_of, by_key = [], [], {}
+    keyed = all('key' in m for m in mols)
+    for m in mols:
+        group = by_key.setdefault(int(m['key']) & _M64 if keyed else None, [])
+        hit = next((r for r in group if same_molecule(reps[r], m)), None)
+        if hit is None:
+            hit = len(reps)
+            reps.append(m)
+            group.append(hit)
+        class_of.append(hit)
+    return reps, class_of
+
+
+@torch.no_grad()
+def duplicate_groups(keys):
+    """Key-level census of a key vector on its own device, no host loop: (first, counts, group) with first[k] the index of the first
+    occurrence of the k-th distinct key (ascending, so in order of appearance), counts[k] how often it occurs and group[i] the k of
+    keys[i].  KEY-LEVEL ONLY: molecules with different keys differ, molecules with one key are very likely, not certainly, the same --
+    copy the representatives `keys[first]` points at and let `unique_molecules` confirm where that matters."""
+    keys = keys.reshape(-1)
+    n, dev = keys.numel(), keys.device
+    srt, perm = torch.sort(keys, stable=True)                          # stable: the first occurrence leads its run
+    new = torch.ones(n, dtype=torch.bool, device=dev)
+    new[1:] = srt[1:] != srt[:-1]
+    starts = new.nonzero().reshape(-1)
+    counts = torch.diff(starts, append=torch.tensor([n], device=dev))
+    first, by_first = perm[starts].sort()
+    rank = torch.empty_like(by_first)
+    rank[by_first] = torch.arange(by_first.numel(), device=dev)
+    group = torch.empty(n, dtype=torch.long, device=dev)
+    group[perm] = rank[new.cumsum(0) - 1]
+    return first, counts[by_first], group
+
+
 # ---- the top-up loop of sample_all.py:79-84,172 ------------------------------------------------------------------------------
-def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, device='cuda', **sample_kwargs):
+def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, device='cuda', unique=False, **sample_kwargs):
     """Sample until `num_samples` molecules have passed the screen, giving up once more than `max_failed_factor * num_samples` have
     failed (checked before every draw, as the reference does).  Every draw asks for min(batch_size, what is still missing) graphs,
     so never more than `num_samples` are finished.  `sample_kwargs` (fragment=, pos_guidance_opt=, rng=, seed=, ...) go to
     `model.sample`; a fixed seed= repeats the same draw in every call of the same size, so leave it unset (a fresh key per call, drawn
-    from torch's default generator) unless that is meant.  Returns {'finished': [...], 'failed': [...], 'n_calls': int} with `assemble`'s dicts."""
-    finished, failed, n_calls = [], [], 0
+    from torch's default generator) unless that is meant.  Returns {'finished': [...], 'failed': [...], 'n_calls': int} with `assemble`'s dicts.
+    unique=True: a valid molecule is finished only if it is not `same_molecule` to one already finished (looked up by key, confirmed
+    exactly); a repeat goes to the additional list 'duplicates', counts neither as finished nor as failed, and the loop also gives up
+    once more than `max_failed_factor * num_samples` repeats have been seen.  The molecules then carry 'key' and 'atom_colour'."""
+    finished, failed, duplicates, n_calls = [], [], [], 0
+    by_key = {}                                                        # key -> finished molecules that have it
     while len(finished) < num_samples:
-        if len(failed) > max_failed_factor * num_samples:
+        if len(failed) > max_failed_factor * num_samples or len(duplicates) > max_failed_factor * num_samples:
             break
         n = min(batch_size, num_samples - len(finished))
         res = model.sample(data, n, device, return_traj=False, **sample_kwargs)
         n_calls += 1
-        for m in assemble(res):
-            (finished if m['valid'] else failed).append(m)
-    return {'finished': finished, 'failed': failed, 'n_calls': n_calls}
+        for m in (assemble(res, keys=True) if unique else assemble(res)):
+            if not m['valid']:
+                failed.append(m)
+            elif unique and any(same_molecule(m, other) for other in by_key.setdefault(m['key'], [])):
+                duplicates.append(m)
+            else:
+                finished.append(m)
+                if unique:
+                    by_key[m['key']].append(m)
+    out = {'finished': finished, 'failed': failed, 'n_calls': n_calls}
+    if unique:
+        out['duplicates'] = duplicates
+    return out

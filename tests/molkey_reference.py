@@ -1,0 +1,247 @@
+"""Plain restatement of the molecule identity key (DESIGN.md 2.9 "Identity"; phoregen_amd/molecule.py, csrc/mol_key.hip) for the
+tests, written from the text: Python ints masked to 64 bits, breadth-first hop distances, no device code.  It shares nothing with
+the kernel but the named constants of phoregen_amd.molecule.  Also here: the frozen corpus of the identity tests and the yardstick
+for identity, networkx's labelled graph isomorphism (tests only; the product does not import networkx)."""
+import numpy as np
+import torch
+
+from phoregen_amd import molecule as M
+from phoregen_amd.utils.sample_utils import ATOM_TYPES
+
+M64 = (1 << 64) - 1
+
+
+def mix(x):
+    s1, s2, s3 = M.KEY_MIX_SHIFTS
+    x = (x + M.KEY_MIX_GAMMA) & M64
+    x = ((x ^ (x >> s1)) * M.KEY_MIX_M1) & M64
+    x = ((x ^ (x >> s2)) * M.KEY_MIX_M2) & M64
+    return x ^ (x >> s3)
+
+
+def hop_distances(n, adj):
+    d = [[M.KEY_NO_PATH] * n for _ in range(n)]
+    for s in range(n):
+        d[s][s], front, k = 0, [s], 0
+        while front:
+            k += 1
+            nxt = []
+            for u in front:
+                for v in adj[u]:
+                    if d[s][v] == M.KEY_NO_PATH and v != s:
+                        d[s][v] = k
+                        nxt.append(v)
+            front = nxt
+    return d
+
+
+def key_of(classes, bonds):
+    """classes: atom class 0..10 of every (kept) atom; bonds {(a, b): order 1..4}, a != b, every pair once.
+    Returns (key, [colour per atom]) as unsigned ints."""
+    n = len(classes)
+    adj, order = [[] for _ in range(n)], {}
+    degree, valence2, aromatic = [0] * n, [0] * n, [0] * n
+    for (a, b), t in bonds.items():
+        assert a != b and 1 <= t <= 4 and (b, a) not in bonds
+        adj[a].append(b), adj[b].append(a)
+        order[(a, b)] = order[(b, a)] = t
+        for x in (a, b):
+            degree[x] += 1
+            valence2[x] += 3 if t == 4 else 2 * t
+            aromatic[x] += t == 4
+    dist = hop_distances(n, adj)
+    c = [mix(classes[i] | valence2[i] << 8 | degree[i] << 24 | aromatic[i] << 32) for i in range(n)]
+    for _ in range(M.KEY_ROUNDS):
+        nxt = []
+        for i in range(n):
+            s = 0
+            for j in range(n):
+                if j != i:
+                    s = (s + mix(c[j] ^ mix(dist[i][j] | order.get((i, j), 0) << 8))) & M64
+            nxt.append(mix(c[i] ^ mix(s)))
+        c = nxt
+    s = 0
+    for v in c:
+        s = (s + mix(v)) & M64
+    return mix(s ^ (n | len(bonds) << 16)), c
+
+
+def key_of_rows(cls, order):
+    """One graph as the screen wrote it: cls int8 [n] (-1 = dropped), order int8 [n (n - 1) / 2] for the pairs a < b in row-major
+    order.  Returns (key, colours [n] with 0 for a dropped atom)."""
+    cls, order = [int(v) for v in cls], [int(v) for v in order]
+    n = len(cls)
+    kept = [i for i in range(n) if 0 <= cls[i] <= 10]
+    compact = {i: k for k, i in enumerate(kept)}
+    bonds, row = {}, 0
+    for a in range(n):
+        for b in range(a + 1, n):
+            if 1 <= order[row] <= 4 and a in compact and b in compact:
+                bonds[(compact[a], compact[b])] = order[row]
+            row += 1
+    assert row == len(order)
+    key, c = key_of([cls[i] for i in kept], bonds)
+    colour = [0] * n
+    for k, i in enumerate(kept):
+        colour[i] = c[k]
+    return key, colour
+
+
+def key_of_mol(m):
+    """An assembled molecule ('element', 'bond_index', 'bond_type'): (key, colours per atom)."""
+    bi, bt = np.asarray(m['bond_index']).reshape(2, -1), np.asarray(m['bond_type']).reshape(-1)
+    return key_of([ATOM_TYPES.index(int(z)) for z in m['element']],
+                  {(int(a), int(b)): int(t) for a, b, t in zip(bi[0], bi[1], bt)})
+
+
+def with_key(m):
+    key, colour = key_of_mol(m)
+    return dict(m, key=key, atom_colour=np.array(colour, dtype=np.uint64))
+
+
+# ---- molecules as assemble() hands them over ------------------------------------------------------------------------------------
+def mol_from(classes, bonds):
+    """An assembled-style dict from atom classes and {(a, b): order}; bonds as pairs a < b in row order, coordinates made up."""
+    pairs = sorted((min(a, b), max(a, b), t) for (a, b), t in bonds.items())
+    assert len({p[:2] for p in pairs}) == len(pairs)
+    n = len(classes)
+    return {'element': [ATOM_TYPES[c] for c in classes],
+            'atom_pos': torch.arange(3 * n, dtype=torch.float32).reshape(n, 3) * 0.5,
+            'bond_index': torch.tensor([[p[0] for p in pairs], [p[1] for p in pairs]], dtype=torch.long).reshape(2, -1),
+            'bond_type': torch.tensor([p[2] for p in pairs], dtype=torch.long), 'status': 0, 'valid': True}
+
+
+def permuted(classes, bonds, perm):
+    """The same molecule with atom i renumbered to perm[i]."""
+    out = [0] * len(classes)
+    for i, c in enumerate(classes):
+        out[perm[i]] = c
+    return out, {(min(perm[a], perm[b]), max(perm[a], perm[b])): t for (a, b), t in bonds.items()}
+
+
+# ---- the yardstick: networkx ---------------------------------------------------------------------------------------------------
+def nx_graph(m):
+    import networkx as nx
+    g = nx.Graph()
+    for i, z in enumerate(m['element']):
+        g.add_node(i, z=int(z))
+    bi, bt = np.asarray(m['bond_index']).reshape(2, -1), np.asarray(m['bond_type']).reshape(-1)
+    for a, b, t in zip(bi[0].tolist(), bi[1].tolist(), bt.tolist()):
+        g.add_edge(a, b, t=int(t))
+    return g
+
+
+def nx_same(g1, g2):
+    import networkx as nx
+    return nx.is_isomorphic(g1, g2, node_match=lambda a, b: a['z'] == b['z'], edge_match=lambda a, b: a['t'] == b['t'])
+
+
+def nx_partition(mols):
+    """class_of[i] = index of the isomorphism class of mols[i], classes numbered by first appearance, judged by networkx alone.
+    (Graphs are first bucketed by networkx's Weisfeiler-Lehman hash, which isomorphic graphs share; is_isomorphic decides inside.)"""
+    import networkx as nx
+    graphs = [nx_graph(m) for m in mols]
+    buckets, reps, class_of = {}, [], []
+    for i, g in enumerate(graphs):
+        h = (g.number_of_nodes(), g.number_of_edges(), nx.weisfeiler_lehman_graph_hash(g, node_attr='z', edge_attr='t'))
+        hit = next((r for r in buckets.setdefault(h, []) if nx_same(graphs[reps[r]], g)), None)
+        if hit is None:
+            hit = len(reps)
+            reps.append(i)
+            buckets[h].append(hit)
+        class_of.append(hit)
+    return class_of
+
+
+# ---- the frozen corpus ----------------------------------------------------------------------------------------------------------
+CORPUS_SEED = 20240911
+CORPUS_RANDOM_BASES = 40
+CORPUS_MAX_ATOMS = 40
+
+
+def _ring(n, order=1, off=0):
+    return {(min(off + i, off + (i + 1) % n), max(off + i, off + (i + 1) % n)): order for i in range(n)}
+
+
+def named_bases():
+    """Small molecules the identity tests name: (name, classes, bonds)."""
+    C_, N_, O_ = 1, 2, 3
+    decalin = _ring(6)
+    decalin.update({(0, 6): 1, (6, 7): 1, (7, 8): 1, (8, 9): 1, (1, 9): 1})
+    bicyclopentyl = _ring(5)
+    bicyclopentyl.update(_ring(5, off=5))
+    bicyclopentyl[(0, 5)] = 1
+    kekule = {p: 1 + (i % 2) for i, p in enumerate([(0, 1), (1, 2), (2, 3), (3, 4), (4, 5), (0, 5)])}
+    pyridine = _ring(6, order=4)
+    return [('decalin', [C_] * 10, decalin), ('bicyclopentyl', [C_] * 10, bicyclopentyl),
+            ('benzene', [C_] * 6, _ring(6, order=4)), ('cyclohexane', [C_] * 6, _ring(6)), ('benzene_kekule', [C_] * 6, kekule),
+            ('pyridine', [N_] + [C_] * 5, pyridine), ('ethanol_water', [C_, C_, O_, O_], {(0, 1): 1, (1, 2): 1})]
+
+
+def _random_base(rng):
+    """A molecule-like graph: a spanning tree with degree at most 4, a few ring closures, mostly carbon, mostly single bonds."""
+    n = int(rng.integers(5, CORPUS_MAX_ATOMS + 1))
+    classes = [int(v) for v in rng.choice([1, 1, 1, 1, 1, 2, 2, 3, 3, 7, 8], n)]
+    bonds, degree = {}, [0] * n
+    for v in range(1, n):
+        u = int(rng.integers(max(0, v - 6), v))
+        while degree[u] >= 4:
+            u = int(rng.integers(0, v))
+        bonds[(u, v)] = int(rng.choice([1, 1, 1, 1, 2, 4]))
+        degree[u] += 1
+        degree[v] += 1
+    for _ in range(int(rng.integers(0, 4))):
+        a, b = sorted(int(v) for v in rng.choice(n, 2, replace=False))
+        if (a, b) not in bonds and degree[a] < 4 and degree[b] < 4:
+            bonds[(a, b)] = 1
+            degree[a] += 1
+            degree[b] += 1
+    return classes, bonds
+
+
+def _near_misses(rng, classes, bonds):
+    """[(kind, classes, bonds)]: one element changed, one bond order changed, one bond moved to another pair with the degree
+    sequence kept (where the graph has such a move)."""
+    n, out = len(classes), []
+    i = int(rng.integers(0, n))
+    out.append(('element', [(c % 10) + 1 if k == i else c for k, c in enumerate(classes)], dict(bonds)))
+    if bonds:
+        pairs = sorted(bonds)
+        p = pairs[int(rng.integers(0, len(pairs)))]
+        out.append(('order', list(classes), {k: (t % 4 + 1 if k == p else t) for k, t in bonds.items()}))
+        degree = [0] * n
+        for a, b in pairs:
+            degree[a] += 1
+            degree[b] += 1
+        moves = [((a, b), (a, c)) for a, b in pairs + [(y, x) for x, y in pairs] for c in range(n)
+                 if c not in (a, b) and degree[c] == degree[b] - 1 and (min(a, c), max(a, c)) not in bonds]
+        if moves:
+            (a, b), (_, c) = moves[int(rng.integers(0, len(moves)))]
+            moved = {k: v for k, v in bonds.items() if k != (min(a, b), max(a, b))}
+            moved[(min(a, c), max(a, c))] = bonds[(min(a, b), max(a, b))]
+            out.append(('moved', list(classes), moved))
+    return out
+
+
+def corpus():
+    """The frozen corpus: every base (named and random), two renumbered copies of it, its near-misses and one renumbered copy of each.
+    Returns (mols, iso_pairs, near_pairs, names): assembled-style dicts, index pairs that are renumberings of each other by
+    construction, index pairs (base, near-miss of it), and a label per molecule."""
+    rng = np.random.default_rng(CORPUS_SEED)
+    bases = named_bases() + [('random%d' % k,) + _random_base(rng) for k in range(CORPUS_RANDOM_BASES)]
+    mols, names, iso_pairs, near_pairs = [], [], [], []
+
+    def add(name, classes, bonds):
+        mols.append(mol_from(classes, bonds))
+        names.append(name)
+        return len(mols) - 1
+
+    for name, classes, bonds in bases:
+        b = add(name, classes, bonds)
+        for k in range(2):
+            iso_pairs.append((b, add(f'{name}/perm{k}', *permuted(classes, bonds, rng.permutation(len(classes)).tolist()))))
+        for kind, cl, bo in _near_misses(rng, classes, bonds):
+            m = add(f'{name}/{kind}', cl, bo)
+            near_pairs.append((b, m))
+            iso_pairs.append((m, add(f'{name}/{kind}/perm', *permuted(cl, bo, rng.permutation(len(cl)).tolist()))))
+    return mols, iso_pairs, near_pairs, names

@@ -7,7 +7,10 @@ element / position / bond arrays (.pt), the input of the reference's reconstruct
 
 --valid_only keeps sampling until --num_samples molecules have passed the device-side screen (one connected molecule, no atom
 above its largest valence; phoregen_amd/molecule.py) and prints sample_all.py's `Finished n | Failed m` line; --sdf writes one V2000
-.sdf per molecule as sample_all.py names them, <outdir>/sdf_results/{pidx}_{name}_{i}.sdf.  Without them nothing changes.
+.sdf per molecule as sample_all.py names them, <outdir>/sdf_results/{pidx}_{name}_{i}.sdf.  --unique (implies --valid_only) finishes
+a molecule only if it is new: repeats, judged by the identity key and confirmed exactly (phoregen_amd.molecule.same_molecule), are
+counted apart; <outdir>/{name}_keys.txt then lists one 16-digit hex key per finished molecule (the part sample_all.py's
+{name}_SMILES_all.txt plays) and the .sdf files carry the key as a data item.  Without them nothing changes.
 """
 import argparse
 import json
@@ -46,8 +49,11 @@ def main():
                          '(world coordinates of the .phore frame; device RNG only)')
     ap.add_argument('--valid_only', action='store_true',
                     help='sample until num_samples molecules have passed the screen (give up after 3 * num_samples failures)')
+    ap.add_argument('--unique', action='store_true',
+                    help='implies --valid_only: a repeat of a finished molecule is not finished (also give up after 3 * num_samples repeats)')
     ap.add_argument('--sdf', action='store_true', help='write one .sdf per molecule under <outdir>/sdf_results/')
     args = ap.parse_args()
+    args.valid_only = args.valid_only or args.unique
     torch.manual_seed(args.seed)
     cfg = default_model_config()
     if args.config:
@@ -72,9 +78,12 @@ def main():
                   rng=args.rng, fragment=fragment)
         if args.valid_only:
             # sample_all.py:79-84,172: top up until num_samples molecules have passed
-            out = sample_valid(model, data, args.num_samples, batch_size=args.batch_size, **kw)
+            out = sample_valid(model, data, args.num_samples, batch_size=args.batch_size, unique=args.unique, **kw)
             done = out['finished']
-            print(f"Finished {len(done)} | Failed {len(out['failed'])}")
+            print(f"Finished {len(done)} | Failed {len(out['failed'])}" + (f" | Duplicates {len(out['duplicates'])}" if args.unique else ''))
+            if args.unique:
+                with open(os.path.join(args.outdir, data.name + '_keys.txt'), 'w') as fh:
+                    fh.writelines('%016x\n' % m['key'] for m in done)
         while len(done) < args.num_samples and not args.valid_only:
             n = min(args.batch_size, args.num_samples - len(done))
             res = model.sample(data, n, 'cuda', return_traj=False, **kw)
