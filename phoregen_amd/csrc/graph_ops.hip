@@ -504,6 +504,7 @@ static int check_graph_size(const PgTopo* t, const char* what) {
 extern "C" int pg_knn_ctx(const PgTopo* t, const float* x_ctx, int k, int* nbr, int* deg, void* stream) {
   if (k < 1 || k > 64) { set_error("pg_knn_ctx: k = %d out of range [1, 64]", k); return PG_ERR_ARG; }
   if (int rc = check_graph_size(t, "pg_knn_ctx")) return rc;
+  if (t->n_ctx == 0) return PG_OK;
   hipLaunchKernelGGL(knn_ctx_kernel, dim3((t->n_ctx + 3) / 4), dim3(256), 0, (hipStream_t)stream, *t, x_ctx, k, nbr, deg);
   return check_launch("pg_knn_ctx");
 }
@@ -519,6 +520,7 @@ extern "C" int pg_lig_normals(const PgTopo* t, const float* x_ctx, const float* 
                               float* nrm, void* stream) {
   if (t->max_nlig > 64 * KNN_MAXC) { set_error("pg_lig_normals: ligand of %d atoms (limit %d)", t->max_nlig, 64 * KNN_MAXC); return PG_ERR_ARG; }
   const int n = t->n_lig + t->n_phore;
+  if (n == 0) return PG_OK;
   hipLaunchKernelGGL(lig_normals_kernel, dim3((n + 3) / 4), dim3(256), 0, (hipStream_t)stream, *t, x_ctx, phore_norm,
                      phore2ctx, nrm);
   return check_launch("pg_lig_normals");
@@ -535,6 +537,7 @@ extern "C" int pg_edge_gate(const PgTopo* t, const float* x_ctx, const int* nbr,
                             const float* b0, const float* gamma, const float* beta, const float* W3, float b3,
                             float* ew, void* stream) {
   (void)gamma;
+  if (t->n_ctx == 0) return PG_OK;
   hipLaunchKernelGGL(edge_gate_kernel, dim3((t->n_ctx + 3) / 4), dim3(256), 0, (hipStream_t)stream, t->n_ctx, x_ctx, nbr,
                      deg, k, W0, b0, beta, W3, b3, ew);
   return check_launch("pg_edge_gate");
@@ -551,6 +554,7 @@ extern "C" int pg_bond_smear(const PgTopo* t, const float* x_ctx, float* G, void
 extern "C" int pg_apply_dx(const PgTopo* t, const float* x, const float* dx1, const float* dx2, float* x_new,
                            void* stream) {
   const int n = t->n_ctx * 3;
+  if (n == 0) return PG_OK;
   hipLaunchKernelGGL(apply_dx_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, t->n_ctx,
                      t->ctx_is_lig, x, dx1, dx2, x_new);
   return check_launch("pg_apply_dx");

@@ -81,6 +81,9 @@ def t(a):
     return torch.as_tensor(np.asarray(a))
 
 
+TOL = 2e-5   # max-abs error <= 2e-5 x max-abs(reference), fp32 re-association
+
+
 def rel_err(a, b):
     a, b = np.asarray(a, dtype=np.float64), np.asarray(b, dtype=np.float64)
     return float(np.abs(a - b).max() / max(np.abs(b).max(), 1e-30))
