@@ -26,32 +26,15 @@
 // four values of a chunk are one 16-byte slot.
 #include <type_traits>
 
-#include "common.h"
+#include "wave_prims.h"
 #include "../../include/phoregen_hip.h"
 
 namespace pg {
 
-typedef int i4v __attribute__((ext_vector_type(4)));
 typedef int i2v __attribute__((ext_vector_type(2)));
 
 constexpr int ST_BM = 64;                       // rows per tile
 constexpr int ST_STAGE = ST_BM * 128 * 4;       // 32 KB
-
-__device__ __forceinline__ i4v st_desc(const void* base, unsigned bytes) {
-  const unsigned long long a = reinterpret_cast<unsigned long long>(base);
-  i4v d;
-  d[0] = __builtin_amdgcn_readfirstlane((int)(a & 0xffffffffu));
-  d[1] = __builtin_amdgcn_readfirstlane((int)((a >> 32) & 0xffffu));      // stride 0: raw buffer, byte offsets
-  d[2] = __builtin_amdgcn_readfirstlane((int)bytes);
-  d[3] = 0x00020000;
-  return d;
-}
-
-// one 1 KB piece: 64 lanes x 16 bytes from base + voff + soff to LDS byte address lds_dst + 16 * lane
-__device__ __forceinline__ void st_dma(unsigned lds_dst, unsigned voff, i4v desc, unsigned soff) {
-  asm volatile("s_nop 4\n\ts_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-               :: "s"(lds_dst), "v"(voff), "s"(desc), "s"(soff) : "memory");
-}
 
 template <int NW /* waves: 32 output columns each */, int NADD /* 0 | 1: rows add1[idx1[r]] | 2: rows add1[r] */, int K1 /* 128 | 0 */,
           int K2 /* 0 | 20 */, bool LN /* LayerNorm(128) + ReLU on the X rows (K1 = 128, NW = 4) */,
@@ -114,7 +97,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void gemm_stream_kernel(P
 
   // ---- lane-fixed offsets ----
   const unsigned ldxb = (unsigned)p.ldx * 4u, ldyb = (unsigned)p.ldy * 4u;
-  const i4v descX = st_desc(p.X, (unsigned)p.M * ldxb);
+  const i4v descX = raw_buffer_desc(p.X, (unsigned)p.M * ldxb);
   const __amdgpu_buffer_rsrc_t descY = __builtin_amdgcn_make_buffer_rsrc(p.Y, 0, (unsigned)p.M * ldyb, 0x00020000);
   // DMA source of lane (row_sub, slot pp) in a piece: the slot holds k-group pp ^ ((row >> 1) & 7), row = 8 i + row_sub
   const unsigned row_sub = lane >> 3, pp = lane & 7;
@@ -177,12 +160,12 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void gemm_stream_kernel(P
 #pragma unroll
       for (int q = 0; q < 8; ++q) {
         const unsigned i = 2u * wave + (q >> 2), j = q & 3;
-        st_dma(stage * ST_STAGE + (i * 4u + j) * 1024u, (q >> 2) ? voff_odd : voff_even, descX, row0b + i * 8u * ldxb + j * 128u);
+        lds_dma_1k(stage * ST_STAGE + (i * 4u + j) * 1024u, (q >> 2) ? voff_odd : voff_even, descX, row0b + i * 8u * ldxb + j * 128u);
       }
     } else {
 #pragma unroll
       for (int j = 0; j < 4; ++j)
-        st_dma(stage * ST_STAGE + ((unsigned)wave * 4u + j) * 1024u, voff_wave, descX, row0b + (unsigned)wave * 8u * ldxb + j * 128u);
+        lds_dma_1k(stage * ST_STAGE + ((unsigned)wave * 4u + j) * 1024u, voff_wave, descX, row0b + (unsigned)wave * 8u * ldxb + j * 128u);
     }
   };
 

@@ -11,45 +11,10 @@
 // gfx950 (profiles/r01_micro_mfma_valu_coexec.md): the kernel is written for low instruction count, occupancy only
 // hides the row-gather latency.
 // Lane l = (g = l>>4, m = l&15); 16x16x4 maps as in seg_attn.hip.
-#include "common.h"
+#include "wave_prims.h"
 #include "../../include/phoregen_hip.h"
 
 namespace pg {
-
-constexpr float NA_NEG = -1.0e30f;
-
-template <int CTRL>
-__device__ __forceinline__ float dpp_na(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float row16_sum_na(float v) {
-  v += dpp_na<0xB1>(v);
-  v += dpp_na<0x4E>(v);
-  v += dpp_na<0x141>(v);
-  v += dpp_na<0x140>(v);
-  return v;
-}
-
-// folded LayerNorm + ReLU on a K-path tile (hid[tau][r] = hidden[c = 16 tau + 4g + r][row = m]); returns rstd of row m
-__device__ __forceinline__ float ln_fold_k(f4 (&hid)[8], const float* bp, int g) {
-  float q = 0.f;
-#pragma unroll
-  for (int tq = 0; tq < 8; ++tq)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) q = fmaf(hid[tq][r], hid[tq][r], q);
-  q += __shfl_xor(q, 16);
-  q += __shfl_xor(q, 32);
-  const float var = q * (1.f / 128.f) + 1e-5f;
-  const float rs = __builtin_amdgcn_rsqf(var);
-  const float sigma = var * rs;
-#pragma unroll
-  for (int tq = 0; tq < 8; ++tq) {
-    const f4 bt = *reinterpret_cast<const f4*>(bp + 16 * tq + 4 * g);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) hid[tq][r] = fmaxf(fmaf(bt[r], sigma, hid[tq][r]), 0.f);
-  }
-  return rs;
-}
 
 template <bool KNN, bool POS, int MAXT, int THREADS, bool FUSED>
 __global__ __launch_bounds__(THREADS, FUSED ? 1 : 3) void node_attn_kernel(PgTopo t, PgSegAttn p) {
@@ -174,7 +139,7 @@ __global__ __launch_bounds__(THREADS, FUSED ? 1 : 3) void node_attn_kernel(PgTop
       }
 #pragma unroll
       for (int tile = 0; tile < MAXT; ++tile) {
-        lg[tile] = (f4){NA_NEG, NA_NEG, NA_NEG, NA_NEG};
+        lg[tile] = (f4){NEG_BIG, NEG_BIG, NEG_BIG, NEG_BIG};
         if constexpr (POS) vv[tile] = (f4){0.f, 0.f, 0.f, 0.f};
         if (tile < n_tiles) {
           const int k = tile * 16 + m;
@@ -232,7 +197,7 @@ __global__ __launch_bounds__(THREADS, FUSED ? 1 : 3) void node_attn_kernel(PgTop
               f4 c = {0.f, 0.f, 0.f, 0.f};
               if constexpr (KNN) {
                 // an invalid row keeps context row 0 here: the key path is row-local (the feature MFMAs, the LayerNorm over the
-                // channels of row m, the logit MFMAs) and its logit is replaced by NA_NEG below, so nothing of it reaches a valid row
+                // channels of row m, the logit MFMAs) and its logit is replaced by NEG_BIG below, so nothing of it reaches a valid row
                 c = *reinterpret_cast<const f4*>(pk + 16 * tq);
               } else {
                 if (valid) c = *reinterpret_cast<const f4*>(pk + 16 * tq);
@@ -253,7 +218,7 @@ __global__ __launch_bounds__(THREADS, FUSED ? 1 : 3) void node_attn_kernel(PgTop
                 hid[tq] = mfma16(w, feat[tile][st], hid[tq]);
               }
           }
-          const float rs = ln_fold_k(hid, bpk, g);
+          const float rs = ln_relu_kpath(hid, bpk, g);
           f4 acc = {0.f, 0.f, 0.f, 0.f}, acc2 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
           for (int tq = 0; tq < 8; ++tq)
@@ -268,7 +233,7 @@ __global__ __launch_bounds__(THREADS, FUSED ? 1 : 3) void node_attn_kernel(PgTop
             const int kr = tile * 16 + 4 * g + r;
             const bool vr = kr < n_rows && (KNN || kr != li);
             const float sc_ = acc[r] * __shfl(rs, 4 * g + r);      // shuffle outside the select: every source lane must be live
-            lg[tile][r] = vr ? sc_ : NA_NEG;
+            lg[tile][r] = vr ? sc_ : NEG_BIG;
           }
           if constexpr (POS) {
             // ---- value MLP of the position update (K-path form): v[row,h] = z . W2xv[h,:] + b ----
@@ -299,7 +264,7 @@ __global__ __launch_bounds__(THREADS, FUSED ? 1 : 3) void node_attn_kernel(PgTop
                   hx[tq] = mfma16(w, feat[tile][st], hx[tq]);
                 }
             }
-            const float rsx = ln_fold_k(hx, bpv, g);
+            const float rsx = ln_relu_kpath(hx, bpv, g);
             f4 a1 = {0.f, 0.f, 0.f, 0.f}, a2 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int tq = 0; tq < 8; ++tq)
@@ -331,7 +296,7 @@ __global__ __launch_bounds__(THREADS, FUSED ? 1 : 3) void node_attn_kernel(PgTop
     }
 
     // ======================= softmax over all rows, head m =======================
-    float mx = NA_NEG;
+    float mx = NEG_BIG;
 #pragma unroll
     for (int tile = 0; tile < MAXT; ++tile)
 #pragma unroll
@@ -347,7 +312,7 @@ __global__ __launch_bounds__(THREADS, FUSED ? 1 : 3) void node_attn_kernel(PgTop
       }
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float e = lg[tile][r] > 0.5f * NA_NEG ? __builtin_amdgcn_exp2f(lg[tile][r] - mx) : 0.f;
+        const float e = lg[tile][r] > 0.5f * NEG_BIG ? __builtin_amdgcn_exp2f(lg[tile][r] - mx) : 0.f;
         l += e;
         lg[tile][r] = e * gate[r];           // attention weight x edge gate (v = MLP(...) * e_w, uni_denoiser.py:52-54)
         sw += lg[tile][r];
@@ -448,7 +413,7 @@ __global__ __launch_bounds__(THREADS, FUSED ? 1 : 3) void node_attn_kernel(PgTop
           f4 sg, aw;
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const float var = row16_sum_na(q2[r]) * (1.f / 128.f) + 1e-5f;
+            const float var = row16_total(q2[r]) * (1.f / 128.f) + 1e-5f;
             const float rsq = __builtin_amdgcn_rsqf(var);
             sg[r] = var * rsq;
             aw[r] = lg[tile][r] * rsq;
@@ -598,7 +563,7 @@ __global__ __launch_bounds__(768, 1) void node_attn_pos_tiled_kernel(PgTopo t, P
     int seg = 0, n_rows = 0, lig0 = 0, n = 0, li = 0, n_tiles = 0;
     const int* eid_g = nullptr;
     float xd[3] = {0.f, 0.f, 0.f}, nd[3] = {0.f, 0.f, 0.f};
-    f4 lg = {NA_NEG, NA_NEG, NA_NEG, NA_NEG}, vv = {0.f, 0.f, 0.f, 0.f};
+    f4 lg = {NEG_BIG, NEG_BIG, NEG_BIG, NEG_BIG}, vv = {0.f, 0.f, 0.f, 0.f};
     if (active) {
       seg = p.seg_ids ? p.seg_ids[si] : si;
       if constexpr (KNN) {
@@ -708,7 +673,7 @@ __global__ __launch_bounds__(768, 1) void node_attn_pos_tiled_kernel(PgTopo t, P
             hid[tq] = mfma16(w, feat[st], hid[tq]);
           }
       }
-      const float rs = ln_fold_k(hid, bpk, g);
+      const float rs = ln_relu_kpath(hid, bpk, g);
       f4 acc = {0.f, 0.f, 0.f, 0.f}, acc2 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int tq = 0; tq < 8; ++tq)
@@ -723,7 +688,7 @@ __global__ __launch_bounds__(768, 1) void node_attn_pos_tiled_kernel(PgTopo t, P
         const int kr = tile * 16 + 4 * g + r;
         const bool vr = kr < n_rows && (KNN || kr != li);
         const float sc_ = acc[r] * __shfl(rs, 4 * g + r);
-        lg[r] = vr ? sc_ : NA_NEG;
+        lg[r] = vr ? sc_ : NEG_BIG;
       }
       // ---- value MLP of the position update: v[row,h] ----
       f4 hx[8];
@@ -749,7 +714,7 @@ __global__ __launch_bounds__(768, 1) void node_attn_pos_tiled_kernel(PgTopo t, P
             hx[tq] = mfma16(w, feat[st], hx[tq]);
           }
       }
-      const float rsx = ln_fold_k(hx, bpv, g);
+      const float rsx = ln_relu_kpath(hx, bpv, g);
       f4 a1 = {0.f, 0.f, 0.f, 0.f}, a2 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int tq = 0; tq < 8; ++tq)
@@ -767,7 +732,7 @@ __global__ __launch_bounds__(768, 1) void node_attn_pos_tiled_kernel(PgTopo t, P
     // ---- the tiles of a node meet: per-head maximum (exact in any order) ----
     xmax[wave * 64 + lane] = fmaxf(fmaxf(lg[0], lg[1]), fmaxf(lg[2], lg[3]));
     __syncthreads();
-    float mx = NA_NEG;
+    float mx = NEG_BIG;
 #pragma unroll
     for (int tt = 0; tt < T; ++tt) mx = fmaxf(mx, xmax[(slot * T + tt) * 64 + lane]);
     mx = fmaxf(mx, __shfl_xor(mx, 16));
@@ -780,7 +745,7 @@ __global__ __launch_bounds__(768, 1) void node_attn_pos_tiled_kernel(PgTopo t, P
       f4 e4, w4;
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
-        const float e = lg[r] > 0.5f * NA_NEG ? __builtin_amdgcn_exp2f(lg[r] - mx) : 0.f;
+        const float e = lg[r] > 0.5f * NEG_BIG ? __builtin_amdgcn_exp2f(lg[r] - mx) : 0.f;
         e4[r] = e;
         w4[r] = (e * gate[r]) * vv[r];
       }

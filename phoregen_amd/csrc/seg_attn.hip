@@ -21,29 +21,7 @@ int launch_triplet_staged(const PgTopo* t, const PgSegAttn* p, hipStream_t st); 
 int launch_node_attn(const PgTopo* t, const PgSegAttn* p, hipStream_t st);   // node_attn.hip (-1: shape not covered)
 bool node_attn_fused_request(const PgSegAttn* p);                            // node_attn.hip
 
-// Folded LayerNorm + ReLU (packing._kv_mlp: hidden is centred and sign-normalised, |gamma| lives in the next Linear):
-// z = ReLU(hidden + b' * sigma); returns 1/sigma, which the caller applies to the row's logits / attention weights.
-// K-path tile: hid[tau][r] = hidden[c = 16 tau + 4g + r][row = m]
-__device__ __forceinline__ float ln_relu_kpath(f4 (&hid)[8], const float* bp, int g) {
-  float q = 0.f;
-#pragma unroll
-  for (int tq = 0; tq < 8; ++tq)
-#pragma unroll
-    for (int r = 0; r < 4; ++r) q = fmaf(hid[tq][r], hid[tq][r], q);
-  q += __shfl_xor(q, 16);
-  q += __shfl_xor(q, 32);
-  const float var = q * (1.f / 128.f) + 1e-5f;
-  const float rs = __builtin_amdgcn_rsqf(var);
-  const float sigma = var * rs;
-#pragma unroll
-  for (int tq = 0; tq < 8; ++tq) {
-    const f4 bt = *reinterpret_cast<const f4*>(bp + 16 * tq + 4 * g);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) hid[tq][r] = fmaxf(fmaf(bt[r], sigma, hid[tq][r]), 0.f);
-  }
-  return rs;
-}
-
+// Folded LayerNorm + ReLU like ln_relu_kpath (wave_prims.h) on a
 // V-path tile: hid[tau][r] = hidden[row = 4g + r][c = 16 tau + m]; returns 1/sigma per row r
 __device__ __forceinline__ f4 ln_relu_vpath(f4 (&hid)[8], const float* bp, int m) {
   f4 q = {0.f, 0.f, 0.f, 0.f};

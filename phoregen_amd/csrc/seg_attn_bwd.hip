@@ -50,26 +50,6 @@ struct RowGeo {
   bool src_lig;
 };
 
-// sin(x) or cos(x) for 0 <= x <= ~10 (angular code arguments are bounded by 3 pi): k = rint(x * 2/pi), two-constant
-// Cody-Waite reduction, degree-9 / degree-8 polynomials on [-pi/4, pi/4], quadrant select (csrc/triplet2.hip uses the same)
-__device__ __forceinline__ float sincos_bounded(float arg, bool want_cos) {
-  const float kf = rintf(arg * 0.63661977236758134308f);
-  float r = fmaf(-kf, 1.57079637050628662109375f, arg);
-  r = fmaf(-kf, -4.37113900018624283e-8f, r);
-  const int q = ((int)kf + (want_cos ? 1 : 0)) & 3;
-  const float s = r * r;
-  float ps = fmaf(s, 2.7557314297e-6f, -1.9841270114e-4f);
-  ps = fmaf(ps, s, 8.3333337680e-3f);
-  ps = fmaf(ps, s, -1.6666667163e-1f);
-  ps = fmaf(ps * s, r, r);
-  float pc = fmaf(s, 2.4801587642e-5f, -1.3888889225e-3f);
-  pc = fmaf(pc, s, 4.1666667908e-2f);
-  pc = fmaf(pc, s, -0.5f);
-  pc = fmaf(pc, s, 1.0f);
-  const float v = (q & 1) ? pc : ps;
-  return (q & 2) ? -v : v;
-}
-
 // features of row rk for f = 4 step + g (same definitions as seg_attn.hip), plus what the backward needs
 template <int MODE, int NS>
 __device__ __forceinline__ void row_features(const PgTopo& t, const PgSegAttn& p, const RowInfo& rk, const float (&xd)[3],

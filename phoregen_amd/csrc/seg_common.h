@@ -1,11 +1,9 @@
 // Definitions shared by the generic segment-attention kernels (forward: seg_attn.hip, backward: seg_attn_bwd.hip).
 #pragma once
-#include "common.h"
+#include "wave_prims.h"
 #include "../../include/phoregen_hip.h"
 
 namespace pg {
-
-constexpr float NEG_BIG = -1.0e30f;
 
 template <int MODE> struct ModeTraits;
 template <> struct ModeTraits<PG_SEG_KNN_NODE>  { static constexpr int NSTEP = 12; static constexpr bool POS = false, KNN = true,  BOND = false, TRI = false, PH = false; };
@@ -14,10 +12,6 @@ template <> struct ModeTraits<PG_SEG_BOND_NODE> { static constexpr int NSTEP = 0
 template <> struct ModeTraits<PG_SEG_BOND_POS>  { static constexpr int NSTEP = 0;  static constexpr bool POS = true,  KNN = false, BOND = true,  TRI = false, PH = false; };
 template <> struct ModeTraits<PG_SEG_TRIPLET>   { static constexpr int NSTEP = 3;  static constexpr bool POS = false, KNN = false, BOND = false, TRI = true,  PH = false; };
 template <> struct ModeTraits<PG_SEG_PHORE>     { static constexpr int NSTEP = 1;  static constexpr bool POS = false, KNN = false, BOND = false, TRI = false, PH = true;  };
-
-// angular features of the triplet update (models/common.py:67-87 with duplicated sin/cos(theta) columns merged)
-__device__ __constant__ const float kAngFreq[12] = {0.f, 1.f, 2.f, 3.f, 0.5f, (float)(1.0 / 3.0), 1.f, 2.f, 3.f, 0.5f,
-                                                    (float)(1.0 / 3.0), 0.f};
 
 struct RowInfo {
   bool valid;
@@ -95,26 +89,6 @@ __device__ __forceinline__ Seg<MODE> setup_seg(const PgTopo& t, const PgSegAttn&
     s.n_rows = t.g_nph[gi];
   }
   return s;
-}
-
-template <int CTRL>
-__device__ __forceinline__ float dpp_mov(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-// sum over the 16 lanes of a DPP row (lanes with equal lane>>4); every lane ends up with the total
-__device__ __forceinline__ float row16_total(float v) {
-  v += dpp_mov<0xB1>(v);    // quad_perm [1,0,3,2]
-  v += dpp_mov<0x4E>(v);    // quad_perm [2,3,0,1]
-  v += dpp_mov<0x141>(v);   // row_half_mirror
-  v += dpp_mov<0x140>(v);   // row_mirror
-  return v;
-}
-
-// LDS written by some lanes of a wave and read by others: order the accesses without a workgroup barrier
-__device__ __forceinline__ void wave_lds_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
 }
 
 }  // namespace pg

@@ -17,7 +17,7 @@
 // Q = Wg2 . smear(d_ji) comes in as a row of Cdst (a [n_bond,20]x[20,256] GEMM per layer) and reaches the MFMA through the
 // spare feature column.
 // Lane l = (g = l>>4, m = l&15); 16x16x4 maps as in seg_attn.hip.
-#include "common.h"
+#include "wave_prims.h"
 #include "../../include/phoregen_hip.h"
 
 namespace pg {
@@ -44,66 +44,6 @@ typedef float t2_f2 __attribute__((ext_vector_type(2)));
 constexpr int T2_ROW = 260;          // floats per staged row: P_k[128] | P_v[128] | 4 (bank spread of the b128 key-layout reads)
 constexpr int T2_ROWS = 80;          // staged rows per workgroup
 constexpr int T2_XS = 96;            // ligand atoms whose coordinates are staged
-constexpr float T2_NEG = -1.0e30f;
-
-template <int CTRL>
-__device__ __forceinline__ float t2_dpp(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float t2_row16_sum(float v) {
-  v += t2_dpp<0xB1>(v);    // quad_perm [1,0,3,2]
-  v += t2_dpp<0x4E>(v);    // quad_perm [2,3,0,1]
-  v += t2_dpp<0x141>(v);   // row_half_mirror
-  v += t2_dpp<0x140>(v);   // row_mirror
-  return v;
-}
-__device__ __forceinline__ float t2_from_lane(float v, int src_lane) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(src_lane << 2, __builtin_bit_cast(int, v)));
-}
-
-// sin(w*theta) or cos(w*theta) for 0 <= arg <= ~10: k = rint(arg * 2/pi), r = arg - k*pi/2 (two constants),
-// sin/cos polynomials on [-pi/4, pi/4], quadrant select; cos(x) = sin-quadrant shifted by one (exact)
-__device__ __forceinline__ float t2_sincos(float arg, bool want_cos) {
-  const float kf = rintf(arg * 0.63661977236758134308f);
-  float r = fmaf(-kf, 1.57079637050628662109375f, arg);
-  r = fmaf(-kf, -4.37113900018624283e-8f, r);
-  const int q = ((int)kf + (want_cos ? 1 : 0)) & 3;
-  const float s = r * r;
-  float ps = fmaf(s, 2.7557314297e-6f, -1.9841270114e-4f);
-  ps = fmaf(ps, s, 8.3333337680e-3f);
-  ps = fmaf(ps, s, -1.6666667163e-1f);
-  ps = fmaf(ps * s, r, r);
-  float pc = fmaf(s, 2.4801587642e-5f, -1.3888889225e-3f);
-  pc = fmaf(pc, s, 4.1666667908e-2f);
-  pc = fmaf(pc, s, -0.5f);
-  pc = fmaf(pc, s, 1.0f);
-  const float v = (q & 1) ? pc : ps;
-  return (q & 2) ? -v : v;
-}
-
-// sin and cos of one argument (0 <= arg <= ~4) from ONE range reduction: k = rint(arg * 2/pi), r = arg - k pi/2 (two constants),
-// both polynomials on [-pi/4, pi/4], quadrant rotation
-__device__ __forceinline__ void t2_sincos_pair(float arg, float& sn, float& cs) {
-  const float kf = rintf(arg * 0.63661977236758134308f);
-  float r = fmaf(-kf, 1.57079637050628662109375f, arg);
-  r = fmaf(-kf, -4.37113900018624283e-8f, r);
-  const int q = (int)kf;
-  const float s = r * r;
-  float ps = fmaf(s, 2.7557314297e-6f, -1.9841270114e-4f);
-  ps = fmaf(ps, s, 8.3333337680e-3f);
-  ps = fmaf(ps, s, -1.6666667163e-1f);
-  ps = fmaf(ps * s, r, r);
-  float pc = fmaf(s, 2.4801587642e-5f, -1.3888889225e-3f);
-  pc = fmaf(pc, s, 4.1666667908e-2f);
-  pc = fmaf(pc, s, -0.5f);
-  pc = fmaf(pc, s, 1.0f);
-  const float a = (q & 1) ? pc : ps, b = (q & 1) ? ps : pc;       // sin(arg) = +-a, cos(arg) = +-b
-  sn = (q & 2) ? -a : a;
-  cs = ((q + 1) & 2) ? -b : b;
-}
-
-__device__ __constant__ const float kT2Freq[12] = {0.f, 1.f, 2.f, 3.f, 0.5f, (float)(1.0 / 3.0), 1.f, 2.f, 3.f, 0.5f,
-                                                    (float)(1.0 / 3.0), 0.f};
 
 constexpr size_t t2_lds_floats() { return 16384 + 2 * 1536 + 3 * 128 + 3 * T2_XS + 4 + (size_t)T2_ROWS * T2_ROW; }
 
@@ -271,21 +211,21 @@ __global__ __launch_bounds__(THREADS) void triplet2_kernel(PgTopo t, PgSegAttn p
         }
 #pragma unroll
         for (int tile = 0; tile < MAXT; ++tile) {
-          lg[tile] = (f4){T2_NEG, T2_NEG, T2_NEG, T2_NEG};
+          lg[tile] = (f4){NEG_BIG, NEG_BIG, NEG_BIG, NEG_BIG};
           feat[tile][0] = feat[tile][1] = feat[tile][2] = 0.f;
           if (tile < n_tiles) {
             const int kp = tile * 16 + m;                                  // row = k-th atom that is neither j nor i
             const int kq = kp < nr ? kp : 0;                               // rows past the ligand read the first row (finite, masked below)
             const int kc = kq + (kq >= ip ? 1 : 0);
-            const float theta = t2_from_lane(th_own[tile >> 2], 16 * (tile & 3) + m);
+            const float theta = from_lane(th_own[tile >> 2], 16 * (tile & 3) + m);
             // angular features of row kp for f = 4 step + g  (common.py:85); f = 11 carries the per-segment constant Q
             // the four lanes of a row share the work: lane g evaluates sin / cos of theta, theta/2, theta/3 (one range reduction
             // each; g = 3 idles), three ds_bpermutes hand round what the others need, the multiples come from
             // sin 2t = 2 s c, sin 3t = s (3 - 4 s^2), cos 2t = 1 - 2 s^2, cos 3t = c (4 c^2 - 3)
             float sg, cg;
-            t2_sincos_pair(theta * (g == 0 ? 1.0f : (g == 1 ? 0.5f : (float)(1.0 / 3.0))), sg, cg);
-            const float s1 = t2_from_lane(sg, m), c1 = t2_from_lane(cg, m);
-            const float sx = t2_from_lane(sg, m + (g == 0 ? 16 : 32));      // g = 0: sin(theta/2), g = 1: sin(theta/3)
+            sincos_bounded_pair(theta * (g == 0 ? 1.0f : (g == 1 ? 0.5f : (float)(1.0 / 3.0))), sg, cg);
+            const float s1 = from_lane(sg, m), c1 = from_lane(cg, m);
+            const float sx = from_lane(sg, m + (g == 0 ? 16 : 32));      // g = 0: sin(theta/2), g = 1: sin(theta/3)
             // f = 4 st + g: [theta, sin t, sin 2t, sin 3t | sin t/2, sin t/3, cos t, cos 2t | cos 3t, cos t/2, cos t/3, 1 (Q)]
             feat[tile][0] = g == 0 ? theta : (g == 1 ? s1 : (g == 2 ? 2.0f * s1 * c1 : s1 * fmaf(-4.0f * s1, s1, 3.0f)));
             feat[tile][1] = g < 2 ? sx : (g == 2 ? c1 : fmaf(-2.0f * s1, s1, 1.0f));
@@ -334,7 +274,7 @@ __global__ __launch_bounds__(THREADS) void triplet2_kernel(PgTopo t, PgSegAttn p
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
               const int kr = tile * 16 + 4 * g + r;
-              lg[tile][r] = kr < nr ? acc[r] : T2_NEG;
+              lg[tile][r] = kr < nr ? acc[r] : NEG_BIG;
             }
           }
         }
@@ -342,7 +282,7 @@ __global__ __launch_bounds__(THREADS) void triplet2_kernel(PgTopo t, PgSegAttn p
 
       T2_STAMP(3);                                // theta, fold, pass A
       // =============================== softmax over all rows, per head m ===============================
-      float mx = T2_NEG;
+      float mx = NEG_BIG;
 #pragma unroll
       for (int tile = 0; tile < MAXT; ++tile)
 #pragma unroll
@@ -354,7 +294,7 @@ __global__ __launch_bounds__(THREADS) void triplet2_kernel(PgTopo t, PgSegAttn p
       for (int tile = 0; tile < MAXT; ++tile)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const float e = lg[tile][r] > 0.5f * T2_NEG ? __builtin_amdgcn_exp2f(lg[tile][r] - mx) : 0.f;
+          const float e = lg[tile][r] > 0.5f * NEG_BIG ? __builtin_amdgcn_exp2f(lg[tile][r] - mx) : 0.f;
           lg[tile][r] = e;
           l += e;
         }
@@ -412,7 +352,7 @@ __global__ __launch_bounds__(THREADS) void triplet2_kernel(PgTopo t, PgSegAttn p
           f4 sg, aw;
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const float var = t2_row16_sum(q2[r]) * (1.f / 128.f) + 1e-5f;
+            const float var = row16_total(q2[r]) * (1.f / 128.f) + 1e-5f;
             const float rsq = __builtin_amdgcn_rsqf(var);
             sg[r] = var * rsq;
             aw[r] = lg[tile][r] * rsq;                                      // alpha * rstd of the row

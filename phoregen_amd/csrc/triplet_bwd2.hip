@@ -40,24 +40,6 @@ namespace {
 
 constexpr float TB2_LN2 = 0.69314718055994530942f;
 
-__device__ __forceinline__ float tb2_sincos(float arg, bool want_cos) {     // as seg_attn_bwd.hip sincos_bounded
-  const float kf = rintf(arg * 0.63661977236758134308f);
-  float r = fmaf(-kf, 1.57079637050628662109375f, arg);
-  r = fmaf(-kf, -4.37113900018624283e-8f, r);
-  const int q = ((int)kf + (want_cos ? 1 : 0)) & 3;
-  const float s = r * r;
-  float ps = fmaf(s, 2.7557314297e-6f, -1.9841270114e-4f);
-  ps = fmaf(ps, s, 8.3333337680e-3f);
-  ps = fmaf(ps, s, -1.6666667163e-1f);
-  ps = fmaf(ps * s, r, r);
-  float pc = fmaf(s, 2.4801587642e-5f, -1.3888889225e-3f);
-  pc = fmaf(pc, s, 4.1666667908e-2f);
-  pc = fmaf(pc, s, -0.5f);
-  pc = fmaf(pc, s, 1.0f);
-  const float v = (q & 1) ? pc : ps;
-  return (q & 2) ? -v : v;
-}
-
 template <int NW, int MAXT>
 struct Tb2Layout {
   static constexpr int NB = 8 / NW, CW = 16 * NB, ROWS = 16 * MAXT;
@@ -83,35 +65,6 @@ struct Tb2Layout {
   static constexpr int PW = CW * 17 + 3;                          // (odd tile stride between the waves)
   static constexpr int total = o_wave + NW * PW;
 };
-
-template <int CTRL>
-__device__ __forceinline__ float tb2_dpp(float v) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float tb2_row16_max(float v) {
-  v = fmaxf(v, tb2_dpp<0xB1>(v));
-  v = fmaxf(v, tb2_dpp<0x4E>(v));
-  v = fmaxf(v, tb2_dpp<0x141>(v));
-  v = fmaxf(v, tb2_dpp<0x140>(v));
-  return v;
-}
-
-typedef int tb2_i4 __attribute__((ext_vector_type(4)));
-// raw buffer descriptor over `bytes` at `base` (wave-uniform)
-__device__ __forceinline__ tb2_i4 tb2_desc(const void* base, unsigned bytes) {
-  const unsigned long long a = reinterpret_cast<unsigned long long>(base);
-  tb2_i4 d;
-  d[0] = __builtin_amdgcn_readfirstlane((int)(a & 0xffffffffu));
-  d[1] = __builtin_amdgcn_readfirstlane((int)((a >> 32) & 0xffffu));
-  d[2] = __builtin_amdgcn_readfirstlane((int)bytes);
-  d[3] = 0x00020000;
-  return d;
-}
-// one 1 KB piece HBM -> LDS without registers (as gemm_stream.hip st_dma): lane l's 16 bytes from base + voff + soff land at lds_dst + 16 l
-__device__ __forceinline__ void tb2_dma(unsigned lds_dst, unsigned voff, tb2_i4 desc, unsigned soff) {
-  asm volatile("s_nop 4\n\ts_mov_b32 m0, %0\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds"
-               :: "s"(lds_dst), "v"(voff), "s"(desc), "s"(soff) : "memory");
-}
 
 }  // namespace
 
@@ -144,14 +97,14 @@ __global__ __launch_bounds__(64 * NW, PG_TB2_MINWAVES) void triplet_bwd2_kernel(
   // the 17 one-KB pieces of a segment's operands (8 of U, 8 of d S, the Cdst row k | v), dealt out over the waves; `lds` is the kernel's
   // only LDS object, so a float offset into it is the LDS address
   auto stage_operands = [&](int seg_next, int ob) {
-    const tb2_i4 dU = tb2_desc(p.U + (size_t)seg_next * 2048, 8192), dM = tb2_desc(gr.gS + (size_t)seg_next * 2048, 8192);
-    const tb2_i4 dC = tb2_desc(p.Cdst_k + (size_t)seg_next * p.ld_cdst, 1024);
+    const i4v dU = raw_buffer_desc(p.U + (size_t)seg_next * 2048, 8192), dM = raw_buffer_desc(gr.gS + (size_t)seg_next * 2048, 8192);
+    const i4v dC = raw_buffer_desc(p.Cdst_k + (size_t)seg_next * p.ld_cdst, 1024);
     for (int pc = __builtin_amdgcn_readfirstlane(wave); pc < 17; pc += NW) {
       const unsigned dst = (unsigned)__builtin_amdgcn_readfirstlane((Ly::o_op + ob * 4352 + pc * 256) * 4);
       const unsigned so = (unsigned)__builtin_amdgcn_readfirstlane((pc & 7) * 1024);
-      if (pc < 8) tb2_dma(dst, 16u * lane, dU, so);
-      else if (pc < 16) tb2_dma(dst, 16u * lane, dM, so);
-      else tb2_dma(dst, 16u * lane, dC, 0u);
+      if (pc < 8) lds_dma_1k(dst, 16u * lane, dU, so);
+      else if (pc < 16) lds_dma_1k(dst, 16u * lane, dM, so);
+      else lds_dma_1k(dst, 16u * lane, dC, 0u);
     }
   };
   constexpr int YT = Ly::YT, QT = Ly::QT, ROWS = Ly::ROWS;
@@ -203,7 +156,7 @@ __global__ __launch_bounds__(64 * NW, PG_TB2_MINWAVES) void triplet_bwd2_kernel(
 #pragma unroll
     for (int st = 0; st < 3; ++st) {
       const int f = 4 * st + g;
-      float v = tb2_sincos(theta * kAngFreq[f], f >= 6);
+      float v = sincos_bounded(theta * kAngFreq[f], f >= 6);
       v = f == 0 ? theta : v;
       dst[f] = (valid && f != 11) ? v : 0.f;
     }
@@ -448,7 +401,7 @@ __global__ __launch_bounds__(64 * NW, PG_TB2_MINWAVES) void triplet_bwd2_kernel(
             mx = fmaxf(mx, lg[q]);
           }
         }
-        mx = tb2_row16_max(mx);
+        mx = row16_max(mx);
         if constexpr (RS == 32) mx = fmaxf(mx, __shfl_xor(mx, 16));
         float e[NQ], l = 0.f;
 #pragma unroll
