@@ -473,6 +473,40 @@ int pg_mol_screen(const float* node_scores, int64_t node_fs, const float* edge_s
 int pg_mol_key(const int8_t* cls, const int8_t* order, const int* g_lig_off /*[B+1]*/, const int* g_bond_off /*[B+1]*/, int B, int F,
                int n_lig, int n_bond, int max_n, int64_t* key, int64_t* colour, void* stream);
 
+/* Geometry and pharmacophore fit of the molecules the screen decoded, one wave per (frame, graph).  Reads the coordinates (pos, pos_fs
+ * as pg_mol_screen takes them) and the screen's outputs cls [F][n_lig] and order [F][n_bond / 2] (frames dense) with the same offsets.
+ * An atom is kept if its class is 0..10 and its three coordinates are finite; a kept-class atom with a non-finite coordinate sets
+ * PG_GEOM_NONFINITE and is left out of everything else.  A pair a < b of kept atoms is bonded if its order is 1..4, else non-bonded.
+ * Distance = sqrtf(dx*dx + dy*dy + dz*dz) in fp32 from fp32 differences.  Points: point_pos [n_point][3] in the coordinates of pos,
+ * point_is_ex [n_point] (non-zero = exclusion sphere, else feature); graph g has the rows g_point_range[g][0] .. [g][1] (ranges may
+ * coincide between graphs and may be empty) and writes its per-point outputs from g_point_out_off[g] on (g_point_out_off [B+1], the
+ * running sum of the range lengths; n_point_out = its last entry).  A non-finite point sets PG_GEOM_NONFINITE too, has point_dist +inf
+ * and point_atom -1, and is left out of everything else.  limits: five floats in HOST memory, read during the call: bond_min,
+ * bond_max, clash_min, ex_clear, feat_cut; all comparisons are strict.
+ *   point_dist [F][n_point_out], point_atom [F][n_point_out]: distance to the nearest kept atom and that atom's compact index (its
+ *     index among the graph's atoms of class 0..10, as the screen's `compact`); first minimum in atom order; +inf and -1 without one
+ *   metrics [F][B][8]: 0 min / 1 max bonded distance (+inf / -inf without a bond), 2 min non-bonded distance (+inf if none),
+ *     3 min point_dist over exclusion spheres (+inf if none), 4 max point_dist over features (-inf if none), 5 |centroid of the kept
+ *     atoms - mean of the features| (NaN if either is empty), 6 mean over bonds of max(d - bond_max, 0) + max(bond_min - d, 0)
+ *     (0 without a bond), 7 = 0 (reserved).  5 and 6 are summed in fp64 from the fp32 inputs and rounded once.
+ *   counts [F][B][6]: bonds with d < bond_min, bonds with d > bond_max, non-bonded pairs with d < clash_min, (atom, exclusion sphere)
+ *     pairs with d < ex_clear, features with point_dist < feat_cut, features
+ *   status [F][B]: PG_GEOM_* bits; the first four are set exactly when their count is non-zero, FEATURE_MISSED when covered < features
+ * Sums are per-lane partials in a fixed lane-to-element assignment and a fixed butterfly, no floating-point atomics: a graph's row does
+ * not depend on its batch.  max_n above PG_MOL_MAX_ATOMS or a negative size: error before anything is launched, outputs untouched.
+ * Every element of every output is written (nothing needs zeroing). */
+#define PG_GEOM_BOND_SHORT 1
+#define PG_GEOM_BOND_LONG 2
+#define PG_GEOM_CLASH 4
+#define PG_GEOM_EX_CLASH 8
+#define PG_GEOM_FEATURE_MISSED 16    /* informational: a feature without a kept atom inside feat_cut */
+#define PG_GEOM_NONFINITE 32
+int pg_mol_geom(const float* pos, int64_t pos_fs, const int8_t* cls, const int8_t* order, const int* g_lig_off /*[B+1]*/,
+                const int* g_bond_off /*[B+1]*/, int B, int F, int n_lig, int n_bond, int max_n, const float* point_pos,
+                const uint8_t* point_is_ex, int n_point, const int* g_point_range /*[B][2]*/, const int* g_point_out_off /*[B+1]*/,
+                int n_point_out, const float* limits /*[5] host*/, float* point_dist, int16_t* point_atom, float* metrics, int* counts,
+                int* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,6 +33,20 @@ __device__ __forceinline__ float row16_max(float v) {
   v = fmaxf(v, dpp_mov<0x140>(v));
   return v;
 }
+// max / min / sum over all 64 lanes, every lane ends up with the result: a fixed butterfly, so the result depends on the lanes'
+// values alone (call with the whole wave active)
+__device__ __forceinline__ float wave_max(float v) {
+  v = row16_max(v);
+  v = fmaxf(v, __shfl_xor(v, 16));
+  return fmaxf(v, __shfl_xor(v, 32));
+}
+__device__ __forceinline__ float wave_min(float v) { return -wave_max(-v); }
+template <typename T>
+__device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
 // v of lane src_lane (any lane of the wave, ds_bpermute)
 __device__ __forceinline__ float from_lane(float v, int src_lane) {
   return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(src_lane << 2, __builtin_bit_cast(int, v)));

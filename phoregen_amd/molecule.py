@@ -9,8 +9,14 @@ that samples until enough molecules have passed.  No RDKit, no OpenBabel: `valid
 Identity: `molecule_keys` gives every decoded molecule a 64-bit key that does not depend on the numbering of its atoms
 (csrc/mol_key.hip; the definition is in DESIGN.md 2.9 "Identity"), `same_molecule` decides exactly whether two assembled molecules
 have the same atoms and bonds, `unique_molecules` / `duplicate_groups` / `sample_valid(unique=True)` use the two.  Equal keys are
-necessary, not sufficient, for equal molecules; this is not SMILES."""
-from dataclasses import dataclass
+necessary, not sufficient, for equal molecules; this is not SMILES.
+
+Geometry: `geometry` / `geometry_for` measure the decoded molecules where they lie (csrc/mol_geom.hip; DESIGN.md 2.9 "Geometry"):
+bond lengths, non-bonded clashes, clearance from the exclusion spheres, which feature points have an atom nearby, and the reference's
+two guidance energies on the decoded molecule.  `assemble(geometry=)`, `sample_valid(geometry=)` and `write_sdf` carry it.  Again
+necessary, not sufficient: no force field, no hydrogens, no feature typing."""
+import ctypes
+from dataclasses import astuple, dataclass
 
 import numpy as np
 import torch
@@ -48,6 +54,33 @@ KEY_ROUNDS = 3
 KEY_NO_PATH = 255
 KEY_EMPTY = 0xE220A8397B1DCDAF
 _M64 = (1 << 64) - 1
+
+# The geometry screen (DESIGN.md 2.9 "Geometry"): status bits, and the names of the metric and count columns in the kernel's order
+GEOM_BOND_SHORT = 1              # a bond shorter than bond_min
+GEOM_BOND_LONG = 2               # a bond longer than bond_max
+GEOM_CLASH = 4                   # two kept atoms without a bond closer than clash_min
+GEOM_EX_CLASH = 8                # a kept atom closer than ex_clear to an exclusion sphere's centre
+GEOM_FEATURE_MISSED = 16         # informational: a feature point without a kept atom closer than feat_cut
+GEOM_NONFINITE = 32              # a kept-class atom or a point with a non-finite coordinate
+GEOM_FAIL_MASK = GEOM_BOND_SHORT | GEOM_BOND_LONG | GEOM_CLASH | GEOM_EX_CLASH | GEOM_NONFINITE
+GEOM_NAMES = {GEOM_BOND_SHORT: 'BOND_SHORT', GEOM_BOND_LONG: 'BOND_LONG', GEOM_CLASH: 'CLASH', GEOM_EX_CLASH: 'EX_CLASH',
+              GEOM_FEATURE_MISSED: 'FEATURE_MISSED', GEOM_NONFINITE: 'NONFINITE'}
+GEOM_METRICS = ('bond_min', 'bond_max', 'nonbonded_min', 'ex_min', 'feature_max', 'centre_dist', 'bond_energy', 'reserved')
+GEOM_COUNTS = ('bonds_short', 'bonds_long', 'clashes', 'ex_clashes', 'features_covered', 'features')
+
+
+@dataclass(frozen=True)
+class GeomLimits:
+    """Limits of the geometry screen in Angstrom; every comparison is strict.  bond_min / bond_max: `compute_atom_prox_loss`'s min_d /
+    max_d (utils/sample_utils.py:135); ex_clear: the clearance `exclude_clashed_ex(low=3.0)` keeps between exclusion spheres and ligand
+    atoms (utils/phore_utils.py:511); feat_cut: `check_nearby_phore`'s cutoff (utils/phore_utils.py:406).  clash_min has no value in the
+    reference: it is bond_min, as a one-sided rule -- atoms without a bond closer than the shortest tolerated bond are wrong."""
+    bond_min: float = 1.2
+    bond_max: float = 2.8
+    clash_min: float = 1.2
+    ex_clear: float = 3.0
+    feat_cut: float = 2.0
+
 
 _max_valence2 = {}               # device -> uint8 [11], twice MAX_VALENCE in class order
 
@@ -127,6 +160,9 @@ def screen(results, frames='final'):
     return Screen(valid=(out['status'] & FAIL_MASK) == 0, lig_off=lig_off, bond_off=bond_off, num_atoms=num_atoms, **out)
 
 
+_screen = screen                 # (functions below take a `screen=` argument)
+
+
 @dataclass
 class MolKeys:
     """Device tensors of one `molecule_keys` call.  The int64 values are 64-bit patterns: read them as unsigned (`& 2**64 - 1`)."""
@@ -172,6 +208,118 @@ def _launch(lib, node, node_fs, edge, edge_fs, pos, pos_fs, lig_off, bond_off, B
                                 out['order'].data_ptr(), hip.stream_ptr()), 'pg_mol_screen')
 
 
+@dataclass
+class Geometry:
+    """Device tensors of one `geometry` call; F frames, B graphs, Q = the graphs' point counts summed (graph g owns the columns
+    point_off[g] .. point_off[g + 1] of the per-point tensors)."""
+    status: torch.Tensor         # int32 [F, B]    GEOM_* bits
+    metrics: torch.Tensor        # fp32  [F, B, 8] GEOM_METRICS
+    counts: torch.Tensor         # int32 [F, B, 6] GEOM_COUNTS
+    ok: torch.Tensor             # bool  [F, B]    no bit of GEOM_FAIL_MASK
+    point_dist: torch.Tensor     # fp32  [F, Q]    distance of a point to the nearest kept atom (+inf: none)
+    point_atom: torch.Tensor     # int16 [F, Q]    that atom's compact index (the screen's), -1: none
+    point_off: torch.Tensor      # int32 [B + 1]
+    point_range: torch.Tensor    # int32 [B, 2]    rows of the graph's points in the point tensors that were handed in
+    limits: GeomLimits
+    screen: Screen               # the screen it was measured on
+
+
+def _point_ranges(point_batch, P, B, dev):
+    """(ranges [B, 2], offsets [B + 1]) of the graphs' points, int32 on the device, without a host read of device data."""
+    if point_batch is None:                                            # every graph has all points
+        ranges = torch.tensor([0, P], dtype=torch.int32).repeat(B, 1)
+        return ranges.to(dev), (torch.arange(B + 1, dtype=torch.int64) * P).int().to(dev)
+    pb = point_batch.reshape(-1)
+    if pb.numel() != P or pb.dtype not in (torch.int32, torch.int64):
+        raise ValueError(f'phoregen_amd.molecule.geometry: point_batch must hold one integer graph id per point ({P}), it has '
+                         f'{pb.numel()} of {pb.dtype}')
+    if pb.device.type == 'cpu' and P and (bool((pb[1:] < pb[:-1]).any()) or int(pb[0]) < 0 or int(pb[-1]) >= B):
+        raise ValueError(f'phoregen_amd.molecule.geometry: point_batch must be sorted graph ids in 0 .. {B - 1}')
+    # (a device tensor is taken as sorted: checking it would be a host read; the kernel skips a graph whose range does not fit)
+    pb = pb.to(dev).long().contiguous()
+    ids = torch.arange(B, device=dev)
+    start, end = torch.searchsorted(pb, ids), torch.searchsorted(pb, ids, right=True)
+    off = torch.zeros(B + 1, dtype=torch.int64, device=dev)
+    off[1:] = (end - start).cumsum(0)
+    return torch.stack([start, end], 1).int().contiguous(), off.int()
+
+
+@torch.no_grad()
+def geometry(results, point_pos, point_is_ex, point_batch=None, frames='final', screen=None, limits=GeomLimits()):
+    """Measure every decoded (frame, graph) of a `sample` / `sample_batch` result against its pharmacophore, on the device, in one
+    launch (pg_mol_geom).  point_pos [P, 3]: the points in the coordinates the frames hold (world coordinates for the final
+    prediction); point_is_ex [P]: non-zero = exclusion sphere, else feature.  point_batch=None: every graph has all P points (what
+    `sample` draws); else sorted graph ids per point, as `sample_batch`'s batch_phore.  A `Screen` of the same result and frames is
+    reused if handed in.  No host read beyond the screen's.  Necessary, not sufficient: a molecule that passes has plausible bond
+    lengths and stays out of the spheres, nothing more; 'covered' says an atom is near a feature, not that it is the matching group."""
+    _, pos, edge, F, (_, _, pos_fs) = _frames(results, frames)
+    dev = pos.device
+    if dev.type != 'cuda':
+        raise RuntimeError('phoregen_amd.molecule.geometry: the geometry screen is a HIP kernel and the result lives on %s; there is '
+                           'no CPU fallback' % dev)
+    lim = tuple(float(v) for v in astuple(limits))
+    if len(lim) != 5 or not all(np.isfinite(lim)):
+        raise ValueError(f'phoregen_amd.molecule.geometry: limits must be five finite numbers, not {limits!r}')
+    if not torch.is_tensor(point_pos) or point_pos.dim() != 2 or point_pos.size(1) != 3:
+        raise ValueError('phoregen_amd.molecule.geometry: point_pos must be a tensor [P, 3]')
+    P = point_pos.size(0)
+    if not torch.is_tensor(point_is_ex) or point_is_ex.numel() != P:
+        raise ValueError(f'phoregen_amd.molecule.geometry: {P} points, point_is_ex has {getattr(point_is_ex, "shape", None)}')
+    sc = screen if screen is not None else _screen(results, frames)
+    B, N = len(sc.num_atoms), pos.size(-2)
+    if tuple(sc.status.shape) != (F, B) or sc.cls.size(1) != N or sc.cls.device != dev or 2 * sc.order.size(1) != edge.size(-2):
+        raise ValueError(f'phoregen_amd.molecule.geometry: the screen ({tuple(sc.status.shape)} frames x graphs, {sc.cls.size(1)} atom '
+                         f'rows) is not one of this result and frames ({F} frames, {N} atom rows)')
+    row = pos[0] if pos.dim() == 3 and F > 0 else pos
+    if pos.dtype != torch.float32 or not (row.is_contiguous() or row.numel() == 0):
+        raise ValueError('phoregen_amd.molecule.geometry: coordinates must be contiguous fp32 [.., 3]')
+    with torch.cuda.device(dev):
+        lib = hip.lib()
+        ranges, off = _point_ranges(point_batch, P, B, dev)
+        Q = P * B if point_batch is None else P
+        ppos = point_pos.to(dev, torch.float32).contiguous()
+        pex = (point_is_ex.reshape(-1).to(dev) != 0).to(torch.uint8)
+        out = dict(status=torch.empty(F, B, dtype=torch.int32, device=dev), metrics=torch.empty(F, B, 8, dtype=torch.float32, device=dev),
+                   counts=torch.empty(F, B, 6, dtype=torch.int32, device=dev), point_dist=torch.empty(F, Q, dtype=torch.float32, device=dev),
+                   point_atom=torch.empty(F, Q, dtype=torch.int16, device=dev))
+        _launch_geom(lib, pos, pos_fs, sc.cls, sc.order, sc.lig_off, sc.bond_off, B, F, max(sc.num_atoms, default=0), ppos, pex, ranges,
+                     off, Q, lim, out)
+    return Geometry(ok=(out['status'] & GEOM_FAIL_MASK) == 0, point_off=off, point_range=ranges, limits=limits, screen=sc, **out)
+
+
+def geometry_for(data, results, frames='final', screen=None, limits=GeomLimits(), ex_col=12):
+    """`geometry` with the pharmacophore of `data` as `PhoreDiff.sample` reads it: the points are data['phore'].pos + data.center
+    (world coordinates, as the final prediction and the trajectory frames 1.. are), exclusion spheres are the rows with column
+    `ex_col` of data['phore'].x equal to 1 (12 for zinc_300 / pdbbind, `PhoreDiff.ex_col`), every graph has all points.  Frames are
+    measured in the coordinates they hold: trajectory frame 0 is stored without the centre, as in the reference, so its row says
+    little unless data.center is zero."""
+    ph = data['phore']
+    return geometry(results, ph.pos.float() + data.center.to(ph.pos.device).float(), ph.x[:, ex_col] == 1, None, frames, screen, limits)
+
+
+def _launch_geom(lib, pos, pos_fs, cls, order, lig_off, bond_off, B, F, max_n, point_pos, point_is_ex, ranges, off, n_out, limits, out):
+    """pg_mol_geom on the current stream.  A graph above MAX_ATOMS is the library's error: nothing is launched and `out` is not
+    written."""
+    dev = pos.device
+    for t, dt in ((cls, torch.int8), (order, torch.int8), (lig_off, torch.int32), (bond_off, torch.int32), (point_pos, torch.float32),
+                  (point_is_ex, torch.uint8), (ranges, torch.int32), (off, torch.int32)):
+        if t.dtype != dt or not t.is_contiguous() or t.device != dev:
+            raise ValueError('phoregen_amd.molecule.geometry: cls / order must be contiguous int8, offsets and ranges int32, points fp32, '
+                             'their kinds uint8, all on the device of the coordinates')
+    if (lig_off.numel() != B + 1 or bond_off.numel() != B + 1 or off.numel() != B + 1 or ranges.numel() != 2 * B or cls.numel() != F * cls.size(-1)
+            or order.numel() != F * order.size(-1) or point_is_ex.numel() != point_pos.size(0) or pos.size(-2) != cls.size(-1)
+            or tuple(out['point_dist'].shape) != (F, n_out) or tuple(out['point_atom'].shape) != (F, n_out)
+            or out['status'].numel() != F * B or out['metrics'].numel() != 8 * F * B or out['counts'].numel() != 6 * F * B):
+        raise ValueError('phoregen_amd.molecule.geometry: sizes of the offsets, ranges, screen arrays, points and outputs do not fit '
+                         f'{F} frames x {B} graphs, {cls.size(-1)} atom rows, {point_pos.size(0)} points, {n_out} point outputs')
+    hip.check(lib.pg_mol_geom(pos.data_ptr(), pos_fs, cls.data_ptr(), order.data_ptr(), lig_off.data_ptr(), bond_off.data_ptr(), B, F,
+                              cls.size(-1), 2 * order.size(-1), max_n, point_pos.data_ptr(), point_is_ex.data_ptr(), point_pos.size(0),
+                              ranges.data_ptr(), off.data_ptr(), n_out, (ctypes.c_float * 5)(*limits), out['point_dist'].data_ptr(),
+                              out['point_atom'].data_ptr(), out['metrics'].data_ptr(), out['counts'].data_ptr(),
+                              out['status'].data_ptr(), hip.stream_ptr()), 'pg_mol_geom')
+
+
+_geometry = geometry             # (functions below take a `geometry=` argument)
 _PAIRS = {}
 
 
@@ -185,16 +333,26 @@ def _pairs(n):
 
 
 @torch.no_grad()
-def assemble(results, keys=False):
+def assemble(results, keys=False, geometry=None):
     """The final prediction as one dict per graph with `decode_data`'s keys and meaning -- 'element' (atomic numbers), 'atom_pos'
     (kept atoms, the tensor's own fp32 values), 'bond_index' [2, n_b] (indices among the kept atoms) and 'bond_type' [n_b] for
     a < b only, in row order -- plus 'status', 'valid', 'n_components' and 'valence' (per kept atom, halves allowed).  The screen runs
     on the device; ONE device-to-host copy brings the compact arrays over, the split by offsets is on the host.
     keys=True: every dict also has 'key' (the identity key of `molecule_keys` as an unsigned Python int) and 'atom_colour' (uint64
-    per kept atom); they ride in the same copy."""
-    sc = screen(results, 'final')
+    per kept atom); they ride in the same copy.
+    geometry=a `Geometry` of this result's final frame: every dict also has 'geom' -- 'status' (GEOM_* bits), 'geom_ok' (no bit of
+    GEOM_FAIL_MASK), the eight GEOM_METRICS and the six GEOM_COUNTS by name, and 'point_dist' / 'point_atom' of the graph's points
+    (an index into this dict's atoms, -1 = none) -- in the same copy; its screen is reused."""
+    geom = geometry
+    if geom is not None and (geom.status.size(0) != 1 or geom.screen.cls.size(1) != results['pred'][1].size(-2)
+                             or geom.status.device != results['pred'][1].device):
+        raise ValueError('phoregen_amd.molecule.assemble: geometry= must be a Geometry of the final frame of this result')
+    sc = geom.screen if geom is not None else screen(results, 'final')
     parts = [sc.status[0], sc.counts[0], results['pred'][1], sc.compact[0], sc.cls[0], sc.valence2[0], sc.order[0]]
     dtypes = [np.int32, np.int32, np.float32, np.int16, np.int8, np.uint8, np.int8]
+    if geom is not None:                                               # (4-byte parts in front, the 2-byte one beside `compact`)
+        parts = [geom.status[0], geom.metrics[0], geom.counts[0], geom.point_dist[0], geom.point_off] + parts[:4] + [geom.point_atom[0]] + parts[4:]
+        dtypes = [np.int32, np.float32, np.int32, np.float32, np.int32] + dtypes[:4] + [np.int16] + dtypes[4:]
     if keys:                                                           # (64-bit parts first: every part stays aligned in the blob)
         mk = molecule_keys(sc)
         parts, dtypes = [mk.key[0], mk.colour[0]] + parts, [np.uint64, np.uint64] + dtypes
@@ -202,8 +360,12 @@ def assemble(results, keys=False):
     blob = torch.cat([p.reshape(-1).view(torch.uint8) for p in parts]).cpu().numpy()
     cut = np.cumsum([0] + sizes)
     views = [blob[cut[i]:cut[i + 1]].view(dt) for i, dt in enumerate(dtypes)]
-    status, counts, pos, compact, cls, valence2, order = views[-7:]
+    status, counts, pos, compact = views[-8:-4] if geom is not None else views[-7:-3]
+    cls, valence2, order = views[-3:]
     counts, pos = counts.reshape(-1, 4), pos.reshape(-1, 3)
+    if geom is not None:
+        g_status, g_metrics, g_counts, g_dist, g_off = views[-13:-8]
+        g_metrics, g_counts, g_atom = g_metrics.reshape(-1, 8), g_counts.reshape(-1, 6), views[-4]
     mols, n0, h0 = [], 0, 0
     for g, n in enumerate(sc.num_atoms):
         h = n * (n - 1) // 2
@@ -220,6 +382,12 @@ def assemble(results, keys=False):
                      'valence': valence2[n0:n0 + n][keep].astype(np.float64) / 2.0})
         if keys:
             mols[-1]['key'], mols[-1]['atom_colour'] = int(views[0][g]), views[1][n0:n0 + n][keep].copy()
+        if geom is not None:
+            q0, q1 = int(g_off[g]), int(g_off[g + 1])
+            mols[-1]['geom'] = dict({'status': int(g_status[g]), 'geom_ok': (int(g_status[g]) & GEOM_FAIL_MASK) == 0},
+                                    **{k: float(v) for k, v in zip(GEOM_METRICS, g_metrics[g])},
+                                    **{k: int(v) for k, v in zip(GEOM_COUNTS, g_counts[g])},
+                                    point_dist=g_dist[q0:q1].copy(), point_atom=g_atom[q0:q1].copy())
         n0, h0 = n0 + n, h0 + h
     return mols
 
@@ -246,7 +414,9 @@ def mol_block(mol, name=''):
 
 def write_sdf(path, mols, names=None):
     """An SDF file: one mol block per molecule, each closed by a '$$$$' line.  A molecule that carries 'key' (assemble(keys=True))
-    gets one data item `> <PHOREGEN_KEY>` with the key as 16 hex digits between its block and the '$$$$'."""
+    gets one data item `> <PHOREGEN_KEY>` with the key as 16 hex digits between its block and the '$$$$'.  A molecule that carries
+    'geom' (assemble(geometry=)) gets `> <PHOREGEN_GEOM>`: one line with the status as hex, then one 'name value' line per metric
+    (GEOM_METRICS without the reserved one) with four decimals."""
     names = names if names is not None else [''] * len(mols)
     if len(names) != len(mols):
         raise ValueError(f'write_sdf: {len(mols)} molecules, {len(names)} names')
@@ -255,6 +425,9 @@ def write_sdf(path, mols, names=None):
             fh.write(mol_block(m, nm))
             if 'key' in m:
                 fh.write('> <PHOREGEN_KEY>\n%016x\n\n' % (int(m['key']) & _M64))
+            if 'geom' in m:
+                fh.write('> <PHOREGEN_GEOM>\nstatus 0x%02x\n' % int(m['geom']['status'])
+                         + ''.join('%s %.4f\n' % (k, m['geom'][k]) for k in GEOM_METRICS[:7]) + '\n')
             fh.write('$$$$\n')
 
 
@@ -387,7 +560,8 @@ def duplicate_groups(keys):
 
 
 # ---- the top-up loop of sample_all.py:79-84,172 ------------------------------------------------------------------------------
-def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, device='cuda', unique=False, **sample_kwargs):
+def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, device='cuda', unique=False, geometry=None,
+                 **sample_kwargs):
     """Sample until `num_samples` molecules have passed the screen, giving up once more than `max_failed_factor * num_samples` have
     failed (checked before every draw, as the reference does).  Every draw asks for min(batch_size, what is still missing) graphs,
     so never more than `num_samples` are finished.  `sample_kwargs` (fragment=, pos_guidance_opt=, rng=, seed=, ...) go to
@@ -395,7 +569,9 @@ def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, d
     from torch's default generator) unless that is meant.  Returns {'finished': [...], 'failed': [...], 'n_calls': int} with `assemble`'s dicts.
     unique=True: a valid molecule is finished only if it is not `same_molecule` to one already finished (looked up by key, confirmed
     exactly); a repeat goes to the additional list 'duplicates', counts neither as finished nor as failed, and the loop also gives up
-    once more than `max_failed_factor * num_samples` repeats have been seen.  The molecules then carry 'key' and 'atom_colour'."""
+    once more than `max_failed_factor * num_samples` repeats have been seen.  The molecules then carry 'key' and 'atom_colour'.
+    geometry=(point_pos, point_is_ex, limits), or True to take the pharmacophore of `data` (`geometry_for`, default limits): a valid
+    molecule is finished only if it is also 'geom_ok'; one that is not goes to 'failed'.  The molecules then carry 'geom'."""
     finished, failed, duplicates, n_calls = [], [], [], 0
     by_key = {}                                                        # key -> finished molecules that have it
     while len(finished) < num_samples:
@@ -404,8 +580,15 @@ def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, d
         n = min(batch_size, num_samples - len(finished))
         res = model.sample(data, n, device, return_traj=False, **sample_kwargs)
         n_calls += 1
-        for m in (assemble(res, keys=True) if unique else assemble(res)):
-            if not m['valid']:
+        if geometry is None:
+            mols = assemble(res, keys=True) if unique else assemble(res)
+        elif geometry is True:
+            mols = assemble(res, keys=unique, geometry=geometry_for(data, res, ex_col=getattr(model, 'ex_col', 12)))
+        else:
+            point_pos, point_is_ex, limits = geometry
+            mols = assemble(res, keys=unique, geometry=_geometry(res, point_pos, point_is_ex, limits=limits))
+        for m in mols:
+            if not m['valid'] or (geometry is not None and not m['geom']['geom_ok']):
                 failed.append(m)
             elif unique and any(same_molecule(m, other) for other in by_key.setdefault(m['key'], [])):
                 duplicates.append(m)

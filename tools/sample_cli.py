@@ -10,7 +10,10 @@ above its largest valence; phoregen_amd/molecule.py) and prints sample_all.py's 
 .sdf per molecule as sample_all.py names them, <outdir>/sdf_results/{pidx}_{name}_{i}.sdf.  --unique (implies --valid_only) finishes
 a molecule only if it is new: repeats, judged by the identity key and confirmed exactly (phoregen_amd.molecule.same_molecule), are
 counted apart; <outdir>/{name}_keys.txt then lists one 16-digit hex key per finished molecule (the part sample_all.py's
-{name}_SMILES_all.txt plays) and the .sdf files carry the key as a data item.  Without them nothing changes.
+{name}_SMILES_all.txt plays) and the .sdf files carry the key as a data item.  --geometry (implies --valid_only) also measures every
+molecule against the pharmacophore it was generated for (phoregen_amd.molecule.geometry_for: bond lengths, clashes, clearance from the
+exclusion spheres, features with an atom nearby) and finishes it only if no limit is broken; --geom_limits '{"bond_max": 2.2}' replaces
+single limits of phoregen_amd.molecule.GeomLimits; the .sdf files carry the figures as a data item.  Without them nothing changes.
 """
 import argparse
 import json
@@ -26,7 +29,7 @@ from phoregen_amd.config import default_model_config, load_config  # noqa: E402
 from phoregen_amd.data import parse_phore_file  # noqa: E402
 from phoregen_amd.fragment import load_fragment_json  # noqa: E402
 from phoregen_amd.models.diffusion import PhoreDiff  # noqa: E402
-from phoregen_amd.molecule import STATUS_NONFINITE, assemble, sample_valid, write_sdf  # noqa: E402
+from phoregen_amd.molecule import GeomLimits, STATUS_NONFINITE, assemble, sample_valid, write_sdf  # noqa: E402
 from phoregen_amd.utils.sample_utils import decode_batch  # noqa: E402
 from phoregen_amd.weights import init_deterministic_  # noqa: E402
 
@@ -51,9 +54,15 @@ def main():
                     help='sample until num_samples molecules have passed the screen (give up after 3 * num_samples failures)')
     ap.add_argument('--unique', action='store_true',
                     help='implies --valid_only: a repeat of a finished molecule is not finished (also give up after 3 * num_samples repeats)')
+    ap.add_argument('--geometry', action='store_true',
+                    help='implies --valid_only: a molecule that breaks a geometry limit against its pharmacophore is not finished')
+    ap.add_argument('--geom_limits', type=json.loads, default=None, help='JSON object replacing single limits of GeomLimits (with --geometry)')
     ap.add_argument('--sdf', action='store_true', help='write one .sdf per molecule under <outdir>/sdf_results/')
     args = ap.parse_args()
-    args.valid_only = args.valid_only or args.unique
+    if args.geom_limits is not None and not args.geometry:
+        ap.error('--geom_limits needs --geometry')
+    args.valid_only = args.valid_only or args.unique or args.geometry
+    geom_limits = GeomLimits(**(args.geom_limits or {}))
     torch.manual_seed(args.seed)
     cfg = default_model_config()
     if args.config:
@@ -78,7 +87,11 @@ def main():
                   rng=args.rng, fragment=fragment)
         if args.valid_only:
             # sample_all.py:79-84,172: top up until num_samples molecules have passed
-            out = sample_valid(model, data, args.num_samples, batch_size=args.batch_size, unique=args.unique, **kw)
+            geometry = None
+            if args.geometry:                                          # the points PhoreDiff.sample reads, in world coordinates
+                ph = data['phore']
+                geometry = (ph.pos.float() + data.center.float(), ph.x[:, model.ex_col] == 1, geom_limits)
+            out = sample_valid(model, data, args.num_samples, batch_size=args.batch_size, unique=args.unique, geometry=geometry, **kw)
             done = out['finished']
             print(f"Finished {len(done)} | Failed {len(out['failed'])}" + (f" | Duplicates {len(out['duplicates'])}" if args.unique else ''))
             if args.unique:
