@@ -507,6 +507,32 @@ int pg_mol_geom(const float* pos, int64_t pos_fs, const int8_t* cls, const int8_
                 int n_point_out, const float* limits /*[5] host*/, float* point_dist, int16_t* point_atom, float* metrics, int* counts,
                 int* status, void* stream);
 
+/* Ring perception of the molecules the screen decoded, one wave per (frame, graph).  Reads the screen's outputs cls [F][n_lig] and
+ * order [F][n_bond / 2] (frames dense) with the same offsets, as pg_mol_key does: an atom is kept if its class is 0..10, a pair row
+ * a < b is a bond if its order is 1..4 and both ends are kept; degree = an atom's bonds.  Definition: DESIGN.md 2.9 "Rings".
+ *   ring_size [F][n_bond / 2] (aligned with order): 1 + bonds on a shortest path between the bond's ends that does not use the bond,
+ *     i.e. the atoms of the smallest ring through it; 0 for a bridge and for a pair that is no bond.  Ring bond: ring_size > 0.
+ *   atom_ring [F][n_lig]: smallest ring_size among the atom's ring bonds; 0 for an atom without one or a dropped atom
+ *   ring_sys [F][n_lig]: smallest local atom index reachable over ring bonds (rings that share an atom are one system); -1 likewise
+ *   counts [F][B][PG_RING_N_COUNTS]: 0 rings = bonds - kept atoms + components, 1 ring bonds, 2 ring atoms, 3 ring systems, 4 smallest
+ *     and 5 largest ring_size among ring bonds (0 without one), 6 atoms of the largest ring system, 7 rotatable = bonds of order 1 with
+ *     ring_size 0 and both ends of degree >= 2, 8 bonds of order 4 with ring_size 0, 9 kept atoms with exactly one bond of order 4
+ *   status [F][B]: PG_RING_* bits
+ * limits: four ints in HOST memory, read during the call: ring_min, ring_max, system_max, rotatable_max.  Integer work only, counts are
+ * per-lane partials in a fixed butterfly or integer LDS atomics: results are exact and a graph's rows do not depend on its batch.
+ * max_n above PG_MOL_MAX_ATOMS, a negative size or null limits: error before anything is launched, outputs untouched.  Every element
+ * of every output is written (nothing needs zeroing). */
+#define PG_RING_AROMATIC_OUTSIDE 1   /* a bond of order 4 that is in no ring                                   */
+#define PG_RING_SMALL 2              /* a ring bond whose smallest ring has fewer than limits.ring_min atoms   */
+#define PG_RING_LARGE 4              /* ... more than limits.ring_max atoms                                    */
+#define PG_RING_SYSTEM_LARGE 8       /* a ring system of more than limits.system_max atoms                     */
+#define PG_RING_ROTATABLE 16         /* more than limits.rotatable_max rotatable bonds                         */
+#define PG_RING_AROMATIC_LONE 32     /* informational: an atom with exactly one bond of order 4                */
+#define PG_RING_N_COUNTS 10
+int pg_mol_rings(const int8_t* cls, const int8_t* order, const int* g_lig_off /*[B+1]*/, const int* g_bond_off /*[B+1]*/, int B, int F,
+                 int n_lig, int n_bond, int max_n, const int* limits /*[4] host*/, uint8_t* ring_size, uint8_t* atom_ring,
+                 int16_t* ring_sys, int* counts, int* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,302 @@
+// Ring perception of the molecules the screen decoded: smallest ring through every bond and atom, ring systems, and the counts users
+// filter on (pg_mol_rings, include/phoregen_hip.h; phoregen_amd/molecule.py; definition: DESIGN.md 2.9 "Rings").  Reads the screen's
+// outputs (cls, order), not the scores.  One wave per (frame, graph); a workgroup IS one wave, so __syncthreads() orders the wave's LDS
+// traffic, and every loop that holds one (or a vote) has a wave-uniform trip count: the divergent loops below (bond rows, the search
+// of a bond's ring) hold neither.  Integer work only, no floating point anywhere, so every output is exact.
+#include "wave_prims.h"
+#include "../../include/phoregen_hip.h"
+
+namespace pg {
+
+constexpr int kRingMax = PG_MOL_MAX_ATOMS;  // atoms of the largest graph
+constexpr int kRingCh = kRingMax / 64;      // atoms per lane = 64-bit adjacency words per atom
+static_assert(kRingCh == 2 && kRingMax <= 255, "a mask row is one 16-byte LDS read; a ring size fits one byte");
+
+struct RingLimits {
+  int ring_min, ring_max, system_max, rotatable_max;
+};
+
+// An atom's bonds as a bit per local atom index.  Rows are 16 bytes and dense: one row is one 128-bit LDS read, 16 consecutive rows
+// fill the 256-byte bank row exactly, so the 16 lanes that share a read cycle collide only where their row indices agree mod 16; the
+// searches read rows at data-dependent indices, and for those any padded stride is a permutation of the same residues or worse.
+struct __align__(16) RingRow {
+  unsigned long long w[kRingCh];
+};
+
+__device__ __forceinline__ int wave_imax(int v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v = max(v, __shfl_xor(v, o));
+  return v;
+}
+__device__ __forceinline__ int wave_imin(int v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v = min(v, __shfl_xor(v, o));
+  return v;
+}
+
+// Atoms of the smallest ring through the bond (a, b), 0 if the bond is a bridge: breadth-first from a over the masks with b struck
+// from a's own row (a is never expanded again, so the bond itself is never walked); the frontier at step d holds the atoms d bonds
+// from a, and the first of them that has b as a neighbour closes a ring of d + 2 atoms.
+__device__ __forceinline__ int ring_through(const RingRow* adj, int a, int b) {
+  const int bw = b >> 6;
+  const unsigned long long bbit = 1ull << (b & 63);
+  unsigned long long seen[kRingCh], front[kRingCh];
+  const RingRow ra = adj[a];
+  bool more = false;
+#pragma unroll
+  for (int w = 0; w < kRingCh; ++w) {
+    front[w] = ra.w[w] & ~(w == bw ? bbit : 0ull);
+    seen[w] = front[w] | (w == (a >> 6) ? 1ull << (a & 63) : 0ull);
+    more |= front[w] != 0ull;
+  }
+  for (int d = 1; more; ++d) {                                    // (d <= n - 2: every step adds an atom to `seen`)
+    unsigned long long next[kRingCh];
+#pragma unroll
+    for (int w = 0; w < kRingCh; ++w) next[w] = 0ull;
+#pragma unroll
+    for (int w = 0; w < kRingCh; ++w) {
+      unsigned long long m = front[w];
+      while (m) {
+        const int j = w * 64 + __builtin_ctzll(m);
+        m &= m - 1ull;
+        const RingRow rj = adj[j];
+#pragma unroll
+        for (int v = 0; v < kRingCh; ++v) next[v] |= rj.w[v];
+        if ((bw ? next[kRingCh - 1] : next[0]) & bbit) return d + 2;
+      }
+    }
+    more = false;
+#pragma unroll
+    for (int w = 0; w < kRingCh; ++w) {
+      next[w] &= ~seen[w];
+      seen[w] |= next[w];
+      front[w] = next[w];
+      more |= next[w] != 0ull;
+    }
+  }
+  return 0;
+}
+
+__global__ __launch_bounds__(64) void mol_rings_kernel(const int8_t* __restrict__ cls_i, const int8_t* __restrict__ order_i,
+                                                       const int* __restrict__ g_lig_off, const int* __restrict__ g_bond_off, int B,
+                                                       int n_lig, int n_half, RingLimits lim, uint8_t* __restrict__ ring_size_o,
+                                                       uint8_t* __restrict__ atom_ring_o, int16_t* __restrict__ ring_sys_o,
+                                                       int* __restrict__ counts_o, int* __restrict__ status_o) {
+  __shared__ int s_cls[kRingMax];                                 // atom class, -1 = dropped
+  __shared__ RingRow s_adj[kRingMax];                             // kept bonds of an atom
+  __shared__ RingRow s_radj[kRingMax];                            // its ring bonds
+  __shared__ unsigned int s_stat[kRingMax];                       // degree | bonds of order 4 << 16
+  __shared__ unsigned int s_aring[kRingMax];                      // smallest ring_size among the atom's ring bonds, ~0 = none
+  __shared__ int s_comp[kRingMax];                                // component label over all bonds (a local atom index)
+  __shared__ int s_sys[kRingMax];                                 // ring-system label over ring bonds
+  __shared__ unsigned int s_size[kRingMax];                       // atoms of the ring system whose label this index is
+
+  const int lane = threadIdx.x;
+  const int f = blockIdx.x / B, g = blockIdx.x - f * B;
+  const int a0 = g_lig_off[g], n = g_lig_off[g + 1] - a0;
+  if (n > kRingMax || n < 0) return;                              // (the host wrapper has refused such a batch: never index LDS past its end)
+  const int h0 = g_bond_off[g] >> 1, n_pair = n * (n - 1) / 2;
+  if (a0 < 0 || a0 + n > n_lig || h0 < 0 || h0 + n_pair > n_half) return;   // (offsets that leave the frame: never read or write past it)
+  const size_t arow = (size_t)f * n_lig + a0, hrow = (size_t)f * n_half + h0;
+
+  // ---- atoms: class; empty masks, counters and labels -------------------------------------------------------------------------
+  int n_kept = 0;
+#pragma unroll
+  for (int c = 0; c < kRingCh; ++c) {
+    const int i = c * 64 + lane;
+    int k = -1;
+    if (i < n) {
+      k = cls_i[arow + i];
+      k = (k >= 0 && k < 11) ? k : -1;
+      s_cls[i] = k;
+      s_stat[i] = 0u, s_size[i] = 0u;
+      s_aring[i] = ~0u;
+      s_comp[i] = s_sys[i] = i;
+#pragma unroll
+      for (int w = 0; w < kRingCh; ++w) s_adj[i].w[w] = s_radj[i].w[w] = 0ull;
+    }
+    n_kept += __popcll(__ballot(k >= 0));
+  }
+  __syncthreads();
+
+  // ---- bonds: the pairs a < b in row-major order, dealt to lanes (pair p is lane p mod 64's) -----------------------------------
+  int n_bond = 0;
+  {
+    int a = 0, b = 1 + lane;
+    for (int p = lane; p < n_pair; p += 64, b += 64) {
+      while (b >= n) {                                            // next row of the triangle (p < n_pair: ends with a < n - 1)
+        ++a;
+        b = b - n + a + 1;
+      }
+      const int o = order_i[hrow + p];
+      if (o >= 1 && o <= 4 && s_cls[a] >= 0 && s_cls[b] >= 0) {
+        ++n_bond;
+        const unsigned int inc = 1u | (o == 4 ? 1u << 16 : 0u);
+        atomicAdd(&s_stat[a], inc);
+        atomicAdd(&s_stat[b], inc);
+        atomicOr(&s_adj[a].w[b >> 6], 1ull << (b & 63));
+        atomicOr(&s_adj[b].w[a >> 6], 1ull << (a & 63));
+      }
+    }
+  }
+  __syncthreads();
+
+  // ---- rings: the same deal; a lane searches the ring of each of its bonds and writes the row of every one of its pairs ------
+  int n_ringb = 0, rmin = 255, rmax = 0, n_rot = 0, n_arom_out = 0;
+  {
+    int a = 0, b = 1 + lane;
+    for (int p = lane; p < n_pair; p += 64, b += 64) {
+      while (b >= n) {
+        ++a;
+        b = b - n + a + 1;
+      }
+      const int o = order_i[hrow + p];
+      int rs = 0;
+      if (o >= 1 && o <= 4 && s_cls[a] >= 0 && s_cls[b] >= 0) {
+        rs = ring_through(s_adj, a, b);
+        if (rs > 0) {
+          ++n_ringb;
+          rmin = min(rmin, rs);
+          rmax = max(rmax, rs);
+          atomicOr(&s_radj[a].w[b >> 6], 1ull << (b & 63));
+          atomicOr(&s_radj[b].w[a >> 6], 1ull << (a & 63));
+          atomicMin(&s_aring[a], (unsigned int)rs);
+          atomicMin(&s_aring[b], (unsigned int)rs);
+        } else {
+          n_rot += (o == 1 && (s_stat[a] & 0xffffu) >= 2u && (s_stat[b] & 0xffffu) >= 2u) ? 1 : 0;
+          n_arom_out += o == 4 ? 1 : 0;
+        }
+      }
+      ring_size_o[hrow + p] = (uint8_t)rs;
+    }
+  }
+  __syncthreads();
+
+  // ---- components (all bonds) and ring systems (ring bonds): every atom takes the smallest label among itself and its neighbours,
+  // then its label's label, until a wave-wide vote sees no change in either.  Labels only decrease and stay inside their class, so
+  // reading a neighbour's label of either round is fine; at the fixed point a class holds one label, the index of its first atom. ----
+  bool changed;
+  do {
+    changed = false;
+#pragma unroll
+    for (int c = 0; c < kRingCh; ++c) {
+      const int i = c * 64 + lane;
+      if (i < n && s_cls[i] >= 0) {
+        const int c0 = s_comp[i], y0 = s_sys[i];
+        int lc = c0, ly = y0;
+        const RingRow all = s_adj[i], ring = s_radj[i];
+#pragma unroll
+        for (int w = 0; w < kRingCh; ++w) {
+          unsigned long long m = all.w[w];
+          while (m) {
+            const int j = w * 64 + __builtin_ctzll(m);
+            m &= m - 1ull;
+            lc = min(lc, s_comp[j]);
+          }
+          m = ring.w[w];
+          while (m) {
+            const int j = w * 64 + __builtin_ctzll(m);
+            m &= m - 1ull;
+            ly = min(ly, s_sys[j]);
+          }
+        }
+        lc = min(lc, s_comp[lc]);
+        ly = min(ly, s_sys[ly]);
+        if (lc < c0) s_comp[i] = lc;
+        if (ly < y0) s_sys[i] = ly;
+        changed |= lc < c0 || ly < y0;
+      }
+    }
+    __syncthreads();
+  } while (__any(changed));
+
+  // ---- per-atom outputs, system sizes, counts --------------------------------------------------------------------------------
+  int n_comp = 0, n_sys = 0, n_ringa = 0, n_lone = 0;
+#pragma unroll
+  for (int c = 0; c < kRingCh; ++c) {
+    const int i = c * 64 + lane;
+    bool comp_root = false, sys_root = false, in_ring = false, lone = false;
+    if (i < n) {
+      const bool kept = s_cls[i] >= 0;
+      const unsigned int ar = s_aring[i];
+      in_ring = kept && ar != ~0u;
+      comp_root = kept && s_comp[i] == i;
+      sys_root = in_ring && s_sys[i] == i;
+      lone = kept && (s_stat[i] >> 16) == 1u;
+      if (in_ring) atomicAdd(&s_size[s_sys[i]], 1u);
+      atom_ring_o[arow + i] = (uint8_t)(in_ring ? ar : 0u);
+      ring_sys_o[arow + i] = (int16_t)(in_ring ? s_sys[i] : -1);
+    }
+    n_comp += __popcll(__ballot(comp_root));
+    n_sys += __popcll(__ballot(sys_root));
+    n_ringa += __popcll(__ballot(in_ring));
+    n_lone += __popcll(__ballot(lone));
+  }
+  __syncthreads();
+  int largest = 0;
+#pragma unroll
+  for (int c = 0; c < kRingCh; ++c) {
+    const int i = c * 64 + lane;
+    if (i < n) largest = max(largest, (int)s_size[i]);
+  }
+  largest = wave_imax(largest);
+  n_bond = wave_sum(n_bond);
+  n_ringb = wave_sum(n_ringb);
+  n_rot = wave_sum(n_rot);
+  n_arom_out = wave_sum(n_arom_out);
+  rmin = wave_imin(rmin);
+  rmax = wave_imax(rmax);
+  rmin = n_ringb > 0 ? rmin : 0;
+  int st = 0;
+  st |= n_arom_out > 0 ? PG_RING_AROMATIC_OUTSIDE : 0;
+  st |= (rmin > 0 && rmin < lim.ring_min) ? PG_RING_SMALL : 0;
+  st |= rmax > lim.ring_max ? PG_RING_LARGE : 0;
+  st |= largest > lim.system_max ? PG_RING_SYSTEM_LARGE : 0;
+  st |= n_rot > lim.rotatable_max ? PG_RING_ROTATABLE : 0;
+  st |= n_lone > 0 ? PG_RING_AROMATIC_LONE : 0;
+  if (lane == 0) {
+    status_o[blockIdx.x] = st;
+    int* cnt = counts_o + (size_t)blockIdx.x * PG_RING_N_COUNTS;
+    cnt[0] = n_bond - n_kept + n_comp;
+    cnt[1] = n_ringb;
+    cnt[2] = n_ringa;
+    cnt[3] = n_sys;
+    cnt[4] = rmin;
+    cnt[5] = rmax;
+    cnt[6] = largest;
+    cnt[7] = n_rot;
+    cnt[8] = n_arom_out;
+    cnt[9] = n_lone;
+  }
+}
+
+}  // namespace pg
+
+using namespace pg;
+
+extern "C" int pg_mol_rings(const int8_t* cls, const int8_t* order, const int* g_lig_off, const int* g_bond_off, int B, int F,
+                            int n_lig, int n_bond, int max_n, const int* limits, uint8_t* ring_size, uint8_t* atom_ring,
+                            int16_t* ring_sys, int* counts, int* status, void* stream) {
+  if (B < 0 || F < 0 || n_lig < 0 || n_bond < 0 || (n_bond & 1) || max_n < 0) {
+    set_error("pg_mol_rings: B %d, F %d, n_lig %d, n_bond %d, max_n %d (n_bond counts both directions of every pair)", B, F, n_lig,
+              n_bond, max_n);
+    return PG_ERR_ARG;
+  }
+  if (max_n > PG_MOL_MAX_ATOMS) {
+    set_error("pg_mol_rings: a graph of %d atoms, the kernel holds at most PG_MOL_MAX_ATOMS = %d", max_n, PG_MOL_MAX_ATOMS);
+    return PG_ERR_ARG;
+  }
+  if (!limits) {
+    set_error("pg_mol_rings: limits is null (four ints in host memory)");
+    return PG_ERR_ARG;
+  }
+  if (B == 0 || F == 0) return PG_OK;
+  if ((long long)B * F > 0x7fffffffLL) {
+    set_error("pg_mol_rings: %d frames x %d graphs exceed one launch", F, B);
+    return PG_ERR_ARG;
+  }
+  const RingLimits lim = {limits[0], limits[1], limits[2], limits[3]};
+  hipLaunchKernelGGL(mol_rings_kernel, dim3((unsigned)(B * F)), dim3(64), 0, (hipStream_t)stream, cls, order, g_lig_off, g_bond_off, B,
+                     n_lig, n_bond / 2, lim, ring_size, atom_ring, ring_sys, counts, status);
+  return check_launch("pg_mol_rings");
+}

@@ -152,6 +152,8 @@ _PROTOS = {
     'pg_mol_key': (C.c_int, [c_ip, c_ip, c_ip, c_ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_ip, c_ip, C.c_void_p]),
     'pg_mol_geom': (C.c_int, [c_fp, C.c_int64, c_ip, c_ip, c_ip, c_ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_fp, c_ip, C.c_int,
                               c_ip, c_ip, C.c_int, C.POINTER(C.c_float), c_fp, c_ip, c_fp, c_ip, c_ip, C.c_void_p]),
+    'pg_mol_rings': (C.c_int, [c_ip, c_ip, c_ip, c_ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), c_ip, c_ip, c_ip,
+                               c_ip, c_ip, C.c_void_p]),
 }
 
 EXPORTS = tuple(_PROTOS)

@@ -14,7 +14,11 @@ necessary, not sufficient, for equal molecules; this is not SMILES.
 Geometry: `geometry` / `geometry_for` measure the decoded molecules where they lie (csrc/mol_geom.hip; DESIGN.md 2.9 "Geometry"):
 bond lengths, non-bonded clashes, clearance from the exclusion spheres, which feature points have an atom nearby, and the reference's
 two guidance energies on the decoded molecule.  `assemble(geometry=)`, `sample_valid(geometry=)` and `write_sdf` carry it.  Again
-necessary, not sufficient: no force field, no hydrogens, no feature typing."""
+necessary, not sufficient: no force field, no hydrogens, no feature typing.
+
+Rings: `rings` finds the smallest ring through every bond and atom, the ring systems and the counts users filter on (csrc/mol_rings.hip;
+DESIGN.md 2.9 "Rings"): three- and four-membered rings, macrocycles, oversized fused systems, aromatic bonds outside a ring, rotatable
+bonds.  `assemble(rings=)`, `sample_valid(rings=)` and `write_sdf` carry it.  Exact integer answers; no kekulisation, no ring list."""
 import ctypes
 from dataclasses import astuple, dataclass
 
@@ -67,6 +71,35 @@ GEOM_NAMES = {GEOM_BOND_SHORT: 'BOND_SHORT', GEOM_BOND_LONG: 'BOND_LONG', GEOM_C
               GEOM_FEATURE_MISSED: 'FEATURE_MISSED', GEOM_NONFINITE: 'NONFINITE'}
 GEOM_METRICS = ('bond_min', 'bond_max', 'nonbonded_min', 'ex_min', 'feature_max', 'centre_dist', 'bond_energy', 'reserved')
 GEOM_COUNTS = ('bonds_short', 'bonds_long', 'clashes', 'ex_clashes', 'features_covered', 'features')
+
+# The ring screen (DESIGN.md 2.9 "Rings"): status bits, and the names of the count columns in the kernel's order
+RING_AROMATIC_OUTSIDE = 1        # a bond of order 4 that is in no ring
+RING_SMALL = 2                   # a ring bond whose smallest ring has fewer than ring_min atoms
+RING_LARGE = 4                   # a ring bond whose smallest ring has more than ring_max atoms
+RING_SYSTEM_LARGE = 8            # a ring system of more than system_max atoms
+RING_ROTATABLE = 16              # more than rotatable_max rotatable bonds
+RING_AROMATIC_LONE = 32          # informational: an atom with exactly one bond of order 4
+RING_FAIL_MASK = RING_AROMATIC_OUTSIDE | RING_SMALL | RING_LARGE | RING_SYSTEM_LARGE | RING_ROTATABLE
+RING_NAMES = {RING_AROMATIC_OUTSIDE: 'AROMATIC_OUTSIDE', RING_SMALL: 'SMALL', RING_LARGE: 'LARGE', RING_SYSTEM_LARGE: 'SYSTEM_LARGE',
+              RING_ROTATABLE: 'ROTATABLE', RING_AROMATIC_LONE: 'AROMATIC_LONE'}
+RING_COUNTS = ('rings', 'ring_bonds', 'ring_atoms', 'ring_systems', 'ring_min', 'ring_max', 'largest_system', 'rotatable',
+               'aromatic_outside_ring', 'aromatic_lone')
+
+
+@dataclass(frozen=True)
+class RingLimits:
+    """Limits of the ring screen, in atoms / bonds.  The defaults cannot be broken by a graph of MAX_ATOMS atoms (no ring below 3 or
+    above 128 atoms, no system above 128, at most 8128 bonds), so with them only the aromatic rule can fail; the others are the user's
+    filters, e.g. RingLimits(ring_min=5, ring_max=8).  RING_SMALL: 0 < smallest ring < ring_min; the other three: value > limit."""
+    ring_min: int = 3
+    ring_max: int = 128
+    system_max: int = 128
+    rotatable_max: int = 8128
+
+    def __post_init__(self):
+        for k, v in zip(('ring_min', 'ring_max', 'system_max', 'rotatable_max'), astuple(self)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= 0x7fffffff:
+                raise ValueError(f'RingLimits: {k} must be an integer in 0 .. 2**31 - 1, not {v!r}')
 
 
 @dataclass(frozen=True)
@@ -319,7 +352,71 @@ def _launch_geom(lib, pos, pos_fs, cls, order, lig_off, bond_off, B, F, max_n, p
                               out['status'].data_ptr(), hip.stream_ptr()), 'pg_mol_geom')
 
 
+@dataclass
+class Rings:
+    """Device tensors of one `rings` call; F frames, B graphs, N atom rows, H pair rows (as the screen's `order`)."""
+    status: torch.Tensor         # int32 [F, B]     RING_* bits
+    counts: torch.Tensor         # int32 [F, B, 10] RING_COUNTS
+    ok: torch.Tensor             # bool  [F, B]     no bit of RING_FAIL_MASK
+    ring_size: torch.Tensor      # uint8 [F, H]     atoms of the smallest ring through the bond of this pair row; 0 = bridge or no bond
+    atom_ring: torch.Tensor      # uint8 [F, N]     atoms of the smallest ring through the atom; 0 = none (or dropped)
+    ring_sys: torch.Tensor       # int16 [F, N]     smallest local atom index of the atom's ring system, -1 = none (or dropped)
+    limits: RingLimits
+    screen: Screen               # the screen it was computed from
+
+
+@torch.no_grad()
+def rings(results, frames='final', screen=None, limits=RingLimits()):
+    """Ring perception of every decoded (frame, graph) of a `sample` / `sample_batch` result, on the device, in one launch
+    (pg_mol_rings): per bond the smallest ring through it (0 = bridge), per atom the smallest ring through it and its ring system
+    (rings that share an atom, spiro atoms included, are one system), ten counts (RING_COUNTS) and a status word (RING_* bits).
+    A `Screen` of the same result and frames is reused if handed in.  No host read beyond the screen's.  `ok` is a separate answer
+    from the screen's `valid`: with the default limits it fails only on an aromatic bond outside a ring.  No kekulisation, no ring
+    list, no hydrogens; `rotatable` has no amide or terminal-group exceptions and is not RDKit's NumRotatableBonds."""
+    node, _, edge, F, _ = _frames(results, frames)
+    dev = node.device
+    if dev.type != 'cuda':
+        raise RuntimeError('phoregen_amd.molecule.rings: the ring screen is a HIP kernel and the result lives on %s; there is no CPU '
+                           'fallback' % dev)
+    if not isinstance(limits, RingLimits):
+        raise ValueError(f'phoregen_amd.molecule.rings: limits must be a RingLimits, not {limits!r}')
+    sc = screen if screen is not None else _screen(results, frames)
+    B, N = len(sc.num_atoms), node.size(-2)
+    if tuple(sc.status.shape) != (F, B) or sc.cls.size(1) != N or sc.cls.device != dev or 2 * sc.order.size(1) != edge.size(-2):
+        raise ValueError(f'phoregen_amd.molecule.rings: the screen ({tuple(sc.status.shape)} frames x graphs, {sc.cls.size(1)} atom '
+                         f'rows) is not one of this result and frames ({F} frames, {N} atom rows)')
+    with torch.cuda.device(dev):
+        lib = hip.lib()
+        out = dict(status=torch.empty(F, B, dtype=torch.int32, device=dev),
+                   counts=torch.empty(F, B, len(RING_COUNTS), dtype=torch.int32, device=dev),
+                   ring_size=torch.empty(F, sc.order.size(1), dtype=torch.uint8, device=dev),
+                   atom_ring=torch.empty(F, N, dtype=torch.uint8, device=dev), ring_sys=torch.empty(F, N, dtype=torch.int16, device=dev))
+        _launch_rings(lib, sc.cls, sc.order, sc.lig_off, sc.bond_off, B, F, max(sc.num_atoms, default=0), astuple(limits), out)
+    return Rings(ok=(out['status'] & RING_FAIL_MASK) == 0, limits=limits, screen=sc, **out)
+
+
+def _launch_rings(lib, cls, order, lig_off, bond_off, B, F, max_n, limits, out):
+    """pg_mol_rings on the current stream.  A graph above MAX_ATOMS is the library's error: nothing is launched and `out` is not
+    written."""
+    dev = cls.device
+    for t, dt in ((cls, torch.int8), (order, torch.int8), (lig_off, torch.int32), (bond_off, torch.int32), (out['ring_size'], torch.uint8),
+                  (out['atom_ring'], torch.uint8), (out['ring_sys'], torch.int16), (out['counts'], torch.int32), (out['status'], torch.int32)):
+        if t.dtype != dt or not t.is_contiguous() or t.device != dev:
+            raise ValueError('phoregen_amd.molecule.rings: cls / order must be contiguous int8, the offsets int32, ring_size / atom_ring '
+                             'uint8, ring_sys int16, counts / status int32, all on one device')
+    if (lig_off.numel() != B + 1 or bond_off.numel() != B + 1 or cls.numel() != F * cls.size(-1) or order.numel() != F * order.size(-1)
+            or out['ring_size'].shape != order.shape or out['atom_ring'].shape != cls.shape or out['ring_sys'].shape != cls.shape
+            or out['status'].numel() != F * B or out['counts'].numel() != len(RING_COUNTS) * F * B):
+        raise ValueError(f'phoregen_amd.molecule.rings: sizes of the offsets, screen arrays and outputs do not fit {F} frames x {B} graphs, '
+                         f'{cls.size(-1)} atom rows, {order.size(-1)} pair rows')
+    hip.check(lib.pg_mol_rings(cls.data_ptr(), order.data_ptr(), lig_off.data_ptr(), bond_off.data_ptr(), B, F, cls.size(-1),
+                               2 * order.size(-1), max_n, (ctypes.c_int * 4)(*(int(v) for v in limits)), out['ring_size'].data_ptr(),
+                               out['atom_ring'].data_ptr(), out['ring_sys'].data_ptr(), out['counts'].data_ptr(),
+                               out['status'].data_ptr(), hip.stream_ptr()), 'pg_mol_rings')
+
+
 _geometry = geometry             # (functions below take a `geometry=` argument)
+_rings = rings                   # (and a `rings=` argument)
 _PAIRS = {}
 
 
@@ -333,7 +430,7 @@ def _pairs(n):
 
 
 @torch.no_grad()
-def assemble(results, keys=False, geometry=None):
+def assemble(results, keys=False, geometry=None, rings=None):
     """The final prediction as one dict per graph with `decode_data`'s keys and meaning -- 'element' (atomic numbers), 'atom_pos'
     (kept atoms, the tensor's own fp32 values), 'bond_index' [2, n_b] (indices among the kept atoms) and 'bond_type' [n_b] for
     a < b only, in row order -- plus 'status', 'valid', 'n_components' and 'valence' (per kept atom, halves allowed).  The screen runs
@@ -342,30 +439,51 @@ def assemble(results, keys=False, geometry=None):
     per kept atom); they ride in the same copy.
     geometry=a `Geometry` of this result's final frame: every dict also has 'geom' -- 'status' (GEOM_* bits), 'geom_ok' (no bit of
     GEOM_FAIL_MASK), the eight GEOM_METRICS and the six GEOM_COUNTS by name, and 'point_dist' / 'point_atom' of the graph's points
-    (an index into this dict's atoms, -1 = none) -- in the same copy; its screen is reused."""
-    geom = geometry
-    if geom is not None and (geom.status.size(0) != 1 or geom.screen.cls.size(1) != results['pred'][1].size(-2)
-                             or geom.status.device != results['pred'][1].device):
-        raise ValueError('phoregen_amd.molecule.assemble: geometry= must be a Geometry of the final frame of this result')
-    sc = geom.screen if geom is not None else screen(results, 'final')
-    parts = [sc.status[0], sc.counts[0], results['pred'][1], sc.compact[0], sc.cls[0], sc.valence2[0], sc.order[0]]
-    dtypes = [np.int32, np.int32, np.float32, np.int16, np.int8, np.uint8, np.int8]
-    if geom is not None:                                               # (4-byte parts in front, the 2-byte one beside `compact`)
-        parts = [geom.status[0], geom.metrics[0], geom.counts[0], geom.point_dist[0], geom.point_off] + parts[:4] + [geom.point_atom[0]] + parts[4:]
-        dtypes = [np.int32, np.float32, np.int32, np.float32, np.int32] + dtypes[:4] + [np.int16] + dtypes[4:]
-    if keys:                                                           # (64-bit parts first: every part stays aligned in the blob)
+    (an index into this dict's atoms, -1 = none) -- in the same copy; its screen is reused.
+    rings=a `Rings` of this result's final frame: every dict also has 'rings' -- 'status' (RING_* bits), 'rings_ok' (no bit of
+    RING_FAIL_MASK), the ten RING_COUNTS by name, 'bond_ring_size' (per entry of 'bond_type', in its order), 'atom_ring' and
+    'ring_sys' (per kept atom; the system's first atom as an index into this dict's atoms, -1 = none) -- in the same copy; its screen
+    is reused, and with geometry= too both must have been computed from one screen."""
+    geom, pos_t = geometry, results['pred'][1]
+    for what, x in (('geometry', geom), ('rings', rings)):
+        if x is not None and (x.status.size(0) != 1 or x.screen.cls.size(1) != pos_t.size(-2) or x.status.device != pos_t.device):
+            raise ValueError(f'phoregen_amd.molecule.assemble: {what}= must be a {what.capitalize()} of the final frame of this result')
+    if geom is not None and rings is not None and geom.screen is not rings.screen:
+        a, b = geom.screen, rings.screen
+        if (a.num_atoms != b.num_atoms or a.status.shape != b.status.shape or a.cls.shape != b.cls.shape or a.order.shape != b.order.shape
+                or a.cls.device != b.cls.device):
+            raise ValueError('phoregen_amd.molecule.assemble: geometry= and rings= were computed from screens of different results')
+    sc = geom.screen if geom is not None else rings.screen if rings is not None else screen(results, 'final')
+    # the parts of the one blob, widest elements first so that every part stays aligned in it
+    parts = []
+    if keys:
         mk = molecule_keys(sc)
-        parts, dtypes = [mk.key[0], mk.colour[0]] + parts, [np.uint64, np.uint64] + dtypes
-    sizes = [p.numel() * p.element_size() for p in parts]
-    blob = torch.cat([p.reshape(-1).view(torch.uint8) for p in parts]).cpu().numpy()
-    cut = np.cumsum([0] + sizes)
-    views = [blob[cut[i]:cut[i + 1]].view(dt) for i, dt in enumerate(dtypes)]
-    status, counts, pos, compact = views[-8:-4] if geom is not None else views[-7:-3]
-    cls, valence2, order = views[-3:]
-    counts, pos = counts.reshape(-1, 4), pos.reshape(-1, 3)
+        parts += [('key', mk.key[0], np.uint64), ('colour', mk.colour[0], np.uint64)]
+    if rings is not None:
+        parts += [('r_status', rings.status[0], np.int32), ('r_counts', rings.counts[0], np.int32)]
     if geom is not None:
-        g_status, g_metrics, g_counts, g_dist, g_off = views[-13:-8]
-        g_metrics, g_counts, g_atom = g_metrics.reshape(-1, 8), g_counts.reshape(-1, 6), views[-4]
+        parts += [('g_status', geom.status[0], np.int32), ('g_metrics', geom.metrics[0], np.float32), ('g_counts', geom.counts[0], np.int32),
+                  ('g_dist', geom.point_dist[0], np.float32), ('g_off', geom.point_off, np.int32)]
+    parts += [('status', sc.status[0], np.int32), ('counts', sc.counts[0], np.int32), ('pos', pos_t, np.float32),
+              ('compact', sc.compact[0], np.int16)]
+    if geom is not None:
+        parts += [('g_atom', geom.point_atom[0], np.int16)]
+    if rings is not None:
+        parts += [('r_sys', rings.ring_sys[0], np.int16)]
+    parts += [('cls', sc.cls[0], np.int8), ('valence2', sc.valence2[0], np.uint8), ('order', sc.order[0], np.int8)]
+    if rings is not None:
+        parts += [('r_atom', rings.atom_ring[0], np.uint8), ('r_size', rings.ring_size[0], np.uint8)]
+    sizes = [t.numel() * t.element_size() for _, t, _ in parts]
+    blob = torch.cat([t.reshape(-1).view(torch.uint8) for _, t, _ in parts]).cpu().numpy()
+    cut = np.cumsum([0] + sizes)
+    v = {name: blob[cut[i]:cut[i + 1]].view(dt) for i, (name, _, dt) in enumerate(parts)}
+    status, cls, valence2, order, compact = v['status'], v['cls'], v['valence2'], v['order'], v['compact']
+    counts, pos = v['counts'].reshape(-1, 4), v['pos'].reshape(-1, 3)
+    if geom is not None:
+        g_status, g_dist, g_off, g_atom = v['g_status'], v['g_dist'], v['g_off'], v['g_atom']
+        g_metrics, g_counts = v['g_metrics'].reshape(-1, 8), v['g_counts'].reshape(-1, 6)
+    if rings is not None:
+        r_counts = v['r_counts'].reshape(-1, len(RING_COUNTS))
     mols, n0, h0 = [], 0, 0
     for g, n in enumerate(sc.num_atoms):
         h = n * (n - 1) // 2
@@ -381,13 +499,19 @@ def assemble(results, keys=False, geometry=None):
                      'status': int(status[g]), 'valid': (int(status[g]) & FAIL_MASK) == 0, 'n_components': int(counts[g, 2]),
                      'valence': valence2[n0:n0 + n][keep].astype(np.float64) / 2.0})
         if keys:
-            mols[-1]['key'], mols[-1]['atom_colour'] = int(views[0][g]), views[1][n0:n0 + n][keep].copy()
+            mols[-1]['key'], mols[-1]['atom_colour'] = int(v['key'][g]), v['colour'][n0:n0 + n][keep].copy()
         if geom is not None:
             q0, q1 = int(g_off[g]), int(g_off[g + 1])
             mols[-1]['geom'] = dict({'status': int(g_status[g]), 'geom_ok': (int(g_status[g]) & GEOM_FAIL_MASK) == 0},
-                                    **{k: float(v) for k, v in zip(GEOM_METRICS, g_metrics[g])},
-                                    **{k: int(v) for k, v in zip(GEOM_COUNTS, g_counts[g])},
+                                    **{k: float(x) for k, x in zip(GEOM_METRICS, g_metrics[g])},
+                                    **{k: int(x) for k, x in zip(GEOM_COUNTS, g_counts[g])},
                                     point_dist=g_dist[q0:q1].copy(), point_atom=g_atom[q0:q1].copy())
+        if rings is not None:
+            sys_g = v['r_sys'][n0:n0 + n][keep].astype(np.int64)         # local index of the system's first atom -> its compact index
+            mols[-1]['rings'] = dict({'status': int(v['r_status'][g]), 'rings_ok': (int(v['r_status'][g]) & RING_FAIL_MASK) == 0},
+                                     **{k: int(x) for k, x in zip(RING_COUNTS, r_counts[g])},
+                                     bond_ring_size=v['r_size'][h0:h0 + h][nz].copy(), atom_ring=v['r_atom'][n0:n0 + n][keep].copy(),
+                                     ring_sys=np.where(sys_g >= 0, cmp_g[np.maximum(sys_g, 0)], -1).astype(np.int16))
         n0, h0 = n0 + n, h0 + h
     return mols
 
@@ -416,7 +540,8 @@ def write_sdf(path, mols, names=None):
     """An SDF file: one mol block per molecule, each closed by a '$$$$' line.  A molecule that carries 'key' (assemble(keys=True))
     gets one data item `> <PHOREGEN_KEY>` with the key as 16 hex digits between its block and the '$$$$'.  A molecule that carries
     'geom' (assemble(geometry=)) gets `> <PHOREGEN_GEOM>`: one line with the status as hex, then one 'name value' line per metric
-    (GEOM_METRICS without the reserved one) with four decimals."""
+    (GEOM_METRICS without the reserved one) with four decimals.  A molecule that carries 'rings' (assemble(rings=)) gets
+    `> <PHOREGEN_RINGS>`: one line with the status as hex, then one 'name value' line per count (RING_COUNTS)."""
     names = names if names is not None else [''] * len(mols)
     if len(names) != len(mols):
         raise ValueError(f'write_sdf: {len(mols)} molecules, {len(names)} names')
@@ -428,6 +553,9 @@ def write_sdf(path, mols, names=None):
             if 'geom' in m:
                 fh.write('> <PHOREGEN_GEOM>\nstatus 0x%02x\n' % int(m['geom']['status'])
                          + ''.join('%s %.4f\n' % (k, m['geom'][k]) for k in GEOM_METRICS[:7]) + '\n')
+            if 'rings' in m:
+                fh.write('> <PHOREGEN_RINGS>\nstatus 0x%02x\n' % int(m['rings']['status'])
+                         + ''.join('%s %d\n' % (k, m['rings'][k]) for k in RING_COUNTS) + '\n')
             fh.write('$$$$\n')
 
 
@@ -561,7 +689,7 @@ def duplicate_groups(keys):
 
 # ---- the top-up loop of sample_all.py:79-84,172 ------------------------------------------------------------------------------
 def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, device='cuda', unique=False, geometry=None,
-                 **sample_kwargs):
+                 rings=None, **sample_kwargs):
     """Sample until `num_samples` molecules have passed the screen, giving up once more than `max_failed_factor * num_samples` have
     failed (checked before every draw, as the reference does).  Every draw asks for min(batch_size, what is still missing) graphs,
     so never more than `num_samples` are finished.  `sample_kwargs` (fragment=, pos_guidance_opt=, rng=, seed=, ...) go to
@@ -571,7 +699,12 @@ def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, d
     exactly); a repeat goes to the additional list 'duplicates', counts neither as finished nor as failed, and the loop also gives up
     once more than `max_failed_factor * num_samples` repeats have been seen.  The molecules then carry 'key' and 'atom_colour'.
     geometry=(point_pos, point_is_ex, limits), or True to take the pharmacophore of `data` (`geometry_for`, default limits): a valid
-    molecule is finished only if it is also 'geom_ok'; one that is not goes to 'failed'.  The molecules then carry 'geom'."""
+    molecule is finished only if it is also 'geom_ok'; one that is not goes to 'failed'.  The molecules then carry 'geom'.
+    rings=a `RingLimits`, or True for the default limits: a valid molecule is finished only if it is also 'rings_ok'; one that is not
+    goes to 'failed'.  The molecules then carry 'rings'."""
+    ring_limits = RingLimits() if rings is True else rings
+    if ring_limits is not None and not isinstance(ring_limits, RingLimits):
+        raise ValueError(f'phoregen_amd.molecule.sample_valid: rings= must be True or a RingLimits, not {rings!r}')
     finished, failed, duplicates, n_calls = [], [], [], 0
     by_key = {}                                                        # key -> finished molecules that have it
     while len(finished) < num_samples:
@@ -580,15 +713,19 @@ def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, d
         n = min(batch_size, num_samples - len(finished))
         res = model.sample(data, n, device, return_traj=False, **sample_kwargs)
         n_calls += 1
-        if geometry is None:
-            mols = assemble(res, keys=True) if unique else assemble(res)
-        elif geometry is True:
-            mols = assemble(res, keys=unique, geometry=geometry_for(data, res, ex_col=getattr(model, 'ex_col', 12)))
-        else:
+        geo = None
+        if geometry is True:
+            geo = geometry_for(data, res, ex_col=getattr(model, 'ex_col', 12))
+        elif geometry is not None:
             point_pos, point_is_ex, limits = geometry
-            mols = assemble(res, keys=unique, geometry=_geometry(res, point_pos, point_is_ex, limits=limits))
+            geo = _geometry(res, point_pos, point_is_ex, limits=limits)
+        ring = None
+        if ring_limits is not None:
+            ring = _rings(res, screen=geo.screen if geo is not None else None, limits=ring_limits)
+        mols = assemble(res, keys=unique, **{k: v for k, v in (('geometry', geo), ('rings', ring)) if v is not None})
         for m in mols:
-            if not m['valid'] or (geometry is not None and not m['geom']['geom_ok']):
+            if (not m['valid'] or (geometry is not None and not m['geom']['geom_ok'])
+                    or (ring_limits is not None and not m['rings']['rings_ok'])):
                 failed.append(m)
             elif unique and any(same_molecule(m, other) for other in by_key.setdefault(m['key'], [])):
                 duplicates.append(m)

@@ -13,7 +13,11 @@ counted apart; <outdir>/{name}_keys.txt then lists one 16-digit hex key per fini
 {name}_SMILES_all.txt plays) and the .sdf files carry the key as a data item.  --geometry (implies --valid_only) also measures every
 molecule against the pharmacophore it was generated for (phoregen_amd.molecule.geometry_for: bond lengths, clashes, clearance from the
 exclusion spheres, features with an atom nearby) and finishes it only if no limit is broken; --geom_limits '{"bond_max": 2.2}' replaces
-single limits of phoregen_amd.molecule.GeomLimits; the .sdf files carry the figures as a data item.  Without them nothing changes.
+single limits of phoregen_amd.molecule.GeomLimits; the .sdf files carry the figures as a data item.  --rings (implies --valid_only)
+also perceives the rings of every molecule (phoregen_amd.molecule.rings: smallest ring through every bond and atom, ring systems,
+rotatable bonds, aromatic bonds outside a ring) and finishes it only if no ring limit is broken; with the default limits that is the
+aromatic rule alone, --ring_limits '{"ring_min": 5, "ring_max": 8}' replaces single limits of phoregen_amd.molecule.RingLimits; the
+.sdf files carry the counts as a data item.  Without them nothing changes.
 """
 import argparse
 import json
@@ -29,7 +33,7 @@ from phoregen_amd.config import default_model_config, load_config  # noqa: E402
 from phoregen_amd.data import parse_phore_file  # noqa: E402
 from phoregen_amd.fragment import load_fragment_json  # noqa: E402
 from phoregen_amd.models.diffusion import PhoreDiff  # noqa: E402
-from phoregen_amd.molecule import GeomLimits, STATUS_NONFINITE, assemble, sample_valid, write_sdf  # noqa: E402
+from phoregen_amd.molecule import GeomLimits, RingLimits, STATUS_NONFINITE, assemble, sample_valid, write_sdf  # noqa: E402
 from phoregen_amd.utils.sample_utils import decode_batch  # noqa: E402
 from phoregen_amd.weights import init_deterministic_  # noqa: E402
 
@@ -57,12 +61,18 @@ def main():
     ap.add_argument('--geometry', action='store_true',
                     help='implies --valid_only: a molecule that breaks a geometry limit against its pharmacophore is not finished')
     ap.add_argument('--geom_limits', type=json.loads, default=None, help='JSON object replacing single limits of GeomLimits (with --geometry)')
+    ap.add_argument('--rings', action='store_true',
+                    help='implies --valid_only: a molecule that breaks a ring limit (default: an aromatic bond outside a ring) is not finished')
+    ap.add_argument('--ring_limits', type=json.loads, default=None, help='JSON object replacing single limits of RingLimits (with --rings)')
     ap.add_argument('--sdf', action='store_true', help='write one .sdf per molecule under <outdir>/sdf_results/')
     args = ap.parse_args()
     if args.geom_limits is not None and not args.geometry:
         ap.error('--geom_limits needs --geometry')
-    args.valid_only = args.valid_only or args.unique or args.geometry
+    if args.ring_limits is not None and not args.rings:
+        ap.error('--ring_limits needs --rings')
+    args.valid_only = args.valid_only or args.unique or args.geometry or args.rings
     geom_limits = GeomLimits(**(args.geom_limits or {}))
+    ring_limits = RingLimits(**(args.ring_limits or {})) if args.rings else None
     torch.manual_seed(args.seed)
     cfg = default_model_config()
     if args.config:
@@ -91,7 +101,8 @@ def main():
             if args.geometry:                                          # the points PhoreDiff.sample reads, in world coordinates
                 ph = data['phore']
                 geometry = (ph.pos.float() + data.center.float(), ph.x[:, model.ex_col] == 1, geom_limits)
-            out = sample_valid(model, data, args.num_samples, batch_size=args.batch_size, unique=args.unique, geometry=geometry, **kw)
+            out = sample_valid(model, data, args.num_samples, batch_size=args.batch_size, unique=args.unique, geometry=geometry,
+                               rings=ring_limits, **kw)
             done = out['finished']
             print(f"Finished {len(done)} | Failed {len(out['failed'])}" + (f" | Duplicates {len(out['duplicates'])}" if args.unique else ''))
             if args.unique:
