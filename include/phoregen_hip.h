@@ -533,6 +533,37 @@ int pg_mol_rings(const int8_t* cls, const int8_t* order, const int* g_lig_off /*
                  int n_lig, int n_bond, int max_n, const int* limits /*[4] host*/, uint8_t* ring_size, uint8_t* atom_ring,
                  int16_t* ring_sys, int* counts, int* status, void* stream);
 
+/* Kekulé form, hydrogens and charges of the molecules the screen decoded, one wave per (frame, graph).  Reads the screen's outputs
+ * cls [F][n_lig] and order [F][n_bond / 2] (frames dense) with the same offsets, as pg_mol_rings does: an atom is kept if its class is
+ * 0..10, a pair row a < b is a bond if its order is 1..4 and both ends are kept.  Definition: DESIGN.md 2.9 "Kekulé form".  Per kept
+ * atom a = its bonds of order 4, s = the sum of the orders of its other bonds; an atom with a >= 1 is aromatic and, in a pass with the
+ * table `cap`, NOT (s + a + 1 > cap[class]), MUST (else, must[class] != 0) or MAY.  Pass 0: cap = dbl_neutral; pass 1, run only if
+ * pass 0 is infeasible and allow_charged != 0: cap = max(dbl_neutral, dbl_charged).  A pass is feasible iff the bonds of order 4
+ * between atoms that are not NOT have a matching that covers every MUST atom; the kernel returns such a matching of maximum
+ * cardinality (Edmonds' algorithm with blossom contraction, exact; which maximum matching is not specified, its cardinality is).
+ * d = 1 for a matched atom; v = s + a + d; q = 1 if (class is N and v == 4) or (d == 1 and v > dbl_neutral[class]), else 0;
+ * h = t - (v - q) with t the smallest non-zero entry of h_valences[class] that is >= v - q, h = 0 without one.  If no pass is feasible
+ * PG_KEKULE_FAILED is set, kekule_order = order and every d = 0.
+ *   dbl_neutral, dbl_charged, must: uint8 [11] in DEVICE memory; h_valences: uint8 [11][4] in device memory, ascending, zero-padded
+ *   kekule_order [F][n_bond / 2] (aligned with order): order with every bond of order 4 replaced by 2 (matched) or 1; other rows copied
+ *   hcount [F][n_lig], charge [F][n_lig]: h and q per atom, 0 for a dropped atom
+ *   counts [F][B][PG_KEKULE_N_COUNTS]: 0 aromatic atoms, 1 bonds of order 4, 2 doubled bonds (0 on failure), 3 MUST atoms, 4 matched
+ *     MAY atoms (3 and 4 by the classification of the last pass run), 5 sum of h, 6 sum of q, 7 N or O atoms with h >= 1, 8 N and O
+ *     atoms, 9 kept atoms
+ *   status [F][B]: PG_KEKULE_* bits
+ * Integer work only: results are exact, and a graph's rows, the matching included, do not depend on its batch.  max_n above
+ * PG_MOL_MAX_ATOMS, a negative size or a null table: error before anything is launched, outputs untouched.  Every element of every
+ * output is written (nothing needs zeroing). */
+#define PG_KEKULE_FAILED 1           /* no feasible pass                                                       */
+#define PG_KEKULE_CHARGED 2          /* informational: the matching is pass 1's (never together with FAILED)   */
+#define PG_KEKULE_HAS_AROMATIC 4     /* informational: an atom with a bond of order 4                          */
+#define PG_KEKULE_CATION 8           /* informational: an atom with q != 0                                     */
+#define PG_KEKULE_N_COUNTS 10
+int pg_mol_kekule(const int8_t* cls, const int8_t* order, const int* g_lig_off /*[B+1]*/, const int* g_bond_off /*[B+1]*/, int B, int F,
+                  int n_lig, int n_bond, int max_n, const uint8_t* dbl_neutral /*[11]*/, const uint8_t* dbl_charged /*[11]*/,
+                  const uint8_t* must /*[11]*/, const uint8_t* h_valences /*[11][4]*/, int allow_charged, int8_t* kekule_order,
+                  uint8_t* hcount, int8_t* charge, int* counts, int* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -154,6 +154,8 @@ _PROTOS = {
                               c_ip, c_ip, C.c_int, C.POINTER(C.c_float), c_fp, c_ip, c_fp, c_ip, c_ip, C.c_void_p]),
     'pg_mol_rings': (C.c_int, [c_ip, c_ip, c_ip, c_ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int), c_ip, c_ip, c_ip,
                                c_ip, c_ip, C.c_void_p]),
+    'pg_mol_kekule': (C.c_int, [c_ip, c_ip, c_ip, c_ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_ip, c_ip, c_ip, c_ip, C.c_int, c_ip,
+                                c_ip, c_ip, c_ip, c_ip, C.c_void_p]),
 }
 
 EXPORTS = tuple(_PROTOS)

@@ -18,7 +18,12 @@ necessary, not sufficient: no force field, no hydrogens, no feature typing.
 
 Rings: `rings` finds the smallest ring through every bond and atom, the ring systems and the counts users filter on (csrc/mol_rings.hip;
 DESIGN.md 2.9 "Rings"): three- and four-membered rings, macrocycles, oversized fused systems, aromatic bonds outside a ring, rotatable
-bonds.  `assemble(rings=)`, `sample_valid(rings=)` and `write_sdf` carry it.  Exact integer answers; no kekulisation, no ring list."""
+bonds.  `assemble(rings=)`, `sample_valid(rings=)` and `write_sdf` carry it.  Exact integer answers; no kekulisation, no ring list.
+
+Kekulé form: `kekulize` resolves the aromatic bond class into single and double bonds and gives every atom its hydrogens and its
+charge (csrc/mol_kekule.hip; DESIGN.md 2.9 "Kekulé form"): an exact matching on the aromatic bonds, neutral first, with N+ / P+ / S+
+if that is allowed and needed.  `assemble(kekule=)`, `sample_valid(kekule=)`, `mol_block` and `write_sdf` carry it.  Which Kekulé
+structure is returned is not canonical; not checked against RDKit."""
 import ctypes
 from dataclasses import astuple, dataclass
 
@@ -85,6 +90,41 @@ RING_NAMES = {RING_AROMATIC_OUTSIDE: 'AROMATIC_OUTSIDE', RING_SMALL: 'SMALL', RI
 RING_COUNTS = ('rings', 'ring_bonds', 'ring_atoms', 'ring_systems', 'ring_min', 'ring_max', 'largest_system', 'rotatable',
                'aromatic_outside_ring', 'aromatic_lone')
 
+# The Kekulé form (DESIGN.md 2.9 "Kekulé form"): status bits, the names of the count columns in the kernel's order, and the tables
+# the kernel is handed, per element in ATOM_TYPES order.  With s = the sum of an atom's non-aromatic bond orders and a = its aromatic
+# bonds, an aromatic atom may carry the ring double bond in neutral form iff s + a + 1 <= KEKULE_DBL_NEUTRAL, as a cation iff
+# s + a + 1 <= KEKULE_DBL_CHARGED; an atom with KEKULE_MUST that can carry one must get one.  H_VALENCES: the valences hydrogens fill
+# an atom up to (the smallest that is not below what it already has).
+# CAVEAT, as for MAX_VALENCE: written from memory; RDKit is not a dependency of this project and the tables have not been checked
+# against it.  These are the tables' only copies: the kernel and the tests' restatement are handed them.
+KEKULE_FAILED = 1                # neither the neutral nor (if allowed) the charged pass has a Kekulé structure
+KEKULE_CHARGED = 2               # informational: the structure is the charged pass's (never together with KEKULE_FAILED)
+KEKULE_HAS_AROMATIC = 4          # informational: an atom with a bond of order 4
+KEKULE_CATION = 8                # informational: an atom with a charge
+KEKULE_FAIL_MASK = KEKULE_FAILED
+KEKULE_NAMES = {KEKULE_FAILED: 'FAILED', KEKULE_CHARGED: 'CHARGED', KEKULE_HAS_AROMATIC: 'HAS_AROMATIC', KEKULE_CATION: 'CATION'}
+KEKULE_COUNTS = ('aromatic_atoms', 'aromatic_bonds', 'doubled', 'must_atoms', 'may_matched', 'hydrogens', 'charge', 'hbd', 'hba',
+                 'heavy_atoms')
+_KEKULE_KEYS = {k: 'net_charge' if k == 'charge' else k for k in KEKULE_COUNTS}   # (a molecule's dict has 'charge' per atom)
+KEKULE_DBL_NEUTRAL = {5: 0, 6: 4, 7: 3, 8: 0, 9: 0, 14: 4, 15: 3, 16: 0, 17: 0, 35: 0, 53: 0}
+KEKULE_DBL_CHARGED = {5: 0, 6: 0, 7: 4, 8: 0, 9: 0, 14: 0, 15: 4, 16: 3, 17: 0, 35: 0, 53: 0}
+KEKULE_MUST = {5: 0, 6: 1, 7: 0, 8: 0, 9: 0, 14: 1, 15: 0, 16: 0, 17: 0, 35: 0, 53: 0}
+H_VALENCES = {5: (3,), 6: (4,), 7: (3,), 8: (2,), 9: (1,), 14: (4,), 15: (3, 5), 16: (2, 4, 6), 17: (1,), 35: (1,), 53: (1, 3, 5)}
+assert list(KEKULE_DBL_NEUTRAL) == list(KEKULE_DBL_CHARGED) == list(KEKULE_MUST) == list(H_VALENCES) == ATOM_TYPES
+# Standard atomic weights for 'mol_weight' (written from memory, abridged values)
+ATOMIC_WEIGHT = {1: 1.008, 5: 10.81, 6: 12.011, 7: 14.007, 8: 15.999, 9: 18.998, 14: 28.085, 15: 30.974, 16: 32.06, 17: 35.45,
+                 35: 79.904, 53: 126.904}
+
+
+@dataclass(frozen=True)
+class KekuleOptions:
+    """allow_charged: if the neutral pass has no Kekulé structure, try again with N+ / P+ / S+ carrying a ring double bond."""
+    allow_charged: bool = True
+
+    def __post_init__(self):
+        if not isinstance(self.allow_charged, (bool, np.bool_)):
+            raise ValueError(f'KekuleOptions: allow_charged must be a bool, not {self.allow_charged!r}')
+
 
 @dataclass(frozen=True)
 class RingLimits:
@@ -122,6 +162,18 @@ def _valence_table(device):
     t = _max_valence2.get(device)
     if t is None:
         t = _max_valence2[device] = torch.tensor([2 * MAX_VALENCE[z] for z in ATOM_TYPES], dtype=torch.uint8, device=device)
+    return t
+
+
+_kekule_tables = {}              # device -> (uint8 [11] x 3, uint8 [11, 4])
+
+
+def _kekule_table(device):
+    t = _kekule_tables.get(device)
+    if t is None:
+        rows = [[d[z] for z in ATOM_TYPES] for d in (KEKULE_DBL_NEUTRAL, KEKULE_DBL_CHARGED, KEKULE_MUST)]
+        rows.append([list(H_VALENCES[z]) + [0] * (4 - len(H_VALENCES[z])) for z in ATOM_TYPES])
+        t = _kekule_tables[device] = tuple(torch.tensor(r, dtype=torch.uint8, device=device) for r in rows)
     return t
 
 
@@ -415,8 +467,97 @@ def _launch_rings(lib, cls, order, lig_off, bond_off, B, F, max_n, limits, out):
                                out['status'].data_ptr(), hip.stream_ptr()), 'pg_mol_rings')
 
 
+@dataclass
+class Kekule:
+    """Device tensors of one `kekulize` call; F frames, B graphs, N atom rows, H pair rows (as the screen's `order`)."""
+    status: torch.Tensor         # int32 [F, B]     KEKULE_* bits
+    counts: torch.Tensor         # int32 [F, B, 10] KEKULE_COUNTS
+    ok: torch.Tensor             # bool  [F, B]     no bit of KEKULE_FAIL_MASK
+    kekule_order: torch.Tensor   # int8  [F, H]     the screen's `order` with every 4 replaced by 2 or 1 (unchanged where not ok)
+    hcount: torch.Tensor         # uint8 [F, N]     hydrogens of the atom; 0 for a dropped one
+    charge: torch.Tensor         # int8  [F, N]     formal charge of the atom (0 or +1); 0 for a dropped one
+    options: KekuleOptions
+    screen: Screen               # the screen it was computed from
+
+
+@torch.no_grad()
+def kekulize(results, frames='final', screen=None, options=KekuleOptions()):
+    """Kekulé form, hydrogens and charges of every decoded (frame, graph) of a `sample` / `sample_batch` result, on the device, in
+    one launch (pg_mol_kekule; DESIGN.md 2.9 "Kekulé form"): double bonds are placed on aromatic bonds, at most one per atom, so that
+    every aromatic C / Si that can still take one gets one (N, P, S may), as many as possible; first with neutral atoms only, then --
+    options.allow_charged -- with N+ / P+ / S+.  `ok` is a separate answer from the screen's `valid` and the rings' `ok`: no ring
+    test is applied, an aromatic bond on a chain takes part like any other.  A `Screen` of the same result and frames is reused if
+    handed in.  No host read beyond the screen's.  Exact: feasibility and the number of double bonds do not depend on the numbering
+    of the atoms; WHICH Kekulé structure is returned does, so this is no canonical form and nothing to build a key from.  `hydrogens -
+    charge` is the same for every structure.  No stereo, tautomers, anions, O+; not checked against RDKit."""
+    node, _, edge, F, _ = _frames(results, frames)
+    dev = node.device
+    if dev.type != 'cuda':
+        raise RuntimeError('phoregen_amd.molecule.kekulize: the Kekulé assignment is a HIP kernel and the result lives on %s; there is '
+                           'no CPU fallback' % dev)
+    if not isinstance(options, KekuleOptions):
+        raise ValueError(f'phoregen_amd.molecule.kekulize: options must be a KekuleOptions, not {options!r}')
+    sc = screen if screen is not None else _screen(results, frames)
+    B, N = len(sc.num_atoms), node.size(-2)
+    if tuple(sc.status.shape) != (F, B) or sc.cls.size(1) != N or sc.cls.device != dev or 2 * sc.order.size(1) != edge.size(-2):
+        raise ValueError(f'phoregen_amd.molecule.kekulize: the screen ({tuple(sc.status.shape)} frames x graphs, {sc.cls.size(1)} atom '
+                         f'rows) is not one of this result and frames ({F} frames, {N} atom rows)')
+    with torch.cuda.device(dev):
+        lib = hip.lib()
+        out = dict(status=torch.empty(F, B, dtype=torch.int32, device=dev),
+                   counts=torch.empty(F, B, len(KEKULE_COUNTS), dtype=torch.int32, device=dev),
+                   kekule_order=torch.empty(F, sc.order.size(1), dtype=torch.int8, device=dev),
+                   hcount=torch.empty(F, N, dtype=torch.uint8, device=dev), charge=torch.empty(F, N, dtype=torch.int8, device=dev))
+        _launch_kekule(lib, sc.cls, sc.order, sc.lig_off, sc.bond_off, B, F, max(sc.num_atoms, default=0), _kekule_table(dev),
+                       bool(options.allow_charged), out)
+    return Kekule(ok=(out['status'] & KEKULE_FAIL_MASK) == 0, options=options, screen=sc, **out)
+
+
+def _launch_kekule(lib, cls, order, lig_off, bond_off, B, F, max_n, tables, allow_charged, out):
+    """pg_mol_kekule on the current stream; tables = (DBL_NEUTRAL, DBL_CHARGED, MUST [11], H_VALENCES [11, 4]) as uint8 on the device.
+    A graph above MAX_ATOMS is the library's error: nothing is launched and `out` is not written."""
+    dev = cls.device
+    for t, dt in ((cls, torch.int8), (order, torch.int8), (lig_off, torch.int32), (bond_off, torch.int32), (out['kekule_order'], torch.int8),
+                  (out['hcount'], torch.uint8), (out['charge'], torch.int8), (out['counts'], torch.int32), (out['status'], torch.int32),
+                  *((t, torch.uint8) for t in tables)):
+        if t.dtype != dt or not t.is_contiguous() or t.device != dev:
+            raise ValueError('phoregen_amd.molecule.kekulize: cls / order / kekule_order / charge must be contiguous int8, the offsets '
+                             'int32, hcount and the tables uint8, counts / status int32, all on one device')
+    if (lig_off.numel() != B + 1 or bond_off.numel() != B + 1 or cls.numel() != F * cls.size(-1) or order.numel() != F * order.size(-1)
+            or out['kekule_order'].shape != order.shape or out['hcount'].shape != cls.shape or out['charge'].shape != cls.shape
+            or out['status'].numel() != F * B or out['counts'].numel() != len(KEKULE_COUNTS) * F * B or len(tables) != 4
+            or [t.numel() for t in tables] != [len(ATOM_TYPES)] * 3 + [4 * len(ATOM_TYPES)]):
+        raise ValueError(f'phoregen_amd.molecule.kekulize: sizes of the offsets, screen arrays, tables and outputs do not fit {F} frames x '
+                         f'{B} graphs, {cls.size(-1)} atom rows, {order.size(-1)} pair rows')
+    hip.check(lib.pg_mol_kekule(cls.data_ptr(), order.data_ptr(), lig_off.data_ptr(), bond_off.data_ptr(), B, F, cls.size(-1),
+                                2 * order.size(-1), max_n, tables[0].data_ptr(), tables[1].data_ptr(), tables[2].data_ptr(),
+                                tables[3].data_ptr(), int(bool(allow_charged)), out['kekule_order'].data_ptr(), out['hcount'].data_ptr(),
+                                out['charge'].data_ptr(), out['counts'].data_ptr(), out['status'].data_ptr(), hip.stream_ptr()),
+              'pg_mol_kekule')
+
+
+def formula_of(elements, hcount, charge=0):
+    """Molecular formula in Hill order (C, H, then the other symbols alphabetically; all alphabetically without carbon) from atomic
+    numbers and per-atom hydrogen counts, with a charge suffix such as '+' / '2+' / '-', and the molecular weight from ATOMIC_WEIGHT
+    (standard atomic weights, written from memory)."""
+    n = {}
+    for z in elements:
+        n[ELEMENT_SYMBOL[int(z)]] = n.get(ELEMENT_SYMBOL[int(z)], 0) + 1
+    n_h = int(np.asarray(hcount, dtype=np.int64).sum())
+    weight = sum(ATOMIC_WEIGHT[int(z)] for z in elements) + n_h * ATOMIC_WEIGHT[1]
+    if n_h:
+        n['H'] = n_h
+    first = [k for k in ('C', 'H') if k in n] if 'C' in n else []
+    text = ''.join(k + (str(n[k]) if n[k] > 1 else '') for k in first + sorted(k for k in n if k not in first))
+    q = int(charge)
+    if q:
+        text += (str(abs(q)) if abs(q) > 1 else '') + ('+' if q > 0 else '-')
+    return text, float(weight)
+
+
 _geometry = geometry             # (functions below take a `geometry=` argument)
 _rings = rings                   # (and a `rings=` argument)
+_kekulize = kekulize
 _PAIRS = {}
 
 
@@ -430,7 +571,7 @@ def _pairs(n):
 
 
 @torch.no_grad()
-def assemble(results, keys=False, geometry=None, rings=None):
+def assemble(results, keys=False, geometry=None, rings=None, kekule=None):
     """The final prediction as one dict per graph with `decode_data`'s keys and meaning -- 'element' (atomic numbers), 'atom_pos'
     (kept atoms, the tensor's own fp32 values), 'bond_index' [2, n_b] (indices among the kept atoms) and 'bond_type' [n_b] for
     a < b only, in row order -- plus 'status', 'valid', 'n_components' and 'valence' (per kept atom, halves allowed).  The screen runs
@@ -443,17 +584,23 @@ def assemble(results, keys=False, geometry=None, rings=None):
     rings=a `Rings` of this result's final frame: every dict also has 'rings' -- 'status' (RING_* bits), 'rings_ok' (no bit of
     RING_FAIL_MASK), the ten RING_COUNTS by name, 'bond_ring_size' (per entry of 'bond_type', in its order), 'atom_ring' and
     'ring_sys' (per kept atom; the system's first atom as an index into this dict's atoms, -1 = none) -- in the same copy; its screen
-    is reused, and with geometry= too both must have been computed from one screen."""
+    is reused, and with geometry= too both must have been computed from one screen.
+    kekule=a `Kekule` of this result's final frame: every dict also has 'kekule' -- 'status' (KEKULE_* bits), 'kekule_ok' (no bit of
+    KEKULE_FAIL_MASK), the ten KEKULE_COUNTS by name (the count 'charge' as 'net_charge': 'charge' is per atom here), 'bond_type' (the Kekulé order per entry of the dict's 'bond_type', in its
+    order; 4 stays 4 where not kekule_ok), 'hcount' and 'charge' (per kept atom), 'formula' (Hill order with the hydrogens and a
+    charge suffix such as '+' / '2+') and 'mol_weight' (`formula_of`: from standard atomic weights written from memory; both computed
+    on the host) -- in the same copy; its screen is reused, and it must have been computed from the screen of geometry= / rings=."""
     geom, pos_t = geometry, results['pred'][1]
-    for what, x in (('geometry', geom), ('rings', rings)):
-        if x is not None and (x.status.size(0) != 1 or x.screen.cls.size(1) != pos_t.size(-2) or x.status.device != pos_t.device):
+    given = [(what, x) for what, x in (('geometry', geom), ('rings', rings), ('kekule', kekule)) if x is not None]
+    for what, x in given:
+        if x.status.size(0) != 1 or x.screen.cls.size(1) != pos_t.size(-2) or x.status.device != pos_t.device:
             raise ValueError(f'phoregen_amd.molecule.assemble: {what}= must be a {what.capitalize()} of the final frame of this result')
-    if geom is not None and rings is not None and geom.screen is not rings.screen:
-        a, b = geom.screen, rings.screen
-        if (a.num_atoms != b.num_atoms or a.status.shape != b.status.shape or a.cls.shape != b.cls.shape or a.order.shape != b.order.shape
-                or a.cls.device != b.cls.device):
-            raise ValueError('phoregen_amd.molecule.assemble: geometry= and rings= were computed from screens of different results')
-    sc = geom.screen if geom is not None else rings.screen if rings is not None else screen(results, 'final')
+    for (what_a, xa), (what_b, xb) in zip(given, given[1:]):
+        a, b = xa.screen, xb.screen
+        if a is not b and (a.num_atoms != b.num_atoms or a.status.shape != b.status.shape or a.cls.shape != b.cls.shape
+                           or a.order.shape != b.order.shape or a.cls.device != b.cls.device):
+            raise ValueError(f'phoregen_amd.molecule.assemble: {what_a}= and {what_b}= were computed from screens of different results')
+    sc = given[0][1].screen if given else screen(results, 'final')
     # the parts of the one blob, widest elements first so that every part stays aligned in it
     parts = []
     if keys:
@@ -461,6 +608,8 @@ def assemble(results, keys=False, geometry=None, rings=None):
         parts += [('key', mk.key[0], np.uint64), ('colour', mk.colour[0], np.uint64)]
     if rings is not None:
         parts += [('r_status', rings.status[0], np.int32), ('r_counts', rings.counts[0], np.int32)]
+    if kekule is not None:
+        parts += [('k_status', kekule.status[0], np.int32), ('k_counts', kekule.counts[0], np.int32)]
     if geom is not None:
         parts += [('g_status', geom.status[0], np.int32), ('g_metrics', geom.metrics[0], np.float32), ('g_counts', geom.counts[0], np.int32),
                   ('g_dist', geom.point_dist[0], np.float32), ('g_off', geom.point_off, np.int32)]
@@ -473,6 +622,8 @@ def assemble(results, keys=False, geometry=None, rings=None):
     parts += [('cls', sc.cls[0], np.int8), ('valence2', sc.valence2[0], np.uint8), ('order', sc.order[0], np.int8)]
     if rings is not None:
         parts += [('r_atom', rings.atom_ring[0], np.uint8), ('r_size', rings.ring_size[0], np.uint8)]
+    if kekule is not None:
+        parts += [('k_order', kekule.kekule_order[0], np.int8), ('k_h', kekule.hcount[0], np.uint8), ('k_q', kekule.charge[0], np.int8)]
     sizes = [t.numel() * t.element_size() for _, t, _ in parts]
     blob = torch.cat([t.reshape(-1).view(torch.uint8) for _, t, _ in parts]).cpu().numpy()
     cut = np.cumsum([0] + sizes)
@@ -484,6 +635,8 @@ def assemble(results, keys=False, geometry=None, rings=None):
         g_metrics, g_counts = v['g_metrics'].reshape(-1, 8), v['g_counts'].reshape(-1, 6)
     if rings is not None:
         r_counts = v['r_counts'].reshape(-1, len(RING_COUNTS))
+    if kekule is not None:
+        k_counts = v['k_counts'].reshape(-1, len(KEKULE_COUNTS))
     mols, n0, h0 = [], 0, 0
     for g, n in enumerate(sc.num_atoms):
         h = n * (n - 1) // 2
@@ -512,6 +665,13 @@ def assemble(results, keys=False, geometry=None, rings=None):
                                      **{k: int(x) for k, x in zip(RING_COUNTS, r_counts[g])},
                                      bond_ring_size=v['r_size'][h0:h0 + h][nz].copy(), atom_ring=v['r_atom'][n0:n0 + n][keep].copy(),
                                      ring_sys=np.where(sys_g >= 0, cmp_g[np.maximum(sys_g, 0)], -1).astype(np.int16))
+        if kekule is not None:
+            k_h, k_q = v['k_h'][n0:n0 + n][keep].copy(), v['k_q'][n0:n0 + n][keep].copy()
+            formula, weight = formula_of(mols[-1]['element'], k_h, int(k_q.astype(np.int64).sum()))
+            mols[-1]['kekule'] = dict({'status': int(v['k_status'][g]), 'kekule_ok': (int(v['k_status'][g]) & KEKULE_FAIL_MASK) == 0},
+                                      **{_KEKULE_KEYS[k]: int(x) for k, x in zip(KEKULE_COUNTS, k_counts[g])},
+                                      bond_type=torch.from_numpy(v['k_order'][h0:h0 + h][nz].astype(np.int64)), hcount=k_h, charge=k_q,
+                                      formula=formula, mol_weight=weight)
         n0, h0 = n0 + n, h0 + h
     return mols
 
@@ -519,19 +679,34 @@ def assemble(results, keys=False, geometry=None, rings=None):
 # ---- V2000 mol blocks (CTfile format) ---------------------------------------------------------------------------------------
 def mol_block(mol, name=''):
     """One V2000 mol block of an assembled molecule: three header lines (name, program line with the '3D' flag, empty comment),
-    the counts line, one line per atom and per bond (type 4 = aromatic), 'M  END'."""
+    the counts line, one line per atom and per bond (type 4 = aromatic), 'M  END'.
+    A molecule that carries 'kekule' (assemble(kekule=)) with 'kekule_ok' is written in Kekulé form: bond types 1 / 2 / 3 from
+    kekule['bond_type'], a charged atom's charge in the atom line's `ccc` field (3 = +1, 2 = +2, 1 = +3, 5 = -1, 6 = -2, 7 = -3) and in
+    'M  CHG' lines of at most eight entries before 'M  END'.  Hydrogens stay implicit.  Without 'kekule', or with a failed one, the
+    block is as it always was."""
     elements, pos = mol['element'], np.asarray(mol['atom_pos'], dtype=np.float64).reshape(-1, 3)
     bi, bt = np.asarray(mol['bond_index']).reshape(2, -1), np.asarray(mol['bond_type']).reshape(-1)
+    kek = mol.get('kekule')
+    kek = kek if kek is not None and kek.get('kekule_ok') else None
+    charge = [0] * len(elements)
+    if kek is not None:
+        bt, charge = np.asarray(kek['bond_type']).reshape(-1), [int(q) for q in np.asarray(kek['charge']).reshape(-1).tolist()]
+        if bt.size != bi.shape[1] or len(charge) != len(elements) or any(abs(q) > 3 for q in charge):
+            raise ValueError(f"mol_block: 'kekule' has {bt.size} bond types and {len(charge)} charges for {bi.shape[1]} bonds and "
+                             f'{len(elements)} atoms (charges within -3 .. 3)')
     if len(elements) > 999 or bt.size > 999:
         raise ValueError(f'mol_block: {len(elements)} atoms / {bt.size} bonds do not fit the 3-digit counts of a V2000 block')
     if not np.isfinite(pos).all():
         raise ValueError('mol_block: non-finite coordinates')
     lines = [str(name).split('\n')[0], '  PhoreGen' + ' ' * 10 + '3D', '',
              '%3d%3d  0  0  0  0  0  0  0  0999 V2000' % (len(elements), bt.size)]
-    for z, (x, y, zc) in zip(elements, pos.tolist()):
-        lines.append('%10.4f%10.4f%10.4f %-3s 0  0  0  0  0  0  0  0  0  0  0  0' % (x, y, zc, ELEMENT_SYMBOL[int(z)]))
+    for z, (x, y, zc), q in zip(elements, pos.tolist(), charge):
+        lines.append('%10.4f%10.4f%10.4f %-3s 0%3d  0  0  0  0  0  0  0  0  0  0' % (x, y, zc, ELEMENT_SYMBOL[int(z)], (4 - q) if q else 0))
     for (a, b), t in zip(bi.T.tolist(), bt.tolist()):
         lines.append('%3d%3d%3d  0' % (a + 1, b + 1, t))
+    charged = [(i + 1, q) for i, q in enumerate(charge) if q]
+    for k in range(0, len(charged), 8):
+        lines.append('M  CHG%3d' % len(charged[k:k + 8]) + ''.join(' %3d %3d' % e for e in charged[k:k + 8]))
     lines.append('M  END')
     return '\n'.join(lines) + '\n'
 
@@ -541,7 +716,9 @@ def write_sdf(path, mols, names=None):
     gets one data item `> <PHOREGEN_KEY>` with the key as 16 hex digits between its block and the '$$$$'.  A molecule that carries
     'geom' (assemble(geometry=)) gets `> <PHOREGEN_GEOM>`: one line with the status as hex, then one 'name value' line per metric
     (GEOM_METRICS without the reserved one) with four decimals.  A molecule that carries 'rings' (assemble(rings=)) gets
-    `> <PHOREGEN_RINGS>`: one line with the status as hex, then one 'name value' line per count (RING_COUNTS)."""
+    `> <PHOREGEN_RINGS>`: one line with the status as hex, then one 'name value' line per count (RING_COUNTS).  A molecule that
+    carries 'kekule' (assemble(kekule=)) is written in Kekulé form if that is ok (`mol_block`) and gets `> <PHOREGEN_KEKULE>`: the
+    status as hex, 'formula', 'mol_weight' with three decimals, then one 'name value' line per count (KEKULE_COUNTS)."""
     names = names if names is not None else [''] * len(mols)
     if len(names) != len(mols):
         raise ValueError(f'write_sdf: {len(mols)} molecules, {len(names)} names')
@@ -556,6 +733,10 @@ def write_sdf(path, mols, names=None):
             if 'rings' in m:
                 fh.write('> <PHOREGEN_RINGS>\nstatus 0x%02x\n' % int(m['rings']['status'])
                          + ''.join('%s %d\n' % (k, m['rings'][k]) for k in RING_COUNTS) + '\n')
+            if 'kekule' in m:
+                fh.write('> <PHOREGEN_KEKULE>\nstatus 0x%02x\nformula %s\nmol_weight %.3f\n'
+                         % (int(m['kekule']['status']), m['kekule']['formula'], m['kekule']['mol_weight'])
+                         + ''.join('%s %d\n' % (k, m['kekule'][_KEKULE_KEYS[k]]) for k in KEKULE_COUNTS) + '\n')
             fh.write('$$$$\n')
 
 
@@ -689,7 +870,7 @@ def duplicate_groups(keys):
 
 # ---- the top-up loop of sample_all.py:79-84,172 ------------------------------------------------------------------------------
 def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, device='cuda', unique=False, geometry=None,
-                 rings=None, **sample_kwargs):
+                 rings=None, kekule=None, **sample_kwargs):
     """Sample until `num_samples` molecules have passed the screen, giving up once more than `max_failed_factor * num_samples` have
     failed (checked before every draw, as the reference does).  Every draw asks for min(batch_size, what is still missing) graphs,
     so never more than `num_samples` are finished.  `sample_kwargs` (fragment=, pos_guidance_opt=, rng=, seed=, ...) go to
@@ -701,10 +882,15 @@ def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, d
     geometry=(point_pos, point_is_ex, limits), or True to take the pharmacophore of `data` (`geometry_for`, default limits): a valid
     molecule is finished only if it is also 'geom_ok'; one that is not goes to 'failed'.  The molecules then carry 'geom'.
     rings=a `RingLimits`, or True for the default limits: a valid molecule is finished only if it is also 'rings_ok'; one that is not
-    goes to 'failed'.  The molecules then carry 'rings'."""
+    goes to 'failed'.  The molecules then carry 'rings'.
+    kekule=a `KekuleOptions`, or True for the default options: a valid molecule is finished only if it is also 'kekule_ok' (it has a
+    Kekulé structure); one that is not goes to 'failed'.  The molecules then carry 'kekule'.  All of these share one screen per draw."""
     ring_limits = RingLimits() if rings is True else rings
     if ring_limits is not None and not isinstance(ring_limits, RingLimits):
         raise ValueError(f'phoregen_amd.molecule.sample_valid: rings= must be True or a RingLimits, not {rings!r}')
+    kek_options = KekuleOptions() if kekule is True else kekule
+    if kek_options is not None and not isinstance(kek_options, KekuleOptions):
+        raise ValueError(f'phoregen_amd.molecule.sample_valid: kekule= must be True or a KekuleOptions, not {kekule!r}')
     finished, failed, duplicates, n_calls = [], [], [], 0
     by_key = {}                                                        # key -> finished molecules that have it
     while len(finished) < num_samples:
@@ -722,10 +908,14 @@ def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, d
         ring = None
         if ring_limits is not None:
             ring = _rings(res, screen=geo.screen if geo is not None else None, limits=ring_limits)
-        mols = assemble(res, keys=unique, **{k: v for k, v in (('geometry', geo), ('rings', ring)) if v is not None})
+        kek = None
+        if kek_options is not None:
+            kek = _kekulize(res, screen=geo.screen if geo is not None else ring.screen if ring is not None else None, options=kek_options)
+        mols = assemble(res, keys=unique, **{k: v for k, v in (('geometry', geo), ('rings', ring), ('kekule', kek)) if v is not None})
         for m in mols:
             if (not m['valid'] or (geometry is not None and not m['geom']['geom_ok'])
-                    or (ring_limits is not None and not m['rings']['rings_ok'])):
+                    or (ring_limits is not None and not m['rings']['rings_ok'])
+                    or (kek_options is not None and not m['kekule']['kekule_ok'])):
                 failed.append(m)
             elif unique and any(same_molecule(m, other) for other in by_key.setdefault(m['key'], [])):
                 duplicates.append(m)

@@ -1,0 +1,400 @@
+"""-m gpu: the Kekulé kernel (csrc/mol_kekule.hip through phoregen_amd/molecule.py) against the plain restatement of
+tests/kekule_reference.py, and the functions that carry its answers.  Integer work only: every comparison is `==`.  Which maximum
+matching the kernel returns is its own business: feasibility, the pass, |M| and the counts no matching moves are compared, the
+matching and everything that follows from it are validated by their properties (`check_assignment`)."""
+import dataclasses
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import kekule_reference as K
+import mol_reference as R
+import ring_reference as G
+from phoregen_amd import molecule as M
+
+pytestmark = pytest.mark.gpu
+DEV = 'cuda'
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CI = M.KEKULE_COUNTS.index
+
+
+@pytest.fixture(scope='module')
+def model():
+    from phoregen_amd.config import default_model_config
+    from phoregen_amd.models.diffusion import PhoreDiff
+    from phoregen_amd.weights import init_deterministic_
+    return init_deterministic_(PhoreDiff(default_model_config(), 'zinc_300'), 0).eval().to(DEV)
+
+
+@pytest.fixture(scope='module')
+def family():
+    """The random family, its rows and the restatement's answers: computed once, read by several tests, changed by none."""
+    graphs = K.random_family()
+    rows = [K.rows_of(c, b) for c, b in graphs]
+    return graphs, rows, [K.kekule_of_rows(cls, order) for cls, order in rows]
+
+
+def _result(node, pos, edge, sizes, traj=(None, None, None)):
+    """A sampler-shaped result dict on the device."""
+    from phoregen_amd.plan import make_edge_data
+    na = torch.tensor(sizes, dtype=torch.long)
+    ei, eb = make_edge_data(na)
+    return {'pred': [node.to(DEV), pos.to(DEV), edge.to(DEV)], 'traj': list(traj),
+            'lig_info': [na.to(DEV), torch.repeat_interleave(torch.arange(len(sizes)), na).to(DEV), ei.to(DEV), eb.to(DEV)]}
+
+
+def _permute_batch(node, pos, edge, sizes, seed):
+    """Every graph's atoms renumbered at random (atom i becomes perms[g][i]) and both halves of its bond rows moved to the rows of
+    the renumbered pairs."""
+    rng = np.random.default_rng(seed)
+    node2, pos2, edge2, perms = node.clone(), pos.clone(), edge.clone(), []
+    n0, e0 = 0, 0
+    for n in sizes:
+        h = n * (n - 1) // 2
+        p = rng.permutation(n)
+        perms.append(p)
+        dst = torch.from_numpy(n0 + p)
+        node2[dst], pos2[dst] = node[n0:n0 + n], pos[n0:n0 + n]
+        if h:
+            a, b = np.triu_indices(n, 1)
+            lo, hi = np.minimum(p[a], p[b]), np.maximum(p[a], p[b])
+            rows = torch.from_numpy(lo * n - lo * (lo + 1) // 2 + (hi - lo - 1))
+            edge2[e0 + rows] = edge[e0:e0 + h]
+            edge2[e0 + h + rows] = edge[e0 + h:e0 + 2 * h]
+        n0, e0 = n0 + n, e0 + 2 * h
+    return node2, pos2, edge2, perms
+
+
+def _split(kk, sizes, f=0):
+    """Frame f of a `Kekule` as one dict of numpy arrays per graph, in the restatement's form, plus the screen's rows."""
+    ko, hc, ch = kk.kekule_order[f].cpu().numpy(), kk.hcount[f].cpu().numpy(), kk.charge[f].cpu().numpy()
+    cls, order = kk.screen.cls[f].cpu().numpy(), kk.screen.order[f].cpu().numpy()
+    counts, status, ok = kk.counts[f].cpu().numpy(), kk.status[f].cpu().tolist(), kk.ok[f].cpu().tolist()
+    out, n0, h0 = [], 0, 0
+    for g, n in enumerate(sizes):
+        h = n * (n - 1) // 2
+        out.append({'kekule_order': ko[h0:h0 + h], 'hcount': hc[n0:n0 + n], 'charge': ch[n0:n0 + n], 'counts': counts[g],
+                    'status': status[g], 'ok': ok[g], 'cls': cls[n0:n0 + n], 'order': order[h0:h0 + h]})
+        n0, h0 = n0 + n, h0 + h
+    return out
+
+
+def _run(node, pos, edge, sizes, allow=True):
+    kk = M.kekulize(_result(node, pos, edge, sizes), options=M.KekuleOptions(allow_charged=allow))
+    torch.cuda.synchronize()
+    N, H = sum(sizes), sum(n * (n - 1) // 2 for n in sizes)
+    assert kk.status.shape == kk.ok.shape == (1, len(sizes)) and kk.counts.shape == (1, len(sizes), 10) and kk.kekule_order.shape == (1, H)
+    assert kk.hcount.shape == kk.charge.shape == (1, N) and kk.options == M.KekuleOptions(allow_charged=allow)
+    assert (kk.status.dtype, kk.counts.dtype, kk.ok.dtype) == (torch.int32, torch.int32, torch.bool)
+    assert (kk.kekule_order.dtype, kk.hcount.dtype, kk.charge.dtype) == (torch.int8, torch.uint8, torch.int8)
+    return kk, _split(kk, sizes)
+
+
+def _check(graphs, allow=True, expects=None, where=''):
+    """The kernel on one batch of (classes, bonds) graphs, every graph validated; returns (Kekule, per-graph outputs, solutions)."""
+    node, pos, edge, sizes = G.batch_from(graphs)
+    kk, got = _run(node, pos, edge, sizes, allow)
+    sols = []
+    for g, ((classes, bonds), r) in enumerate(zip(graphs, got)):
+        cls, order = K.rows_of(classes, bonds)
+        assert np.array_equal(r['cls'], cls) and np.array_equal(r['order'], order), (where, g)     # (what the screen decoded)
+        assert r['ok'] == (r['status'] & M.KEKULE_FAILED == 0)
+        sols.append(K.check_assignment(cls, order, r, allow, expect=expects[g] if expects else None, where='%s %d' % (where, g)))
+    return kk, got, sols
+
+
+def _same_facts(r, w, where):
+    """What no choice of matching moves: the status, hydrogens - charge and the INDEPENDENT counts."""
+    assert r['status'] & 7 == w['status'] & 7, (where, r['status'], w['status'])
+    assert int(r['hcount'].sum()) - int(r['charge'].sum()) == w['h_minus_q'], where
+    assert int(r['counts'][CI('hydrogens')]) - int(r['counts'][CI('charge')]) == w['h_minus_q'], where
+    for c in K.INDEPENDENT:
+        assert int(r['counts'][CI(c)]) == int(w['counts'][CI(c)]), (where, c)
+
+
+def test_named_molecules_by_hand_and_by_the_restatement():
+    names = [k for k in K.NAMED if K.NAMED[k][2]]
+    kk, got, sols = _check([K.NAMED[k][:2] for k in names], where='named')
+    for k, r in zip(names, got):
+        _, _, _, status, doubled, hydrogens, charge, atoms = K.NAMED[k]
+        assert r['status'] == status, k
+        assert (int(r['counts'][CI('doubled')]), int(r['counts'][CI('hydrogens')]), int(r['counts'][CI('charge')])) == (doubled, hydrogens, charge), k
+        assert {i: (int(r['hcount'][i]), int(r['charge'][i])) for i in atoms} == atoms, k
+    by = dict(zip(names, got))
+    assert sorted(by['imidazole']['hcount'][[0, 2]].tolist()) == [0, 1] and by['pyrrole']['counts'][CI('hbd')] == 1
+    assert by['pyridazine']['counts'][CI('doubled')] == 3 and by['pyridine']['counts'][CI('may_matched')] == 1
+    assert np.array_equal(by['indene-like']['kekule_order'], by['indene-like']['order'])           # failed: 4 stays 4
+    # the outputs do not depend on what their buffers held: a call into recycled memory agrees
+    first = [dict(r) for r in got]
+    del kk
+    _, again, _ = _check([K.NAMED[k][:2] for k in names], where='again')
+    for a, b in zip(first, again):
+        assert all(np.array_equal(a[key], b[key]) for key in a)
+
+
+def test_random_family(family):
+    graphs, rows, want = family
+    kk, got, sols = _check(graphs, where='family')
+    assert [len(c) for c, _ in graphs[:12]] == [1, 2, 3, 5, 6, 9, 10, 63, 64, 65, 127, 128]
+    for g, (r, w, s) in enumerate(zip(got, want, sols)):
+        _same_facts(r, w, 'family %d' % g)
+        assert s['size'] == w['solution']['size'] and s['pass'] == w['solution']['pass'] and s['feasible'] == w['solution']['feasible']
+    kinds = [K.outcome(s) for s in sols]
+    assert min(kinds.count(k) for k in ('neutral', 'charged', 'failed')) >= 14
+
+
+def test_alone_and_inside_a_batch(family):
+    """The search order depends on the graph alone: the matching, too, is the same alone and in the batch."""
+    graphs, _, _ = family
+    pick = [g for g in range(len(graphs)) if len(graphs[g][0]) in (9, 10, 64, 65, 128)][:10]
+    _, together, _ = _check([graphs[g] for g in pick], where='together')
+    for g, r in zip(pick, together):
+        _, (alone,), _ = _check([graphs[g]], where='alone %d' % g)
+        assert all(np.array_equal(alone[key], r[key]) for key in r), g
+
+
+def test_renumbered_graphs(family):
+    graphs, rows, want = family
+    graphs = list(graphs) + [K.NAMED[k][:2] for k in ('azulene', 'indole', 'N-methylpyridinium', 'imidazole')] + list(K.BLOSSOM.values())
+    node, pos, edge, sizes = G.batch_from(graphs)
+    node2, pos2, edge2, perms = _permute_batch(node, pos, edge, sizes, seed=13)
+    _, base = _run(node, pos, edge, sizes)
+    kk2, moved = _run(node2, pos2, edge2, sizes)
+    for g, (a, b, p) in enumerate(zip(base, moved, perms)):
+        assert np.array_equal(b['cls'][p], a['cls'])
+        sol = K.check_assignment(b['cls'], b['order'], b, where='renumbered %d' % g)   # the matching is validated, not compared
+        assert a['status'] == b['status'], g
+        assert int(a['hcount'].sum()) - int(a['charge'].sum()) == int(b['hcount'].sum()) - int(b['charge'].sum()), g
+        for c in K.INDEPENDENT:
+            assert a['counts'][CI(c)] == b['counts'][CI(c)], (g, c)
+        assert sol['size'] == int(a['counts'][CI('doubled')])
+        if not (a['charge'] != 0).any() and not (b['charge'] != 0).any():
+            assert a['counts'][CI('hydrogens')] == b['counts'][CI('hydrogens')], g
+        # what is not aromatic is carried over as it is
+        n = sizes[g]
+        ia, ib = np.triu_indices(n, 1)
+        lo, hi = np.minimum(p[ia], p[ib]), np.maximum(p[ia], p[ib])
+        rows_b = lo * n - lo * (lo + 1) // 2 + (hi - lo - 1)
+        plain = a['order'] != 4
+        assert np.array_equal(b['kekule_order'][rows_b][plain], a['kekule_order'][plain])
+
+
+def test_large_graphs_with_known_answers():
+    lad = ([K.C_] * 128, K.ladder(64))
+    broken = ([K.C_] * 64 + [K.O_] + [K.C_] * 63, K.ladder(64))        # the O cannot take a double bond: 127 MUST atoms are left
+    ring = ([K.C_] * 128, K.cycle(128))
+    odd_ring = ([K.C_] * 127, K.cycle(127))
+    kk, got, _ = _check([lad, broken, ring, odd_ring], expects=[(True, 0, 64), (False, 1, 0), (True, 0, 64), (False, 1, 0)], where='large')
+    # (126 rail bonds and 32 rungs; the 62 inner rung atoms carry no H, the four rail ends without a rung two, the other 62 one)
+    assert got[0]['counts'].tolist() == [128, 158, 64, 128, 0, 2 * 4 + 60, 0, 0, 0, 128] and got[0]['status'] == M.KEKULE_HAS_AROMATIC
+    assert got[1]['status'] == M.KEKULE_HAS_AROMATIC | M.KEKULE_FAILED and got[1]['counts'].tolist()[:5] == [128, 158, 0, 127, 0]
+    assert np.array_equal(got[1]['kekule_order'], got[1]['order'])
+    assert got[2]['hcount'].tolist() == [1] * 128 and got[3]['hcount'].tolist() == [2] * 127
+
+
+def test_dense_graph_from_random_logits():
+    """Random logits bond about two thirds of all pairs: every atom is far above its cap, nothing is allowed, nothing fails."""
+    n, B = 128, 2
+    gen = torch.Generator().manual_seed(5)
+    node, edge = torch.randn(B * n, 12, generator=gen), torch.randn(B * n * (n - 1), 6, generator=gen)
+    node[:, 11] -= 4.0
+    pos = torch.randn(B * n, 3, generator=gen)
+    kk, got = _run(node, pos, edge, [n] * B)
+    for g, r in enumerate(got):
+        K.check_assignment(r['cls'], r['order'], r, where='dense %d' % g)
+        c = dict(zip(M.KEKULE_COUNTS, r['counts'].tolist()))
+        assert r['status'] & M.KEKULE_FAILED == 0 and c['doubled'] == 0 and c['must_atoms'] == 0 and c['aromatic_bonds'] > 1000
+        assert set(np.unique(r['kekule_order']).tolist()) <= {0, 1, 2, 3} and (r['kekule_order'][r['order'] == 4] == 1).all()
+
+
+def test_graphs_that_need_blossom_contraction():
+    graphs = list(K.BLOSSOM.values())
+    # the same graphs with a tail of ballast in front, so that the aromatic part straddles the lanes' second atom
+    graphs += [([K.C_] * 60 + c, {**K.chain(60, 1), (59, 60): 1, **{(a + 60, b + 60): t for (a, b), t in b_.items()}}) for c, b_ in K.BLOSSOM.values()]
+    kk, got, sols = _check(graphs, where='blossom')
+    for (classes, _), r, s in zip(graphs, got, sols):
+        n_arom = len(classes) - (60 if len(classes) > 60 else 0)
+        assert s['feasible'] and r['counts'][CI('doubled')] == n_arom // 2 and r['counts'][CI('aromatic_atoms')] == n_arom
+
+
+def test_dropped_atom_and_absorbing_row_inside_a_ring():
+    graphs = [([K.C_, K.C_, 11, K.C_, K.C_, K.C_], K.cycle(6)),       # the ring opens: a path of five MUST atoms, no structure
+              ([K.C_, K.C_, 11, K.C_, K.C_, K.C_, K.C_], {**K.cycle(6), (5, 6): 4}),   # ... a sixth atom on the path: three double bonds
+              ([K.C_] * 6, {**K.cycle(6), (2, 3): 5}),                # a class-5 row in the ring: the same path of six
+              ([K.N_] + [K.C_] * 5, {**K.cycle(6), (0, 3): 5, (1, 4): 5}),   # class-5 rows across the ring change nothing
+              ([11] * 5, K.cycle(5))]
+    kk, got, _ = _check(graphs, where='dropped')
+    assert [r['status'] for r in got] == [M.KEKULE_HAS_AROMATIC | M.KEKULE_FAILED, M.KEKULE_HAS_AROMATIC, M.KEKULE_HAS_AROMATIC,
+                                          M.KEKULE_HAS_AROMATIC, 0]
+    assert got[0]['counts'].tolist() == [5, 4, 0, 5, 0, 12, 0, 0, 0, 5] and got[0]['hcount'].tolist() == [2, 3, 0, 3, 2, 2]
+    assert got[1]['counts'].tolist()[:4] == [6, 5, 3, 6] and got[2]['counts'].tolist()[:4] == [6, 5, 3, 6]
+    assert got[3]['counts'].tolist() == [6, 6, 3, 5, 1, 5, 0, 0, 1, 6] and got[4]['counts'].tolist() == [0] * 10
+    sc = kk.screen
+    assert int(sc.status[0, 0]) & M.STATUS_HAD_MASKED_ATOM and int(sc.status[0, 2]) & M.STATUS_HAD_ABSORBING_BOND
+
+
+def test_neutral_only():
+    names = ['thiopyrylium', 'N-methylpyridinium', 'pyridine', 'all-carbon five-ring']
+    graphs = [K.NAMED[k][:2] for k in names]
+    kk, got, sols = _check(graphs, allow=False, where='neutral only')
+    A, F = M.KEKULE_HAS_AROMATIC, M.KEKULE_FAILED
+    assert [r['status'] for r in got] == [A | F, A | F, A, A | F] and [s['pass'] for s in sols] == [0, 0, 0, 0]
+    assert got[0]['counts'].tolist() == [6, 6, 0, 5, 0, 10, 0, 0, 0, 6]
+    _, both, _ = _check(graphs, allow=True, where='charged allowed')
+    assert [r['status'] & (F | M.KEKULE_CHARGED) for r in both] == [M.KEKULE_CHARGED, M.KEKULE_CHARGED, 0, F]
+    with pytest.raises(ValueError, match='KekuleOptions'):
+        M.kekulize(_result(*G.batch_from(graphs)[:3], [len(c) for c, _ in graphs]), options=True)
+
+
+def test_trajectory_frames():
+    """frames='traj', F = 3 in one launch: benzene, then one ring atom turned into O (furan-like six-ring: an odd path), then one
+    bond made single (hexatriene-like: still three double bonds)."""
+    frames = [[([K.C_] * 6, K.cycle(6)), ([K.N_] + [K.C_] * 4, K.cycle(5))],
+              [([K.O_] + [K.C_] * 5, K.cycle(6)), ([K.N_] + [K.C_] * 4, K.cycle(5))],
+              [([K.C_] * 6, {**K.cycle(6), (0, 5): 1}), ([K.C_] * 5, K.cycle(5))]]
+    per = [G.batch_from(f) for f in frames]
+    sizes = per[0][3]
+    traj = tuple(torch.stack([p[k] for p in per]).to(DEV) for k in range(3))
+    res = _result(*per[-1][:3], sizes, traj=traj)
+    kk = M.kekulize(res, frames='traj')
+    assert kk.status.shape == (3, 2) and kk.kekule_order.shape == (3, 15 + 10) and kk.hcount.shape == kk.charge.shape == (3, 11)
+    for f, graphs in enumerate(frames):
+        for (classes, bonds), r in zip(graphs, _split(kk, sizes, f)):
+            K.check_assignment(*K.rows_of(classes, bonds), r, where='frame %d' % f)
+    A, F = M.KEKULE_HAS_AROMATIC, M.KEKULE_FAILED
+    assert kk.status.tolist() == [[A, A], [A | F, A], [A, A | F]] and kk.counts[:, 0, CI('doubled')].tolist() == [3, 0, 3]
+    assert kk.ok.tolist() == [[True, True], [False, True], [True, False]]
+    # a screen handed in is reused; one of other frames is refused
+    sc = M.screen(res, frames='traj')
+    assert M.kekulize(res, frames='traj', screen=sc).screen is sc
+    with pytest.raises(ValueError, match='screen'):
+        M.kekulize(res, frames='final', screen=sc)
+    final = M.kekulize(res)
+    assert torch.equal(final.status[0], kk.status[2]) and torch.equal(final.kekule_order[0], kk.kekule_order[2])
+
+
+def test_assemble_carries_the_kekule_form(tmp_path):
+    names = ['N-methylpyridinium', 'indole', 'all-carbon five-ring', '2-pyridone']
+    graphs = [K.NAMED[k][:2] for k in names] + [([K.C_, 11, K.C_, K.N_, K.C_, K.C_, K.C_, K.O_], {**K.cycle(5, off=2), (0, 2): 1, (4, 7): 1, (1, 2): 1})]
+    node, pos, edge, sizes = G.batch_from(graphs)
+    res = _result(node, pos, edge, sizes)
+    kk = M.kekulize(res)
+    got = _split(kk, sizes)
+    plain, full = M.assemble(res), M.assemble(res, kekule=kk)
+    for g, (p, m, r) in enumerate(zip(plain, full, got)):
+        assert set(m) == set(p) | {'kekule'}
+        for name in p:                                                 # the default output, key for key
+            assert torch.equal(p[name], m[name]) if torch.is_tensor(p[name]) else np.array_equal(p[name], m[name]), name
+        k = m['kekule']
+        assert set(k) == {'status', 'kekule_ok', 'bond_type', 'hcount', 'charge', 'formula', 'mol_weight', 'net_charge'} | (set(M.KEKULE_COUNTS) - {'charge'})
+        assert [k['net_charge' if c == 'charge' else c] for c in M.KEKULE_COUNTS] == r['counts'].tolist()
+        assert k['status'] == r['status'] and k['kekule_ok'] == r['ok']
+        keep = r['cls'] >= 0
+        assert k['hcount'].dtype == np.uint8 and k['hcount'].tolist() == r['hcount'][keep].tolist()
+        assert k['charge'].dtype == np.int8 and k['charge'].tolist() == r['charge'][keep].tolist()
+        rows = np.nonzero(r['order'])[0]
+        assert k['bond_type'].tolist() == r['kekule_order'][rows].tolist() and len(k['bond_type']) == len(m['bond_type'])
+        assert (k['bond_type'] == 4).any().item() == (not k['kekule_ok'])
+        assert (k['formula'], k['mol_weight']) == M.formula_of(m['element'], k['hcount'], k['net_charge'])
+    assert [m['kekule']['formula'] for m in full] == ['C6H8N+', 'C8H7N', 'C5H10', 'C5H5NO', 'C5H7NO']
+    assert full[0]['kekule']['mol_weight'] == pytest.approx(94.137) and full[4]['kekule']['hcount'].tolist() == [3, 0, 1, 0, 1, 1, 1]
+    # the blocks: Kekulé form with the charge where it is ok, as before where it is not
+    block = M.mol_block(full[0], 'x')
+    assert 'M  CHG  1   1   1\n' in block and ' N   0  3  0' in block and all(ln[6:9] in ('  1', '  2') for ln in block.split('\n')[11:18])
+    assert M.mol_block(full[2], 'y') == M.mol_block(plain[2], 'y')
+    path = tmp_path / 'k.sdf'
+    M.write_sdf(str(path), full)
+    text = path.read_text()
+    assert text.count('> <PHOREGEN_KEKULE>') == 5 and 'formula C6H8N+\nmol_weight 94.137\n' in text and text.count('M  CHG') == 1
+    # keys, geometry, rings and the Kekulé form ride in one copy, all from one screen
+    pts, ex = torch.tensor([[0.0, 0.0, 0.0], [4.0, 1.0, 0.0]]), torch.tensor([0, 1])
+    geo = M.geometry(res, pts, ex, screen=kk.screen)
+    rg = M.rings(res, screen=kk.screen)
+    every = M.assemble(res, keys=True, geometry=geo, rings=rg, kekule=kk)
+    without = M.assemble(res, keys=True, geometry=geo, rings=rg)
+    for m, q, w in zip(every, without, full):
+        assert set(m) == set(q) | {'kekule'} and m['key'] == q['key'] and m['geom']['status'] == q['geom']['status']
+        assert m['rings']['status'] == q['rings']['status'] and np.array_equal(m['rings']['ring_sys'], q['rings']['ring_sys'])
+        assert all(np.array_equal(m['kekule'][k], w['kekule'][k]) for k in w['kekule'])
+    assert M.assemble(res, rings=M.rings(res), kekule=kk)[1]['kekule']['status'] == full[1]['kekule']['status']   # equal screens
+    with pytest.raises(ValueError, match='kekule='):                    # of another result
+        M.assemble(res, kekule=M.kekulize(_result(*G.batch_from([K.NAMED['benzene'][:2]])[:3], [6])))
+    with pytest.raises(ValueError, match='kekule='):                    # of more than the final frame
+        M.assemble(res, kekule=dataclasses.replace(kk, status=kk.status.repeat(2, 1)))
+    swapped = _result(node, pos, edge, sizes[:3] + sizes[:2:-1])       # as many atom and bond rows, other graphs
+    with pytest.raises(ValueError, match='different results'):
+        M.assemble(res, rings=M.rings(swapped), kekule=kk)
+    with pytest.raises(ValueError, match='different results'):
+        M.assemble(res, geometry=M.geometry(swapped, pts, ex), kekule=kk)
+
+
+def test_sample_valid_with_kekule(model):
+    """Deterministic noise weights: what they decode to is unknown; whatever is finished has a Kekulé structure, and finished and
+    failed account for every draw."""
+    from phoregen_amd.data import parse_phore_file
+    data = parse_phore_file(os.path.join(ROOT, 'tests', 'data', 'synthetic_test.phore')).to(DEV)
+    torch.manual_seed(5)
+    drawn = []
+    sample = model.sample
+
+    class Counting:
+        ex_col = getattr(model, 'ex_col', 12)
+
+        def sample(self, data, n, device, **kw):
+            drawn.append(n)
+            return sample(data, n, device, **kw)
+    out = M.sample_valid(Counting(), data, num_samples=4, batch_size=4, max_failed_factor=1, kekule=True, num_steps=10)
+    assert set(out) == {'finished', 'failed', 'n_calls'} and out['n_calls'] == len(drawn) >= 1
+    assert len(out['finished']) + len(out['failed']) == sum(drawn)
+    assert len(out['finished']) == 4 or len(out['failed']) > 4
+    for m in out['finished']:
+        assert m['valid'] and m['kekule']['kekule_ok'] and not (np.asarray(m['kekule']['bond_type']) == 4).any()
+    for m in out['failed']:
+        assert not m['valid'] or not m['kekule']['kekule_ok']
+    # a stand-in model that hands out pyridine, the all-carbon five-ring and thiopyrylium in turn
+    parts = [R.scores_from_classes(*K.NAMED[k][:2]) for k in ('pyridine', 'all-carbon five-ring', 'thiopyrylium')]
+
+    class Rota:
+        i = 0
+
+        def sample(self, data, n, device, **kw):
+            pick = [parts[(self.i + j) % 3] for j in range(n)]
+            self.i += n
+            return _result(*(torch.cat([p[k] for p in pick]) for k in range(3)), [p[0].size(0) for p in pick])
+    out = M.sample_valid(Rota(), None, num_samples=4, batch_size=3, kekule=True, rings=True, unique=True)
+    assert [m['kekule']['formula'] for m in out['finished']] == ['C5H5N', 'C5H5S+'] and len(out['duplicates']) > 0
+    assert all(m['kekule']['formula'] == 'C5H10' and m['rings']['rings_ok'] for m in out['failed'])
+    out = M.sample_valid(Rota(), None, num_samples=2, batch_size=3, kekule=M.KekuleOptions(allow_charged=False), max_failed_factor=2)
+    assert [m['kekule']['formula'] for m in out['finished']] == ['C5H5N', 'C5H5N']
+    assert sorted({m['kekule']['formula'] for m in out['failed']}) == ['C5H10', 'C5H10S']
+
+
+def test_cpu_result_and_oversize_graph_are_refused():
+    from phoregen_amd import hip
+    node, pos, edge, _ = R.scores_from_classes([1, 3], {(0, 1): 1})
+    with pytest.raises(RuntimeError, match='no CPU fallback'):
+        M.kekulize({'pred': [node, pos, edge], 'traj': [None, None, None], 'lig_info': [torch.tensor([2])]})
+    n = M.MAX_ATOMS + 1
+    h = n * (n - 1) // 2
+    cls = torch.zeros(1, n, dtype=torch.int8, device=DEV)
+    order = torch.zeros(1, h, dtype=torch.int8, device=DEV)
+    off = torch.tensor([0, n], dtype=torch.int32, device=DEV)
+    boff = torch.tensor([0, 2 * h], dtype=torch.int32, device=DEV)
+    out = dict(status=torch.full((1, 1), 77, dtype=torch.int32, device=DEV), counts=torch.full((1, 1, 10), 77, dtype=torch.int32, device=DEV),
+               kekule_order=torch.full((1, h), 77, dtype=torch.int8, device=DEV), hcount=torch.full((1, n), 77, dtype=torch.uint8, device=DEV),
+               charge=torch.full((1, n), 77, dtype=torch.int8, device=DEV))
+    tables = M._kekule_table(cls.device)
+    with pytest.raises(RuntimeError) as err:
+        M._launch_kekule(hip.lib(), cls, order, off, boff, 1, 1, n, tables, True, out)
+    assert 'PG_MOL_MAX_ATOMS' in str(err.value) and 'pg_mol_kekule' in str(err.value) and str(n) in str(err.value)
+    with pytest.raises(RuntimeError, match='pg_mol_kekule'):
+        M._launch_kekule(hip.lib(), cls, order, off, boff, 1, 1, -1, tables, True, out)
+    with pytest.raises(ValueError, match='kekulize'):
+        M._launch_kekule(hip.lib(), cls, order, off, boff, 1, 1, n, tables[:3], True, out)
+    torch.cuda.synchronize()
+    assert all((t == 77).all() for t in out.values())
+    # empty batches return without a launch
+    empty = M.kekulize(_result(torch.zeros(0, 12), torch.zeros(0, 3), torch.zeros(0, 6), []))
+    assert empty.status.shape == (1, 0) and empty.kekule_order.shape == (1, 0) and empty.counts.shape == (1, 0, 10)

@@ -17,7 +17,11 @@ single limits of phoregen_amd.molecule.GeomLimits; the .sdf files carry the figu
 also perceives the rings of every molecule (phoregen_amd.molecule.rings: smallest ring through every bond and atom, ring systems,
 rotatable bonds, aromatic bonds outside a ring) and finishes it only if no ring limit is broken; with the default limits that is the
 aromatic rule alone, --ring_limits '{"ring_min": 5, "ring_max": 8}' replaces single limits of phoregen_amd.molecule.RingLimits; the
-.sdf files carry the counts as a data item.  Without them nothing changes.
+.sdf files carry the counts as a data item.  --kekule (implies --valid_only) also resolves the aromatic bonds into single and double
+bonds and gives every atom its hydrogens and charge (phoregen_amd.molecule.kekulize), and finishes a molecule only if it has such a
+Kekulé structure; --no_charged forbids the N+ / P+ / S+ structures tried when no neutral one exists; with --sdf the blocks are then
+written in Kekulé form with charges, and carry formula, weight and counts as the data item PHOREGEN_KEKULE.  Without them nothing
+changes.
 """
 import argparse
 import json
@@ -33,7 +37,7 @@ from phoregen_amd.config import default_model_config, load_config  # noqa: E402
 from phoregen_amd.data import parse_phore_file  # noqa: E402
 from phoregen_amd.fragment import load_fragment_json  # noqa: E402
 from phoregen_amd.models.diffusion import PhoreDiff  # noqa: E402
-from phoregen_amd.molecule import GeomLimits, RingLimits, STATUS_NONFINITE, assemble, sample_valid, write_sdf  # noqa: E402
+from phoregen_amd.molecule import GeomLimits, KekuleOptions, RingLimits, STATUS_NONFINITE, assemble, sample_valid, write_sdf  # noqa: E402
 from phoregen_amd.utils.sample_utils import decode_batch  # noqa: E402
 from phoregen_amd.weights import init_deterministic_  # noqa: E402
 
@@ -64,15 +68,21 @@ def main():
     ap.add_argument('--rings', action='store_true',
                     help='implies --valid_only: a molecule that breaks a ring limit (default: an aromatic bond outside a ring) is not finished')
     ap.add_argument('--ring_limits', type=json.loads, default=None, help='JSON object replacing single limits of RingLimits (with --rings)')
+    ap.add_argument('--kekule', action='store_true',
+                    help='implies --valid_only: a molecule without a Kekulé structure is not finished; .sdf blocks are written in Kekulé form')
+    ap.add_argument('--no_charged', action='store_true', help='with --kekule: neutral Kekulé structures only (no N+ / P+ / S+)')
     ap.add_argument('--sdf', action='store_true', help='write one .sdf per molecule under <outdir>/sdf_results/')
     args = ap.parse_args()
     if args.geom_limits is not None and not args.geometry:
         ap.error('--geom_limits needs --geometry')
     if args.ring_limits is not None and not args.rings:
         ap.error('--ring_limits needs --rings')
-    args.valid_only = args.valid_only or args.unique or args.geometry or args.rings
+    if args.no_charged and not args.kekule:
+        ap.error('--no_charged needs --kekule')
+    args.valid_only = args.valid_only or args.unique or args.geometry or args.rings or args.kekule
     geom_limits = GeomLimits(**(args.geom_limits or {}))
     ring_limits = RingLimits(**(args.ring_limits or {})) if args.rings else None
+    kekule = KekuleOptions(allow_charged=not args.no_charged) if args.kekule else None
     torch.manual_seed(args.seed)
     cfg = default_model_config()
     if args.config:
@@ -102,7 +112,7 @@ def main():
                 ph = data['phore']
                 geometry = (ph.pos.float() + data.center.float(), ph.x[:, model.ex_col] == 1, geom_limits)
             out = sample_valid(model, data, args.num_samples, batch_size=args.batch_size, unique=args.unique, geometry=geometry,
-                               rings=ring_limits, **kw)
+                               rings=ring_limits, kekule=kekule, **kw)
             done = out['finished']
             print(f"Finished {len(done)} | Failed {len(out['failed'])}" + (f" | Duplicates {len(out['duplicates'])}" if args.unique else ''))
             if args.unique:
