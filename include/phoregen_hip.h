@@ -564,6 +564,39 @@ int pg_mol_kekule(const int8_t* cls, const int8_t* order, const int* g_lig_off /
                   const uint8_t* must /*[11]*/, const uint8_t* h_valences /*[11][4]*/, int allow_charged, int8_t* kekule_order,
                   uint8_t* hcount, int8_t* charge, int* counts, int* status, void* stream);
 
+/* Pharmacophore feature typing of the molecules the screen decoded and the typed match against their feature points, one wave per
+ * (frame, graph).  Definition: DESIGN.md 2.9 "Features".  Reads the coordinates (pos, pos_fs as pg_mol_geom takes them), the screen's
+ * cls [F][n_lig], order [F][n_bond / 2] and compact [F][n_lig], pg_mol_kekule's kekule_order [F][n_bond / 2], hcount, charge [F][n_lig]
+ * and status [F][B], and pg_mol_rings' ring_size [F][n_bond / 2] (frames dense, the same offsets).  Every kept atom (class 0..10) gets
+ * a byte with one bit per type, in the order HD, AR, PO, HA, HY, NE, XB (bit 0..6): the reference's SMARTS per type restated as
+ * integer rules over element, hydrogens, charge, degree, Kekulé bond orders, the screen's aromatic bond class and ring membership
+ * (csrc/feature_core.h).  A graph whose Kekulé status has PG_KEKULE_FAILED has all bytes 0 and PG_FEAT_NO_KEKULE.
+ * Points: point_pos [n_point][3] in the coordinates of pos, point_kind int8 [n_point]: 0..6 = the type to match, -1 = a feature of a
+ * type that is not typed (counted, never matched, never missed), anything else = ignored (exclusion spheres).  Graph g has the rows
+ * g_point_range[g][0] .. [g][1] and writes its per-point outputs from g_point_out_off[g] on, as in pg_mol_geom.  A typed point of type
+ * t is matched iff a kept atom with finite coordinates carries bit t and lies at a distance < feat_cut (strict; distance =
+ * sqrtf(dx*dx + dy*dy + dz*dz) in fp32, as pg_mol_geom).  A kept atom or a typed or untyped point with a non-finite coordinate sets
+ * PG_FEAT_NONFINITE; such an atom matches nothing, such a point is left out of every count.
+ *   atom_fp [F][n_lig]: the byte; 0 for a dropped atom
+ *   point_dist [F][n_point_out], point_atom [F][n_point_out]: distance to the nearest atom THAT CARRIES THE POINT'S TYPE and that
+ *     atom's compact index; first minimum in atom order; +inf and -1 without one, and for every point that is not typed
+ *   counts [F][B][PG_FEAT_N_COUNTS]: 0 typed points, 1 matched, 2 unmatched, 3 untyped points, 4..10 atoms per type, 11..17 points per
+ *     type, 18..24 matched points per type
+ *   status [F][B]: PG_FEAT_* bits; UNMATCHED iff unmatched > max_unmatched
+ * Typing is integer work and exact; a graph's rows do not depend on its batch.  max_n above PG_MOL_MAX_ATOMS, a negative size or (with
+ * B, F > 0) a null array: error before anything is launched, outputs untouched.  Every element of every output is written. */
+#define PG_FEAT_NO_KEKULE 1          /* the graph has no Kekulé structure to type from                         */
+#define PG_FEAT_UNMATCHED 2          /* more than max_unmatched typed points without a carrying atom in reach  */
+#define PG_FEAT_HAS_UNTYPED 4        /* informational: a point of kind -1                                      */
+#define PG_FEAT_NONFINITE 8          /* a kept atom or a point with a non-finite coordinate                    */
+#define PG_FEAT_N_COUNTS 25
+int pg_mol_feat(const float* pos, int64_t pos_fs, const int8_t* cls, const int8_t* order, const int16_t* compact,
+                const int8_t* kekule_order, const uint8_t* hcount, const int8_t* charge, const int* kekule_status /*[F][B]*/,
+                const uint8_t* ring_size, const int* g_lig_off /*[B+1]*/, const int* g_bond_off /*[B+1]*/, int B, int F, int n_lig,
+                int n_bond, int max_n, const float* point_pos, const int8_t* point_kind, int n_point,
+                const int* g_point_range /*[B][2]*/, const int* g_point_out_off /*[B+1]*/, int n_point_out, float feat_cut,
+                int max_unmatched, uint8_t* atom_fp, float* point_dist, int16_t* point_atom, int* counts, int* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

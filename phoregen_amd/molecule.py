@@ -23,7 +23,13 @@ bonds.  `assemble(rings=)`, `sample_valid(rings=)` and `write_sdf` carry it.  Ex
 Kekulé form: `kekulize` resolves the aromatic bond class into single and double bonds and gives every atom its hydrogens and its
 charge (csrc/mol_kekule.hip; DESIGN.md 2.9 "Kekulé form"): an exact matching on the aromatic bonds, neutral first, with N+ / P+ / S+
 if that is allowed and needed.  `assemble(kekule=)`, `sample_valid(kekule=)`, `mol_block` and `write_sdf` carry it.  Which Kekulé
-structure is returned is not canonical; not checked against RDKit."""
+structure is returned is not canonical; not checked against RDKit.
+
+Features: `features` / `features_for` give every atom the pharmacophore feature types it presents -- the reference's SMARTS for HD, AR,
+PO, HA, HY, NE, XB restated as integer rules over the Kekulé form, the hydrogens, the charges and the ring membership -- and match
+every typed feature point against the atoms that carry its type (csrc/mol_feat.hip; DESIGN.md 2.9 "Features"), as the reference's
+`check_nearby_phore(strict=True)` does with RDKit.  `assemble(features=)`, `sample_valid(features=)` and `write_sdf` carry it.  MB, CV
+and CR are not typed; the tables are written from the SMARTS text and not checked against RDKit."""
 import ctypes
 from dataclasses import astuple, dataclass
 
@@ -111,6 +117,19 @@ KEKULE_DBL_CHARGED = {5: 0, 6: 0, 7: 4, 8: 0, 9: 0, 14: 0, 15: 4, 16: 3, 17: 0, 
 KEKULE_MUST = {5: 0, 6: 1, 7: 0, 8: 0, 9: 0, 14: 1, 15: 0, 16: 0, 17: 0, 35: 0, 53: 0}
 H_VALENCES = {5: (3,), 6: (4,), 7: (3,), 8: (2,), 9: (1,), 14: (4,), 15: (3, 5), 16: (2, 4, 6), 17: (1,), 35: (1,), 53: (1, 3, 5)}
 assert list(KEKULE_DBL_NEUTRAL) == list(KEKULE_DBL_CHARGED) == list(KEKULE_MUST) == list(H_VALENCES) == ATOM_TYPES
+# The feature typing (DESIGN.md 2.9 "Features"): the typed feature types in the order of the bits of an atom's byte, status bits, and
+# the names of the count columns in the kernel's order
+FEATURE_TYPES = ('HD', 'AR', 'PO', 'HA', 'HY', 'NE', 'XB')
+FEAT_NO_KEKULE = 1               # the graph has no Kekulé structure: nothing to type from, every typed point is unmatched
+FEAT_UNMATCHED = 2               # more than max_unmatched typed points without an atom of their type closer than feat_cut
+FEAT_HAS_UNTYPED = 4             # informational: a feature point of a type that is not typed (MB, CV1..CV4, CR)
+FEAT_NONFINITE = 8               # a kept atom or a feature point with a non-finite coordinate
+FEAT_FAIL_MASK = FEAT_NO_KEKULE | FEAT_UNMATCHED | FEAT_NONFINITE
+FEAT_NAMES = {FEAT_NO_KEKULE: 'NO_KEKULE', FEAT_UNMATCHED: 'UNMATCHED', FEAT_HAS_UNTYPED: 'HAS_UNTYPED', FEAT_NONFINITE: 'NONFINITE'}
+FEATURE_COUNTS = (('typed_points', 'matched', 'unmatched', 'untyped_points') + tuple('atoms_' + t for t in FEATURE_TYPES)
+                  + tuple('points_' + t for t in FEATURE_TYPES) + tuple('matched_' + t for t in FEATURE_TYPES))
+POINT_UNTYPED, POINT_IGNORED = -1, -2   # point kinds beside 0..6: a feature that is not typed; an exclusion sphere
+
 # Standard atomic weights for 'mol_weight' (written from memory, abridged values)
 ATOMIC_WEIGHT = {1: 1.008, 5: 10.81, 6: 12.011, 7: 14.007, 8: 15.999, 9: 18.998, 14: 28.085, 15: 30.974, 16: 32.06, 17: 35.45,
                  35: 79.904, 53: 126.904}
@@ -140,6 +159,23 @@ class RingLimits:
         for k, v in zip(('ring_min', 'ring_max', 'system_max', 'rotatable_max'), astuple(self)):
             if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= 0x7fffffff:
                 raise ValueError(f'RingLimits: {k} must be an integer in 0 .. 2**31 - 1, not {v!r}')
+
+
+@dataclass(frozen=True)
+class FeatureLimits:
+    """Limits of the typed feature match.  feat_cut: `check_nearby_phore`'s cutoff in Angstrom (utils/phore_utils.py:406), the
+    comparison is strict; max_unmatched: FEAT_UNMATCHED is set when more typed points than this have no atom of their type within
+    feat_cut.  With the defaults only FEAT_NO_KEKULE / FEAT_NONFINITE can fail; FeatureLimits(max_unmatched=0) asks for every typed
+    feature."""
+    feat_cut: float = 2.0
+    max_unmatched: int = 2 ** 31 - 1
+
+    def __post_init__(self):
+        c, m = self.feat_cut, self.max_unmatched
+        if isinstance(c, bool) or not isinstance(c, (int, float, np.integer, np.floating)) or not np.isfinite(c) or c < 0:
+            raise ValueError(f'FeatureLimits: feat_cut must be a finite number >= 0, not {c!r}')
+        if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not 0 <= m <= 0x7fffffff:
+            raise ValueError(f'FeatureLimits: max_unmatched must be an integer in 0 .. 2**31 - 1, not {m!r}')
 
 
 @dataclass(frozen=True)
@@ -536,6 +572,141 @@ def _launch_kekule(lib, cls, order, lig_off, bond_off, B, F, max_n, tables, allo
               'pg_mol_kekule')
 
 
+@dataclass
+class Features:
+    """Device tensors of one `features` call; F frames, B graphs, N atom rows, Q = the graphs' point counts summed (graph g owns the
+    columns point_off[g] .. point_off[g + 1] of the per-point tensors)."""
+    status: torch.Tensor         # int32 [F, B]     FEAT_* bits
+    counts: torch.Tensor         # int32 [F, B, 25] FEATURE_COUNTS
+    ok: torch.Tensor             # bool  [F, B]     no bit of FEAT_FAIL_MASK
+    atom_fp: torch.Tensor        # uint8 [F, N]     bit t: the atom presents FEATURE_TYPES[t]; 0 for a dropped atom
+    point_dist: torch.Tensor     # fp32  [F, Q]     distance of a typed point to the nearest kept atom that carries its type (+inf: none)
+    point_atom: torch.Tensor     # int16 [F, Q]     that atom's compact index (the screen's), -1: none
+    point_off: torch.Tensor      # int32 [B + 1]
+    point_range: torch.Tensor    # int32 [B, 2]     rows of the graph's points in the point tensors that were handed in
+    point_kind: torch.Tensor     # int8  [P]        the kinds that were handed in: 0..6 = FEATURE_TYPES, -1 = untyped, -2 = ignored
+    limits: FeatureLimits
+    screen: Screen               # the screen it was computed from
+    kekule: Kekule               # the Kekulé form it typed from
+    rings: Rings                 # the rings it typed from
+
+
+def _same_screen(a, b):
+    return a is b or not (a.num_atoms != b.num_atoms or a.status.shape != b.status.shape or a.cls.shape != b.cls.shape
+                          or a.order.shape != b.order.shape or a.cls.device != b.cls.device)
+
+
+@torch.no_grad()
+def features(results, point_pos, point_kind, point_batch=None, frames='final', screen=None, kekule=None, rings=None,
+             limits=FeatureLimits()):
+    """Type every atom of every decoded (frame, graph) of a `sample` / `sample_batch` result and match its pharmacophore by type, on the
+    device, in one launch (pg_mol_feat; DESIGN.md 2.9 "Features").  point_pos [P, 3]: the points in the coordinates the frames hold;
+    point_kind [P]: 0..6 = the index into FEATURE_TYPES of the point's type, -1 = a feature whose type is not typed (counted, never
+    matched, never missed), -2 = ignored (an exclusion sphere).  point_batch as in `geometry`.  A typed point is matched iff a kept
+    atom that carries its type lies closer than limits.feat_cut (strict) -- the reference's `check_nearby_phore(strict=True)`.
+    Whichever of `screen`, `kekule` (a `Kekule`) and `rings` (a `Rings`) is not handed in is computed; all must come from one screen.
+    No host read beyond the screen's.  `ok` is a separate answer from the other screens': with the default limits it fails only for a
+    graph without a Kekulé structure or with a non-finite coordinate.  The rules are written from the reference's SMARTS text and not
+    checked against RDKit; `arom` is the model's bond class on a ring bond, not RDKit's perception; MB, CV1..CV4 and CR are not typed;
+    atom positions are used, not ring centroids, as in the reference's own check."""
+    node, pos, edge, F, (_, _, pos_fs) = _frames(results, frames)
+    dev = pos.device
+    if dev.type != 'cuda':
+        raise RuntimeError('phoregen_amd.molecule.features: the feature typing is a HIP kernel and the result lives on %s; there is no '
+                           'CPU fallback' % dev)
+    if not isinstance(limits, FeatureLimits):
+        raise ValueError(f'phoregen_amd.molecule.features: limits must be a FeatureLimits, not {limits!r}')
+    if not torch.is_tensor(point_pos) or point_pos.dim() != 2 or point_pos.size(1) != 3:
+        raise ValueError('phoregen_amd.molecule.features: point_pos must be a tensor [P, 3]')
+    P = point_pos.size(0)
+    if not torch.is_tensor(point_kind) or point_kind.numel() != P or point_kind.dtype.is_floating_point or point_kind.dtype == torch.bool:
+        raise ValueError(f'phoregen_amd.molecule.features: {P} points, point_kind must hold one integer kind per point, it has '
+                         f'{getattr(point_kind, "shape", None)} of {getattr(point_kind, "dtype", None)}')
+    given = [(what, x.screen) for what, x in (('kekule', kekule), ('rings', rings)) if x is not None]
+    sc = screen if screen is not None else given[0][1] if given else _screen(results, frames)
+    B, N = len(sc.num_atoms), pos.size(-2)
+    if tuple(sc.status.shape) != (F, B) or sc.cls.size(1) != N or sc.cls.device != dev or 2 * sc.order.size(1) != edge.size(-2):
+        raise ValueError(f'phoregen_amd.molecule.features: the screen ({tuple(sc.status.shape)} frames x graphs, {sc.cls.size(1)} atom '
+                         f'rows) is not one of this result and frames ({F} frames, {N} atom rows)')
+    for what, other in given:
+        if not _same_screen(sc, other):
+            raise ValueError(f'phoregen_amd.molecule.features: screen= and {what}= were computed from screens of different results')
+    row = pos[0] if pos.dim() == 3 and F > 0 else pos
+    if pos.dtype != torch.float32 or not (row.is_contiguous() or row.numel() == 0):
+        raise ValueError('phoregen_amd.molecule.features: coordinates must be contiguous fp32 [.., 3]')
+    kek = kekule if kekule is not None else _kekulize(results, frames, screen=sc)
+    rg = rings if rings is not None else _rings(results, frames, screen=sc)
+    with torch.cuda.device(dev):
+        lib = hip.lib()
+        ranges, off = _point_ranges(point_batch, P, B, dev)
+        Q = P * B if point_batch is None else P
+        ppos = point_pos.to(dev, torch.float32).contiguous()
+        pk = point_kind.reshape(-1).to(dev)
+        pk = torch.where((pk >= POINT_UNTYPED) & (pk < len(FEATURE_TYPES)), pk, torch.full_like(pk, POINT_IGNORED)).to(torch.int8)
+        out = dict(status=torch.empty(F, B, dtype=torch.int32, device=dev),
+                   counts=torch.empty(F, B, len(FEATURE_COUNTS), dtype=torch.int32, device=dev),
+                   atom_fp=torch.empty(F, N, dtype=torch.uint8, device=dev), point_dist=torch.empty(F, Q, dtype=torch.float32, device=dev),
+                   point_atom=torch.empty(F, Q, dtype=torch.int16, device=dev))
+        _launch_feat(lib, pos, pos_fs, sc, kek, rg, B, F, max(sc.num_atoms, default=0), ppos, pk, ranges, off, Q, limits, out)
+    return Features(ok=(out['status'] & FEAT_FAIL_MASK) == 0, point_off=off, point_range=ranges, point_kind=pk, limits=limits, screen=sc,
+                    kekule=kek, rings=rg, **out)
+
+
+def point_kinds_of(x, type_names, ex_name='EX'):
+    """int8 [P] point kinds of one-hot pharmacophore rows x [P, >= len(type_names)]: the argmax over the first len(type_names) columns,
+    mapped by name -- a name of FEATURE_TYPES to its index, `ex_name` to -2 (ignored), any other name to -1 (untyped)."""
+    table = torch.tensor([FEATURE_TYPES.index(t) if t in FEATURE_TYPES else POINT_IGNORED if t == ex_name else POINT_UNTYPED
+                          for t in type_names], dtype=torch.int8, device=x.device)
+    if x.size(0) == 0:
+        return torch.zeros(0, dtype=torch.int8, device=x.device)
+    return table[x[:, :len(type_names)].argmax(-1)]
+
+
+def features_for(data, results, frames='final', screen=None, kekule=None, rings=None, limits=FeatureLimits(), type_names=None):
+    """`features` with the pharmacophore of `data` as `PhoreDiff.sample` reads it: the points are data['phore'].pos + data.center, as in
+    `geometry_for`; a point's type is the argmax over the first len(type_names) columns of data['phore'].x, by name (type_names
+    defaults to data.PHORETYPES1, the zinc_300 / pdbbind order; 'EX' rows are ignored, names outside FEATURE_TYPES are untyped);
+    every graph has all points."""
+    if type_names is None:
+        from .data import PHORETYPES1
+        type_names = PHORETYPES1
+    ph = data['phore']
+    return features(results, ph.pos.float() + data.center.to(ph.pos.device).float(), point_kinds_of(ph.x, type_names), None, frames,
+                    screen, kekule, rings, limits)
+
+
+def _launch_feat(lib, pos, pos_fs, sc, kek, rg, B, F, max_n, point_pos, point_kind, ranges, off, n_out, limits, out):
+    """pg_mol_feat on the current stream; sc, kek, rg: anything with the `Screen`, `Kekule` and `Rings` fields the kernel reads.  A graph
+    above MAX_ATOMS is the library's error: nothing is launched and `out` is not written."""
+    dev = pos.device
+    cls, order = sc.cls, sc.order
+    for t, dt in ((cls, torch.int8), (order, torch.int8), (sc.compact, torch.int16), (kek.kekule_order, torch.int8), (kek.hcount, torch.uint8),
+                  (kek.charge, torch.int8), (kek.status, torch.int32), (rg.ring_size, torch.uint8), (sc.lig_off, torch.int32),
+                  (sc.bond_off, torch.int32), (point_pos, torch.float32), (point_kind, torch.int8), (ranges, torch.int32), (off, torch.int32),
+                  (out['atom_fp'], torch.uint8), (out['point_dist'], torch.float32), (out['point_atom'], torch.int16),
+                  (out['counts'], torch.int32), (out['status'], torch.int32)):
+        if t.dtype != dt or not t.is_contiguous() or t.device != dev:
+            raise ValueError('phoregen_amd.molecule.features: cls / order / kekule_order / charge / point kinds must be contiguous int8, '
+                             'compact and point_atom int16, hcount / ring_size / atom_fp uint8, offsets, ranges, counts and the status '
+                             'words int32, points and point_dist fp32, all on the device of the coordinates')
+    if (sc.lig_off.numel() != B + 1 or sc.bond_off.numel() != B + 1 or off.numel() != B + 1 or ranges.numel() != 2 * B
+            or cls.numel() != F * cls.size(-1) or order.numel() != F * order.size(-1) or pos.size(-2) != cls.size(-1)
+            or sc.compact.shape != cls.shape or kek.hcount.shape != cls.shape or kek.charge.shape != cls.shape
+            or kek.kekule_order.shape != order.shape or rg.ring_size.shape != order.shape or kek.status.numel() != F * B
+            or point_kind.numel() != point_pos.size(0) or out['atom_fp'].shape != cls.shape
+            or tuple(out['point_dist'].shape) != (F, n_out) or tuple(out['point_atom'].shape) != (F, n_out)
+            or out['status'].numel() != F * B or out['counts'].numel() != len(FEATURE_COUNTS) * F * B):
+        raise ValueError('phoregen_amd.molecule.features: sizes of the offsets, ranges, screen / Kekulé / ring arrays, points and outputs do '
+                         f'not fit {F} frames x {B} graphs, {cls.size(-1)} atom rows, {point_pos.size(0)} points, {n_out} point outputs')
+    hip.check(lib.pg_mol_feat(pos.data_ptr(), pos_fs, cls.data_ptr(), order.data_ptr(), sc.compact.data_ptr(), kek.kekule_order.data_ptr(),
+                              kek.hcount.data_ptr(), kek.charge.data_ptr(), kek.status.data_ptr(), rg.ring_size.data_ptr(),
+                              sc.lig_off.data_ptr(), sc.bond_off.data_ptr(), B, F, cls.size(-1), 2 * order.size(-1), max_n,
+                              point_pos.data_ptr(), point_kind.data_ptr(), point_pos.size(0), ranges.data_ptr(), off.data_ptr(), n_out,
+                              float(limits.feat_cut), int(limits.max_unmatched), out['atom_fp'].data_ptr(), out['point_dist'].data_ptr(),
+                              out['point_atom'].data_ptr(), out['counts'].data_ptr(), out['status'].data_ptr(), hip.stream_ptr()),
+              'pg_mol_feat')
+
+
 def formula_of(elements, hcount, charge=0):
     """Molecular formula in Hill order (C, H, then the other symbols alphabetically; all alphabetically without carbon) from atomic
     numbers and per-atom hydrogen counts, with a charge suffix such as '+' / '2+' / '-', and the molecular weight from ATOMIC_WEIGHT
@@ -558,6 +729,7 @@ def formula_of(elements, hcount, charge=0):
 _geometry = geometry             # (functions below take a `geometry=` argument)
 _rings = rings                   # (and a `rings=` argument)
 _kekulize = kekulize
+_features = features
 _PAIRS = {}
 
 
@@ -571,7 +743,7 @@ def _pairs(n):
 
 
 @torch.no_grad()
-def assemble(results, keys=False, geometry=None, rings=None, kekule=None):
+def assemble(results, keys=False, geometry=None, rings=None, kekule=None, features=None):
     """The final prediction as one dict per graph with `decode_data`'s keys and meaning -- 'element' (atomic numbers), 'atom_pos'
     (kept atoms, the tensor's own fp32 values), 'bond_index' [2, n_b] (indices among the kept atoms) and 'bond_type' [n_b] for
     a < b only, in row order -- plus 'status', 'valid', 'n_components' and 'valence' (per kept atom, halves allowed).  The screen runs
@@ -589,9 +761,14 @@ def assemble(results, keys=False, geometry=None, rings=None, kekule=None):
     KEKULE_FAIL_MASK), the ten KEKULE_COUNTS by name (the count 'charge' as 'net_charge': 'charge' is per atom here), 'bond_type' (the Kekulé order per entry of the dict's 'bond_type', in its
     order; 4 stays 4 where not kekule_ok), 'hcount' and 'charge' (per kept atom), 'formula' (Hill order with the hydrogens and a
     charge suffix such as '+' / '2+') and 'mol_weight' (`formula_of`: from standard atomic weights written from memory; both computed
-    on the host) -- in the same copy; its screen is reused, and it must have been computed from the screen of geometry= / rings=."""
+    on the host) -- in the same copy; its screen is reused, and it must have been computed from the screen of geometry= / rings=.
+    features=a `Features` of this result's final frame: every dict also has 'features' -- 'status' (FEAT_* bits), 'features_ok' (no
+    bit of FEAT_FAIL_MASK), the FEATURE_COUNTS by name, 'atom_fp' (uint8 per kept atom, bit t = FEATURE_TYPES[t]), 'atom_types' (per
+    kept atom a tuple of type names), 'point_kind' of the graph's points, their 'point_dist' / 'point_atom' (the nearest atom that
+    carries the point's type, an index into this dict's atoms, -1 = none) and 'point_matched' (distance < feat_cut) -- in the same copy; its screen is reused, and it must
+    have been computed from the screen of the others."""
     geom, pos_t = geometry, results['pred'][1]
-    given = [(what, x) for what, x in (('geometry', geom), ('rings', rings), ('kekule', kekule)) if x is not None]
+    given = [(what, x) for what, x in (('geometry', geom), ('rings', rings), ('kekule', kekule), ('features', features)) if x is not None]
     for what, x in given:
         if x.status.size(0) != 1 or x.screen.cls.size(1) != pos_t.size(-2) or x.status.device != pos_t.device:
             raise ValueError(f'phoregen_amd.molecule.assemble: {what}= must be a {what.capitalize()} of the final frame of this result')
@@ -613,17 +790,25 @@ def assemble(results, keys=False, geometry=None, rings=None, kekule=None):
     if geom is not None:
         parts += [('g_status', geom.status[0], np.int32), ('g_metrics', geom.metrics[0], np.float32), ('g_counts', geom.counts[0], np.int32),
                   ('g_dist', geom.point_dist[0], np.float32), ('g_off', geom.point_off, np.int32)]
+    if features is not None:
+        parts += [('f_status', features.status[0], np.int32), ('f_counts', features.counts[0], np.int32),
+                  ('f_dist', features.point_dist[0], np.float32), ('f_off', features.point_off, np.int32),
+                  ('f_range', features.point_range, np.int32)]
     parts += [('status', sc.status[0], np.int32), ('counts', sc.counts[0], np.int32), ('pos', pos_t, np.float32),
               ('compact', sc.compact[0], np.int16)]
     if geom is not None:
         parts += [('g_atom', geom.point_atom[0], np.int16)]
     if rings is not None:
         parts += [('r_sys', rings.ring_sys[0], np.int16)]
+    if features is not None:
+        parts += [('f_atom', features.point_atom[0], np.int16)]
     parts += [('cls', sc.cls[0], np.int8), ('valence2', sc.valence2[0], np.uint8), ('order', sc.order[0], np.int8)]
     if rings is not None:
         parts += [('r_atom', rings.atom_ring[0], np.uint8), ('r_size', rings.ring_size[0], np.uint8)]
     if kekule is not None:
         parts += [('k_order', kekule.kekule_order[0], np.int8), ('k_h', kekule.hcount[0], np.uint8), ('k_q', kekule.charge[0], np.int8)]
+    if features is not None:
+        parts += [('f_fp', features.atom_fp[0], np.uint8), ('f_kind', features.point_kind, np.int8)]
     sizes = [t.numel() * t.element_size() for _, t, _ in parts]
     blob = torch.cat([t.reshape(-1).view(torch.uint8) for _, t, _ in parts]).cpu().numpy()
     cut = np.cumsum([0] + sizes)
@@ -637,6 +822,8 @@ def assemble(results, keys=False, geometry=None, rings=None, kekule=None):
         r_counts = v['r_counts'].reshape(-1, len(RING_COUNTS))
     if kekule is not None:
         k_counts = v['k_counts'].reshape(-1, len(KEKULE_COUNTS))
+    if features is not None:
+        f_counts, f_range = v['f_counts'].reshape(-1, len(FEATURE_COUNTS)), v['f_range'].reshape(-1, 2)
     mols, n0, h0 = [], 0, 0
     for g, n in enumerate(sc.num_atoms):
         h = n * (n - 1) // 2
@@ -672,6 +859,16 @@ def assemble(results, keys=False, geometry=None, rings=None, kekule=None):
                                       **{_KEKULE_KEYS[k]: int(x) for k, x in zip(KEKULE_COUNTS, k_counts[g])},
                                       bond_type=torch.from_numpy(v['k_order'][h0:h0 + h][nz].astype(np.int64)), hcount=k_h, charge=k_q,
                                       formula=formula, mol_weight=weight)
+        if features is not None:
+            q0, q1 = int(v['f_off'][g]), int(v['f_off'][g + 1])
+            fp = v['f_fp'][n0:n0 + n][keep].copy()
+            mols[-1]['features'] = dict({'status': int(v['f_status'][g]), 'features_ok': (int(v['f_status'][g]) & FEAT_FAIL_MASK) == 0},
+                                        **{k: int(x) for k, x in zip(FEATURE_COUNTS, f_counts[g])}, atom_fp=fp,
+                                        atom_types=[tuple(t for k, t in enumerate(FEATURE_TYPES) if b >> k & 1) for b in fp.tolist()],
+                                        point_kind=v['f_kind'][int(f_range[g, 0]):int(f_range[g, 1])].copy(),
+                                        point_dist=v['f_dist'][q0:q1].copy(), point_atom=v['f_atom'][q0:q1].copy())
+            # (the kernel's own comparison: fp32 distance < fp32 cutoff; a non-finite point has distance +inf)
+            mols[-1]['features']['point_matched'] = mols[-1]['features']['point_dist'] < np.float32(features.limits.feat_cut)
         n0, h0 = n0 + n, h0 + h
     return mols
 
@@ -711,6 +908,17 @@ def mol_block(mol, name=''):
     return '\n'.join(lines) + '\n'
 
 
+def _features_item(ft):
+    """The PHOREGEN_FEATURES data item of a molecule's 'features' dict (`assemble`)."""
+    lines = ['> <PHOREGEN_FEATURES>', 'status 0x%02x' % int(ft['status'])] + ['%s %d' % (k, ft[k]) for k in FEATURE_COUNTS]
+    kinds = np.asarray(ft['point_kind']).reshape(-1).tolist()
+    dist, atom = np.asarray(ft['point_dist']).reshape(-1).tolist(), np.asarray(ft['point_atom']).reshape(-1).tolist()
+    for k, d, a, hit in zip(kinds, dist, atom, np.asarray(ft['point_matched']).reshape(-1).tolist()):
+        if 0 <= k < len(FEATURE_TYPES):
+            lines.append('%s %s %s' % (FEATURE_TYPES[k], str(a + 1) if hit else '-', '%.4f' % d if np.isfinite(d) else 'inf'))
+    return '\n'.join(lines) + '\n\n'
+
+
 def write_sdf(path, mols, names=None):
     """An SDF file: one mol block per molecule, each closed by a '$$$$' line.  A molecule that carries 'key' (assemble(keys=True))
     gets one data item `> <PHOREGEN_KEY>` with the key as 16 hex digits between its block and the '$$$$'.  A molecule that carries
@@ -718,7 +926,10 @@ def write_sdf(path, mols, names=None):
     (GEOM_METRICS without the reserved one) with four decimals.  A molecule that carries 'rings' (assemble(rings=)) gets
     `> <PHOREGEN_RINGS>`: one line with the status as hex, then one 'name value' line per count (RING_COUNTS).  A molecule that
     carries 'kekule' (assemble(kekule=)) is written in Kekulé form if that is ok (`mol_block`) and gets `> <PHOREGEN_KEKULE>`: the
-    status as hex, 'formula', 'mol_weight' with three decimals, then one 'name value' line per count (KEKULE_COUNTS)."""
+    status as hex, 'formula', 'mol_weight' with three decimals, then one 'name value' line per count (KEKULE_COUNTS).  A molecule that
+    carries 'features' (assemble(features=)) gets `> <PHOREGEN_FEATURES>`: the status as hex, one 'name value' line per count
+    (FEATURE_COUNTS), then one line per typed point: its type, the matched atom (1-based; '-' if no atom of the type lies within the
+    cutoff) and the distance to the nearest atom of the type with four decimals ('inf' without one)."""
     names = names if names is not None else [''] * len(mols)
     if len(names) != len(mols):
         raise ValueError(f'write_sdf: {len(mols)} molecules, {len(names)} names')
@@ -737,6 +948,8 @@ def write_sdf(path, mols, names=None):
                 fh.write('> <PHOREGEN_KEKULE>\nstatus 0x%02x\nformula %s\nmol_weight %.3f\n'
                          % (int(m['kekule']['status']), m['kekule']['formula'], m['kekule']['mol_weight'])
                          + ''.join('%s %d\n' % (k, m['kekule'][_KEKULE_KEYS[k]]) for k in KEKULE_COUNTS) + '\n')
+            if 'features' in m:
+                fh.write(_features_item(m['features']))
             fh.write('$$$$\n')
 
 
@@ -870,7 +1083,7 @@ def duplicate_groups(keys):
 
 # ---- the top-up loop of sample_all.py:79-84,172 ------------------------------------------------------------------------------
 def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, device='cuda', unique=False, geometry=None,
-                 rings=None, kekule=None, **sample_kwargs):
+                 rings=None, kekule=None, features=None, **sample_kwargs):
     """Sample until `num_samples` molecules have passed the screen, giving up once more than `max_failed_factor * num_samples` have
     failed (checked before every draw, as the reference does).  Every draw asks for min(batch_size, what is still missing) graphs,
     so never more than `num_samples` are finished.  `sample_kwargs` (fragment=, pos_guidance_opt=, rng=, seed=, ...) go to
@@ -884,13 +1097,21 @@ def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, d
     rings=a `RingLimits`, or True for the default limits: a valid molecule is finished only if it is also 'rings_ok'; one that is not
     goes to 'failed'.  The molecules then carry 'rings'.
     kekule=a `KekuleOptions`, or True for the default options: a valid molecule is finished only if it is also 'kekule_ok' (it has a
-    Kekulé structure); one that is not goes to 'failed'.  The molecules then carry 'kekule'.  All of these share one screen per draw."""
+    Kekulé structure); one that is not goes to 'failed'.  The molecules then carry 'kekule'.
+    features=(point_pos, point_kind, limits), or True to take the pharmacophore of `data` (`features_for`, default limits): a valid
+    molecule is finished only if it is also 'features_ok'; one that is not goes to 'failed'.  The molecules then carry 'features'.
+    The typing needs the Kekulé form and the rings of the draw: they are computed (with kekule= / rings= if given, else with the
+    defaults) and carried, and filtered on, only if asked for by their own arguments.  All of these share one screen per draw."""
     ring_limits = RingLimits() if rings is True else rings
     if ring_limits is not None and not isinstance(ring_limits, RingLimits):
         raise ValueError(f'phoregen_amd.molecule.sample_valid: rings= must be True or a RingLimits, not {rings!r}')
     kek_options = KekuleOptions() if kekule is True else kekule
     if kek_options is not None and not isinstance(kek_options, KekuleOptions):
         raise ValueError(f'phoregen_amd.molecule.sample_valid: kekule= must be True or a KekuleOptions, not {kekule!r}')
+    if features is not None and features is not True:
+        if not (isinstance(features, tuple) and len(features) == 3 and isinstance(features[2], FeatureLimits)):
+            raise ValueError(f'phoregen_amd.molecule.sample_valid: features= must be True or (point_pos, point_kind, FeatureLimits), not '
+                             f'{features!r}')
     finished, failed, duplicates, n_calls = [], [], [], 0
     by_key = {}                                                        # key -> finished molecules that have it
     while len(finished) < num_samples:
@@ -911,11 +1132,20 @@ def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, d
         kek = None
         if kek_options is not None:
             kek = _kekulize(res, screen=geo.screen if geo is not None else ring.screen if ring is not None else None, options=kek_options)
-        mols = assemble(res, keys=unique, **{k: v for k, v in (('geometry', geo), ('rings', ring), ('kekule', kek)) if v is not None})
+        feat = None
+        if features is not None:
+            sc = next((x.screen for x in (geo, ring, kek) if x is not None), None)
+            if features is True:
+                feat = features_for(data, res, screen=sc, kekule=kek, rings=ring)
+            else:
+                feat = _features(res, features[0], features[1], screen=sc, kekule=kek, rings=ring, limits=features[2])
+        mols = assemble(res, keys=unique, **{k: v for k, v in (('geometry', geo), ('rings', ring), ('kekule', kek), ('features', feat))
+                                             if v is not None})
         for m in mols:
             if (not m['valid'] or (geometry is not None and not m['geom']['geom_ok'])
                     or (ring_limits is not None and not m['rings']['rings_ok'])
-                    or (kek_options is not None and not m['kekule']['kekule_ok'])):
+                    or (kek_options is not None and not m['kekule']['kekule_ok'])
+                    or (features is not None and not m['features']['features_ok'])):
                 failed.append(m)
             elif unique and any(same_molecule(m, other) for other in by_key.setdefault(m['key'], [])):
                 duplicates.append(m)

@@ -20,8 +20,11 @@ aromatic rule alone, --ring_limits '{"ring_min": 5, "ring_max": 8}' replaces sin
 .sdf files carry the counts as a data item.  --kekule (implies --valid_only) also resolves the aromatic bonds into single and double
 bonds and gives every atom its hydrogens and charge (phoregen_amd.molecule.kekulize), and finishes a molecule only if it has such a
 Kekulé structure; --no_charged forbids the N+ / P+ / S+ structures tried when no neutral one exists; with --sdf the blocks are then
-written in Kekulé form with charges, and carry formula, weight and counts as the data item PHOREGEN_KEKULE.  Without them nothing
-changes.
+written in Kekulé form with charges, and carry formula, weight and counts as the data item PHOREGEN_KEKULE.  --features (implies
+--valid_only) also types every atom (HD, AR, PO, HA, HY, NE, XB; phoregen_amd.molecule.features_for) and matches every typed feature
+point of the pharmacophore against the atoms that carry its type, and finishes a molecule only if it has a Kekulé structure to type
+from and no more typed points are unmatched than --feature_limits '{"max_unmatched": 0}' allows (default: any number); the .sdf files
+carry the counts and the per-point matches as the data item PHOREGEN_FEATURES.  Without them nothing changes.
 """
 import argparse
 import json
@@ -34,10 +37,10 @@ import torch
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from phoregen_amd.config import default_model_config, load_config  # noqa: E402
-from phoregen_amd.data import parse_phore_file  # noqa: E402
+from phoregen_amd.data import PHORETYPES1, parse_phore_file  # noqa: E402
 from phoregen_amd.fragment import load_fragment_json  # noqa: E402
 from phoregen_amd.models.diffusion import PhoreDiff  # noqa: E402
-from phoregen_amd.molecule import GeomLimits, KekuleOptions, RingLimits, STATUS_NONFINITE, assemble, sample_valid, write_sdf  # noqa: E402
+from phoregen_amd.molecule import FeatureLimits, GeomLimits, KekuleOptions, RingLimits, STATUS_NONFINITE, assemble, point_kinds_of, sample_valid, write_sdf  # noqa: E402
 from phoregen_amd.utils.sample_utils import decode_batch  # noqa: E402
 from phoregen_amd.weights import init_deterministic_  # noqa: E402
 
@@ -71,6 +74,11 @@ def main():
     ap.add_argument('--kekule', action='store_true',
                     help='implies --valid_only: a molecule without a Kekulé structure is not finished; .sdf blocks are written in Kekulé form')
     ap.add_argument('--no_charged', action='store_true', help='with --kekule: neutral Kekulé structures only (no N+ / P+ / S+)')
+    ap.add_argument('--features', action='store_true',
+                    help='implies --valid_only: a molecule without a Kekulé structure, or with more unmatched typed feature points than '
+                         '--feature_limits allows, is not finished')
+    ap.add_argument('--feature_limits', type=json.loads, default=None,
+                    help='JSON object replacing single limits of FeatureLimits (with --features), e.g. \'{"max_unmatched": 0}\'')
     ap.add_argument('--sdf', action='store_true', help='write one .sdf per molecule under <outdir>/sdf_results/')
     args = ap.parse_args()
     if args.geom_limits is not None and not args.geometry:
@@ -79,7 +87,10 @@ def main():
         ap.error('--ring_limits needs --rings')
     if args.no_charged and not args.kekule:
         ap.error('--no_charged needs --kekule')
-    args.valid_only = args.valid_only or args.unique or args.geometry or args.rings or args.kekule
+    if args.feature_limits is not None and not args.features:
+        ap.error('--feature_limits needs --features')
+    args.valid_only = args.valid_only or args.unique or args.geometry or args.rings or args.kekule or args.features
+    feature_limits = FeatureLimits(**(args.feature_limits or {})) if args.features else None
     geom_limits = GeomLimits(**(args.geom_limits or {}))
     ring_limits = RingLimits(**(args.ring_limits or {})) if args.rings else None
     kekule = KekuleOptions(allow_charged=not args.no_charged) if args.kekule else None
@@ -111,8 +122,12 @@ def main():
             if args.geometry:                                          # the points PhoreDiff.sample reads, in world coordinates
                 ph = data['phore']
                 geometry = (ph.pos.float() + data.center.float(), ph.x[:, model.ex_col] == 1, geom_limits)
+            features = None
+            if args.features:                                          # the same points, their kinds by the type columns' names
+                ph = data['phore']
+                features = (ph.pos.float() + data.center.float(), point_kinds_of(ph.x, PHORETYPES1), feature_limits)
             out = sample_valid(model, data, args.num_samples, batch_size=args.batch_size, unique=args.unique, geometry=geometry,
-                               rings=ring_limits, kekule=kekule, **kw)
+                               rings=ring_limits, kekule=kekule, features=features, **kw)
             done = out['finished']
             print(f"Finished {len(done)} | Failed {len(out['failed'])}" + (f" | Duplicates {len(out['duplicates'])}" if args.unique else ''))
             if args.unique:
