@@ -444,7 +444,8 @@ int pg_attn_unfold_bias_grad(const float* gout, int ldg, const float* swn, const
  * Scores are logits or one-hots, fp32, rows contiguous: frame f of node_scores starts at node_scores + f * node_fs ELEMENTS (likewise
  * edge_scores / pos; F = 1 with stride 0 for a single prediction).  node_scores and node_fs 16-byte, edge_scores and edge_fs 8-byte
  * aligned.  max_valence2 [11]: twice the largest explicit valence per atom class (one more is allowed to an atom with an aromatic bond).
- * max_n = the largest atom count of the batch: above PG_MOL_MAX_ATOMS the call returns an error before anything is launched.
+ * max_n = the largest atom count of the batch: above PG_MOL_MAX_ATOMS, or with a negative size, the call returns an error before
+ * anything is launched.
  * Every element of every output is written (nothing needs zeroing); integer work only, so results are exact.
  *   status [F][B], counts [F][B][4] = kept atoms, bonds, components, atoms of the largest component
  *   cls [F][n_lig] (-1 = dropped), compact [F][n_lig] (-1 = dropped), valence2 [F][n_lig] (saturates at 255), comp [F][n_lig] (-1 = dropped)

@@ -1,22 +1,18 @@
 // Pharmacophore feature typing of the molecules the screen decoded, and the typed match against their feature points (pg_mol_feat,
 // include/phoregen_hip.h; phoregen_amd/molecule.py; definition: DESIGN.md 2.9 "Features").  Reads the screen's outputs (cls, order,
 // compact), the Kekulé form (kekule_order, hcount, charge, status), the rings' ring_size and the coordinates.  One wave per
-// (frame, graph); a workgroup IS one wave, so __syncthreads() orders the wave's LDS traffic, and every loop that holds one (or a vote)
-// has a wave-uniform trip count: the divergent loops below (pair rows, an atom's neighbours, points) hold neither.  Typing is integer
-// work (feature_core.h) and exact; the only floating point is a point's distance to an atom, the fp32 expression of mol_geom.hip.
-#include "common.h"
+// (frame, graph) (mol_common.h); the divergent loops below (pair rows, an atom's neighbours, points) hold no barrier or vote.  Typing
+// is integer work (feature_core.h) and exact; the only floating point is a point's distance to an atom, which is mol_geom.hip's
+// (mol_nearest_atom).
+#include "mol_common.h"
 #include "wave_prims.h"
 #include "feature_core.h"
-#include "../../include/phoregen_hip.h"
 
 namespace pg {
 
-constexpr int kFeatMax = PG_MOL_MAX_ATOMS;   // atoms of the largest graph
-constexpr int kFeatCh = kFeatMax / 64;       // atoms per lane = 64-bit adjacency words per atom
+constexpr int kFeatMax = kMolMax, kFeatCh = kMolCh;
 constexpr int kFeatPairs = kFeatMax * (kFeatMax - 1) / 2;
-static_assert(kFeatCh == 2 && kFeatMax <= 255, "feature_core.h walks two mask words per atom; a degree fits one byte");
-
-__device__ __forceinline__ bool feat_nonfinite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
+static_assert(kFeatMax <= 255, "a degree fits one byte");
 
 __global__ __launch_bounds__(64) void mol_feat_kernel(
     const float* __restrict__ pos, long pos_fs, const int8_t* __restrict__ cls_i, const int8_t* __restrict__ order_i,
@@ -27,22 +23,20 @@ __global__ __launch_bounds__(64) void mol_feat_kernel(
     const int* __restrict__ g_point_out_off, int n_out, float feat_cut, int max_unmatched, uint8_t* __restrict__ atom_fp,
     float* __restrict__ point_dist, int16_t* __restrict__ point_atom, int* __restrict__ counts, int* __restrict__ status) {
   __shared__ float4 s_atom[kFeatMax];                              // x, y, z, compact index as bits (-1 = dropped or non-finite)
-  __shared__ __align__(16) unsigned long long s_adj[kFeatMax * kFeatCh];   // kept bonds of an atom, a bit per local index
+  __shared__ MolAdjRow s_adj[kFeatMax];                            // kept bonds of an atom
   __shared__ uint8_t s_pair[kFeatPairs];                           // feature_core.h's byte per pair row
   __shared__ int8_t s_el[kFeatMax];
   __shared__ uint8_t s_h[kFeatMax], s_q[kFeatMax], s_deg[kFeatMax], s_flags[kFeatMax], s_fp[kFeatMax];
   __shared__ uint16_t s_v[kFeatMax];
 
   const int lane = threadIdx.x;
-  const int f = blockIdx.x / B, g = blockIdx.x - f * B;
-  const int a0 = g_lig_off[g], n = g_lig_off[g + 1] - a0;
-  if (n > kFeatMax || n < 0) return;                               // (the host wrapper has refused such a batch: never index LDS past its end)
-  const int h0 = g_bond_off[g] >> 1, n_pair = n * (n - 1) / 2;
-  if (a0 < 0 || a0 + n > n_lig || h0 < 0 || h0 + n_pair > n_half) return;   // (offsets that leave the frame: never read or write past it)
-  const int ps = g_point_range[2 * g], pe = g_point_range[2 * g + 1], o0 = g_point_out_off[g];
-  if (ps < 0 || pe < ps || pe > n_point || o0 < 0 || g_point_out_off[g + 1] - o0 != pe - ps || o0 + (pe - ps) > n_out) return;
-  const float* prow = pos + (size_t)f * pos_fs + (size_t)a0 * 3;
-  const size_t arow = (size_t)f * n_lig + a0, hrow = (size_t)f * n_half + h0, orow = (size_t)f * n_out + o0;
+  MolFrame m;
+  MolPoints pt;
+  if (!mol_frame(m, blockIdx.x, B, g_lig_off, g_bond_off, n_lig, n_half)) return;
+  if (!mol_points(pt, m, g_point_range, g_point_out_off, n_point, n_out)) return;
+  const int n = m.n;
+  const size_t arow = m.arow, hrow = m.hrow;
+  const float* prow = pos + (size_t)m.f * pos_fs + (size_t)m.a0 * 3;
   const float inf = __builtin_inff();
   const bool kek_ok = (kek_status[blockIdx.x] & PG_KEKULE_FAILED) == 0;
 
@@ -52,14 +46,13 @@ __global__ __launch_bounds__(64) void mol_feat_kernel(
   for (int c = 0; c < kFeatCh; ++c) {
     const int i = c * 64 + lane;
     if (i < n) {
-      int k = cls_i[arow + i];
-      k = (k >= 0 && k < 11) ? k : -1;
+      const int k = mol_class(cls_i[arow + i]);
       float x = 0.f, y = 0.f, z = 0.f;
       int ci = -1;
       if (k >= 0) {
         const float* p = prow + (size_t)i * 3;
         x = p[0], y = p[1], z = p[2];
-        const bool fin = !(feat_nonfinite(x) || feat_nonfinite(y) || feat_nonfinite(z));
+        const bool fin = !(mol_nonfinite(x) || mol_nonfinite(y) || mol_nonfinite(z));
         bad |= !fin;
         ci = fin ? (int)compact_i[arow + i] : -1;
       }
@@ -69,7 +62,7 @@ __global__ __launch_bounds__(64) void mol_feat_kernel(
       s_atom[i] = make_float4(x, y, z, __int_as_float(ci));
       s_fp[i] = 0;
 #pragma unroll
-      for (int w = 0; w < kFeatCh; ++w) s_adj[i * kFeatCh + w] = 0ull;
+      for (int w = 0; w < kFeatCh; ++w) s_adj[i].w[w] = 0ull;
     }
   }
   __syncthreads();
@@ -79,28 +72,20 @@ __global__ __launch_bounds__(64) void mol_feat_kernel(
   for (int t = 0; t < kFeatTypes; ++t) n_atoms_t[t] = 0;
 
   if (kek_ok) {                                                    // (wave-uniform: one status word per block)
-    // ---- bonds: the pairs a < b in row-major order, dealt to lanes (pair p is lane p mod 64's) ---------------------------------
-    {
-      int a = 0, b = 1 + lane;
-      for (int p = lane; p < n_pair; p += 64, b += 64) {
-        while (b >= n) {                                           // next row of the triangle (p < n_pair: ends with a < n - 1)
-          ++a;
-          b = b - n + a + 1;
-        }
-        const int o = order_i[hrow + p];
-        int pb = 0;
-        if (o >= 1 && o <= 4 && s_el[a] >= 0 && s_el[b] >= 0) {
-          const int k = kek_i[hrow + p];
-          pb = ((k >= 1 && k <= 3) ? k : 1) | (o == 4 ? kPairArom : 0) | (ring_size_i[hrow + p] > 0 ? kPairRing : 0);
-          atomicOr(&s_adj[a * kFeatCh + (b >> 6)], 1ull << (b & 63));
-          atomicOr(&s_adj[b * kFeatCh + (a >> 6)], 1ull << (a & 63));
-        }
-        s_pair[p] = (uint8_t)pb;
+    // ---- bonds ----------------------------------------------------------------------------------------------------------------
+    for_each_pair(lane, n, m.n_pair, [&](int p, int a, int b) {
+      const int o = order_i[hrow + p];
+      int pb = 0;
+      if (mol_is_bond(o) && s_el[a] >= 0 && s_el[b] >= 0) {
+        const int k = kek_i[hrow + p];
+        pb = ((k >= 1 && k <= 3) ? k : 1) | (o == 4 ? kPairArom : 0) | (ring_size_i[hrow + p] > 0 ? kPairRing : 0);
+        mol_adj_set(s_adj, a, b);
       }
-    }
+      s_pair[p] = (uint8_t)pb;
+    });
     __syncthreads();
 
-    const FeatGraph fg = {n, s_el, s_h, s_q, s_adj, s_pair, s_deg, s_v, s_flags};
+    const FeatGraph fg = {n, s_el, s_h, s_q, mol_adj_words(s_adj), s_pair, s_deg, s_v, s_flags};
     // ---- per atom: degree, valence, arom; then the double-bond flags, which read every neighbour's arom ------------------------
 #pragma unroll
     for (int c = 0; c < kFeatCh; ++c) {
@@ -148,27 +133,20 @@ __global__ __launch_bounds__(64) void mol_feat_kernel(
   int n_points_t[kFeatTypes], n_matched_t[kFeatTypes], n_untyped = 0;
 #pragma unroll
   for (int t = 0; t < kFeatTypes; ++t) n_points_t[t] = n_matched_t[t] = 0;
-  for (int q = ps + lane; q < pe; q += 64) {
+  for (int q = pt.ps + lane; q < pt.pe; q += 64) {
     const float* pp = point_pos + (size_t)q * 3;
     const float x = pp[0], y = pp[1], z = pp[2];
     const int kind = point_kind[q];
     float best = inf;
     int best_i = -1;
     if (kind >= -1 && kind < kFeatTypes) {                         // (anything else is an exclusion sphere or to be ignored)
-      if (feat_nonfinite(x) || feat_nonfinite(y) || feat_nonfinite(z)) {
+      if (mol_nonfinite(x) || mol_nonfinite(y) || mol_nonfinite(z)) {
         bad = true;                                                // left out of everything but its own two outputs
       } else if (kind < 0) {
         ++n_untyped;
       } else {
-        for (int i = 0; i < n; ++i) {
-          const float4 pa = s_atom[i];
-          const int ci = __float_as_int(pa.w);
-          if (ci < 0 || !((s_fp[i] >> kind) & 1)) continue;
-          const float dx = pa.x - x, dy = pa.y - y, dz = pa.z - z;
-          const float d = sqrtf(dx * dx + dy * dy + dz * dz);
-          best_i = d < best ? ci : best_i;                         // (strict: the first minimum in atom order stays)
-          best = fminf(best, d);
-        }
+        int close = 0;                                             // (not asked for: with clear = 0 no d < clear, the count is dead code)
+        mol_nearest_atom(s_atom, n, x, y, z, 0.f, [&](int i) { return (s_fp[i] >> kind) & 1; }, best, best_i, close);
         const bool hit = best < feat_cut;
 #pragma unroll
         for (int t = 0; t < kFeatTypes; ++t) {                     // (constant indices: the counters stay in registers)
@@ -177,8 +155,8 @@ __global__ __launch_bounds__(64) void mol_feat_kernel(
         }
       }
     }
-    point_dist[orow + (q - ps)] = best;
-    point_atom[orow + (q - ps)] = (int16_t)best_i;
+    point_dist[pt.orow + (q - pt.ps)] = best;
+    point_atom[pt.orow + (q - pt.ps)] = (int16_t)best_i;
   }
 
   // ---- the wave's totals (all lanes are back together here), then lane 0 writes the graph's row --------------------------------
@@ -219,24 +197,17 @@ extern "C" int pg_mol_feat(const float* pos, int64_t pos_fs, const int8_t* cls, 
                            int max_n, const float* point_pos, const int8_t* point_kind, int n_point, const int* g_point_range,
                            const int* g_point_out_off, int n_point_out, float feat_cut, int max_unmatched, uint8_t* atom_fp,
                            float* point_dist, int16_t* point_atom, int* counts, int* status, void* stream) {
-  if (B < 0 || F < 0 || n_lig < 0 || n_bond < 0 || (n_bond & 1) || max_n < 0 || n_point < 0 || n_point_out < 0 || max_unmatched < 0) {
-    set_error("pg_mol_feat: B %d, F %d, n_lig %d, n_bond %d, max_n %d, n_point %d, n_point_out %d, max_unmatched %d (n_bond counts both "
-              "directions of every pair)", B, F, n_lig, n_bond, max_n, n_point, n_point_out, max_unmatched);
-    return PG_ERR_ARG;
-  }
-  if (max_n > PG_MOL_MAX_ATOMS) {
-    set_error("pg_mol_feat: a graph of %d atoms, the kernel holds at most PG_MOL_MAX_ATOMS = %d", max_n, PG_MOL_MAX_ATOMS);
+  const int rc = mol_check_batch("pg_mol_feat", B, F, n_lig, n_bond, max_n);
+  if (rc == PG_ERR_ARG) return rc;
+  if (n_point < 0 || n_point_out < 0 || max_unmatched < 0) {
+    set_error("pg_mol_feat: n_point %d, n_point_out %d, max_unmatched %d", n_point, n_point_out, max_unmatched);
     return PG_ERR_ARG;
   }
   if (!(feat_cut == feat_cut)) {
     set_error("pg_mol_feat: feat_cut is not a number");
     return PG_ERR_ARG;
   }
-  if (B == 0 || F == 0) return PG_OK;
-  if ((long long)B * F > 0x7fffffffLL) {
-    set_error("pg_mol_feat: %d frames x %d graphs exceed one launch", F, B);
-    return PG_ERR_ARG;
-  }
+  if (rc == kMolNothing) return PG_OK;
   if (!pos || !cls || !order || !compact || !kekule_order || !hcount || !charge || !kekule_status || !ring_size || !g_lig_off ||
       !g_bond_off || !g_point_range || !g_point_out_off || !atom_fp || !counts || !status ||
       (n_point > 0 && (!point_pos || !point_kind)) || (n_point_out > 0 && (!point_dist || !point_atom))) {

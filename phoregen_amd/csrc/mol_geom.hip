@@ -1,25 +1,20 @@
 // Geometry and pharmacophore fit of the molecules the screen decoded: bond lengths, clashes, exclusion spheres, feature coverage of
 // every (frame, graph) in one launch (pg_mol_geom, include/phoregen_hip.h; phoregen_amd/molecule.py; definition: DESIGN.md 2.9
-// "Geometry").  Reads the coordinates and the screen's outputs (cls, order), not the scores.  One wave per (frame, graph); a workgroup
-// IS one wave, so __syncthreads() orders the wave's LDS traffic.  The two loops with a lane-dependent trip count (pairs, points) hold
-// no barrier, vote or cross-lane move.  Distances are fp32; the two energies (metrics 5 and 6) are differences of nearly equal numbers,
-// so their sums run in fp64 from the fp32 inputs and are rounded to fp32 once.  Every sum is a per-lane partial over a fixed
-// lane-to-element assignment followed by a fixed butterfly: a graph's answer does not depend on the batch it sits in.
-#include "common.h"
+// "Geometry").  Reads the coordinates and the screen's outputs (cls, order), not the scores.  One wave per (frame, graph)
+// (mol_common.h); the two loops with a lane-dependent trip count (pairs, points) hold no barrier, vote or cross-lane move.  Distances
+// are fp32; the two energies (metrics 5 and 6) are differences of nearly equal numbers, so their sums run in fp64 from the fp32 inputs
+// and are rounded to fp32 once.  Every sum is a per-lane partial over a fixed lane-to-element assignment followed by a fixed
+// butterfly: a graph's answer does not depend on the batch it sits in.
+#include "mol_common.h"
 #include "wave_prims.h"
-#include "../../include/phoregen_hip.h"
 
 namespace pg {
 
-constexpr int kGeomMax = PG_MOL_MAX_ATOMS;   // atoms of the largest graph
-constexpr int kGeomCh = kGeomMax / 64;       // atoms per lane
-static_assert(kGeomMax % 64 == 0, "atoms are dealt to the lanes in chunks of 64");
+constexpr int kGeomMax = kMolMax, kGeomCh = kMolCh;
 
 struct GeomLimits {
   float bond_min, bond_max, clash_min, ex_clear, feat_cut;
 };
-
-__device__ __forceinline__ bool geom_nonfinite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
 
 __global__ __launch_bounds__(64) void mol_geom_kernel(
     const float* __restrict__ pos, long pos_fs, const int8_t* __restrict__ cls_i, const int8_t* __restrict__ order_i,
@@ -30,15 +25,13 @@ __global__ __launch_bounds__(64) void mol_geom_kernel(
   __shared__ float4 s_atom[kGeomMax];                    // x, y, z, compact index as bits (-1 = not kept)
 
   const int lane = threadIdx.x;
-  const int f = blockIdx.x / B, g = blockIdx.x - f * B;
-  const int a0 = g_lig_off[g], n = g_lig_off[g + 1] - a0;
-  if (n > kGeomMax || n < 0) return;                     // (the host wrapper has refused such a batch: never index LDS past its end)
-  const int h0 = g_bond_off[g] >> 1, n_pair = n * (n - 1) / 2;
-  if (a0 < 0 || a0 + n > n_lig || h0 < 0 || h0 + n_pair > n_half) return;   // (offsets that leave the frame: never read past it)
-  const int ps = g_point_range[2 * g], pe = g_point_range[2 * g + 1], o0 = g_point_out_off[g];
-  if (ps < 0 || pe < ps || pe > n_point || o0 < 0 || g_point_out_off[g + 1] - o0 != pe - ps || o0 + (pe - ps) > n_out) return;
-  const float* prow = pos + (size_t)f * pos_fs + (size_t)a0 * 3;
-  const size_t arow = (size_t)f * n_lig + a0, hrow = (size_t)f * n_half + h0, orow = (size_t)f * n_out + o0;
+  MolFrame m;
+  MolPoints pt;
+  if (!mol_frame(m, blockIdx.x, B, g_lig_off, g_bond_off, n_lig, n_half)) return;
+  if (!mol_points(pt, m, g_point_range, g_point_out_off, n_point, n_out)) return;
+  const int n = m.n;
+  const size_t arow = m.arow, hrow = m.hrow;
+  const float* prow = pos + (size_t)m.f * pos_fs + (size_t)m.a0 * 3;
   const float inf = __builtin_inff();
 
   // ---- atoms: kept = class 0..10 and finite; the compact index counts the atoms of a kept class, as the screen does -------
@@ -51,18 +44,17 @@ __global__ __launch_bounds__(64) void mol_geom_kernel(
     bool kc = false, fin = false;
     float x = 0.f, y = 0.f, z = 0.f;
     if (i < n) {
-      const int k = cls_i[arow + i];
-      kc = k >= 0 && k < 11;
+      kc = mol_class(cls_i[arow + i]) >= 0;
       if (kc) {
         const float* p = prow + (size_t)i * 3;
         x = p[0], y = p[1], z = p[2];
-        fin = !(geom_nonfinite(x) || geom_nonfinite(y) || geom_nonfinite(z));
+        fin = !(mol_nonfinite(x) || mol_nonfinite(y) || mol_nonfinite(z));
         bad |= !fin;
       }
     }
-    const unsigned long long m = __ballot(kc);
-    const int compact = n_class + __popcll(m & ((1ull << lane) - 1ull));
-    n_class += __popcll(m);
+    const unsigned long long km = __ballot(kc);
+    const int compact = n_class + __popcll(km & ((1ull << lane) - 1ull));
+    n_class += __popcll(km);
     if (i < n) s_atom[i] = make_float4(x, y, z, __int_as_float((kc && fin) ? compact : -1));
     if (kc && fin) {
       ax += (double)x, ay += (double)y, az += (double)z;
@@ -71,60 +63,43 @@ __global__ __launch_bounds__(64) void mol_geom_kernel(
   }
   __syncthreads();
 
-  // ---- pairs a < b of kept atoms in row-major order, lane-strided: pair p is lane p % 64's ----------------------------------
+  // ---- pairs of kept atoms --------------------------------------------------------------------------------------------------
   float bmin = inf, bmax = -inf, nbmin = inf;
   int c_short = 0, c_long = 0, c_clash = 0, n_bond = 0;
   double e_bond = 0.0;
-  {
-    int a = 0, b = 1 + lane;
-    for (int p = lane; p < n_pair; p += 64, b += 64) {
-      while (b >= n) {                                   // next row of the triangle (p < n_pair: ends with a < n - 1)
-        ++a;
-        b = b - n + a + 1;
-      }
-      const float4 pa = s_atom[a], pb = s_atom[b];
-      if (__float_as_int(pa.w) < 0 || __float_as_int(pb.w) < 0) continue;
-      const float dx = pa.x - pb.x, dy = pa.y - pb.y, dz = pa.z - pb.z;
-      const float d = sqrtf(dx * dx + dy * dy + dz * dz);
-      const int o = order_i[hrow + p];
-      if (o >= 1 && o <= 4) {
-        ++n_bond;
-        bmin = fminf(bmin, d), bmax = fmaxf(bmax, d);
-        c_short += d < lim.bond_min, c_long += d > lim.bond_max;
-        const double ex = (double)pa.x - (double)pb.x, ey = (double)pa.y - (double)pb.y, ez = (double)pa.z - (double)pb.z;
-        const double dd = sqrt(ex * ex + ey * ey + ez * ez);
-        e_bond += fmax(dd - (double)lim.bond_max, 0.0) + fmax((double)lim.bond_min - dd, 0.0);
-      } else {
-        nbmin = fminf(nbmin, d);
-        c_clash += d < lim.clash_min;
-      }
+  for_each_pair(lane, n, m.n_pair, [&](int p, int a, int b) {
+    const float4 pa = s_atom[a], pb = s_atom[b];
+    if (__float_as_int(pa.w) < 0 || __float_as_int(pb.w) < 0) return;
+    const float dx = pa.x - pb.x, dy = pa.y - pb.y, dz = pa.z - pb.z;
+    const float d = sqrtf(dx * dx + dy * dy + dz * dz);
+    if (mol_is_bond(order_i[hrow + p])) {
+      ++n_bond;
+      bmin = fminf(bmin, d), bmax = fmaxf(bmax, d);
+      c_short += d < lim.bond_min, c_long += d > lim.bond_max;
+      const double ex = (double)pa.x - (double)pb.x, ey = (double)pa.y - (double)pb.y, ez = (double)pa.z - (double)pb.z;
+      const double dd = sqrt(ex * ex + ey * ey + ez * ez);
+      e_bond += fmax(dd - (double)lim.bond_max, 0.0) + fmax((double)lim.bond_min - dd, 0.0);
+    } else {
+      nbmin = fminf(nbmin, d);
+      c_clash += d < lim.clash_min;
     }
-  }
+  });
 
   // ---- points, lane-strided: every lane walks all atoms for its own points (one LDS address per step: a broadcast) ----------
   float exmin = inf, featmax = -inf;
   int c_ex = 0, n_feat = 0, n_cov = 0;
   double fx = 0.0, fy = 0.0, fz = 0.0;                    // this lane's part of the coordinate sums of the feature points
-  for (int q = ps + lane; q < pe; q += 64) {
+  for (int q = pt.ps + lane; q < pt.pe; q += 64) {
     const float* pp = point_pos + (size_t)q * 3;
     const float x = pp[0], y = pp[1], z = pp[2];
     float best = inf;
     int best_i = -1;
-    if (geom_nonfinite(x) || geom_nonfinite(y) || geom_nonfinite(z)) {
+    if (mol_nonfinite(x) || mol_nonfinite(y) || mol_nonfinite(z)) {
       bad = true;                                        // left out of everything but its own two outputs
     } else {
       const bool is_ex = point_is_ex[q] != 0;
       int close = 0;
-      for (int i = 0; i < n; ++i) {
-        const float4 pa = s_atom[i];
-        const int ci = __float_as_int(pa.w);
-        if (ci < 0) continue;
-        const float dx = pa.x - x, dy = pa.y - y, dz = pa.z - z;
-        const float d = sqrtf(dx * dx + dy * dy + dz * dz);
-        best_i = d < best ? ci : best_i;                 // (strict: the first minimum in atom order stays)
-        best = fminf(best, d);
-        close += d < lim.ex_clear;
-      }
+      mol_nearest_atom(s_atom, n, x, y, z, lim.ex_clear, [](int) { return true; }, best, best_i, close);
       if (is_ex) {
         exmin = fminf(exmin, best);
         c_ex += close;
@@ -135,8 +110,8 @@ __global__ __launch_bounds__(64) void mol_geom_kernel(
         fx += (double)x, fy += (double)y, fz += (double)z;
       }
     }
-    point_dist[orow + (q - ps)] = best;
-    point_atom[orow + (q - ps)] = (int16_t)best_i;
+    point_dist[pt.orow + (q - pt.ps)] = best;
+    point_atom[pt.orow + (q - pt.ps)] = (int16_t)best_i;
   }
 
   // ---- the wave's totals (all lanes are back together here), then lane 0 writes the graph's row ------------------------------
@@ -177,24 +152,17 @@ extern "C" int pg_mol_geom(const float* pos, int64_t pos_fs, const int8_t* cls, 
                            const uint8_t* point_is_ex, int n_point, const int* g_point_range, const int* g_point_out_off,
                            int n_point_out, const float* limits, float* point_dist, int16_t* point_atom, float* metrics,
                            int* counts, int* status, void* stream) {
-  if (B < 0 || F < 0 || n_lig < 0 || n_bond < 0 || (n_bond & 1) || max_n < 0 || n_point < 0 || n_point_out < 0) {
-    set_error("pg_mol_geom: B %d, F %d, n_lig %d, n_bond %d, max_n %d, n_point %d, n_point_out %d (n_bond counts both directions of "
-              "every pair)", B, F, n_lig, n_bond, max_n, n_point, n_point_out);
-    return PG_ERR_ARG;
-  }
-  if (max_n > PG_MOL_MAX_ATOMS) {
-    set_error("pg_mol_geom: a graph of %d atoms, the kernel holds at most PG_MOL_MAX_ATOMS = %d", max_n, PG_MOL_MAX_ATOMS);
+  const int rc = mol_check_batch("pg_mol_geom", B, F, n_lig, n_bond, max_n);
+  if (rc == PG_ERR_ARG) return rc;
+  if (n_point < 0 || n_point_out < 0) {
+    set_error("pg_mol_geom: n_point %d, n_point_out %d", n_point, n_point_out);
     return PG_ERR_ARG;
   }
   if (!limits) {
     set_error("pg_mol_geom: limits is null (five floats in host memory)");
     return PG_ERR_ARG;
   }
-  if (B == 0 || F == 0) return PG_OK;
-  if ((long long)B * F > 0x7fffffffLL) {
-    set_error("pg_mol_geom: %d frames x %d graphs exceed one launch", F, B);
-    return PG_ERR_ARG;
-  }
+  if (rc == kMolNothing) return PG_OK;
   const GeomLimits lim = {limits[0], limits[1], limits[2], limits[3], limits[4]};
   hipLaunchKernelGGL(mol_geom_kernel, dim3((unsigned)(B * F)), dim3(64), 0, (hipStream_t)stream, pos, (long)pos_fs, cls, order,
                      g_lig_off, g_bond_off, B, n_lig, n_bond / 2, point_pos, point_is_ex, n_point, g_point_range, g_point_out_off,

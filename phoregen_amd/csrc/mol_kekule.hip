@@ -1,21 +1,18 @@
 // Kekulé form, hydrogens and charges of the molecules the screen decoded (pg_mol_kekule, include/phoregen_hip.h;
 // phoregen_amd/molecule.py; definition: DESIGN.md 2.9 "Kekulé form").  Reads the screen's outputs (cls, order), not the scores.  One
-// wave per (frame, graph); a workgroup IS one wave, so __syncthreads() orders the wave's LDS traffic, and every loop that holds one
-// (or a vote) has a wave-uniform trip count.  The wave deals the pairs, builds the aromatic adjacency, classifies the atoms, computes
+// wave per (frame, graph) (mol_common.h).  The wave deals the pairs, builds the aromatic adjacency, classifies the atoms, computes
 // the per-atom results and the counts and writes kekule_order; the matching itself (Edmonds' algorithm with blossom contraction,
 // kekule_core.h) runs on lane 0 over arrays in LDS.  Integer work only, no floating point anywhere, so every output is exact.
+#include "mol_common.h"
 #include "wave_prims.h"
 #include "kekule_core.h"
-#include "../../include/phoregen_hip.h"
 
 namespace pg {
 
-constexpr int kKekMax = PG_MOL_MAX_ATOMS;   // atoms of the largest graph
-constexpr int kKekCh = kKekMax / 64;        // atoms per lane = 64-bit adjacency words per atom
+constexpr int kKekMax = kMolMax, kKekCh = kMolCh;
 constexpr int kKekEl = 11;                  // elements (atom classes 0..10)
 constexpr int kKekN = 2;                    // the class of N
 constexpr int kKekO = 3;                    // the class of O
-static_assert(kKekCh == 2, "kekule_core.h walks two mask words per atom");
 
 struct KekuleTables {
   uint8_t dbl_neutral[kKekEl], dbl_charged[kKekEl], must[kKekEl], hval[kKekEl][4];
@@ -31,8 +28,8 @@ __global__ __launch_bounds__(64) void mol_kekule_kernel(const int8_t* __restrict
                                                         int* __restrict__ status_o) {
   __shared__ int s_cls[kKekMax];                                  // atom class, -1 = dropped
   __shared__ unsigned int s_sa[kKekMax];                          // s | a << 16
-  __shared__ __align__(16) unsigned long long s_arom[kKekMax * kKekCh];    // bonds of order 4 of an atom, a bit per local index
-  __shared__ __align__(16) unsigned long long s_allow[kKekMax * kKekCh];   // the pass's allowed graph
+  __shared__ MolAdjRow s_arom[kKekMax];                           // bonds of order 4 of an atom
+  __shared__ MolAdjRow s_allow[kKekMax];                          // the pass's allowed graph
   __shared__ uint8_t s_kind[kKekMax];
   __shared__ int16_t s_match[2 * kKekMax], s_parent[2 * kKekMax], s_base[kKekMax], s_queue[kKekMax];
   __shared__ uint8_t s_flags[kKekMax];
@@ -40,12 +37,10 @@ __global__ __launch_bounds__(64) void mol_kekule_kernel(const int8_t* __restrict
   __shared__ int s_feasible;
 
   const int lane = threadIdx.x;
-  const int f = blockIdx.x / B, g = blockIdx.x - f * B;
-  const int a0 = g_lig_off[g], n = g_lig_off[g + 1] - a0;
-  if (n > kKekMax || n < 0) return;                               // (the host wrapper has refused such a batch: never index LDS past its end)
-  const int h0 = g_bond_off[g] >> 1, n_pair = n * (n - 1) / 2;
-  if (a0 < 0 || a0 + n > n_lig || h0 < 0 || h0 + n_pair > n_half) return;   // (offsets that leave the frame: never read or write past it)
-  const size_t arow = (size_t)f * n_lig + a0, hrow = (size_t)f * n_half + h0;
+  MolFrame m;
+  if (!mol_frame(m, blockIdx.x, B, g_lig_off, g_bond_off, n_lig, n_half)) return;
+  const int n = m.n;
+  const size_t arow = m.arow, hrow = m.hrow;
 
   // ---- tables and atoms ------------------------------------------------------------------------------------------------------
   if (lane < kKekEl) {
@@ -60,39 +55,29 @@ __global__ __launch_bounds__(64) void mol_kekule_kernel(const int8_t* __restrict
     const int i = c * 64 + lane;
     int k = -1;
     if (i < n) {
-      k = cls_i[arow + i];
-      k = (k >= 0 && k < kKekEl) ? k : -1;
-      s_cls[i] = k;
+      s_cls[i] = k = mol_class(cls_i[arow + i]);
       s_sa[i] = 0u;
 #pragma unroll
-      for (int w = 0; w < kKekCh; ++w) s_arom[i * kKekCh + w] = 0ull;
+      for (int w = 0; w < kKekCh; ++w) s_arom[i].w[w] = 0ull;
     }
     n_kept += __popcll(__ballot(k >= 0));
   }
   __syncthreads();
 
-  // ---- bonds: the pairs a < b in row-major order, dealt to lanes (pair p is lane p mod 64's) -----------------------------------
+  // ---- bonds ------------------------------------------------------------------------------------------------------------------
   int n_arom_bond = 0;
-  {
-    int a = 0, b = 1 + lane;
-    for (int p = lane; p < n_pair; p += 64, b += 64) {
-      while (b >= n) {                                            // next row of the triangle (p < n_pair: ends with a < n - 1)
-        ++a;
-        b = b - n + a + 1;
-      }
-      const int o = order_i[hrow + p];
-      if (o >= 1 && o <= 4 && s_cls[a] >= 0 && s_cls[b] >= 0) {
-        const unsigned int inc = o == 4 ? 1u << 16 : (unsigned int)o;
-        atomicAdd(&s_sa[a], inc);
-        atomicAdd(&s_sa[b], inc);
-        if (o == 4) {
-          ++n_arom_bond;
-          atomicOr(&s_arom[a * kKekCh + (b >> 6)], 1ull << (b & 63));
-          atomicOr(&s_arom[b * kKekCh + (a >> 6)], 1ull << (a & 63));
-        }
+  for_each_pair(lane, n, m.n_pair, [&](int p, int a, int b) {
+    const int o = order_i[hrow + p];
+    if (mol_is_bond(o) && s_cls[a] >= 0 && s_cls[b] >= 0) {
+      const unsigned int inc = o == 4 ? 1u << 16 : (unsigned int)o;
+      atomicAdd(&s_sa[a], inc);
+      atomicAdd(&s_sa[b], inc);
+      if (o == 4) {
+        ++n_arom_bond;
+        mol_adj_set(s_arom, a, b);
       }
     }
-  }
+  });
   __syncthreads();
 
   // ---- the passes: classify, restrict the aromatic graph to the atoms that may carry a double bond, match ---------------------
@@ -122,12 +107,12 @@ __global__ __launch_bounds__(64) void mol_kekule_kernel(const int8_t* __restrict
       if (i < n) {
         const bool in = (ok[c] >> lane) & 1ull;
 #pragma unroll
-        for (int w = 0; w < kKekCh; ++w) s_allow[i * kKekCh + w] = in ? s_arom[i * kKekCh + w] & ok[w] : 0ull;
+        for (int w = 0; w < kKekCh; ++w) s_allow[i].w[w] = in ? s_arom[i].w[w] & ok[w] : 0ull;
       }
     }
     for (int i = lane; i < 2 * n; i += 64) s_match[i] = -1;
     __syncthreads();
-    if (lane == 0) s_feasible = (ok[0] | ok[1]) == 0ull ? (n_must == 0) : kekule_match(n, s_allow, s_kind, s_match, s_parent, s_base, s_queue, s_flags);
+    if (lane == 0) s_feasible = (ok[0] | ok[1]) == 0ull ? (n_must == 0) : kekule_match(n, mol_adj_words(s_allow), s_kind, s_match, s_parent, s_base, s_queue, s_flags);
     __syncthreads();
     feasible = s_feasible;
     pass_used = pass;
@@ -164,18 +149,11 @@ __global__ __launch_bounds__(64) void mol_kekule_kernel(const int8_t* __restrict
   n_arom_bond = wave_sum(n_arom_bond);
 
   // ---- kekule_order: the same deal of the pairs ----------------------------------------------------------------------------------
-  {
-    int a = 0, b = 1 + lane;
-    for (int p = lane; p < n_pair; p += 64, b += 64) {
-      while (b >= n) {
-        ++a;
-        b = b - n + a + 1;
-      }
-      int o = order_i[hrow + p];
-      if (feasible && o == 4 && s_cls[a] >= 0 && s_cls[b] >= 0) o = s_match[a] == b ? 2 : 1;
-      kek_o[hrow + p] = (int8_t)o;
-    }
-  }
+  for_each_pair(lane, n, m.n_pair, [&](int p, int a, int b) {
+    int o = order_i[hrow + p];
+    if (feasible && o == 4 && s_cls[a] >= 0 && s_cls[b] >= 0) o = s_match[a] == b ? 2 : 1;
+    kek_o[hrow + p] = (int8_t)o;
+  });
 
   if (lane == 0) {
     int st = 0;
@@ -206,24 +184,13 @@ extern "C" int pg_mol_kekule(const int8_t* cls, const int8_t* order, const int* 
                              int n_bond, int max_n, const uint8_t* dbl_neutral, const uint8_t* dbl_charged, const uint8_t* must,
                              const uint8_t* h_valences, int allow_charged, int8_t* kekule_order, uint8_t* hcount, int8_t* charge,
                              int* counts, int* status, void* stream) {
-  if (B < 0 || F < 0 || n_lig < 0 || n_bond < 0 || (n_bond & 1) || max_n < 0) {
-    set_error("pg_mol_kekule: B %d, F %d, n_lig %d, n_bond %d, max_n %d (n_bond counts both directions of every pair)", B, F, n_lig,
-              n_bond, max_n);
-    return PG_ERR_ARG;
-  }
-  if (max_n > PG_MOL_MAX_ATOMS) {
-    set_error("pg_mol_kekule: a graph of %d atoms, the kernel holds at most PG_MOL_MAX_ATOMS = %d", max_n, PG_MOL_MAX_ATOMS);
-    return PG_ERR_ARG;
-  }
+  const int rc = mol_check_batch("pg_mol_kekule", B, F, n_lig, n_bond, max_n);
+  if (rc == PG_ERR_ARG) return rc;
   if (!dbl_neutral || !dbl_charged || !must || !h_valences) {
     set_error("pg_mol_kekule: a table is null (dbl_neutral, dbl_charged, must: uint8 [11]; h_valences: uint8 [11][4], device memory)");
     return PG_ERR_ARG;
   }
-  if (B == 0 || F == 0) return PG_OK;
-  if ((long long)B * F > 0x7fffffffLL) {
-    set_error("pg_mol_kekule: %d frames x %d graphs exceed one launch", F, B);
-    return PG_ERR_ARG;
-  }
+  if (rc == kMolNothing) return PG_OK;
   hipLaunchKernelGGL(mol_kekule_kernel, dim3((unsigned)(B * F)), dim3(64), 0, (hipStream_t)stream, cls, order, g_lig_off, g_bond_off, B,
                      n_lig, n_bond / 2, dbl_neutral, dbl_charged, must, h_valences, allow_charged, kekule_order, hcount, charge, counts,
                      status);

@@ -1,47 +1,28 @@
 // Ring perception of the molecules the screen decoded: smallest ring through every bond and atom, ring systems, and the counts users
 // filter on (pg_mol_rings, include/phoregen_hip.h; phoregen_amd/molecule.py; definition: DESIGN.md 2.9 "Rings").  Reads the screen's
-// outputs (cls, order), not the scores.  One wave per (frame, graph); a workgroup IS one wave, so __syncthreads() orders the wave's LDS
-// traffic, and every loop that holds one (or a vote) has a wave-uniform trip count: the divergent loops below (bond rows, the search
-// of a bond's ring) hold neither.  Integer work only, no floating point anywhere, so every output is exact.
+// outputs (cls, order), not the scores.  One wave per (frame, graph) (mol_common.h); the divergent loops below (bond rows, the search
+// of a bond's ring) hold no barrier or vote.  Integer work only, no floating point anywhere, so every output is exact.
+#include "mol_common.h"
 #include "wave_prims.h"
-#include "../../include/phoregen_hip.h"
 
 namespace pg {
 
-constexpr int kRingMax = PG_MOL_MAX_ATOMS;  // atoms of the largest graph
-constexpr int kRingCh = kRingMax / 64;      // atoms per lane = 64-bit adjacency words per atom
-static_assert(kRingCh == 2 && kRingMax <= 255, "a mask row is one 16-byte LDS read; a ring size fits one byte");
+constexpr int kRingMax = kMolMax, kRingCh = kMolCh;
+static_assert(kRingMax <= 255, "a ring size fits one byte");
 
 struct RingLimits {
   int ring_min, ring_max, system_max, rotatable_max;
 };
 
-// An atom's bonds as a bit per local atom index.  Rows are 16 bytes and dense: one row is one 128-bit LDS read, 16 consecutive rows
-// fill the 256-byte bank row exactly, so the 16 lanes that share a read cycle collide only where their row indices agree mod 16; the
-// searches read rows at data-dependent indices, and for those any padded stride is a permutation of the same residues or worse.
-struct __align__(16) RingRow {
-  unsigned long long w[kRingCh];
-};
-
-__device__ __forceinline__ int wave_imax(int v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = max(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ int wave_imin(int v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = min(v, __shfl_xor(v, o));
-  return v;
-}
-
 // Atoms of the smallest ring through the bond (a, b), 0 if the bond is a bridge: breadth-first from a over the masks with b struck
 // from a's own row (a is never expanded again, so the bond itself is never walked); the frontier at step d holds the atoms d bonds
-// from a, and the first of them that has b as a neighbour closes a ring of d + 2 atoms.
-__device__ __forceinline__ int ring_through(const RingRow* adj, int a, int b) {
+// from a, and the first of them that has b as a neighbour closes a ring of d + 2 atoms.  (The walk over the frontier's bits is written
+// out: it returns from inside.)
+__device__ __forceinline__ int ring_through(const MolAdjRow* adj, int a, int b) {
   const int bw = b >> 6;
   const unsigned long long bbit = 1ull << (b & 63);
   unsigned long long seen[kRingCh], front[kRingCh];
-  const RingRow ra = adj[a];
+  const MolAdjRow ra = adj[a];
   bool more = false;
 #pragma unroll
   for (int w = 0; w < kRingCh; ++w) {
@@ -59,7 +40,7 @@ __device__ __forceinline__ int ring_through(const RingRow* adj, int a, int b) {
       while (m) {
         const int j = w * 64 + __builtin_ctzll(m);
         m &= m - 1ull;
-        const RingRow rj = adj[j];
+        const MolAdjRow rj = adj[j];
 #pragma unroll
         for (int v = 0; v < kRingCh; ++v) next[v] |= rj.w[v];
         if ((bw ? next[kRingCh - 1] : next[0]) & bbit) return d + 2;
@@ -83,8 +64,8 @@ __global__ __launch_bounds__(64) void mol_rings_kernel(const int8_t* __restrict_
                                                        uint8_t* __restrict__ atom_ring_o, int16_t* __restrict__ ring_sys_o,
                                                        int* __restrict__ counts_o, int* __restrict__ status_o) {
   __shared__ int s_cls[kRingMax];                                 // atom class, -1 = dropped
-  __shared__ RingRow s_adj[kRingMax];                             // kept bonds of an atom
-  __shared__ RingRow s_radj[kRingMax];                            // its ring bonds
+  __shared__ MolAdjRow s_adj[kRingMax];                           // kept bonds of an atom
+  __shared__ MolAdjRow s_radj[kRingMax];                          // its ring bonds
   __shared__ unsigned int s_stat[kRingMax];                       // degree | bonds of order 4 << 16
   __shared__ unsigned int s_aring[kRingMax];                      // smallest ring_size among the atom's ring bonds, ~0 = none
   __shared__ int s_comp[kRingMax];                                // component label over all bonds (a local atom index)
@@ -92,12 +73,10 @@ __global__ __launch_bounds__(64) void mol_rings_kernel(const int8_t* __restrict_
   __shared__ unsigned int s_size[kRingMax];                       // atoms of the ring system whose label this index is
 
   const int lane = threadIdx.x;
-  const int f = blockIdx.x / B, g = blockIdx.x - f * B;
-  const int a0 = g_lig_off[g], n = g_lig_off[g + 1] - a0;
-  if (n > kRingMax || n < 0) return;                              // (the host wrapper has refused such a batch: never index LDS past its end)
-  const int h0 = g_bond_off[g] >> 1, n_pair = n * (n - 1) / 2;
-  if (a0 < 0 || a0 + n > n_lig || h0 < 0 || h0 + n_pair > n_half) return;   // (offsets that leave the frame: never read or write past it)
-  const size_t arow = (size_t)f * n_lig + a0, hrow = (size_t)f * n_half + h0;
+  MolFrame m;
+  if (!mol_frame(m, blockIdx.x, B, g_lig_off, g_bond_off, n_lig, n_half)) return;
+  const int n = m.n;
+  const size_t arow = m.arow, hrow = m.hrow;
 
   // ---- atoms: class; empty masks, counters and labels -------------------------------------------------------------------------
   int n_kept = 0;
@@ -106,9 +85,7 @@ __global__ __launch_bounds__(64) void mol_rings_kernel(const int8_t* __restrict_
     const int i = c * 64 + lane;
     int k = -1;
     if (i < n) {
-      k = cls_i[arow + i];
-      k = (k >= 0 && k < 11) ? k : -1;
-      s_cls[i] = k;
+      s_cls[i] = k = mol_class(cls_i[arow + i]);
       s_stat[i] = 0u, s_size[i] = 0u;
       s_aring[i] = ~0u;
       s_comp[i] = s_sys[i] = i;
@@ -119,57 +96,41 @@ __global__ __launch_bounds__(64) void mol_rings_kernel(const int8_t* __restrict_
   }
   __syncthreads();
 
-  // ---- bonds: the pairs a < b in row-major order, dealt to lanes (pair p is lane p mod 64's) -----------------------------------
+  // ---- bonds ------------------------------------------------------------------------------------------------------------------
   int n_bond = 0;
-  {
-    int a = 0, b = 1 + lane;
-    for (int p = lane; p < n_pair; p += 64, b += 64) {
-      while (b >= n) {                                            // next row of the triangle (p < n_pair: ends with a < n - 1)
-        ++a;
-        b = b - n + a + 1;
-      }
-      const int o = order_i[hrow + p];
-      if (o >= 1 && o <= 4 && s_cls[a] >= 0 && s_cls[b] >= 0) {
-        ++n_bond;
-        const unsigned int inc = 1u | (o == 4 ? 1u << 16 : 0u);
-        atomicAdd(&s_stat[a], inc);
-        atomicAdd(&s_stat[b], inc);
-        atomicOr(&s_adj[a].w[b >> 6], 1ull << (b & 63));
-        atomicOr(&s_adj[b].w[a >> 6], 1ull << (a & 63));
-      }
+  for_each_pair(lane, n, m.n_pair, [&](int p, int a, int b) {
+    const int o = order_i[hrow + p];
+    if (mol_is_bond(o) && s_cls[a] >= 0 && s_cls[b] >= 0) {
+      ++n_bond;
+      const unsigned int inc = 1u | (o == 4 ? 1u << 16 : 0u);
+      atomicAdd(&s_stat[a], inc);
+      atomicAdd(&s_stat[b], inc);
+      mol_adj_set(s_adj, a, b);
     }
-  }
+  });
   __syncthreads();
 
   // ---- rings: the same deal; a lane searches the ring of each of its bonds and writes the row of every one of its pairs ------
   int n_ringb = 0, rmin = 255, rmax = 0, n_rot = 0, n_arom_out = 0;
-  {
-    int a = 0, b = 1 + lane;
-    for (int p = lane; p < n_pair; p += 64, b += 64) {
-      while (b >= n) {
-        ++a;
-        b = b - n + a + 1;
+  for_each_pair(lane, n, m.n_pair, [&](int p, int a, int b) {
+    const int o = order_i[hrow + p];
+    int rs = 0;
+    if (mol_is_bond(o) && s_cls[a] >= 0 && s_cls[b] >= 0) {
+      rs = ring_through(s_adj, a, b);
+      if (rs > 0) {
+        ++n_ringb;
+        rmin = min(rmin, rs);
+        rmax = max(rmax, rs);
+        mol_adj_set(s_radj, a, b);
+        atomicMin(&s_aring[a], (unsigned int)rs);
+        atomicMin(&s_aring[b], (unsigned int)rs);
+      } else {
+        n_rot += (o == 1 && (s_stat[a] & 0xffffu) >= 2u && (s_stat[b] & 0xffffu) >= 2u) ? 1 : 0;
+        n_arom_out += o == 4 ? 1 : 0;
       }
-      const int o = order_i[hrow + p];
-      int rs = 0;
-      if (o >= 1 && o <= 4 && s_cls[a] >= 0 && s_cls[b] >= 0) {
-        rs = ring_through(s_adj, a, b);
-        if (rs > 0) {
-          ++n_ringb;
-          rmin = min(rmin, rs);
-          rmax = max(rmax, rs);
-          atomicOr(&s_radj[a].w[b >> 6], 1ull << (b & 63));
-          atomicOr(&s_radj[b].w[a >> 6], 1ull << (a & 63));
-          atomicMin(&s_aring[a], (unsigned int)rs);
-          atomicMin(&s_aring[b], (unsigned int)rs);
-        } else {
-          n_rot += (o == 1 && (s_stat[a] & 0xffffu) >= 2u && (s_stat[b] & 0xffffu) >= 2u) ? 1 : 0;
-          n_arom_out += o == 4 ? 1 : 0;
-        }
-      }
-      ring_size_o[hrow + p] = (uint8_t)rs;
     }
-  }
+    ring_size_o[hrow + p] = (uint8_t)rs;
+  });
   __syncthreads();
 
   // ---- components (all bonds) and ring systems (ring bonds): every atom takes the smallest label among itself and its neighbours,
@@ -184,21 +145,11 @@ __global__ __launch_bounds__(64) void mol_rings_kernel(const int8_t* __restrict_
       if (i < n && s_cls[i] >= 0) {
         const int c0 = s_comp[i], y0 = s_sys[i];
         int lc = c0, ly = y0;
-        const RingRow all = s_adj[i], ring = s_radj[i];
+        const MolAdjRow all = s_adj[i], ring = s_radj[i];
 #pragma unroll
-        for (int w = 0; w < kRingCh; ++w) {
-          unsigned long long m = all.w[w];
-          while (m) {
-            const int j = w * 64 + __builtin_ctzll(m);
-            m &= m - 1ull;
-            lc = min(lc, s_comp[j]);
-          }
-          m = ring.w[w];
-          while (m) {
-            const int j = w * 64 + __builtin_ctzll(m);
-            m &= m - 1ull;
-            ly = min(ly, s_sys[j]);
-          }
+        for (int w = 0; w < kRingCh; ++w) {                         // (both rows are on their way before either is walked)
+          for_each_bit(all.w[w], w * 64, [&](int j) { lc = min(lc, s_comp[j]); });
+          for_each_bit(ring.w[w], w * 64, [&](int j) { ly = min(ly, s_sys[j]); });
         }
         lc = min(lc, s_comp[lc]);
         ly = min(ly, s_sys[ly]);
@@ -277,24 +228,13 @@ using namespace pg;
 extern "C" int pg_mol_rings(const int8_t* cls, const int8_t* order, const int* g_lig_off, const int* g_bond_off, int B, int F,
                             int n_lig, int n_bond, int max_n, const int* limits, uint8_t* ring_size, uint8_t* atom_ring,
                             int16_t* ring_sys, int* counts, int* status, void* stream) {
-  if (B < 0 || F < 0 || n_lig < 0 || n_bond < 0 || (n_bond & 1) || max_n < 0) {
-    set_error("pg_mol_rings: B %d, F %d, n_lig %d, n_bond %d, max_n %d (n_bond counts both directions of every pair)", B, F, n_lig,
-              n_bond, max_n);
-    return PG_ERR_ARG;
-  }
-  if (max_n > PG_MOL_MAX_ATOMS) {
-    set_error("pg_mol_rings: a graph of %d atoms, the kernel holds at most PG_MOL_MAX_ATOMS = %d", max_n, PG_MOL_MAX_ATOMS);
-    return PG_ERR_ARG;
-  }
+  const int rc = mol_check_batch("pg_mol_rings", B, F, n_lig, n_bond, max_n);
+  if (rc == PG_ERR_ARG) return rc;
   if (!limits) {
     set_error("pg_mol_rings: limits is null (four ints in host memory)");
     return PG_ERR_ARG;
   }
-  if (B == 0 || F == 0) return PG_OK;
-  if ((long long)B * F > 0x7fffffffLL) {
-    set_error("pg_mol_rings: %d frames x %d graphs exceed one launch", F, B);
-    return PG_ERR_ARG;
-  }
+  if (rc == kMolNothing) return PG_OK;
   const RingLimits lim = {limits[0], limits[1], limits[2], limits[3]};
   hipLaunchKernelGGL(mol_rings_kernel, dim3((unsigned)(B * F)), dim3(64), 0, (hipStream_t)stream, cls, order, g_lig_off, g_bond_off, B,
                      n_lig, n_bond / 2, lim, ring_size, atom_ring, ring_sys, counts, status);

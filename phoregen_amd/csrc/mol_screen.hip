@@ -1,15 +1,12 @@
 // From sampler output to molecules: decode, connectivity and valence screen of every (frame, graph) in one launch
-// (pg_mol_screen, include/phoregen_hip.h; phoregen_amd/molecule.py).  One wave per (frame, graph); a workgroup IS one wave, so
-// __syncthreads() orders the wave's LDS traffic and every loop that holds one (or a vote) has a wave-uniform trip count.
+// (pg_mol_screen, include/phoregen_hip.h; phoregen_amd/molecule.py).  One wave per (frame, graph) (mol_common.h).
 // Integer work only (the scores are compared, never added), so every output is exact.
-#include "common.h"
-#include "../../include/phoregen_hip.h"
+#include "mol_common.h"
+#include "wave_prims.h"
 
 namespace pg {
 
-constexpr int kMolMax = PG_MOL_MAX_ATOMS;   // atoms of the largest graph
-constexpr int kMolCh = kMolMax / 64;        // atoms per lane = 64-bit adjacency words per atom
-static_assert(kMolMax % 64 == 0 && kMolMax <= 256, "per-atom counters below hold a degree in 8 bits");
+static_assert(kMolMax <= 256, "per-atom counters below hold a degree in 8 bits");
 
 // torch.argmax: first maximum, a NaN counts as the largest
 template <int K>
@@ -25,19 +22,6 @@ __device__ __forceinline__ int first_argmax(const float* v) {
   return best;
 }
 
-__device__ __forceinline__ bool nonfinite_bits(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }
-
-__device__ __forceinline__ int wave_isum(int v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-__device__ __forceinline__ int wave_imax(int v) {
-#pragma unroll
-  for (int o = 32; o >= 1; o >>= 1) v = max(v, __shfl_xor(v, o));
-  return v;
-}
-
 __global__ __launch_bounds__(64) void mol_screen_kernel(
     const float* __restrict__ node_scores, long node_fs, const float* __restrict__ edge_scores, long edge_fs,
     const float* __restrict__ pos, long pos_fs, const int* __restrict__ g_lig_off, const int* __restrict__ g_bond_off, int B,
@@ -45,20 +29,19 @@ __global__ __launch_bounds__(64) void mol_screen_kernel(
     int8_t* __restrict__ cls_o, int16_t* __restrict__ compact_o, uint8_t* __restrict__ val2_o, int16_t* __restrict__ comp_o,
     int8_t* __restrict__ order_o) {
   __shared__ int s_cls[kMolMax];                          // atom class, -1 = dropped
-  __shared__ unsigned long long s_adj[kMolMax][kMolCh];   // kept bonds of an atom as a bit per local atom index
+  __shared__ MolAdjRow s_adj[kMolMax];                    // kept bonds of an atom
   __shared__ unsigned int s_stat[kMolMax];                // valence2 | degree << 16 | aromatic bonds << 24
   __shared__ int s_label[kMolMax];                        // component label (a local atom index)
   __shared__ unsigned int s_size[kMolMax];                // atoms of the component whose label this index is
 
   const int lane = threadIdx.x;
-  const int f = blockIdx.x / B, g = blockIdx.x - f * B;
-  const int a0 = g_lig_off[g], n = g_lig_off[g + 1] - a0;
-  if (n > kMolMax || n < 0) return;                       // (the host wrapper has refused such a batch: never index LDS past its end)
-  const int h0 = g_bond_off[g] >> 1, n_pair = n * (n - 1) / 2;
-  const float* nrow = node_scores + (size_t)f * node_fs + (size_t)a0 * 12;
-  const float* erow = edge_scores + (size_t)f * edge_fs + (size_t)h0 * 12;       // first half of the graph's rows, 6 floats each
-  const float* prow = pos + (size_t)f * pos_fs + (size_t)a0 * 3;
-  const size_t arow = (size_t)f * n_lig + a0, hrow = (size_t)f * n_half + h0;
+  MolFrame m;
+  if (!mol_frame(m, blockIdx.x, B, g_lig_off, g_bond_off, n_lig, n_half)) return;
+  const int n = m.n;
+  const size_t arow = m.arow, hrow = m.hrow;
+  const float* nrow = node_scores + (size_t)m.f * node_fs + (size_t)m.a0 * 12;
+  const float* erow = edge_scores + (size_t)m.f * edge_fs + (size_t)m.h0 * 12;   // first half of the graph's rows, 6 floats each
+  const float* prow = pos + (size_t)m.f * pos_fs + (size_t)m.a0 * 3;
 
   // ---- atoms: class, compact index, coordinates -------------------------------------------------------------------------------
   int n_kept = 0;
@@ -79,67 +62,59 @@ __global__ __launch_bounds__(64) void mol_screen_kernel(
       masked |= k == 11;
     }
     const bool keep = k < 11;
-    const unsigned long long m = __ballot(keep);
-    const int compact = n_kept + __popcll(m & ((1ull << lane) - 1ull));
-    n_kept += __popcll(m);
+    const unsigned long long km = __ballot(keep);
+    const int compact = n_kept + __popcll(km & ((1ull << lane) - 1ull));
+    n_kept += __popcll(km);
     if (i < n) {
       s_cls[i] = keep ? k : -1;
       s_label[i] = keep ? i : -1;
       s_stat[i] = 0u, s_size[i] = 0u;
 #pragma unroll
-      for (int w = 0; w < kMolCh; ++w) s_adj[i][w] = 0ull;
+      for (int w = 0; w < kMolCh; ++w) s_adj[i].w[w] = 0ull;
       cls_o[arow + i] = (int8_t)(keep ? k : -1);
       compact_o[arow + i] = (int16_t)(keep ? compact : -1);
       if (keep) {
         const float* p = prow + (size_t)i * 3;
-        bad_pos |= nonfinite_bits(p[0]) || nonfinite_bits(p[1]) || nonfinite_bits(p[2]);
+        bad_pos |= mol_nonfinite(p[0]) || mol_nonfinite(p[1]) || mol_nonfinite(p[2]);
       }
     }
   }
   __syncthreads();
 
-  // ---- bonds: the pairs a < b in row-major order, lane-strided (a wave reads 64 consecutive rows) ---------------------------
+  // ---- bonds ------------------------------------------------------------------------------------------------------------------
   int n_bond = 0;
   bool absorbing = false;
-  {
-    int a = 0, b = 1 + lane;
-    for (int p = lane; p < n_pair; p += 64, b += 64) {
-      while (b >= n) {                                   // next row of the triangle (p < n_pair: ends with a < n - 1)
-        ++a;
-        b = b - n + a + 1;
-      }
-      float v[6];
-      const float2* r = reinterpret_cast<const float2*>(erow + (size_t)p * 6);
+  for_each_pair(lane, n, m.n_pair, [&](int p, int a, int b) {
+    float v[6];
+    const float2* r = reinterpret_cast<const float2*>(erow + (size_t)p * 6);
 #pragma unroll
-      for (int q = 0; q < 3; ++q) {
-        const float2 t = r[q];
-        v[2 * q] = t.x, v[2 * q + 1] = t.y;
-      }
-      const int o = first_argmax<6>(v);
-      absorbing |= o == 5;
-      const bool bond = o >= 1 && o <= 4 && s_cls[a] >= 0 && s_cls[b] >= 0;
-      order_o[hrow + p] = (int8_t)(bond ? o : 0);
-      if (bond) {
-        ++n_bond;
-        const unsigned int inc = (o == 4 ? 3u : 2u * o) | (1u << 16) | (o == 4 ? 1u << 24 : 0u);
-        atomicAdd(&s_stat[a], inc);
-        atomicAdd(&s_stat[b], inc);
-        atomicOr(&s_adj[a][b >> 6], 1ull << (b & 63));
-        atomicOr(&s_adj[b][a >> 6], 1ull << (a & 63));
-      }
+    for (int q = 0; q < 3; ++q) {
+      const float2 t = r[q];
+      v[2 * q] = t.x, v[2 * q + 1] = t.y;
     }
-  }
+    const int o = first_argmax<6>(v);
+    absorbing |= o == 5;
+    const bool bond = mol_is_bond(o) && s_cls[a] >= 0 && s_cls[b] >= 0;
+    order_o[hrow + p] = (int8_t)(bond ? o : 0);
+    if (bond) {
+      ++n_bond;
+      const unsigned int inc = (o == 4 ? 3u : 2u * o) | (1u << 16) | (o == 4 ? 1u << 24 : 0u);
+      atomicAdd(&s_stat[a], inc);
+      atomicAdd(&s_stat[b], inc);
+      mol_adj_set(s_adj, a, b);
+    }
+  });
   __syncthreads();
 
   // ---- components: every atom takes the smallest label among itself and its neighbours, then its label's label; until a
   // wave-wide vote sees no change.  Labels only decrease and stay inside the component, so reading a neighbour's label of
   // either round is fine; at the fixed point a component holds one label, the index of its first atom. ------------------------
-  unsigned long long adj[kMolCh][kMolCh];
+  MolAdjRow adj[kMolCh];
 #pragma unroll
   for (int c = 0; c < kMolCh; ++c) {
     const int i = c * 64 + lane;
 #pragma unroll
-    for (int w = 0; w < kMolCh; ++w) adj[c][w] = (i < n && s_cls[i] >= 0) ? s_adj[i][w] : 0ull;
+    for (int w = 0; w < kMolCh; ++w) adj[c].w[w] = (i < n && s_cls[i] >= 0) ? s_adj[i].w[w] : 0ull;
   }
   bool changed;
   do {
@@ -150,15 +125,7 @@ __global__ __launch_bounds__(64) void mol_screen_kernel(
       if (i < n && s_cls[i] >= 0) {
         const int l0 = s_label[i];
         int l = l0;
-#pragma unroll
-        for (int w = 0; w < kMolCh; ++w) {
-          unsigned long long m = adj[c][w];
-          while (m) {
-            const int j = w * 64 + __builtin_ctzll(m);
-            m &= m - 1ull;
-            l = min(l, s_label[j]);
-          }
-        }
+        for_each_neighbour(adj[c], [&](int j) { l = min(l, s_label[j]); });
         l = min(l, s_label[l]);
         if (l < l0) {
           s_label[i] = l;
@@ -201,7 +168,7 @@ __global__ __launch_bounds__(64) void mol_screen_kernel(
     if (i < n) largest = max(largest, (int)s_size[i]);
   }
   largest = wave_imax(largest);
-  n_bond = wave_isum(n_bond);
+  n_bond = wave_sum(n_bond);
   int st = 0;
   st |= n_kept == 0 ? PG_MOL_NO_ATOMS : 0;
   st |= n_comp > 1 ? PG_MOL_DISCONNECTED : 0;
@@ -223,19 +190,8 @@ extern "C" int pg_mol_screen(const float* node_scores, int64_t node_fs, const fl
                              int64_t pos_fs, const int* g_lig_off, const int* g_bond_off, int B, int F, int n_lig, int n_bond,
                              int max_n, const uint8_t* max_valence2, int* status, int* counts, int8_t* cls, int16_t* compact,
                              uint8_t* valence2, int16_t* comp, int8_t* order, void* stream) {
-  if (B < 0 || F < 0 || n_lig < 0 || n_bond < 0 || (n_bond & 1)) {
-    set_error("pg_mol_screen: B %d, F %d, n_lig %d, n_bond %d (n_bond counts both directions of every pair)", B, F, n_lig, n_bond);
-    return PG_ERR_ARG;
-  }
-  if (max_n > PG_MOL_MAX_ATOMS) {
-    set_error("pg_mol_screen: a graph of %d atoms, the kernel holds at most PG_MOL_MAX_ATOMS = %d", max_n, PG_MOL_MAX_ATOMS);
-    return PG_ERR_ARG;
-  }
-  if (B == 0 || F == 0) return PG_OK;
-  if ((long long)B * F > 0x7fffffffLL) {
-    set_error("pg_mol_screen: %d frames x %d graphs exceed one launch", F, B);
-    return PG_ERR_ARG;
-  }
+  const int rc = mol_check_batch("pg_mol_screen", B, F, n_lig, n_bond, max_n);
+  if (rc != PG_OK) return rc == kMolNothing ? PG_OK : rc;
   if (((uintptr_t)node_scores & 15) || (node_fs & 3) || ((uintptr_t)edge_scores & 7) || (edge_fs & 1) || ((uintptr_t)counts & 15)) {
     set_error("pg_mol_screen: node_scores / node_fs must be 16-byte, edge_scores / edge_fs 8-byte, counts 16-byte aligned");
     return PG_ERR_ARG;

@@ -47,6 +47,16 @@ __device__ __forceinline__ T wave_sum(T v) {
   for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
   return v;
 }
+__device__ __forceinline__ int wave_imax(int v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v = max(v, __shfl_xor(v, o));
+  return v;
+}
+__device__ __forceinline__ int wave_imin(int v) {
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v = min(v, __shfl_xor(v, o));
+  return v;
+}
 // v of lane src_lane (any lane of the wave, ds_bpermute)
 __device__ __forceinline__ float from_lane(float v, int src_lane) {
   return __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(src_lane << 2, __builtin_bit_cast(int, v)));

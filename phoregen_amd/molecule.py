@@ -229,6 +229,41 @@ class Screen:
     num_atoms: list              # B ints
 
 
+def _need_cuda(fn, noun, dev, holder='result'):
+    if dev.type != 'cuda':
+        raise RuntimeError(f'phoregen_amd.molecule.{fn}: {noun} is a HIP kernel and the {holder} lives on {dev}; there is no CPU fallback')
+
+
+def _check_rows(fn, t, F, k, what, dev):
+    """t is [rows, k] or [F, rows, k]: fp32 on dev, every frame contiguous (the frames may be strided)."""
+    row = t[0] if t.dim() == 3 and F > 0 else t
+    if t.dtype != torch.float32 or t.device != dev or t.size(-1) != k or not (row.is_contiguous() or row.numel() == 0):
+        raise ValueError(f'phoregen_amd.molecule.{fn}: {what} must be contiguous fp32 [.., {k}] on one device')
+
+
+def _check_arrays(who, dev, arrays):
+    """arrays: (tensor, dtype) pairs in the order of the launch; each must be contiguous, of that dtype and on dev."""
+    for i, (t, dt) in enumerate(arrays):
+        if t.dtype != dt or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f'phoregen_amd.molecule.{who}: array {i} of the launch must be contiguous {dt} on {dev}, it is '
+                             f'{"" if t.is_contiguous() else "non-contiguous "}{t.dtype} on {t.device}')
+
+
+def _screen_of(fn, screen, results, frames, F, N, E, dev):
+    """The `Screen` a function works on: the one handed in, else a new one; it must be one of this result and frames."""
+    sc = screen if screen is not None else _screen(results, frames)
+    if tuple(sc.status.shape) != (F, len(sc.num_atoms)) or sc.cls.size(1) != N or sc.cls.device != dev or 2 * sc.order.size(1) != E:
+        raise ValueError(f'phoregen_amd.molecule.{fn}: the screen ({tuple(sc.status.shape)} frames x graphs, {sc.cls.size(1)} atom '
+                         f'rows) is not one of this result and frames ({F} frames, {N} atom rows)')
+    return sc
+
+
+def _point_count(fn, point_pos):
+    if not torch.is_tensor(point_pos) or point_pos.dim() != 2 or point_pos.size(1) != 3:
+        raise ValueError(f'phoregen_amd.molecule.{fn}: point_pos must be a tensor [P, 3]')
+    return point_pos.size(0)
+
+
 def _frames(results, frames):
     if frames == 'final':
         node, pos, edge = results['pred']
@@ -250,13 +285,9 @@ def screen(results, frames='final'):
     `results` is only read."""
     node, pos, edge, F, (node_fs, edge_fs, pos_fs) = _frames(results, frames)
     dev = node.device
-    if dev.type != 'cuda':
-        raise RuntimeError('phoregen_amd.molecule.screen: the screen is a HIP kernel and the result lives on %s; there is no CPU '
-                           'fallback' % dev)
+    _need_cuda('screen', 'the screen', dev)
     for t, k, what in ((node, 12, 'atom scores'), (pos, 3, 'coordinates'), (edge, 6, 'bond scores')):
-        row = t[0] if t.dim() == 3 and F > 0 else t
-        if t.dtype != torch.float32 or t.device != dev or t.size(-1) != k or not (row.is_contiguous() or row.numel() == 0):
-            raise ValueError(f'phoregen_amd.molecule.screen: {what} must be contiguous fp32 [.., {k}] on one device')
+        _check_rows('screen', t, F, k, what, dev)
     N, E = node.size(-2), edge.size(-2)
     na = results['lig_info'][0].to(dev).long().reshape(-1)
     B = na.numel()
@@ -297,9 +328,7 @@ def molecule_keys(sc):
     atoms' elements and the bonds' orders alone (4 = aromatic is its own label), not on the numbering of the atoms, coordinates,
     dropped atoms or absorbing rows.  Equal keys are NECESSARY, not sufficient, for equal molecules: `same_molecule` decides."""
     dev = sc.cls.device
-    if dev.type != 'cuda':
-        raise RuntimeError('phoregen_amd.molecule.molecule_keys: the key is a HIP kernel and the screen lives on %s; there is no CPU '
-                           'fallback' % dev)
+    _need_cuda('molecule_keys', 'the key', dev, 'screen')
     F, B = sc.status.shape
     with torch.cuda.device(dev):
         lib = hip.lib()
@@ -312,9 +341,7 @@ def molecule_keys(sc):
 def _launch_key(lib, cls, order, lig_off, bond_off, B, F, max_n, key, colour):
     """pg_mol_key on the current stream; `colour` may be None.  A graph above MAX_ATOMS is the library's error: nothing is launched
     and the outputs are not written."""
-    for t, dt in ((cls, torch.int8), (order, torch.int8), (lig_off, torch.int32), (bond_off, torch.int32)):
-        if t.dtype != dt or not t.is_contiguous() or t.device != cls.device:
-            raise ValueError('phoregen_amd.molecule.molecule_keys: cls / order must be contiguous int8, the offsets int32, on one device')
+    _check_arrays('molecule_keys', cls.device, [(cls, torch.int8), (order, torch.int8), (lig_off, torch.int32), (bond_off, torch.int32)])
     hip.check(lib.pg_mol_key(cls.data_ptr(), order.data_ptr(), lig_off.data_ptr(), bond_off.data_ptr(), B, F, cls.size(-1),
                              2 * order.size(-1), max_n, key.data_ptr(), hip.ptr(colour), hip.stream_ptr()), 'pg_mol_key')
 
@@ -365,6 +392,13 @@ def _point_ranges(point_batch, P, B, dev):
     return torch.stack([start, end], 1).int().contiguous(), off.int()
 
 
+def _points(point_pos, point_batch, B, dev):
+    """(ranges, offsets, Q = the point outputs of a frame, the points as contiguous fp32 on the device)"""
+    P = point_pos.size(0)
+    ranges, off = _point_ranges(point_batch, P, B, dev)
+    return ranges, off, P * B if point_batch is None else P, point_pos.to(dev, torch.float32).contiguous()
+
+
 @torch.no_grad()
 def geometry(results, point_pos, point_is_ex, point_batch=None, frames='final', screen=None, limits=GeomLimits()):
     """Measure every decoded (frame, graph) of a `sample` / `sample_batch` result against its pharmacophore, on the device, in one
@@ -375,30 +409,19 @@ def geometry(results, point_pos, point_is_ex, point_batch=None, frames='final', 
     lengths and stays out of the spheres, nothing more; 'covered' says an atom is near a feature, not that it is the matching group."""
     _, pos, edge, F, (_, _, pos_fs) = _frames(results, frames)
     dev = pos.device
-    if dev.type != 'cuda':
-        raise RuntimeError('phoregen_amd.molecule.geometry: the geometry screen is a HIP kernel and the result lives on %s; there is '
-                           'no CPU fallback' % dev)
+    _need_cuda('geometry', 'the geometry screen', dev)
     lim = tuple(float(v) for v in astuple(limits))
     if len(lim) != 5 or not all(np.isfinite(lim)):
         raise ValueError(f'phoregen_amd.molecule.geometry: limits must be five finite numbers, not {limits!r}')
-    if not torch.is_tensor(point_pos) or point_pos.dim() != 2 or point_pos.size(1) != 3:
-        raise ValueError('phoregen_amd.molecule.geometry: point_pos must be a tensor [P, 3]')
-    P = point_pos.size(0)
+    P = _point_count('geometry', point_pos)
     if not torch.is_tensor(point_is_ex) or point_is_ex.numel() != P:
         raise ValueError(f'phoregen_amd.molecule.geometry: {P} points, point_is_ex has {getattr(point_is_ex, "shape", None)}')
-    sc = screen if screen is not None else _screen(results, frames)
-    B, N = len(sc.num_atoms), pos.size(-2)
-    if tuple(sc.status.shape) != (F, B) or sc.cls.size(1) != N or sc.cls.device != dev or 2 * sc.order.size(1) != edge.size(-2):
-        raise ValueError(f'phoregen_amd.molecule.geometry: the screen ({tuple(sc.status.shape)} frames x graphs, {sc.cls.size(1)} atom '
-                         f'rows) is not one of this result and frames ({F} frames, {N} atom rows)')
-    row = pos[0] if pos.dim() == 3 and F > 0 else pos
-    if pos.dtype != torch.float32 or not (row.is_contiguous() or row.numel() == 0):
-        raise ValueError('phoregen_amd.molecule.geometry: coordinates must be contiguous fp32 [.., 3]')
+    sc = _screen_of('geometry', screen, results, frames, F, pos.size(-2), edge.size(-2), dev)
+    B = len(sc.num_atoms)
+    _check_rows('geometry', pos, F, 3, 'coordinates', dev)
     with torch.cuda.device(dev):
         lib = hip.lib()
-        ranges, off = _point_ranges(point_batch, P, B, dev)
-        Q = P * B if point_batch is None else P
-        ppos = point_pos.to(dev, torch.float32).contiguous()
+        ranges, off, Q, ppos = _points(point_pos, point_batch, B, dev)
         pex = (point_is_ex.reshape(-1).to(dev) != 0).to(torch.uint8)
         out = dict(status=torch.empty(F, B, dtype=torch.int32, device=dev), metrics=torch.empty(F, B, 8, dtype=torch.float32, device=dev),
                    counts=torch.empty(F, B, 6, dtype=torch.int32, device=dev), point_dist=torch.empty(F, Q, dtype=torch.float32, device=dev),
@@ -421,12 +444,8 @@ def geometry_for(data, results, frames='final', screen=None, limits=GeomLimits()
 def _launch_geom(lib, pos, pos_fs, cls, order, lig_off, bond_off, B, F, max_n, point_pos, point_is_ex, ranges, off, n_out, limits, out):
     """pg_mol_geom on the current stream.  A graph above MAX_ATOMS is the library's error: nothing is launched and `out` is not
     written."""
-    dev = pos.device
-    for t, dt in ((cls, torch.int8), (order, torch.int8), (lig_off, torch.int32), (bond_off, torch.int32), (point_pos, torch.float32),
-                  (point_is_ex, torch.uint8), (ranges, torch.int32), (off, torch.int32)):
-        if t.dtype != dt or not t.is_contiguous() or t.device != dev:
-            raise ValueError('phoregen_amd.molecule.geometry: cls / order must be contiguous int8, offsets and ranges int32, points fp32, '
-                             'their kinds uint8, all on the device of the coordinates')
+    _check_arrays('geometry', pos.device, [(cls, torch.int8), (order, torch.int8), (lig_off, torch.int32), (bond_off, torch.int32),
+                                           (point_pos, torch.float32), (point_is_ex, torch.uint8), (ranges, torch.int32), (off, torch.int32)])
     if (lig_off.numel() != B + 1 or bond_off.numel() != B + 1 or off.numel() != B + 1 or ranges.numel() != 2 * B or cls.numel() != F * cls.size(-1)
             or order.numel() != F * order.size(-1) or point_is_ex.numel() != point_pos.size(0) or pos.size(-2) != cls.size(-1)
             or tuple(out['point_dist'].shape) != (F, n_out) or tuple(out['point_atom'].shape) != (F, n_out)
@@ -463,16 +482,11 @@ def rings(results, frames='final', screen=None, limits=RingLimits()):
     list, no hydrogens; `rotatable` has no amide or terminal-group exceptions and is not RDKit's NumRotatableBonds."""
     node, _, edge, F, _ = _frames(results, frames)
     dev = node.device
-    if dev.type != 'cuda':
-        raise RuntimeError('phoregen_amd.molecule.rings: the ring screen is a HIP kernel and the result lives on %s; there is no CPU '
-                           'fallback' % dev)
+    _need_cuda('rings', 'the ring screen', dev)
     if not isinstance(limits, RingLimits):
         raise ValueError(f'phoregen_amd.molecule.rings: limits must be a RingLimits, not {limits!r}')
-    sc = screen if screen is not None else _screen(results, frames)
+    sc = _screen_of('rings', screen, results, frames, F, node.size(-2), edge.size(-2), dev)
     B, N = len(sc.num_atoms), node.size(-2)
-    if tuple(sc.status.shape) != (F, B) or sc.cls.size(1) != N or sc.cls.device != dev or 2 * sc.order.size(1) != edge.size(-2):
-        raise ValueError(f'phoregen_amd.molecule.rings: the screen ({tuple(sc.status.shape)} frames x graphs, {sc.cls.size(1)} atom '
-                         f'rows) is not one of this result and frames ({F} frames, {N} atom rows)')
     with torch.cuda.device(dev):
         lib = hip.lib()
         out = dict(status=torch.empty(F, B, dtype=torch.int32, device=dev),
@@ -486,12 +500,9 @@ def rings(results, frames='final', screen=None, limits=RingLimits()):
 def _launch_rings(lib, cls, order, lig_off, bond_off, B, F, max_n, limits, out):
     """pg_mol_rings on the current stream.  A graph above MAX_ATOMS is the library's error: nothing is launched and `out` is not
     written."""
-    dev = cls.device
-    for t, dt in ((cls, torch.int8), (order, torch.int8), (lig_off, torch.int32), (bond_off, torch.int32), (out['ring_size'], torch.uint8),
-                  (out['atom_ring'], torch.uint8), (out['ring_sys'], torch.int16), (out['counts'], torch.int32), (out['status'], torch.int32)):
-        if t.dtype != dt or not t.is_contiguous() or t.device != dev:
-            raise ValueError('phoregen_amd.molecule.rings: cls / order must be contiguous int8, the offsets int32, ring_size / atom_ring '
-                             'uint8, ring_sys int16, counts / status int32, all on one device')
+    _check_arrays('rings', cls.device, [(cls, torch.int8), (order, torch.int8), (lig_off, torch.int32), (bond_off, torch.int32),
+                                        (out['ring_size'], torch.uint8), (out['atom_ring'], torch.uint8), (out['ring_sys'], torch.int16),
+                                        (out['counts'], torch.int32), (out['status'], torch.int32)])
     if (lig_off.numel() != B + 1 or bond_off.numel() != B + 1 or cls.numel() != F * cls.size(-1) or order.numel() != F * order.size(-1)
             or out['ring_size'].shape != order.shape or out['atom_ring'].shape != cls.shape or out['ring_sys'].shape != cls.shape
             or out['status'].numel() != F * B or out['counts'].numel() != len(RING_COUNTS) * F * B):
@@ -528,16 +539,11 @@ def kekulize(results, frames='final', screen=None, options=KekuleOptions()):
     charge` is the same for every structure.  No stereo, tautomers, anions, O+; not checked against RDKit."""
     node, _, edge, F, _ = _frames(results, frames)
     dev = node.device
-    if dev.type != 'cuda':
-        raise RuntimeError('phoregen_amd.molecule.kekulize: the Kekulé assignment is a HIP kernel and the result lives on %s; there is '
-                           'no CPU fallback' % dev)
+    _need_cuda('kekulize', 'the Kekulé assignment', dev)
     if not isinstance(options, KekuleOptions):
         raise ValueError(f'phoregen_amd.molecule.kekulize: options must be a KekuleOptions, not {options!r}')
-    sc = screen if screen is not None else _screen(results, frames)
+    sc = _screen_of('kekulize', screen, results, frames, F, node.size(-2), edge.size(-2), dev)
     B, N = len(sc.num_atoms), node.size(-2)
-    if tuple(sc.status.shape) != (F, B) or sc.cls.size(1) != N or sc.cls.device != dev or 2 * sc.order.size(1) != edge.size(-2):
-        raise ValueError(f'phoregen_amd.molecule.kekulize: the screen ({tuple(sc.status.shape)} frames x graphs, {sc.cls.size(1)} atom '
-                         f'rows) is not one of this result and frames ({F} frames, {N} atom rows)')
     with torch.cuda.device(dev):
         lib = hip.lib()
         out = dict(status=torch.empty(F, B, dtype=torch.int32, device=dev),
@@ -552,13 +558,9 @@ def kekulize(results, frames='final', screen=None, options=KekuleOptions()):
 def _launch_kekule(lib, cls, order, lig_off, bond_off, B, F, max_n, tables, allow_charged, out):
     """pg_mol_kekule on the current stream; tables = (DBL_NEUTRAL, DBL_CHARGED, MUST [11], H_VALENCES [11, 4]) as uint8 on the device.
     A graph above MAX_ATOMS is the library's error: nothing is launched and `out` is not written."""
-    dev = cls.device
-    for t, dt in ((cls, torch.int8), (order, torch.int8), (lig_off, torch.int32), (bond_off, torch.int32), (out['kekule_order'], torch.int8),
-                  (out['hcount'], torch.uint8), (out['charge'], torch.int8), (out['counts'], torch.int32), (out['status'], torch.int32),
-                  *((t, torch.uint8) for t in tables)):
-        if t.dtype != dt or not t.is_contiguous() or t.device != dev:
-            raise ValueError('phoregen_amd.molecule.kekulize: cls / order / kekule_order / charge must be contiguous int8, the offsets '
-                             'int32, hcount and the tables uint8, counts / status int32, all on one device')
+    _check_arrays('kekulize', cls.device, [(cls, torch.int8), (order, torch.int8), (lig_off, torch.int32), (bond_off, torch.int32),
+                                           (out['kekule_order'], torch.int8), (out['hcount'], torch.uint8), (out['charge'], torch.int8),
+                                           (out['counts'], torch.int32), (out['status'], torch.int32), *((t, torch.uint8) for t in tables)])
     if (lig_off.numel() != B + 1 or bond_off.numel() != B + 1 or cls.numel() != F * cls.size(-1) or order.numel() != F * order.size(-1)
             or out['kekule_order'].shape != order.shape or out['hcount'].shape != cls.shape or out['charge'].shape != cls.shape
             or out['status'].numel() != F * B or out['counts'].numel() != len(KEKULE_COUNTS) * F * B or len(tables) != 4
@@ -611,36 +613,26 @@ def features(results, point_pos, point_kind, point_batch=None, frames='final', s
     atom positions are used, not ring centroids, as in the reference's own check."""
     node, pos, edge, F, (_, _, pos_fs) = _frames(results, frames)
     dev = pos.device
-    if dev.type != 'cuda':
-        raise RuntimeError('phoregen_amd.molecule.features: the feature typing is a HIP kernel and the result lives on %s; there is no '
-                           'CPU fallback' % dev)
+    _need_cuda('features', 'the feature typing', dev)
     if not isinstance(limits, FeatureLimits):
         raise ValueError(f'phoregen_amd.molecule.features: limits must be a FeatureLimits, not {limits!r}')
-    if not torch.is_tensor(point_pos) or point_pos.dim() != 2 or point_pos.size(1) != 3:
-        raise ValueError('phoregen_amd.molecule.features: point_pos must be a tensor [P, 3]')
-    P = point_pos.size(0)
+    P = _point_count('features', point_pos)
     if not torch.is_tensor(point_kind) or point_kind.numel() != P or point_kind.dtype.is_floating_point or point_kind.dtype == torch.bool:
         raise ValueError(f'phoregen_amd.molecule.features: {P} points, point_kind must hold one integer kind per point, it has '
                          f'{getattr(point_kind, "shape", None)} of {getattr(point_kind, "dtype", None)}')
     given = [(what, x.screen) for what, x in (('kekule', kekule), ('rings', rings)) if x is not None]
-    sc = screen if screen is not None else given[0][1] if given else _screen(results, frames)
+    sc = _screen_of('features', screen if screen is not None or not given else given[0][1], results, frames, F, pos.size(-2),
+                    edge.size(-2), dev)
     B, N = len(sc.num_atoms), pos.size(-2)
-    if tuple(sc.status.shape) != (F, B) or sc.cls.size(1) != N or sc.cls.device != dev or 2 * sc.order.size(1) != edge.size(-2):
-        raise ValueError(f'phoregen_amd.molecule.features: the screen ({tuple(sc.status.shape)} frames x graphs, {sc.cls.size(1)} atom '
-                         f'rows) is not one of this result and frames ({F} frames, {N} atom rows)')
     for what, other in given:
         if not _same_screen(sc, other):
             raise ValueError(f'phoregen_amd.molecule.features: screen= and {what}= were computed from screens of different results')
-    row = pos[0] if pos.dim() == 3 and F > 0 else pos
-    if pos.dtype != torch.float32 or not (row.is_contiguous() or row.numel() == 0):
-        raise ValueError('phoregen_amd.molecule.features: coordinates must be contiguous fp32 [.., 3]')
+    _check_rows('features', pos, F, 3, 'coordinates', dev)
     kek = kekule if kekule is not None else _kekulize(results, frames, screen=sc)
     rg = rings if rings is not None else _rings(results, frames, screen=sc)
     with torch.cuda.device(dev):
         lib = hip.lib()
-        ranges, off = _point_ranges(point_batch, P, B, dev)
-        Q = P * B if point_batch is None else P
-        ppos = point_pos.to(dev, torch.float32).contiguous()
+        ranges, off, Q, ppos = _points(point_pos, point_batch, B, dev)
         pk = point_kind.reshape(-1).to(dev)
         pk = torch.where((pk >= POINT_UNTYPED) & (pk < len(FEATURE_TYPES)), pk, torch.full_like(pk, POINT_IGNORED)).to(torch.int8)
         out = dict(status=torch.empty(F, B, dtype=torch.int32, device=dev),
@@ -678,17 +670,12 @@ def features_for(data, results, frames='final', screen=None, kekule=None, rings=
 def _launch_feat(lib, pos, pos_fs, sc, kek, rg, B, F, max_n, point_pos, point_kind, ranges, off, n_out, limits, out):
     """pg_mol_feat on the current stream; sc, kek, rg: anything with the `Screen`, `Kekule` and `Rings` fields the kernel reads.  A graph
     above MAX_ATOMS is the library's error: nothing is launched and `out` is not written."""
-    dev = pos.device
     cls, order = sc.cls, sc.order
-    for t, dt in ((cls, torch.int8), (order, torch.int8), (sc.compact, torch.int16), (kek.kekule_order, torch.int8), (kek.hcount, torch.uint8),
-                  (kek.charge, torch.int8), (kek.status, torch.int32), (rg.ring_size, torch.uint8), (sc.lig_off, torch.int32),
-                  (sc.bond_off, torch.int32), (point_pos, torch.float32), (point_kind, torch.int8), (ranges, torch.int32), (off, torch.int32),
-                  (out['atom_fp'], torch.uint8), (out['point_dist'], torch.float32), (out['point_atom'], torch.int16),
-                  (out['counts'], torch.int32), (out['status'], torch.int32)):
-        if t.dtype != dt or not t.is_contiguous() or t.device != dev:
-            raise ValueError('phoregen_amd.molecule.features: cls / order / kekule_order / charge / point kinds must be contiguous int8, '
-                             'compact and point_atom int16, hcount / ring_size / atom_fp uint8, offsets, ranges, counts and the status '
-                             'words int32, points and point_dist fp32, all on the device of the coordinates')
+    _check_arrays('features', pos.device, [
+        (cls, torch.int8), (order, torch.int8), (sc.compact, torch.int16), (kek.kekule_order, torch.int8), (kek.hcount, torch.uint8),
+        (kek.charge, torch.int8), (kek.status, torch.int32), (rg.ring_size, torch.uint8), (sc.lig_off, torch.int32), (sc.bond_off, torch.int32),
+        (point_pos, torch.float32), (point_kind, torch.int8), (ranges, torch.int32), (off, torch.int32), (out['atom_fp'], torch.uint8),
+        (out['point_dist'], torch.float32), (out['point_atom'], torch.int16), (out['counts'], torch.int32), (out['status'], torch.int32)])
     if (sc.lig_off.numel() != B + 1 or sc.bond_off.numel() != B + 1 or off.numel() != B + 1 or ranges.numel() != 2 * B
             or cls.numel() != F * cls.size(-1) or order.numel() != F * order.size(-1) or pos.size(-2) != cls.size(-1)
             or sc.compact.shape != cls.shape or kek.hcount.shape != cls.shape or kek.charge.shape != cls.shape
@@ -773,9 +760,7 @@ def assemble(results, keys=False, geometry=None, rings=None, kekule=None, featur
         if x.status.size(0) != 1 or x.screen.cls.size(1) != pos_t.size(-2) or x.status.device != pos_t.device:
             raise ValueError(f'phoregen_amd.molecule.assemble: {what}= must be a {what.capitalize()} of the final frame of this result')
     for (what_a, xa), (what_b, xb) in zip(given, given[1:]):
-        a, b = xa.screen, xb.screen
-        if a is not b and (a.num_atoms != b.num_atoms or a.status.shape != b.status.shape or a.cls.shape != b.cls.shape
-                           or a.order.shape != b.order.shape or a.cls.device != b.cls.device):
+        if not _same_screen(xa.screen, xb.screen):
             raise ValueError(f'phoregen_amd.molecule.assemble: {what_a}= and {what_b}= were computed from screens of different results')
     sc = given[0][1].screen if given else screen(results, 'final')
     # the parts of the one blob, widest elements first so that every part stays aligned in it

@@ -10,6 +10,7 @@ import pytest
 import torch
 from scipy import stats
 
+from helpers import default_model
 from oracle import philox_ref as pr
 
 pytestmark = pytest.mark.gpu
@@ -18,10 +19,7 @@ DEV = 'cuda'
 
 @pytest.fixture(scope='module')
 def model():
-    from phoregen_amd.config import default_model_config
-    from phoregen_amd.models.diffusion import PhoreDiff
-    from phoregen_amd.weights import init_deterministic_
-    return init_deterministic_(PhoreDiff(default_model_config(), 'zinc_300'), 0).eval().to(DEV)
+    return default_model(DEV)
 
 
 def _fragment(nf, seed):

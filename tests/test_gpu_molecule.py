@@ -7,6 +7,7 @@ import pytest
 import torch
 
 import mol_reference as R
+from helpers import default_model, mol_result as _result
 from phoregen_amd import molecule as M
 
 pytestmark = pytest.mark.gpu
@@ -16,19 +17,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.fixture(scope='module')
 def model():
-    from phoregen_amd.config import default_model_config
-    from phoregen_amd.models.diffusion import PhoreDiff
-    from phoregen_amd.weights import init_deterministic_
-    return init_deterministic_(PhoreDiff(default_model_config(), 'zinc_300'), 0).eval().to(DEV)
-
-
-def _result(node, pos, edge, sizes):
-    """A sampler-shaped result dict on the device (no trajectory)."""
-    from phoregen_amd.plan import make_edge_data
-    na = torch.tensor(sizes, dtype=torch.long)
-    ei, eb = make_edge_data(na)
-    return {'pred': [node.to(DEV), pos.to(DEV), edge.to(DEV)], 'traj': [None, None, None],
-            'lig_info': [na.to(DEV), torch.repeat_interleave(torch.arange(len(sizes)), na).to(DEV), ei.to(DEV), eb.to(DEV)]}
+    return default_model(DEV)
 
 
 def _compare_frame(sc, f, refs, sizes):

@@ -17,21 +17,13 @@ import feature_reference as FR
 import kekule_reference as K
 import mol_reference as R
 from phoregen_amd import hip
+from helpers import mol_result as _result
 from phoregen_amd import molecule as M
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
 REL = 16.0 * 2.0 ** -24
 CI = M.FEATURE_COUNTS.index
-
-
-def _result(node, pos, edge, sizes, traj=(None, None, None)):
-    """A sampler-shaped result dict on the device."""
-    from phoregen_amd.plan import make_edge_data
-    na = torch.tensor(sizes, dtype=torch.long)
-    ei, eb = make_edge_data(na)
-    return {'pred': [node.to(DEV), pos.to(DEV), edge.to(DEV)], 'traj': [None if t is None else t.to(DEV) for t in traj],
-            'lig_info': [na.to(DEV), torch.repeat_interleave(torch.arange(len(sizes)), na).to(DEV), ei.to(DEV), eb.to(DEV)]}
 
 
 def _batch(cases):

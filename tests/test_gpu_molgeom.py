@@ -17,6 +17,7 @@ import torch
 import geom_reference as G
 import mol_reference as R
 from phoregen_amd import hip
+from helpers import default_model, mol_result as _result
 from phoregen_amd import molecule as M
 
 pytestmark = pytest.mark.gpu
@@ -28,10 +29,7 @@ OUT_KEYS = ('status', 'counts', 'metrics', 'point_dist', 'point_atom')
 
 @pytest.fixture(scope='module')
 def model():
-    from phoregen_amd.config import default_model_config
-    from phoregen_amd.models.diffusion import PhoreDiff
-    from phoregen_amd.weights import init_deterministic_
-    return init_deterministic_(PhoreDiff(default_model_config(), 'zinc_300'), 0).eval().to(DEV)
+    return default_model(DEV)
 
 
 @pytest.fixture(scope='module')
@@ -43,15 +41,6 @@ def generated():
     census = G.check_batch(batch, refs)
     print('census of the generated batch:', census)
     return batch, refs
-
-
-def _result(node, pos, edge, sizes, traj=(None, None, None)):
-    """A sampler-shaped result dict on the device."""
-    from phoregen_amd.plan import make_edge_data
-    na = torch.tensor(sizes, dtype=torch.long)
-    ei, eb = make_edge_data(na)
-    return {'pred': [node.to(DEV), pos.to(DEV), edge.to(DEV)], 'traj': [None if t is None else t.to(DEV) for t in traj],
-            'lig_info': [na.to(DEV), torch.repeat_interleave(torch.arange(len(sizes)), na).to(DEV), ei.to(DEV), eb.to(DEV)]}
 
 
 def _launch(res, point_pos, point_is_ex, ranges, frames='final', limits=None, out=None, max_n=None):

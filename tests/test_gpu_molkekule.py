@@ -12,6 +12,7 @@ import torch
 import kekule_reference as K
 import mol_reference as R
 import ring_reference as G
+from helpers import default_model, mol_result as _result, permute_batch as _permute_batch
 from phoregen_amd import molecule as M
 
 pytestmark = pytest.mark.gpu
@@ -22,10 +23,7 @@ CI = M.KEKULE_COUNTS.index
 
 @pytest.fixture(scope='module')
 def model():
-    from phoregen_amd.config import default_model_config
-    from phoregen_amd.models.diffusion import PhoreDiff
-    from phoregen_amd.weights import init_deterministic_
-    return init_deterministic_(PhoreDiff(default_model_config(), 'zinc_300'), 0).eval().to(DEV)
+    return default_model(DEV)
 
 
 @pytest.fixture(scope='module')
@@ -34,37 +32,6 @@ def family():
     graphs = K.random_family()
     rows = [K.rows_of(c, b) for c, b in graphs]
     return graphs, rows, [K.kekule_of_rows(cls, order) for cls, order in rows]
-
-
-def _result(node, pos, edge, sizes, traj=(None, None, None)):
-    """A sampler-shaped result dict on the device."""
-    from phoregen_amd.plan import make_edge_data
-    na = torch.tensor(sizes, dtype=torch.long)
-    ei, eb = make_edge_data(na)
-    return {'pred': [node.to(DEV), pos.to(DEV), edge.to(DEV)], 'traj': list(traj),
-            'lig_info': [na.to(DEV), torch.repeat_interleave(torch.arange(len(sizes)), na).to(DEV), ei.to(DEV), eb.to(DEV)]}
-
-
-def _permute_batch(node, pos, edge, sizes, seed):
-    """Every graph's atoms renumbered at random (atom i becomes perms[g][i]) and both halves of its bond rows moved to the rows of
-    the renumbered pairs."""
-    rng = np.random.default_rng(seed)
-    node2, pos2, edge2, perms = node.clone(), pos.clone(), edge.clone(), []
-    n0, e0 = 0, 0
-    for n in sizes:
-        h = n * (n - 1) // 2
-        p = rng.permutation(n)
-        perms.append(p)
-        dst = torch.from_numpy(n0 + p)
-        node2[dst], pos2[dst] = node[n0:n0 + n], pos[n0:n0 + n]
-        if h:
-            a, b = np.triu_indices(n, 1)
-            lo, hi = np.minimum(p[a], p[b]), np.maximum(p[a], p[b])
-            rows = torch.from_numpy(lo * n - lo * (lo + 1) // 2 + (hi - lo - 1))
-            edge2[e0 + rows] = edge[e0:e0 + h]
-            edge2[e0 + h + rows] = edge[e0 + h:e0 + 2 * h]
-        n0, e0 = n0 + n, e0 + 2 * h
-    return node2, pos2, edge2, perms
 
 
 def _split(kk, sizes, f=0):

@@ -8,6 +8,7 @@ import torch
 
 import mol_reference as R
 import molkey_reference as K
+from helpers import default_model, mol_result as _result, permute_batch as _permute_batch
 from phoregen_amd import molecule as M
 
 pytestmark = pytest.mark.gpu
@@ -18,19 +19,7 @@ M64 = (1 << 64) - 1
 
 @pytest.fixture(scope='module')
 def model():
-    from phoregen_amd.config import default_model_config
-    from phoregen_amd.models.diffusion import PhoreDiff
-    from phoregen_amd.weights import init_deterministic_
-    return init_deterministic_(PhoreDiff(default_model_config(), 'zinc_300'), 0).eval().to(DEV)
-
-
-def _result(node, pos, edge, sizes, traj=(None, None, None)):
-    """A sampler-shaped result dict on the device."""
-    from phoregen_amd.plan import make_edge_data
-    na = torch.tensor(sizes, dtype=torch.long)
-    ei, eb = make_edge_data(na)
-    return {'pred': [node.to(DEV), pos.to(DEV), edge.to(DEV)], 'traj': list(traj),
-            'lig_info': [na.to(DEV), torch.repeat_interleave(torch.arange(len(sizes)), na).to(DEV), ei.to(DEV), eb.to(DEV)]}
+    return default_model(DEV)
 
 
 def _unsigned(t):
@@ -45,31 +34,6 @@ def _restated(refs):
         keys.append(k)
         colours += c
     return keys, colours
-
-
-def _permute_batch(node, pos, edge, sizes, seed):
-    """Every graph's atoms renumbered at random (atom i becomes perms[g][i]) and both halves of its bond rows moved to the rows of
-    the renumbered pairs.  The kernel reads the first half only, so the pair's first-half scores stay in the first half whichever
-    of its ends now has the smaller index."""
-    rng = np.random.default_rng(seed)
-    node2, pos2, edge2, perms = node.clone(), pos.clone(), edge.clone(), []
-    n0, e0 = 0, 0
-    for n in sizes:
-        h = n * (n - 1) // 2
-        p = rng.permutation(n)
-        perms.append(p)
-        dst = torch.from_numpy(n0 + p)
-        node2[dst], pos2[dst] = node[n0:n0 + n], pos[n0:n0 + n]
-        if h:
-            a, b = np.triu_indices(n, 1)
-            pa, pb = p[a], p[b]
-            lo, hi = np.minimum(pa, pb), np.maximum(pa, pb)
-            rows = torch.from_numpy(lo * n - lo * (lo + 1) // 2 + (hi - lo - 1))
-            assert sorted(rows.tolist()) == list(range(h))
-            edge2[e0 + rows] = edge[e0:e0 + h]
-            edge2[e0 + h + rows] = edge[e0 + h:e0 + 2 * h]
-        n0, e0 = n0 + n, e0 + 2 * h
-    return node2, pos2, edge2, perms
 
 
 def test_kernel_equals_restatement_on_the_ragged_batch():

@@ -9,6 +9,7 @@ import torch
 
 import mol_reference as R
 import ring_reference as G
+from helpers import default_model, mol_result as _result, permute_batch as _permute_batch, onehot_graph as _onehot, cat_graphs as _cat
 from phoregen_amd import molecule as M
 
 pytestmark = pytest.mark.gpu
@@ -19,44 +20,7 @@ C_ = 1
 
 @pytest.fixture(scope='module')
 def model():
-    from phoregen_amd.config import default_model_config
-    from phoregen_amd.models.diffusion import PhoreDiff
-    from phoregen_amd.weights import init_deterministic_
-    return init_deterministic_(PhoreDiff(default_model_config(), 'zinc_300'), 0).eval().to(DEV)
-
-
-def _result(node, pos, edge, sizes, traj=(None, None, None)):
-    """A sampler-shaped result dict on the device."""
-    from phoregen_amd.plan import make_edge_data
-    na = torch.tensor(sizes, dtype=torch.long)
-    ei, eb = make_edge_data(na)
-    return {'pred': [node.to(DEV), pos.to(DEV), edge.to(DEV)], 'traj': list(traj),
-            'lig_info': [na.to(DEV), torch.repeat_interleave(torch.arange(len(sizes)), na).to(DEV), ei.to(DEV), eb.to(DEV)]}
-
-
-def _permute_batch(node, pos, edge, sizes, seed):
-    """Every graph's atoms renumbered at random (atom i becomes perms[g][i]) and both halves of its bond rows moved to the rows of
-    the renumbered pairs.  The kernel reads the first half only, so the pair's first-half scores stay in the first half whichever
-    of its ends now has the smaller index."""
-    rng = np.random.default_rng(seed)
-    node2, pos2, edge2, perms = node.clone(), pos.clone(), edge.clone(), []
-    n0, e0 = 0, 0
-    for n in sizes:
-        h = n * (n - 1) // 2
-        p = rng.permutation(n)
-        perms.append(p)
-        dst = torch.from_numpy(n0 + p)
-        node2[dst], pos2[dst] = node[n0:n0 + n], pos[n0:n0 + n]
-        if h:
-            a, b = np.triu_indices(n, 1)
-            pa, pb = p[a], p[b]
-            lo, hi = np.minimum(pa, pb), np.maximum(pa, pb)
-            rows = torch.from_numpy(lo * n - lo * (lo + 1) // 2 + (hi - lo - 1))
-            assert sorted(rows.tolist()) == list(range(h))
-            edge2[e0 + rows] = edge[e0:e0 + h]
-            edge2[e0 + h + rows] = edge[e0 + h:e0 + 2 * h]
-        n0, e0 = n0 + n, e0 + 2 * h
-    return node2, pos2, edge2, perms
+    return default_model(DEV)
 
 
 def _split(rg, sizes, f=0):
@@ -92,20 +56,6 @@ def _check(node, pos, edge, sizes, limits=M.RingLimits(), where=''):
     assert (rg.ring_size.dtype, rg.atom_ring.dtype, rg.ring_sys.dtype) == (torch.uint8, torch.uint8, torch.int16)
     _same(_split(rg, sizes), want, where)
     return rg, want
-
-
-def _onehot(atom_cls, et_half):
-    """One graph from atom classes [n] and first-half bond classes [h] (written to both halves), one-hot scores."""
-    n, h = len(atom_cls), len(et_half)
-    node = torch.zeros(n, 12)
-    node[torch.arange(n), torch.as_tensor(atom_cls, dtype=torch.long)] = 1.0
-    edge = torch.zeros(2 * h, 6)
-    edge[torch.arange(2 * h), torch.as_tensor(np.concatenate([et_half, et_half]), dtype=torch.long)] = 1.0
-    return node, torch.arange(3 * n, dtype=torch.float32).reshape(n, 3) * 0.25, edge
-
-
-def _cat(parts):
-    return tuple(torch.cat([p[k] for p in parts]) for k in range(3))
 
 
 def test_named_molecules_by_hand_and_by_the_restatement():
