@@ -598,6 +598,36 @@ int pg_mol_feat(const float* pos, int64_t pos_fs, const int8_t* cls, const int8_
                 const int* g_point_range /*[B][2]*/, const int* g_point_out_off /*[B+1]*/, int n_point_out, float feat_cut,
                 int max_unmatched, uint8_t* atom_fp, float* point_dist, int16_t* point_atom, int* counts, int* status, void* stream);
 
+/* SMILES text of the molecules the screen decoded, one wave per (frame, graph).  Definition: DESIGN.md 2.9 "SMILES".  Reads the screen's
+ * cls [F][n_lig] and pg_mol_kekule's kekule_order [F][n_bond / 2], hcount, charge [F][n_lig] and status [F][B] (frames dense, the same
+ * offsets): an atom is kept if its class is 0..10, a pair row a < b is a bond if its Kekulé order is 1, 2 or 3 and both ends are kept.
+ * Depth-first from every kept atom not yet visited, ascending, neighbours ascending; a bond outside the tree is a ring closure, opened
+ * at the ancestor with the smallest label 1..99 not in use and closed at the descendant; Kekulé form ('=' and '#', no aromatic
+ * lower case), bracket atoms where the bare symbol would not read back with the atom's hydrogens and charge.  Not canonical.
+ *   valences: uint8 [11][4] in DEVICE memory: the notation's normal valences per class, ascending, zero-padded; an empty row = the
+ *     element is always bracketed
+ *   text [F][B][capacity]: ASCII, every byte from length on 0; the whole row is written
+ *   length [F][B]: bytes of text; 0 on a failing graph
+ *   atom_rank [F][n_lig]: the atom's position in the text (preorder over the whole graph); -1 for a dropped atom and on a failing graph
+ *   counts [F][B][PG_SMILES_N_COUNTS]: 0 bytes of text, 1 kept atoms, 2 bonds, 3 components, 4 ring closures, 5 '(' in the text,
+ *     6 largest label (0: none), 7 bracket atoms; all 0 on a failing graph, except that with PG_SMILES_TOO_LONG they are the real ones
+ *     and 0 is the bytes the text needs
+ *   status [F][B]: PG_SMILES_* bits; with NO_KEKULE or RING_LABELS no other bit is set
+ * Integer work only: results are exact, and a graph's rows do not depend on its batch.  max_n above PG_MOL_MAX_ATOMS, a negative size,
+ * capacity < 1, a null table or (with B, F > 0) a null array: error before anything is launched, outputs untouched.  Every element of
+ * every output is written (nothing needs zeroing). */
+#define PG_SMILES_NO_KEKULE 1        /* failures: the graph's Kekulé status has PG_KEKULE_FAILED ...           */
+#define PG_SMILES_RING_LABELS 2      /* ... more than 99 ring-closure labels would be in use at once ...       */
+#define PG_SMILES_TOO_LONG 4         /* ... the text needs more than capacity bytes                            */
+#define PG_SMILES_DISCONNECTED 8     /* informational: more than one component, the text has a '.'             */
+#define PG_SMILES_EMPTY 16           /* informational: no kept atom, the text is empty                         */
+#define PG_SMILES_BRACKET 32         /* informational: at least one bracket atom                               */
+#define PG_SMILES_N_COUNTS 8
+int pg_mol_smiles(const int8_t* cls, const int8_t* kekule_order, const uint8_t* hcount, const int8_t* charge,
+                  const int* kekule_status /*[F][B]*/, const int* g_lig_off /*[B+1]*/, const int* g_bond_off /*[B+1]*/, int B, int F,
+                  int n_lig, int n_bond, int max_n, const uint8_t* valences /*[11][4]*/, int capacity, uint8_t* text, int* length,
+                  int16_t* atom_rank, int* counts, int* status, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -159,6 +159,8 @@ _PROTOS = {
     'pg_mol_feat': (C.c_int, [c_fp, C.c_int64, c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, C.c_int, C.c_int, C.c_int,
                               C.c_int, C.c_int, c_fp, c_ip, C.c_int, c_ip, c_ip, C.c_int, C.c_float, C.c_int, c_ip, c_fp, c_ip, c_ip,
                               c_ip, C.c_void_p]),
+    'pg_mol_smiles': (C.c_int, [c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_ip, C.c_int, c_ip,
+                                c_ip, c_ip, c_ip, c_ip, C.c_void_p]),
 }
 
 EXPORTS = tuple(_PROTOS)

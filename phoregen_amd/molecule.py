@@ -29,7 +29,13 @@ Features: `features` / `features_for` give every atom the pharmacophore feature 
 PO, HA, HY, NE, XB restated as integer rules over the Kekulé form, the hydrogens, the charges and the ring membership -- and match
 every typed feature point against the atoms that carry its type (csrc/mol_feat.hip; DESIGN.md 2.9 "Features"), as the reference's
 `check_nearby_phore(strict=True)` does with RDKit.  `assemble(features=)`, `sample_valid(features=)` and `write_sdf` carry it.  MB, CV
-and CR are not typed; the tables are written from the SMARTS text and not checked against RDKit."""
+and CR are not typed; the tables are written from the SMARTS text and not checked against RDKit.
+
+SMILES: `smiles` writes every decoded molecule as Kekulé-form OpenSMILES text on the device (csrc/mol_smiles.hip; DESIGN.md 2.9
+"SMILES"): a depth-first walk in atom order, ring-closure labels 1..99, bracket atoms where the bare symbol would not read back with
+the atom's hydrogens and charge.  `Smiles.strings`, `assemble(smiles=)`, `sample_valid(smiles=)` and `write_sdf` carry it.  The text
+reads back to exactly the molecule `assemble` returns; it is not canonical (identity stays with the keys), has no aromatic lower-case
+form and no stereo, and is not checked against RDKit."""
 import ctypes
 from dataclasses import astuple, dataclass
 
@@ -130,6 +136,26 @@ FEATURE_COUNTS = (('typed_points', 'matched', 'unmatched', 'untyped_points') + t
                   + tuple('points_' + t for t in FEATURE_TYPES) + tuple('matched_' + t for t in FEATURE_TYPES))
 POINT_UNTYPED, POINT_IGNORED = -1, -2   # point kinds beside 0..6: a feature that is not typed; an exclusion sphere
 
+# The SMILES writer (DESIGN.md 2.9 "SMILES"): status bits, the names of the count columns in the kernel's order, and the notation's
+# own table: the OpenSMILES normal valences of the elements that may be written without brackets, per element in ATOM_TYPES order (an
+# empty list: the element is always bracketed).  A bare atom is read with (the smallest entry that is not below the sum of its bond
+# orders) - (that sum) hydrogens, 0 without such an entry.  This is a second table next to H_VALENCES on purpose: it belongs to the
+# notation, not to the hydrogen rule; where the two disagree (N above 3, I above 1) the atom is written in brackets.  This is the
+# table's only copy: the kernel and the tests' restatement are handed it.
+SMILES_NO_KEKULE = 1             # the graph's Kekulé status has KEKULE_FAILED: nothing to write from
+SMILES_RING_LABELS = 2           # more than 99 ring-closure labels would be in use at once
+SMILES_TOO_LONG = 4              # the text needs more bytes than the row's capacity (the count 'length' says how many)
+SMILES_DISCONNECTED = 8          # informational: the text has a '.'
+SMILES_EMPTY = 16                # informational: no kept atom, the text is empty (the screen says NO_ATOMS)
+SMILES_BRACKET = 32              # informational: at least one bracket atom
+SMILES_FAIL_MASK = SMILES_NO_KEKULE | SMILES_RING_LABELS | SMILES_TOO_LONG
+SMILES_NAMES = {SMILES_NO_KEKULE: 'NO_KEKULE', SMILES_RING_LABELS: 'RING_LABELS', SMILES_TOO_LONG: 'TOO_LONG',
+                SMILES_DISCONNECTED: 'DISCONNECTED', SMILES_EMPTY: 'EMPTY', SMILES_BRACKET: 'BRACKET'}
+SMILES_COUNTS = ('length', 'atoms', 'bonds', 'components', 'ring_closures', 'branches', 'max_label', 'bracket_atoms')
+SMILES_VALENCES = {5: (3,), 6: (4,), 7: (3, 5), 8: (2,), 9: (1,), 14: (), 15: (3, 5), 16: (2, 4, 6), 17: (1,), 35: (1,), 53: (1,)}
+SMILES_MAX_LABEL = 99
+assert list(SMILES_VALENCES) == ATOM_TYPES
+
 # Standard atomic weights for 'mol_weight' (written from memory, abridged values)
 ATOMIC_WEIGHT = {1: 1.008, 5: 10.81, 6: 12.011, 7: 14.007, 8: 15.999, 9: 18.998, 14: 28.085, 15: 30.974, 16: 32.06, 17: 35.45,
                  35: 79.904, 53: 126.904}
@@ -210,6 +236,17 @@ def _kekule_table(device):
         rows = [[d[z] for z in ATOM_TYPES] for d in (KEKULE_DBL_NEUTRAL, KEKULE_DBL_CHARGED, KEKULE_MUST)]
         rows.append([list(H_VALENCES[z]) + [0] * (4 - len(H_VALENCES[z])) for z in ATOM_TYPES])
         t = _kekule_tables[device] = tuple(torch.tensor(r, dtype=torch.uint8, device=device) for r in rows)
+    return t
+
+
+_smiles_tables = {}              # device -> uint8 [11, 4]
+
+
+def _smiles_table(device):
+    t = _smiles_tables.get(device)
+    if t is None:
+        rows = [list(SMILES_VALENCES[z]) + [0] * (4 - len(SMILES_VALENCES[z])) for z in ATOM_TYPES]
+        t = _smiles_tables[device] = torch.tensor(rows, dtype=torch.uint8, device=device)
     return t
 
 
@@ -694,6 +731,84 @@ def _launch_feat(lib, pos, pos_fs, sc, kek, rg, B, F, max_n, point_pos, point_ki
               'pg_mol_feat')
 
 
+@dataclass
+class Smiles:
+    """Device tensors of one `smiles` call; F frames, B graphs, N atom rows."""
+    status: torch.Tensor         # int32 [F, B]     SMILES_* bits
+    counts: torch.Tensor         # int32 [F, B, 8]  SMILES_COUNTS
+    ok: torch.Tensor             # bool  [F, B]     no bit of SMILES_FAIL_MASK
+    text: torch.Tensor           # uint8 [F, B, capacity]  ASCII, zeros from `length` on
+    length: torch.Tensor         # int32 [F, B]     bytes of text; 0 where not ok
+    atom_rank: torch.Tensor      # int16 [F, N]     position of the atom in the text, -1 = dropped (or not ok)
+    capacity: int
+    screen: Screen               # the screen it was written from
+    kekule: Kekule               # the Kekulé form it was written from
+
+    def strings(self, frame=0):
+        """The texts of one frame as a list of str, one per graph ('' where not ok), from one device-to-host copy."""
+        B, cap = self.text.size(1), self.capacity
+        blob = torch.cat([self.length[frame].reshape(-1).view(torch.uint8), self.text[frame].reshape(-1)]).cpu().numpy()
+        length, text = blob[:4 * B].view(np.int32), blob[4 * B:]
+        return [text[g * cap:g * cap + int(length[g])].tobytes().decode('ascii') for g in range(B)]
+
+
+@torch.no_grad()
+def smiles(results, frames='final', screen=None, kekule=None, capacity=None):
+    """SMILES text of every decoded (frame, graph) of a `sample` / `sample_batch` result, on the device, in one launch (pg_mol_smiles;
+    DESIGN.md 2.9 "SMILES"): Kekulé-form OpenSMILES of the kept atoms with the Kekulé form's bond orders, hydrogens and charges --
+    depth-first from the lowest atom not yet written, neighbours ascending, ring-closure labels 1..99, '=' and '#', bracket atoms
+    where a bare symbol would not read back with the atom's hydrogens and charge, components joined by '.'.  Whichever of `screen`
+    and `kekule` (a `Kekule`) is not handed in is computed; both must come from one screen.  capacity: bytes of a text row, None =
+    8 * max(largest graph, 8); a text that needs more is SMILES_TOO_LONG, with the need in the count 'length'.  No host read beyond
+    the screen's.  `ok` fails for a graph without a Kekulé structure, with more than 99 labels in use at once or with too long a
+    text.  The text reads back to exactly the molecule `assemble` returns (`atom_rank`: where each atom stands in it); it is NOT
+    canonical -- the numbering of the atoms and the choice of Kekulé structure both change it, identity stays with `molecule_keys` --
+    and has no aromatic lower-case form, no stereo, no anions; not checked against RDKit."""
+    node, _, edge, F, _ = _frames(results, frames)
+    dev = node.device
+    _need_cuda('smiles', 'the SMILES writer', dev)
+    sc = _screen_of('smiles', screen if screen is not None or kekule is None else kekule.screen, results, frames, F, node.size(-2),
+                    edge.size(-2), dev)
+    if kekule is not None and not _same_screen(sc, kekule.screen):
+        raise ValueError('phoregen_amd.molecule.smiles: screen= and kekule= were computed from screens of different results')
+    kek = kekule if kekule is not None else _kekulize(results, frames, screen=sc)
+    B, N, max_n = len(sc.num_atoms), node.size(-2), max(sc.num_atoms, default=0)
+    cap = 8 * max(max_n, 8) if capacity is None else capacity
+    if isinstance(cap, bool) or not isinstance(cap, (int, np.integer)) or not 1 <= cap <= 0x7fffffff:
+        raise ValueError(f'phoregen_amd.molecule.smiles: capacity must be an integer in 1 .. 2**31 - 1, not {capacity!r}')
+    with torch.cuda.device(dev):
+        lib = hip.lib()
+        out = dict(status=torch.empty(F, B, dtype=torch.int32, device=dev),
+                   counts=torch.empty(F, B, len(SMILES_COUNTS), dtype=torch.int32, device=dev),
+                   text=torch.empty(F, B, int(cap), dtype=torch.uint8, device=dev), length=torch.empty(F, B, dtype=torch.int32, device=dev),
+                   atom_rank=torch.empty(F, N, dtype=torch.int16, device=dev))
+        _launch_smiles(lib, sc, kek, B, F, max_n, _smiles_table(dev), int(cap), out)
+    return Smiles(ok=(out['status'] & SMILES_FAIL_MASK) == 0, capacity=int(cap), screen=sc, kekule=kek, **out)
+
+
+def _launch_smiles(lib, sc, kek, B, F, max_n, table, capacity, out):
+    """pg_mol_smiles on the current stream; sc, kek: anything with the `Screen` and `Kekule` fields the kernel reads; table =
+    SMILES_VALENCES [11, 4] as uint8 on the device.  A graph above MAX_ATOMS is the library's error: nothing is launched and `out` is
+    not written."""
+    cls, order = sc.cls, kek.kekule_order
+    _check_arrays('smiles', cls.device, [(cls, torch.int8), (order, torch.int8), (kek.hcount, torch.uint8), (kek.charge, torch.int8),
+                                         (kek.status, torch.int32), (sc.lig_off, torch.int32), (sc.bond_off, torch.int32),
+                                         (table, torch.uint8), (out['text'], torch.uint8), (out['length'], torch.int32),
+                                         (out['atom_rank'], torch.int16), (out['counts'], torch.int32), (out['status'], torch.int32)])
+    if (sc.lig_off.numel() != B + 1 or sc.bond_off.numel() != B + 1 or cls.numel() != F * cls.size(-1) or order.numel() != F * order.size(-1)
+            or order.shape != sc.order.shape or kek.hcount.shape != cls.shape or kek.charge.shape != cls.shape
+            or kek.status.numel() != F * B or table.numel() != 4 * len(ATOM_TYPES) or out['text'].numel() != F * B * capacity
+            or out['length'].numel() != F * B or out['atom_rank'].shape != cls.shape or out['status'].numel() != F * B
+            or out['counts'].numel() != len(SMILES_COUNTS) * F * B):
+        raise ValueError(f'phoregen_amd.molecule.smiles: sizes of the offsets, screen / Kekulé arrays, table and outputs do not fit {F} '
+                         f'frames x {B} graphs, {cls.size(-1)} atom rows, {order.size(-1)} pair rows, capacity {capacity}')
+    hip.check(lib.pg_mol_smiles(cls.data_ptr(), order.data_ptr(), kek.hcount.data_ptr(), kek.charge.data_ptr(), kek.status.data_ptr(),
+                                sc.lig_off.data_ptr(), sc.bond_off.data_ptr(), B, F, cls.size(-1), 2 * order.size(-1), max_n,
+                                table.data_ptr(), capacity, out['text'].data_ptr(), out['length'].data_ptr(),
+                                out['atom_rank'].data_ptr(), out['counts'].data_ptr(), out['status'].data_ptr(), hip.stream_ptr()),
+              'pg_mol_smiles')
+
+
 def formula_of(elements, hcount, charge=0):
     """Molecular formula in Hill order (C, H, then the other symbols alphabetically; all alphabetically without carbon) from atomic
     numbers and per-atom hydrogen counts, with a charge suffix such as '+' / '2+' / '-', and the molecular weight from ATOMIC_WEIGHT
@@ -717,6 +832,7 @@ _geometry = geometry             # (functions below take a `geometry=` argument)
 _rings = rings                   # (and a `rings=` argument)
 _kekulize = kekulize
 _features = features
+_smiles = smiles
 _PAIRS = {}
 
 
@@ -730,7 +846,7 @@ def _pairs(n):
 
 
 @torch.no_grad()
-def assemble(results, keys=False, geometry=None, rings=None, kekule=None, features=None):
+def assemble(results, keys=False, geometry=None, rings=None, kekule=None, features=None, smiles=None):
     """The final prediction as one dict per graph with `decode_data`'s keys and meaning -- 'element' (atomic numbers), 'atom_pos'
     (kept atoms, the tensor's own fp32 values), 'bond_index' [2, n_b] (indices among the kept atoms) and 'bond_type' [n_b] for
     a < b only, in row order -- plus 'status', 'valid', 'n_components' and 'valence' (per kept atom, halves allowed).  The screen runs
@@ -753,9 +869,14 @@ def assemble(results, keys=False, geometry=None, rings=None, kekule=None, featur
     bit of FEAT_FAIL_MASK), the FEATURE_COUNTS by name, 'atom_fp' (uint8 per kept atom, bit t = FEATURE_TYPES[t]), 'atom_types' (per
     kept atom a tuple of type names), 'point_kind' of the graph's points, their 'point_dist' / 'point_atom' (the nearest atom that
     carries the point's type, an index into this dict's atoms, -1 = none) and 'point_matched' (distance < feat_cut) -- in the same copy; its screen is reused, and it must
-    have been computed from the screen of the others."""
+    have been computed from the screen of the others.
+    smiles=a `Smiles` of this result's final frame: every dict also has 'smiles' -- 'status' (SMILES_* bits), 'smiles_ok' (no bit of
+    SMILES_FAIL_MASK), 'text' (str; '' where not ok), the eight SMILES_COUNTS by name and 'atom_rank' (per kept atom: its position in
+    the text, -1 where not ok) -- in the same copy; its screen is reused, and it must have been computed from the screen of the
+    others."""
     geom, pos_t = geometry, results['pred'][1]
-    given = [(what, x) for what, x in (('geometry', geom), ('rings', rings), ('kekule', kekule), ('features', features)) if x is not None]
+    given = [(what, x) for what, x in (('geometry', geom), ('rings', rings), ('kekule', kekule), ('features', features), ('smiles', smiles))
+             if x is not None]
     for what, x in given:
         if x.status.size(0) != 1 or x.screen.cls.size(1) != pos_t.size(-2) or x.status.device != pos_t.device:
             raise ValueError(f'phoregen_amd.molecule.assemble: {what}= must be a {what.capitalize()} of the final frame of this result')
@@ -772,6 +893,8 @@ def assemble(results, keys=False, geometry=None, rings=None, kekule=None, featur
         parts += [('r_status', rings.status[0], np.int32), ('r_counts', rings.counts[0], np.int32)]
     if kekule is not None:
         parts += [('k_status', kekule.status[0], np.int32), ('k_counts', kekule.counts[0], np.int32)]
+    if smiles is not None:
+        parts += [('s_status', smiles.status[0], np.int32), ('s_counts', smiles.counts[0], np.int32), ('s_length', smiles.length[0], np.int32)]
     if geom is not None:
         parts += [('g_status', geom.status[0], np.int32), ('g_metrics', geom.metrics[0], np.float32), ('g_counts', geom.counts[0], np.int32),
                   ('g_dist', geom.point_dist[0], np.float32), ('g_off', geom.point_off, np.int32)]
@@ -787,6 +910,8 @@ def assemble(results, keys=False, geometry=None, rings=None, kekule=None, featur
         parts += [('r_sys', rings.ring_sys[0], np.int16)]
     if features is not None:
         parts += [('f_atom', features.point_atom[0], np.int16)]
+    if smiles is not None:
+        parts += [('s_rank', smiles.atom_rank[0], np.int16)]
     parts += [('cls', sc.cls[0], np.int8), ('valence2', sc.valence2[0], np.uint8), ('order', sc.order[0], np.int8)]
     if rings is not None:
         parts += [('r_atom', rings.atom_ring[0], np.uint8), ('r_size', rings.ring_size[0], np.uint8)]
@@ -794,6 +919,8 @@ def assemble(results, keys=False, geometry=None, rings=None, kekule=None, featur
         parts += [('k_order', kekule.kekule_order[0], np.int8), ('k_h', kekule.hcount[0], np.uint8), ('k_q', kekule.charge[0], np.int8)]
     if features is not None:
         parts += [('f_fp', features.atom_fp[0], np.uint8), ('f_kind', features.point_kind, np.int8)]
+    if smiles is not None:
+        parts += [('s_text', smiles.text[0], np.uint8)]
     sizes = [t.numel() * t.element_size() for _, t, _ in parts]
     blob = torch.cat([t.reshape(-1).view(torch.uint8) for _, t, _ in parts]).cpu().numpy()
     cut = np.cumsum([0] + sizes)
@@ -809,6 +936,8 @@ def assemble(results, keys=False, geometry=None, rings=None, kekule=None, featur
         k_counts = v['k_counts'].reshape(-1, len(KEKULE_COUNTS))
     if features is not None:
         f_counts, f_range = v['f_counts'].reshape(-1, len(FEATURE_COUNTS)), v['f_range'].reshape(-1, 2)
+    if smiles is not None:
+        s_counts, s_text = v['s_counts'].reshape(-1, len(SMILES_COUNTS)), v['s_text'].reshape(-1, smiles.capacity)
     mols, n0, h0 = [], 0, 0
     for g, n in enumerate(sc.num_atoms):
         h = n * (n - 1) // 2
@@ -854,6 +983,12 @@ def assemble(results, keys=False, geometry=None, rings=None, kekule=None, featur
                                         point_dist=v['f_dist'][q0:q1].copy(), point_atom=v['f_atom'][q0:q1].copy())
             # (the kernel's own comparison: fp32 distance < fp32 cutoff; a non-finite point has distance +inf)
             mols[-1]['features']['point_matched'] = mols[-1]['features']['point_dist'] < np.float32(features.limits.feat_cut)
+        if smiles is not None:
+            s_ok = (int(v['s_status'][g]) & SMILES_FAIL_MASK) == 0
+            mols[-1]['smiles'] = dict({'status': int(v['s_status'][g]), 'smiles_ok': s_ok,
+                                       'text': s_text[g, :int(v['s_length'][g])].tobytes().decode('ascii') if s_ok else ''},
+                                      **{k: int(x) for k, x in zip(SMILES_COUNTS, s_counts[g])},
+                                      atom_rank=v['s_rank'][n0:n0 + n][keep].copy())
         n0, h0 = n0 + n, h0 + h
     return mols
 
@@ -914,7 +1049,8 @@ def write_sdf(path, mols, names=None):
     status as hex, 'formula', 'mol_weight' with three decimals, then one 'name value' line per count (KEKULE_COUNTS).  A molecule that
     carries 'features' (assemble(features=)) gets `> <PHOREGEN_FEATURES>`: the status as hex, one 'name value' line per count
     (FEATURE_COUNTS), then one line per typed point: its type, the matched atom (1-based; '-' if no atom of the type lies within the
-    cutoff) and the distance to the nearest atom of the type with four decimals ('inf' without one)."""
+    cutoff) and the distance to the nearest atom of the type with four decimals ('inf' without one).  A molecule that carries 'smiles'
+    (assemble(smiles=)) with 'smiles_ok' gets `> <PHOREGEN_SMILES>` with the text on one line; a failed one gets no item."""
     names = names if names is not None else [''] * len(mols)
     if len(names) != len(mols):
         raise ValueError(f'write_sdf: {len(mols)} molecules, {len(names)} names')
@@ -935,6 +1071,8 @@ def write_sdf(path, mols, names=None):
                          + ''.join('%s %d\n' % (k, m['kekule'][_KEKULE_KEYS[k]]) for k in KEKULE_COUNTS) + '\n')
             if 'features' in m:
                 fh.write(_features_item(m['features']))
+            if 'smiles' in m and m['smiles'].get('smiles_ok'):
+                fh.write('> <PHOREGEN_SMILES>\n%s\n\n' % m['smiles']['text'])
             fh.write('$$$$\n')
 
 
@@ -1068,7 +1206,7 @@ def duplicate_groups(keys):
 
 # ---- the top-up loop of sample_all.py:79-84,172 ------------------------------------------------------------------------------
 def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, device='cuda', unique=False, geometry=None,
-                 rings=None, kekule=None, features=None, **sample_kwargs):
+                 rings=None, kekule=None, features=None, smiles=None, **sample_kwargs):
     """Sample until `num_samples` molecules have passed the screen, giving up once more than `max_failed_factor * num_samples` have
     failed (checked before every draw, as the reference does).  Every draw asks for min(batch_size, what is still missing) graphs,
     so never more than `num_samples` are finished.  `sample_kwargs` (fragment=, pos_guidance_opt=, rng=, seed=, ...) go to
@@ -1086,7 +1224,11 @@ def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, d
     features=(point_pos, point_kind, limits), or True to take the pharmacophore of `data` (`features_for`, default limits): a valid
     molecule is finished only if it is also 'features_ok'; one that is not goes to 'failed'.  The molecules then carry 'features'.
     The typing needs the Kekulé form and the rings of the draw: they are computed (with kekule= / rings= if given, else with the
-    defaults) and carried, and filtered on, only if asked for by their own arguments.  All of these share one screen per draw."""
+    defaults) and carried, and filtered on, only if asked for by their own arguments.
+    smiles=True: a valid molecule is finished only if it is also 'smiles_ok' -- it has a Kekulé structure and its text was written;
+    one that is not goes to 'failed'.  The molecules then carry 'smiles'.  The text needs the Kekulé form of the draw: it is computed
+    (with kekule= if given, else with the default options) and carried, as 'kekule', only if asked for by its own argument.
+    All of these share one screen per draw."""
     ring_limits = RingLimits() if rings is True else rings
     if ring_limits is not None and not isinstance(ring_limits, RingLimits):
         raise ValueError(f'phoregen_amd.molecule.sample_valid: rings= must be True or a RingLimits, not {rings!r}')
@@ -1097,6 +1239,8 @@ def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, d
         if not (isinstance(features, tuple) and len(features) == 3 and isinstance(features[2], FeatureLimits)):
             raise ValueError(f'phoregen_amd.molecule.sample_valid: features= must be True or (point_pos, point_kind, FeatureLimits), not '
                              f'{features!r}')
+    if smiles is not None and smiles is not True:
+        raise ValueError(f'phoregen_amd.molecule.sample_valid: smiles= must be True, not {smiles!r}')
     finished, failed, duplicates, n_calls = [], [], [], 0
     by_key = {}                                                        # key -> finished molecules that have it
     while len(finished) < num_samples:
@@ -1124,13 +1268,18 @@ def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, d
                 feat = features_for(data, res, screen=sc, kekule=kek, rings=ring)
             else:
                 feat = _features(res, features[0], features[1], screen=sc, kekule=kek, rings=ring, limits=features[2])
-        mols = assemble(res, keys=unique, **{k: v for k, v in (('geometry', geo), ('rings', ring), ('kekule', kek), ('features', feat))
-                                             if v is not None})
+        smi = None
+        if smiles is not None:
+            sc = next((x.screen for x in (geo, ring, kek, feat) if x is not None), None)
+            smi = _smiles(res, screen=sc, kekule=kek if kek is not None else feat.kekule if feat is not None else None)
+        mols = assemble(res, keys=unique, **{k: v for k, v in (('geometry', geo), ('rings', ring), ('kekule', kek), ('features', feat),
+                                                               ('smiles', smi)) if v is not None})
         for m in mols:
             if (not m['valid'] or (geometry is not None and not m['geom']['geom_ok'])
                     or (ring_limits is not None and not m['rings']['rings_ok'])
                     or (kek_options is not None and not m['kekule']['kekule_ok'])
-                    or (features is not None and not m['features']['features_ok'])):
+                    or (features is not None and not m['features']['features_ok'])
+                    or (smiles is not None and not m['smiles']['smiles_ok'])):
                 failed.append(m)
             elif unique and any(same_molecule(m, other) for other in by_key.setdefault(m['key'], [])):
                 duplicates.append(m)

@@ -24,7 +24,12 @@ written in Kekulé form with charges, and carry formula, weight and counts as th
 --valid_only) also types every atom (HD, AR, PO, HA, HY, NE, XB; phoregen_amd.molecule.features_for) and matches every typed feature
 point of the pharmacophore against the atoms that carry its type, and finishes a molecule only if it has a Kekulé structure to type
 from and no more typed points are unmatched than --feature_limits '{"max_unmatched": 0}' allows (default: any number); the .sdf files
-carry the counts and the per-point matches as the data item PHOREGEN_FEATURES.  Without them nothing changes.
+carry the counts and the per-point matches as the data item PHOREGEN_FEATURES.  --smiles (implies --valid_only) also writes every
+molecule as Kekulé-form OpenSMILES text (phoregen_amd.molecule.smiles; with --no_charged from the neutral-only Kekulé form, as with --kekule) and finishes a molecule only if it
+has a Kekulé structure to write from; <outdir>/{name}_SMILES_all.txt then holds one line per finished molecule, in the order of the
+.sdf files -- the file sample_all.py writes -- and the .sdf files carry the text as the data item PHOREGEN_SMILES.  The text is not
+canonical: a reader's own toolkit canonicalises it.  --num_steps shortens the reverse process (default: the model's).  Without them
+nothing changes.
 """
 import argparse
 import json
@@ -79,21 +84,25 @@ def main():
                          '--feature_limits allows, is not finished')
     ap.add_argument('--feature_limits', type=json.loads, default=None,
                     help='JSON object replacing single limits of FeatureLimits (with --features), e.g. \'{"max_unmatched": 0}\'')
+    ap.add_argument('--smiles', action='store_true',
+                    help='implies --valid_only: a molecule without a Kekulé structure is not finished; writes <outdir>/<name>_SMILES_all.txt')
+    ap.add_argument('--num_steps', type=int, default=None, help='reverse steps of the sampler (default: the model\'s)')
     ap.add_argument('--sdf', action='store_true', help='write one .sdf per molecule under <outdir>/sdf_results/')
     args = ap.parse_args()
     if args.geom_limits is not None and not args.geometry:
         ap.error('--geom_limits needs --geometry')
     if args.ring_limits is not None and not args.rings:
         ap.error('--ring_limits needs --rings')
-    if args.no_charged and not args.kekule:
-        ap.error('--no_charged needs --kekule')
+    if args.no_charged and not (args.kekule or args.smiles):
+        ap.error('--no_charged needs --kekule or --smiles')
     if args.feature_limits is not None and not args.features:
         ap.error('--feature_limits needs --features')
-    args.valid_only = args.valid_only or args.unique or args.geometry or args.rings or args.kekule or args.features
+    args.valid_only = args.valid_only or args.unique or args.geometry or args.rings or args.kekule or args.features or args.smiles
     feature_limits = FeatureLimits(**(args.feature_limits or {})) if args.features else None
     geom_limits = GeomLimits(**(args.geom_limits or {}))
     ring_limits = RingLimits(**(args.ring_limits or {})) if args.rings else None
-    kekule = KekuleOptions(allow_charged=not args.no_charged) if args.kekule else None
+    # (--smiles --no_charged: the text is written from the neutral-only Kekulé form, which the molecules then carry as with --kekule)
+    kekule = KekuleOptions(allow_charged=not args.no_charged) if args.kekule or (args.smiles and args.no_charged) else None
     torch.manual_seed(args.seed)
     cfg = default_model_config()
     if args.config:
@@ -116,6 +125,8 @@ def main():
         done, t0 = [], time.time()
         kw = dict(pos_guidance_opt=args.pos_guidance_opt, sample_mode=args.sample_nodes_mode, normal_scale=args.normal_scale,
                   rng=args.rng, fragment=fragment)
+        if args.num_steps is not None:
+            kw['num_steps'] = args.num_steps
         if args.valid_only:
             # sample_all.py:79-84,172: top up until num_samples molecules have passed
             geometry = None
@@ -127,12 +138,15 @@ def main():
                 ph = data['phore']
                 features = (ph.pos.float() + data.center.float(), point_kinds_of(ph.x, PHORETYPES1), feature_limits)
             out = sample_valid(model, data, args.num_samples, batch_size=args.batch_size, unique=args.unique, geometry=geometry,
-                               rings=ring_limits, kekule=kekule, features=features, **kw)
+                               rings=ring_limits, kekule=kekule, features=features, smiles=True if args.smiles else None, **kw)
             done = out['finished']
             print(f"Finished {len(done)} | Failed {len(out['failed'])}" + (f" | Duplicates {len(out['duplicates'])}" if args.unique else ''))
             if args.unique:
                 with open(os.path.join(args.outdir, data.name + '_keys.txt'), 'w') as fh:
                     fh.writelines('%016x\n' % m['key'] for m in done)
+            if args.smiles:                                            # sample_all.py:157-159
+                with open(os.path.join(args.outdir, data.name + '_SMILES_all.txt'), 'w') as fh:
+                    fh.writelines(m['smiles']['text'] + '\n' for m in done)
         while len(done) < args.num_samples and not args.valid_only:
             n = min(args.batch_size, args.num_samples - len(done))
             res = model.sample(data, n, 'cuda', return_traj=False, **kw)
