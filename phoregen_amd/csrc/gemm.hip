@@ -136,7 +136,7 @@ __global__ __launch_bounds__(256) void gemm_kernel(PgGemm p PG_ABL_PARAM) {
   static_assert(64 * (BN + 4) <= (BM + BN) * LDT, "epilogue tile must fit the staging buffer");
   constexpr int LDC = BN + 4;
   const int l31 = lane & 31, lh = lane >> 5;
-  const bool vec_ok = (p.ldy & 3) == 0 && ((size_t)p.Y & 15) == 0 && (p.N & 3) == 0 &&
+  const bool vec_ok = (p.ldy & 3) == 0 && ((size_t)p.Y & 15) == 0 && (p.N & 3) == 0 && ((size_t)p.bias & 15) == 0 &&
                       (!p.add1 || ((p.ld_add1 & 3) == 0 && ((size_t)p.add1 & 15) == 0)) &&
                       (!p.add2 || ((p.ld_add2 & 3) == 0 && ((size_t)p.add2 & 15) == 0));
 #pragma unroll
@@ -268,6 +268,7 @@ extern "C" int pg_gemm(const PgGemm* p, void* stream) {
   if (!p || !p->X || !p->W || !p->Y || p->M < 0 || p->N <= 0) { pg::set_error("pg_gemm: bad arguments"); return PG_ERR_ARG; }
   if (p->M == 0) return PG_OK;
   if (p->K2 > 0 && !p->X2) { pg::set_error("pg_gemm: K2 > 0 without X2"); return PG_ERR_ARG; }
+  if (p->ln_gamma && !p->ln_beta) { pg::set_error("pg_gemm: ln_gamma without ln_beta"); return PG_ERR_ARG; }
   if (p->ln_gamma && (p->K2 != 0 || p->K1 != 128 || (p->ldx & 3) || ((size_t)p->X & 15))) { pg::set_error("pg_gemm: LayerNorm-on-load needs K1 == 128, K2 == 0, 16-byte aligned rows"); return PG_ERR_ARG; }
   // K = 128 (+ 20) / K = 20 products with a plain epilogue or LayerNorm-on-load: the streaming kernel (LDS-DMA tiles, no vector-ALU
   // work on the memory path; gemm_stream.hip); everything else (row subsets, odd K, two gathered operands): the tiled kernel
