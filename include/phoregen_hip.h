@@ -622,11 +622,78 @@ int pg_mol_feat(const float* pos, int64_t pos_fs, const int8_t* cls, const int8_
 #define PG_SMILES_DISCONNECTED 8     /* informational: more than one component, the text has a '.'             */
 #define PG_SMILES_EMPTY 16           /* informational: no kept atom, the text is empty                         */
 #define PG_SMILES_BRACKET 32         /* informational: at least one bracket atom                               */
+#define PG_SMILES_STEREO_DROPPED 64   /* informational, pg_mol_smiles_stereo: the marks of a group of double bonds contradicted each other and were left out */
 #define PG_SMILES_N_COUNTS 8
+#define PG_SMILES_N_STEREO_COUNTS 4
 int pg_mol_smiles(const int8_t* cls, const int8_t* kekule_order, const uint8_t* hcount, const int8_t* charge,
                   const int* kekule_status /*[F][B]*/, const int* g_lig_off /*[B+1]*/, const int* g_bond_off /*[B+1]*/, int B, int F,
                   int n_lig, int n_bond, int max_n, const uint8_t* valences /*[11][4]*/, int capacity, uint8_t* text, int* length,
                   int16_t* atom_rank, int* counts, int* status, void* stream);
+
+/* Stereo perception of the molecules the screen decoded, one wave per (frame, graph).  Definition: DESIGN.md 2.9 "Stereo".  Reads the
+ * coordinates (pos, pos_fs as pg_mol_geom takes them), the screen's cls [F][n_lig] and order [F][n_bond / 2], pg_mol_kekule's
+ * kekule_order [F][n_bond / 2], hcount, charge [F][n_lig] and status [F][B], pg_mol_rings' ring_size [F][n_bond / 2] and pg_mol_key's
+ * colour [F][n_lig] and key [F][B] (frames dense, the same offsets).  An atom is kept, a pair is a bond and degree is defined as in
+ * pg_mol_rings; colours compare as unsigned 64-bit values; an implicit hydrogen is a ligand that differs from every heavy neighbour
+ * and comes last in every ordering.
+ * Centres: a candidate is an atom of class C, N, Si, P or S with (degree 4, no hydrogen) or (degree 3, one hydrogen); it is stereogenic
+ * if its heavy neighbours have pairwise distinct colours.  With the neighbours n0 < n1 < n2 (< n3) in local index order, u_k the fp32
+ * unit vector from the centre to n_k, and u3 = -(u0 + u1 + u2), not normalised, for the hydrogen: V = (u0 - u3) . ((u1 - u3) x (u2 - u3)).
+ * Double bonds: a candidate is a pair a < b with Kekulé order 2, order != 4 and ring_size 0 whose ends each have no other bond of
+ * Kekulé order >= 2 and either degree 3 or (degree 2 and at most one hydrogen); it is stereogenic if the two substituents (the
+ * neighbours other than the partner) of every degree-3 end differ in colour.  With e = p_b - p_a, r_x the lowest-index substituent of
+ * end x, d_x = p_r - p_x and w_x = d_x - e (d_x . e) / (e . e): t = (w_a . w_b) / (|d_a| |d_b|).
+ *   atom_parity [F][n_lig]: 0 not stereogenic (or dropped); +1 / -1 the sign of V if |V| >= vol_min; 2 stereogenic but undefined:
+ *     |V| < vol_min, a zero-length vector or a non-finite coordinate
+ *   atom_label [F][n_lig]: atom_parity x the sign of the permutation that sorts the index-ordered ligands by ascending colour; 2 and 0
+ *     stay.  It does not depend on the numbering of the atoms and flips under reflection.
+ *   bond_stereo [F][n_bond / 2] (aligned with order): 0 not stereogenic (or no such bond); +1 cis, t >= planar_min; -1 trans,
+ *     t <= -planar_min; 2 undefined
+ *   bond_label [F][n_bond / 2]: bond_stereo, negated once for every end whose largest-colour substituent is not its lowest-index one
+ *     (so for an end with one heavy substituent and a hydrogen); 2 and 0 stay
+ *   stereo_key [F][B]: key if no element has label +1 or -1, else mix(key ^ mix(sum over such centres c of mix(colour[c] ^ (label > 0
+ *     ? A : B)) + sum over such bonds of mix((mix(colour[a]) + mix(colour[b])) ^ (label > 0 ? C : D)))), wrapping sums, mix as in
+ *     pg_mol_key, A .. D = 0x243F6A8885A308D3, 0x13198A2E03707344, 0xA4093822299F31D0, 0x082EFA98EC4E6C89
+ *   counts [F][B][PG_STEREO_N_COUNTS]: centres 0 candidate, 1 stereogenic, 2 defined, 3 undefined; bonds 4 .. 7 likewise
+ *   status [F][B]: PG_STEREO_* bits.  With NO_KEKULE every other output of the graph is 0 and stereo_key = key.
+ * vol_min, planar_min: finite and above 0; max_undefined >= 0.  Perception is integer work on the colours and exact; the two
+ * thresholds are compared in fp32.  A graph's rows do not depend on its batch.  max_n above PG_MOL_MAX_ATOMS, a negative size, a
+ * threshold outside its range or (with B, F > 0) a null array: error before anything is launched, outputs untouched.  Every element
+ * of every output is written (nothing needs zeroing). */
+#define PG_STEREO_NO_KEKULE 1        /* the graph's Kekulé status has PG_KEKULE_FAILED: nothing to perceive from */
+#define PG_STEREO_UNDEFINED 2        /* more than max_undefined stereogenic elements whose geometry does not decide */
+#define PG_STEREO_HAS_CENTRE 4       /* informational: at least one centre with parity +1 or -1                */
+#define PG_STEREO_HAS_BOND 8         /* informational: at least one double bond that is cis or trans           */
+#define PG_STEREO_NONFINITE 16       /* a kept atom with a non-finite coordinate                               */
+#define PG_STEREO_N_COUNTS 8
+int pg_mol_stereo(const float* pos, int64_t pos_fs, const int8_t* cls, const int8_t* order, const int8_t* kekule_order,
+                  const uint8_t* hcount, const int8_t* charge, const int* kekule_status /*[F][B]*/, const uint8_t* ring_size,
+                  const int64_t* colour, const int64_t* key /*[F][B]*/, const int* g_lig_off /*[B+1]*/, const int* g_bond_off /*[B+1]*/,
+                  int B, int F, int n_lig, int n_bond, int max_n, float vol_min, float planar_min, int max_undefined, int8_t* atom_parity,
+                  int8_t* atom_label, int8_t* bond_stereo, int8_t* bond_label, int64_t* stereo_key, int* counts, int* status, void* stream);
+
+/* pg_mol_smiles with the stereo of pg_mol_stereo in the text (isomeric SMILES).  Definition: DESIGN.md 2.9 "Stereo".  The arguments of
+ * pg_mol_smiles and their meaning, traversal, labels, capacity, status bits and atom_rank included, plus atom_parity [F][n_lig] and
+ * bond_stereo [F][n_bond / 2] (only the values +1 and -1 are read as stereo; with none of them the text is pg_mol_smiles's byte for byte).
+ * Centres: an atom with parity +1 or -1 and (four bonds, no hydrogen) or (three bonds, one hydrogen) is a bracket atom '[', symbol, '@'
+ * or '@@', 'H' with a hydrogen, '+' with a charge, ']'.  Its ligands stand in the text as: the parent, the hydrogen, the closures that
+ * close at it by ascending ancestor, those that open at it by ascending descendant, the children ascending; '@' iff parity x the sign
+ * of the permutation from index order (hydrogen last) to that order is +1 (parity +1: seen from the first ligand in index order the
+ * others run counter-clockwise).  Double bonds: a pair with stereo +1 or -1 and Kekulé order 2 whose ends each have, besides the
+ * partner, one or two neighbours, all joined by single bonds.  Every such single bond carries a mark, '/' = +1 or '\' = -1, written
+ * where its bond symbol would stand (before the child, or before the opening label) and read from the atom written first to the atom
+ * written later.  side(x, r) = the mark if x is written before r, else its opposite; the two substituents of an end have opposite
+ * sides, and side(a, r_a) side(b, r_b) = bond_stereo for the lowest-index substituents.  Of the marked bonds joined by these rules
+ * the one that comes first in the text is '/'.  If the rules contradict each other (never with pg_mol_stereo's output, whose stereo
+ * double bonds are bridges) the marks of that group are left out and PG_SMILES_STEREO_DROPPED is set.
+ *   stereo_counts [F][B][PG_SMILES_N_STEREO_COUNTS]: 0 centres written, 1 of them '@@', 2 marked bonds, 3 double bonds expressed; on a
+ *     failing graph as counts
+ * Errors as pg_mol_smiles; the three further arrays may not be null either. */
+int pg_mol_smiles_stereo(const int8_t* cls, const int8_t* kekule_order, const uint8_t* hcount, const int8_t* charge,
+                         const int* kekule_status /*[F][B]*/, const int8_t* atom_parity, const int8_t* bond_stereo,
+                         const int* g_lig_off /*[B+1]*/, const int* g_bond_off /*[B+1]*/, int B, int F, int n_lig, int n_bond, int max_n,
+                         const uint8_t* valences /*[11][4]*/, int capacity, uint8_t* text, int* length, int16_t* atom_rank, int* counts,
+                         int* status, int* stereo_counts, void* stream);
 
 #ifdef __cplusplus
 }

@@ -161,6 +161,10 @@ _PROTOS = {
                               c_ip, C.c_void_p]),
     'pg_mol_smiles': (C.c_int, [c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_ip, C.c_int, c_ip,
                                 c_ip, c_ip, c_ip, c_ip, C.c_void_p]),
+    'pg_mol_stereo': (C.c_int, [c_fp, C.c_int64, c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, C.c_int, C.c_int, C.c_int,
+                                C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, C.c_void_p]),
+    'pg_mol_smiles_stereo': (C.c_int, [c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_ip,
+                                       C.c_int, c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, C.c_void_p]),
 }
 
 EXPORTS = tuple(_PROTOS)

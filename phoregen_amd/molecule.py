@@ -9,7 +9,8 @@ that samples until enough molecules have passed.  No RDKit, no OpenBabel: `valid
 Identity: `molecule_keys` gives every decoded molecule a 64-bit key that does not depend on the numbering of its atoms
 (csrc/mol_key.hip; the definition is in DESIGN.md 2.9 "Identity"), `same_molecule` decides exactly whether two assembled molecules
 have the same atoms and bonds, `unique_molecules` / `duplicate_groups` / `sample_valid(unique=True)` use the two.  Equal keys are
-necessary, not sufficient, for equal molecules; this is not SMILES.
+necessary, not sufficient, for equal molecules; this is not SMILES.  The key is constitution only: two enantiomers, or a cis and a
+trans isomer, share it; `stereo`'s `stereo_key` and the `stereo=True` forms of these functions tell them apart.
 
 Geometry: `geometry` / `geometry_for` measure the decoded molecules where they lie (csrc/mol_geom.hip; DESIGN.md 2.9 "Geometry"):
 bond lengths, non-bonded clashes, clearance from the exclusion spheres, which feature points have an atom nearby, and the reference's
@@ -35,7 +36,14 @@ SMILES: `smiles` writes every decoded molecule as Kekulé-form OpenSMILES text o
 "SMILES"): a depth-first walk in atom order, ring-closure labels 1..99, bracket atoms where the bare symbol would not read back with
 the atom's hydrogens and charge.  `Smiles.strings`, `assemble(smiles=)`, `sample_valid(smiles=)` and `write_sdf` carry it.  The text
 reads back to exactly the molecule `assemble` returns; it is not canonical (identity stays with the keys), has no aromatic lower-case
-form and no stereo, and is not checked against RDKit."""
+form, and is not checked against RDKit.  Without `stereo=` it has no stereo.
+
+Stereo: `stereo` reads from the coordinates which way round every tetrahedral centre is and whether every double bond outside a ring is
+cis or trans (csrc/mol_stereo.hip; DESIGN.md 2.9 "Stereo"), gives each a label that does not depend on the numbering of the atoms, and
+a `stereo_key` that tells stereoisomers apart where the identity key cannot.  `smiles(stereo=)` writes them into the text ('@', '@@',
+'/', '\\': isomeric SMILES, csrc/mol_smiles.hip); `assemble(stereo=)`, `same_molecule(stereo=True)`, `unique_molecules(stereo=True)`,
+`sample_valid(stereo=)` and `write_sdf` carry them.  No CIP names (R / S, E / Z), no pseudo-asymmetric centres, no ring double bonds,
+allenes or atropisomers, no three-coordinate N, P or S; the two thresholds are design choices, not calibrated."""
 import ctypes
 from dataclasses import astuple, dataclass
 
@@ -154,7 +162,27 @@ SMILES_NAMES = {SMILES_NO_KEKULE: 'NO_KEKULE', SMILES_RING_LABELS: 'RING_LABELS'
 SMILES_COUNTS = ('length', 'atoms', 'bonds', 'components', 'ring_closures', 'branches', 'max_label', 'bracket_atoms')
 SMILES_VALENCES = {5: (3,), 6: (4,), 7: (3, 5), 8: (2,), 9: (1,), 14: (), 15: (3, 5), 16: (2, 4, 6), 17: (1,), 35: (1,), 53: (1,)}
 SMILES_MAX_LABEL = 99
+# pg_mol_smiles_stereo only (kept out of SMILES_NAMES / SMILES_COUNTS, which describe pg_mol_smiles)
+SMILES_STEREO_DROPPED = 64       # informational: the marks of a group of double bonds contradicted each other and were left out
+SMILES_STEREO_COUNTS = ('centres', 'centres_clockwise', 'marked_bonds', 'double_bonds')
 assert list(SMILES_VALENCES) == ATOM_TYPES
+
+# The stereo perception (DESIGN.md 2.9 "Stereo"): status bits, the names of the count columns in the kernel's order, the value of an
+# element that is stereogenic but whose geometry does not decide, and the four words of the stereo key
+STEREO_NO_KEKULE = 1             # the graph's Kekulé status has KEKULE_FAILED: nothing to perceive from
+STEREO_UNDEFINED = 2             # more than max_undefined stereogenic elements whose geometry does not decide
+STEREO_HAS_CENTRE = 4            # informational: at least one centre with parity +1 or -1
+STEREO_HAS_BOND = 8              # informational: at least one double bond that is cis or trans
+STEREO_NONFINITE = 16            # a kept atom with a non-finite coordinate
+STEREO_FAIL_MASK = STEREO_NO_KEKULE | STEREO_UNDEFINED | STEREO_NONFINITE
+STEREO_NAMES = {STEREO_NO_KEKULE: 'NO_KEKULE', STEREO_UNDEFINED: 'UNDEFINED', STEREO_HAS_CENTRE: 'HAS_CENTRE', STEREO_HAS_BOND: 'HAS_BOND',
+                STEREO_NONFINITE: 'NONFINITE'}
+STEREO_COUNTS = ('centre_candidates', 'centres_stereogenic', 'centres_defined', 'centres_undefined', 'bond_candidates',
+                 'bonds_stereogenic', 'bonds_defined', 'bonds_undefined')
+STEREO_UNDEFINED_VALUE = 2
+STEREO_CENTRE_CLASSES = (6, 7, 14, 15, 16)       # atomic numbers of the elements that can be centres
+STEREO_KEY_A, STEREO_KEY_B = 0x243F6A8885A308D3, 0x13198A2E03707344      # a centre with label +1 / -1
+STEREO_KEY_C, STEREO_KEY_D = 0xA4093822299F31D0, 0x082EFA98EC4E6C89      # a double bond with label +1 / -1
 
 # Standard atomic weights for 'mol_weight' (written from memory, abridged values)
 ATOMIC_WEIGHT = {1: 1.008, 5: 10.81, 6: 12.011, 7: 14.007, 8: 15.999, 9: 18.998, 14: 28.085, 15: 30.974, 16: 32.06, 17: 35.45,
@@ -215,6 +243,28 @@ class GeomLimits:
     clash_min: float = 1.2
     ex_clear: float = 3.0
     feat_cut: float = 2.0
+
+
+@dataclass(frozen=True)
+class StereoLimits:
+    """Thresholds of the stereo perception.  vol_min: a centre is defined iff |V| >= vol_min, V the signed volume of its four unit
+    ligand vectors (an ideal tetrahedron has |V| = 3.08, a planar atom 0); planar_min: a double bond is cis / trans iff |t| >=
+    planar_min, t the normalised product of its two substituents' components across the bond (ideal sp2: 0.75, perpendicular: 0);
+    max_undefined: STEREO_UNDEFINED is set when more stereogenic elements than this are undefined.  The two thresholds are design
+    choices, about a sixth and a third of the ideal values; they are NOT calibrated on sampled molecules.  This is their only copy:
+    the kernel and the tests' restatement are handed them."""
+    vol_min: float = 0.5
+    planar_min: float = 0.25
+    max_undefined: int = 2 ** 31 - 1
+
+    def __post_init__(self):
+        for k in ('vol_min', 'planar_min'):
+            x = getattr(self, k)
+            if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or not np.isfinite(x) or x <= 0:
+                raise ValueError(f'StereoLimits: {k} must be a finite number > 0, not {x!r}')
+        m = self.max_undefined
+        if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not 0 <= m <= 0x7fffffff:
+            raise ValueError(f'StereoLimits: max_undefined must be an integer in 0 .. 2**31 - 1, not {m!r}')
 
 
 _max_valence2 = {}               # device -> uint8 [11], twice MAX_VALENCE in class order
@@ -573,7 +623,8 @@ def kekulize(results, frames='final', screen=None, options=KekuleOptions()):
     test is applied, an aromatic bond on a chain takes part like any other.  A `Screen` of the same result and frames is reused if
     handed in.  No host read beyond the screen's.  Exact: feasibility and the number of double bonds do not depend on the numbering
     of the atoms; WHICH Kekulé structure is returned does, so this is no canonical form and nothing to build a key from.  `hydrogens -
-    charge` is the same for every structure.  No stereo, tautomers, anions, O+; not checked against RDKit."""
+    charge` is the same for every structure.  No tautomers, anions, O+; stereo is read afterwards, from the coordinates (`stereo`);
+    not checked against RDKit."""
     node, _, edge, F, _ = _frames(results, frames)
     dev = node.device
     _need_cuda('kekulize', 'the Kekulé assignment', dev)
@@ -732,6 +783,96 @@ def _launch_feat(lib, pos, pos_fs, sc, kek, rg, B, F, max_n, point_pos, point_ki
 
 
 @dataclass
+class Stereo:
+    """Device tensors of one `stereo` call; F frames, B graphs, N atom rows, H pair rows (as the screen's `order`).  Values: 0 = not
+    stereogenic, +1 / -1, 2 = stereogenic but undefined."""
+    status: torch.Tensor         # int32 [F, B]     STEREO_* bits
+    counts: torch.Tensor         # int32 [F, B, 8]  STEREO_COUNTS
+    ok: torch.Tensor             # bool  [F, B]     no bit of STEREO_FAIL_MASK
+    atom_parity: torch.Tensor    # int8  [F, N]     sign of the centre's signed volume with its neighbours in index order
+    atom_label: torch.Tensor     # int8  [F, N]     the parity with the neighbours in colour order: independent of the numbering
+    bond_stereo: torch.Tensor    # int8  [F, H]     +1 cis / -1 trans of the lowest-index substituents of the pair's double bond
+    bond_label: torch.Tensor     # int8  [F, H]     the same of the largest-colour substituents: independent of the numbering
+    stereo_key: torch.Tensor     # int64 [F, B]     the identity key with the defined labels mixed in (the key itself without any)
+    limits: StereoLimits
+    screen: Screen               # the screen it was computed from
+    kekule: Kekule               # the Kekulé form, the rings and the keys it was computed from
+    rings: Rings
+    keys: MolKeys
+
+
+@torch.no_grad()
+def stereo(results, frames='final', screen=None, kekule=None, rings=None, keys=None, limits=StereoLimits()):
+    """Stereo perception of every decoded (frame, graph) of a `sample` / `sample_batch` result from its coordinates, on the device,
+    in one launch (pg_mol_stereo; DESIGN.md 2.9 "Stereo").  Centres: C, N, Si, P, S with four heavy neighbours, or three and one
+    hydrogen, whose heavy neighbours all differ in colour (`molecule_keys`); the parity is the sign of the signed volume of the unit
+    vectors to the neighbours in index order (the hydrogen opposite the other three), if it reaches limits.vol_min.  Double bonds:
+    Kekulé order 2, not aromatic, in no ring, neither end with another multiple bond, every end with two substituents of different
+    colour or with one and at most one hydrogen; cis / trans of the lowest-index substituents, if the planarity measure reaches
+    limits.planar_min.  The labels restate both relative to the colours, so they -- and `stereo_key` -- do not depend on the numbering
+    of the atoms as far as atoms with equal colours are in fact equivalent (the identity key's own stance); a reflection flips every
+    atom label, leaves the bond labels and changes the key of a chiral molecule but not of a meso one.  Whichever of `screen`,
+    `kekule`, `rings` and `keys` (a `MolKeys`) is not handed in is computed; all must come from one screen.  No host read beyond the
+    screen's.  `ok` fails without a Kekulé structure, with a non-finite coordinate, or with more than limits.max_undefined undefined
+    elements.  No R / S or E / Z names, no pseudo-asymmetric centres, no ring double bonds, allenes or atropisomers; three-coordinate
+    N, P and S are never centres; the thresholds are design choices, not calibrated; not checked against RDKit."""
+    node, pos, edge, F, (_, _, pos_fs) = _frames(results, frames)
+    dev = pos.device
+    _need_cuda('stereo', 'the stereo perception', dev)
+    if not isinstance(limits, StereoLimits):
+        raise ValueError(f'phoregen_amd.molecule.stereo: limits must be a StereoLimits, not {limits!r}')
+    given = [(what, x.screen) for what, x in (('kekule', kekule), ('rings', rings)) if x is not None]
+    sc = _screen_of('stereo', screen if screen is not None or not given else given[0][1], results, frames, F, pos.size(-2), edge.size(-2), dev)
+    for what, other in given:
+        if not _same_screen(sc, other):
+            raise ValueError(f'phoregen_amd.molecule.stereo: screen= and {what}= were computed from screens of different results')
+    if keys is not None and (keys.key.shape != sc.status.shape or keys.colour.shape != sc.cls.shape or keys.key.device != dev):
+        raise ValueError('phoregen_amd.molecule.stereo: screen= and keys= were computed from screens of different results')
+    _check_rows('stereo', pos, F, 3, 'coordinates', dev)
+    kek = kekule if kekule is not None else _kekulize(results, frames, screen=sc)
+    rg = rings if rings is not None else _rings(results, frames, screen=sc)
+    mk = keys if keys is not None else molecule_keys(sc)
+    B, N = len(sc.num_atoms), pos.size(-2)
+    with torch.cuda.device(dev):
+        lib = hip.lib()
+        out = dict(status=torch.empty(F, B, dtype=torch.int32, device=dev),
+                   counts=torch.empty(F, B, len(STEREO_COUNTS), dtype=torch.int32, device=dev),
+                   atom_parity=torch.empty(F, N, dtype=torch.int8, device=dev), atom_label=torch.empty(F, N, dtype=torch.int8, device=dev),
+                   bond_stereo=torch.empty(F, sc.order.size(1), dtype=torch.int8, device=dev),
+                   bond_label=torch.empty(F, sc.order.size(1), dtype=torch.int8, device=dev),
+                   stereo_key=torch.empty(F, B, dtype=torch.int64, device=dev))
+        _launch_stereo(lib, pos, pos_fs, sc, kek, rg, mk, B, F, max(sc.num_atoms, default=0), limits, out)
+    return Stereo(ok=(out['status'] & STEREO_FAIL_MASK) == 0, limits=limits, screen=sc, kekule=kek, rings=rg, keys=mk, **out)
+
+
+def _launch_stereo(lib, pos, pos_fs, sc, kek, rg, mk, B, F, max_n, limits, out):
+    """pg_mol_stereo on the current stream; sc, kek, rg, mk: anything with the `Screen`, `Kekule`, `Rings` and `MolKeys` fields the kernel
+    reads.  A graph above MAX_ATOMS is the library's error: nothing is launched and `out` is not written."""
+    cls, order = sc.cls, sc.order
+    _check_arrays('stereo', pos.device, [
+        (cls, torch.int8), (order, torch.int8), (kek.kekule_order, torch.int8), (kek.hcount, torch.uint8), (kek.charge, torch.int8),
+        (kek.status, torch.int32), (rg.ring_size, torch.uint8), (mk.colour, torch.int64), (mk.key, torch.int64), (sc.lig_off, torch.int32),
+        (sc.bond_off, torch.int32), (out['atom_parity'], torch.int8), (out['atom_label'], torch.int8), (out['bond_stereo'], torch.int8),
+        (out['bond_label'], torch.int8), (out['stereo_key'], torch.int64), (out['counts'], torch.int32), (out['status'], torch.int32)])
+    if (sc.lig_off.numel() != B + 1 or sc.bond_off.numel() != B + 1 or cls.numel() != F * cls.size(-1) or order.numel() != F * order.size(-1)
+            or pos.size(-2) != cls.size(-1) or pos.dtype != torch.float32 or pos.device != cls.device
+            or kek.hcount.shape != cls.shape or kek.charge.shape != cls.shape or kek.kekule_order.shape != order.shape
+            or rg.ring_size.shape != order.shape or kek.status.numel() != F * B or mk.colour.shape != cls.shape or mk.key.numel() != F * B
+            or out['atom_parity'].shape != cls.shape or out['atom_label'].shape != cls.shape or out['bond_stereo'].shape != order.shape
+            or out['bond_label'].shape != order.shape or out['stereo_key'].numel() != F * B or out['status'].numel() != F * B
+            or out['counts'].numel() != len(STEREO_COUNTS) * F * B):
+        raise ValueError('phoregen_amd.molecule.stereo: sizes of the offsets, screen / Kekulé / ring / key arrays and outputs do not fit '
+                         f'{F} frames x {B} graphs, {cls.size(-1)} atom rows, {order.size(-1)} pair rows')
+    hip.check(lib.pg_mol_stereo(pos.data_ptr(), pos_fs, cls.data_ptr(), order.data_ptr(), kek.kekule_order.data_ptr(), kek.hcount.data_ptr(),
+                                kek.charge.data_ptr(), kek.status.data_ptr(), rg.ring_size.data_ptr(), mk.colour.data_ptr(),
+                                mk.key.data_ptr(), sc.lig_off.data_ptr(), sc.bond_off.data_ptr(), B, F, cls.size(-1), 2 * order.size(-1),
+                                max_n, float(limits.vol_min), float(limits.planar_min), int(limits.max_undefined),
+                                out['atom_parity'].data_ptr(), out['atom_label'].data_ptr(), out['bond_stereo'].data_ptr(),
+                                out['bond_label'].data_ptr(), out['stereo_key'].data_ptr(), out['counts'].data_ptr(),
+                                out['status'].data_ptr(), hip.stream_ptr()), 'pg_mol_stereo')
+
+
+@dataclass
 class Smiles:
     """Device tensors of one `smiles` call; F frames, B graphs, N atom rows."""
     status: torch.Tensor         # int32 [F, B]     SMILES_* bits
@@ -743,6 +884,8 @@ class Smiles:
     capacity: int
     screen: Screen               # the screen it was written from
     kekule: Kekule               # the Kekulé form it was written from
+    stereo_counts: torch.Tensor = None   # int32 [F, B, 4]  SMILES_STEREO_COUNTS; None unless written with stereo=
+    stereo: Stereo = None        # the stereo it was written with
 
     def strings(self, frame=0):
         """The texts of one frame as a list of str, one per graph ('' where not ok), from one device-to-host copy."""
@@ -753,7 +896,7 @@ class Smiles:
 
 
 @torch.no_grad()
-def smiles(results, frames='final', screen=None, kekule=None, capacity=None):
+def smiles(results, frames='final', screen=None, kekule=None, capacity=None, stereo=None):
     """SMILES text of every decoded (frame, graph) of a `sample` / `sample_batch` result, on the device, in one launch (pg_mol_smiles;
     DESIGN.md 2.9 "SMILES"): Kekulé-form OpenSMILES of the kept atoms with the Kekulé form's bond orders, hydrogens and charges --
     depth-first from the lowest atom not yet written, neighbours ascending, ring-closure labels 1..99, '=' and '#', bracket atoms
@@ -763,17 +906,25 @@ def smiles(results, frames='final', screen=None, kekule=None, capacity=None):
     the screen's.  `ok` fails for a graph without a Kekulé structure, with more than 99 labels in use at once or with too long a
     text.  The text reads back to exactly the molecule `assemble` returns (`atom_rank`: where each atom stands in it); it is NOT
     canonical -- the numbering of the atoms and the choice of Kekulé structure both change it, identity stays with `molecule_keys` --
-    and has no aromatic lower-case form, no stereo, no anions; not checked against RDKit."""
+    and has no aromatic lower-case form, no anions; not checked against RDKit.
+    stereo=a `Stereo` of the same screen: the text is isomeric (pg_mol_smiles_stereo; DESIGN.md 2.9 "Stereo") -- a centre with parity
+    +1 / -1 is a bracket atom with '@' or '@@', the single bonds next to a cis / trans double bond are '/' or '\\'; undefined
+    elements are written without a mark.  The Kekulé form is the stereo's unless one is handed in; capacity None = 12 * max(largest
+    graph, 8); `stereo_counts` holds SMILES_STEREO_COUNTS.  Without stereo= the text has no stereo and `stereo_counts` is None; with
+    a `Stereo` that has no +1 / -1 the text is the same byte for byte."""
     node, _, edge, F, _ = _frames(results, frames)
     dev = node.device
     _need_cuda('smiles', 'the SMILES writer', dev)
-    sc = _screen_of('smiles', screen if screen is not None or kekule is None else kekule.screen, results, frames, F, node.size(-2),
-                    edge.size(-2), dev)
-    if kekule is not None and not _same_screen(sc, kekule.screen):
-        raise ValueError('phoregen_amd.molecule.smiles: screen= and kekule= were computed from screens of different results')
-    kek = kekule if kekule is not None else _kekulize(results, frames, screen=sc)
+    if stereo is not None and not isinstance(stereo, Stereo):
+        raise ValueError(f'phoregen_amd.molecule.smiles: stereo= must be a Stereo, not {stereo!r}')
+    first = next((x.screen for x in (kekule, stereo) if x is not None), None)
+    sc = _screen_of('smiles', screen if screen is not None or first is None else first, results, frames, F, node.size(-2), edge.size(-2), dev)
+    for what, x in (('kekule', kekule), ('stereo', stereo)):
+        if x is not None and not _same_screen(sc, x.screen):
+            raise ValueError(f'phoregen_amd.molecule.smiles: screen= and {what}= were computed from screens of different results')
+    kek = kekule if kekule is not None else stereo.kekule if stereo is not None else _kekulize(results, frames, screen=sc)
     B, N, max_n = len(sc.num_atoms), node.size(-2), max(sc.num_atoms, default=0)
-    cap = 8 * max(max_n, 8) if capacity is None else capacity
+    cap = (8 if stereo is None else 12) * max(max_n, 8) if capacity is None else capacity
     if isinstance(cap, bool) or not isinstance(cap, (int, np.integer)) or not 1 <= cap <= 0x7fffffff:
         raise ValueError(f'phoregen_amd.molecule.smiles: capacity must be an integer in 1 .. 2**31 - 1, not {capacity!r}')
     with torch.cuda.device(dev):
@@ -782,12 +933,15 @@ def smiles(results, frames='final', screen=None, kekule=None, capacity=None):
                    counts=torch.empty(F, B, len(SMILES_COUNTS), dtype=torch.int32, device=dev),
                    text=torch.empty(F, B, int(cap), dtype=torch.uint8, device=dev), length=torch.empty(F, B, dtype=torch.int32, device=dev),
                    atom_rank=torch.empty(F, N, dtype=torch.int16, device=dev))
-        _launch_smiles(lib, sc, kek, B, F, max_n, _smiles_table(dev), int(cap), out)
-    return Smiles(ok=(out['status'] & SMILES_FAIL_MASK) == 0, capacity=int(cap), screen=sc, kekule=kek, **out)
+        if stereo is not None:
+            out['stereo_counts'] = torch.empty(F, B, len(SMILES_STEREO_COUNTS), dtype=torch.int32, device=dev)
+        _launch_smiles(lib, sc, kek, B, F, max_n, _smiles_table(dev), int(cap), out, stereo)
+    return Smiles(ok=(out['status'] & SMILES_FAIL_MASK) == 0, capacity=int(cap), screen=sc, kekule=kek, stereo=stereo, **out)
 
 
-def _launch_smiles(lib, sc, kek, B, F, max_n, table, capacity, out):
-    """pg_mol_smiles on the current stream; sc, kek: anything with the `Screen` and `Kekule` fields the kernel reads; table =
+def _launch_smiles(lib, sc, kek, B, F, max_n, table, capacity, out, st=None):
+    """pg_mol_smiles -- with st, anything with the `Stereo` fields atom_parity and bond_stereo, pg_mol_smiles_stereo, and `out` then
+    has 'stereo_counts' -- on the current stream; sc, kek: anything with the `Screen` and `Kekule` fields the kernel reads; table =
     SMILES_VALENCES [11, 4] as uint8 on the device.  A graph above MAX_ATOMS is the library's error: nothing is launched and `out` is
     not written."""
     cls, order = sc.cls, kek.kekule_order
@@ -802,6 +956,19 @@ def _launch_smiles(lib, sc, kek, B, F, max_n, table, capacity, out):
             or out['counts'].numel() != len(SMILES_COUNTS) * F * B):
         raise ValueError(f'phoregen_amd.molecule.smiles: sizes of the offsets, screen / Kekulé arrays, table and outputs do not fit {F} '
                          f'frames x {B} graphs, {cls.size(-1)} atom rows, {order.size(-1)} pair rows, capacity {capacity}')
+    if st is not None:
+        _check_arrays('smiles', cls.device, [(st.atom_parity, torch.int8), (st.bond_stereo, torch.int8), (out['stereo_counts'], torch.int32)])
+        if (st.atom_parity.shape != cls.shape or st.bond_stereo.shape != order.shape
+                or out['stereo_counts'].numel() != len(SMILES_STEREO_COUNTS) * F * B):
+            raise ValueError(f'phoregen_amd.molecule.smiles: sizes of the stereo arrays do not fit {F} frames x {B} graphs, {cls.size(-1)} '
+                             f'atom rows, {order.size(-1)} pair rows')
+        hip.check(lib.pg_mol_smiles_stereo(cls.data_ptr(), order.data_ptr(), kek.hcount.data_ptr(), kek.charge.data_ptr(),
+                                           kek.status.data_ptr(), st.atom_parity.data_ptr(), st.bond_stereo.data_ptr(),
+                                           sc.lig_off.data_ptr(), sc.bond_off.data_ptr(), B, F, cls.size(-1), 2 * order.size(-1), max_n,
+                                           table.data_ptr(), capacity, out['text'].data_ptr(), out['length'].data_ptr(),
+                                           out['atom_rank'].data_ptr(), out['counts'].data_ptr(), out['status'].data_ptr(),
+                                           out['stereo_counts'].data_ptr(), hip.stream_ptr()), 'pg_mol_smiles_stereo')
+        return
     hip.check(lib.pg_mol_smiles(cls.data_ptr(), order.data_ptr(), kek.hcount.data_ptr(), kek.charge.data_ptr(), kek.status.data_ptr(),
                                 sc.lig_off.data_ptr(), sc.bond_off.data_ptr(), B, F, cls.size(-1), 2 * order.size(-1), max_n,
                                 table.data_ptr(), capacity, out['text'].data_ptr(), out['length'].data_ptr(),
@@ -833,6 +1000,7 @@ _rings = rings                   # (and a `rings=` argument)
 _kekulize = kekulize
 _features = features
 _smiles = smiles
+_stereo = stereo
 _PAIRS = {}
 
 
@@ -846,7 +1014,7 @@ def _pairs(n):
 
 
 @torch.no_grad()
-def assemble(results, keys=False, geometry=None, rings=None, kekule=None, features=None, smiles=None):
+def assemble(results, keys=False, geometry=None, rings=None, kekule=None, features=None, smiles=None, stereo=None):
     """The final prediction as one dict per graph with `decode_data`'s keys and meaning -- 'element' (atomic numbers), 'atom_pos'
     (kept atoms, the tensor's own fp32 values), 'bond_index' [2, n_b] (indices among the kept atoms) and 'bond_type' [n_b] for
     a < b only, in row order -- plus 'status', 'valid', 'n_components' and 'valence' (per kept atom, halves allowed).  The screen runs
@@ -873,10 +1041,15 @@ def assemble(results, keys=False, geometry=None, rings=None, kekule=None, featur
     smiles=a `Smiles` of this result's final frame: every dict also has 'smiles' -- 'status' (SMILES_* bits), 'smiles_ok' (no bit of
     SMILES_FAIL_MASK), 'text' (str; '' where not ok), the eight SMILES_COUNTS by name and 'atom_rank' (per kept atom: its position in
     the text, -1 where not ok) -- in the same copy; its screen is reused, and it must have been computed from the screen of the
-    others."""
+    others.  A `Smiles` written with stereo= also has the four SMILES_STEREO_COUNTS by name there.
+    stereo=a `Stereo` of this result's final frame: every dict also has 'stereo' -- 'status' (STEREO_* bits), 'stereo_ok' (no bit of
+    STEREO_FAIL_MASK), the eight STEREO_COUNTS by name, 'atom_parity' and 'atom_label' (int8 per kept atom), 'bond_stereo' and
+    'bond_label' (int8 per entry of 'bond_type', in its order; all four: 0 = not stereogenic, +1 / -1, 2 = undefined) and
+    'stereo_key' (an unsigned Python int) -- in the same copy; its screen is reused, and it must have been computed from the screen of
+    the others."""
     geom, pos_t = geometry, results['pred'][1]
-    given = [(what, x) for what, x in (('geometry', geom), ('rings', rings), ('kekule', kekule), ('features', features), ('smiles', smiles))
-             if x is not None]
+    given = [(what, x) for what, x in (('geometry', geom), ('rings', rings), ('kekule', kekule), ('features', features), ('smiles', smiles),
+                                       ('stereo', stereo)) if x is not None]
     for what, x in given:
         if x.status.size(0) != 1 or x.screen.cls.size(1) != pos_t.size(-2) or x.status.device != pos_t.device:
             raise ValueError(f'phoregen_amd.molecule.assemble: {what}= must be a {what.capitalize()} of the final frame of this result')
@@ -889,12 +1062,18 @@ def assemble(results, keys=False, geometry=None, rings=None, kekule=None, featur
     if keys:
         mk = molecule_keys(sc)
         parts += [('key', mk.key[0], np.uint64), ('colour', mk.colour[0], np.uint64)]
+    if stereo is not None:
+        parts += [('t_key', stereo.stereo_key[0], np.uint64)]
     if rings is not None:
         parts += [('r_status', rings.status[0], np.int32), ('r_counts', rings.counts[0], np.int32)]
     if kekule is not None:
         parts += [('k_status', kekule.status[0], np.int32), ('k_counts', kekule.counts[0], np.int32)]
     if smiles is not None:
         parts += [('s_status', smiles.status[0], np.int32), ('s_counts', smiles.counts[0], np.int32), ('s_length', smiles.length[0], np.int32)]
+    if stereo is not None:
+        parts += [('t_status', stereo.status[0], np.int32), ('t_counts', stereo.counts[0], np.int32)]
+    if smiles is not None and smiles.stereo_counts is not None:
+        parts += [('s_stereo', smiles.stereo_counts[0], np.int32)]
     if geom is not None:
         parts += [('g_status', geom.status[0], np.int32), ('g_metrics', geom.metrics[0], np.float32), ('g_counts', geom.counts[0], np.int32),
                   ('g_dist', geom.point_dist[0], np.float32), ('g_off', geom.point_off, np.int32)]
@@ -921,6 +1100,9 @@ def assemble(results, keys=False, geometry=None, rings=None, kekule=None, featur
         parts += [('f_fp', features.atom_fp[0], np.uint8), ('f_kind', features.point_kind, np.int8)]
     if smiles is not None:
         parts += [('s_text', smiles.text[0], np.uint8)]
+    if stereo is not None:
+        parts += [('t_parity', stereo.atom_parity[0], np.int8), ('t_alabel', stereo.atom_label[0], np.int8),
+                  ('t_bond', stereo.bond_stereo[0], np.int8), ('t_blabel', stereo.bond_label[0], np.int8)]
     sizes = [t.numel() * t.element_size() for _, t, _ in parts]
     blob = torch.cat([t.reshape(-1).view(torch.uint8) for _, t, _ in parts]).cpu().numpy()
     cut = np.cumsum([0] + sizes)
@@ -989,6 +1171,15 @@ def assemble(results, keys=False, geometry=None, rings=None, kekule=None, featur
                                        'text': s_text[g, :int(v['s_length'][g])].tobytes().decode('ascii') if s_ok else ''},
                                       **{k: int(x) for k, x in zip(SMILES_COUNTS, s_counts[g])},
                                       atom_rank=v['s_rank'][n0:n0 + n][keep].copy())
+            if smiles.stereo_counts is not None:
+                mols[-1]['smiles'].update({k: int(x) for k, x in zip(SMILES_STEREO_COUNTS, v['s_stereo'].reshape(-1, 4)[g])})
+        if stereo is not None:
+            t_st = int(v['t_status'][g])
+            mols[-1]['stereo'] = dict({'status': t_st, 'stereo_ok': (t_st & STEREO_FAIL_MASK) == 0},
+                                      **{k: int(x) for k, x in zip(STEREO_COUNTS, v['t_counts'].reshape(-1, len(STEREO_COUNTS))[g])},
+                                      atom_parity=v['t_parity'][n0:n0 + n][keep].copy(), atom_label=v['t_alabel'][n0:n0 + n][keep].copy(),
+                                      bond_stereo=v['t_bond'][h0:h0 + h][nz].copy(), bond_label=v['t_blabel'][h0:h0 + h][nz].copy(),
+                                      stereo_key=int(v['t_key'][g]))
         n0, h0 = n0 + n, h0 + h
     return mols
 
@@ -1039,6 +1230,21 @@ def _features_item(ft):
     return '\n'.join(lines) + '\n\n'
 
 
+def _stereo_item(m):
+    """The PHOREGEN_STEREO data item of a molecule that carries 'stereo' (`assemble`)."""
+    st, sign = m['stereo'], {1: '+', -1: '-', STEREO_UNDEFINED_VALUE: '?'}
+    lines = ['> <PHOREGEN_STEREO>', 'status 0x%02x' % int(st['status']), 'stereo_key %016x' % (int(st['stereo_key']) & _M64)]
+    lines += ['%s %d' % (k, st[k]) for k in STEREO_COUNTS]
+    for i, (p, l) in enumerate(zip(np.asarray(st['atom_parity']).tolist(), np.asarray(st['atom_label']).tolist())):
+        if p:
+            lines.append('centre %d %s %s' % (i + 1, sign[p], sign[l]))
+    bi = np.asarray(m['bond_index']).reshape(2, -1)
+    for (a, b), p, l in zip(bi.T.tolist(), np.asarray(st['bond_stereo']).tolist(), np.asarray(st['bond_label']).tolist()):
+        if p:
+            lines.append('bond %d %d %s %s' % (a + 1, b + 1, sign[p], sign[l]))
+    return '\n'.join(lines) + '\n\n'
+
+
 def write_sdf(path, mols, names=None):
     """An SDF file: one mol block per molecule, each closed by a '$$$$' line.  A molecule that carries 'key' (assemble(keys=True))
     gets one data item `> <PHOREGEN_KEY>` with the key as 16 hex digits between its block and the '$$$$'.  A molecule that carries
@@ -1050,7 +1256,11 @@ def write_sdf(path, mols, names=None):
     carries 'features' (assemble(features=)) gets `> <PHOREGEN_FEATURES>`: the status as hex, one 'name value' line per count
     (FEATURE_COUNTS), then one line per typed point: its type, the matched atom (1-based; '-' if no atom of the type lies within the
     cutoff) and the distance to the nearest atom of the type with four decimals ('inf' without one).  A molecule that carries 'smiles'
-    (assemble(smiles=)) with 'smiles_ok' gets `> <PHOREGEN_SMILES>` with the text on one line; a failed one gets no item."""
+    (assemble(smiles=)) with 'smiles_ok' gets `> <PHOREGEN_SMILES>` with the text on one line; a failed one gets no item.  A molecule
+    that carries 'stereo' (assemble(stereo=)) gets `> <PHOREGEN_STEREO>`: the status as hex, 'stereo_key' as 16 hex digits, one 'name
+    value' line per count (STEREO_COUNTS), then one line 'centre atom parity label' per stereogenic centre (atom 1-based) and one line
+    'bond atom atom stereo label' per stereogenic double bond, values as '+', '-' or '?' (undefined).  The mol block itself does not
+    change: its 3D coordinates carry the stereo."""
     names = names if names is not None else [''] * len(mols)
     if len(names) != len(mols):
         raise ValueError(f'write_sdf: {len(mols)} molecules, {len(names)} names')
@@ -1073,19 +1283,29 @@ def write_sdf(path, mols, names=None):
                 fh.write(_features_item(m['features']))
             if 'smiles' in m and m['smiles'].get('smiles_ok'):
                 fh.write('> <PHOREGEN_SMILES>\n%s\n\n' % m['smiles']['text'])
+            if 'stereo' in m:
+                fh.write(_stereo_item(m))
             fh.write('$$$$\n')
 
 
 # ---- identity: exact comparison and grouping of assembled molecules ---------------------------------------------------------
 
-def _mol_graph(m):
-    """Adjacency {neighbour: order} per atom, the atoms' exact local signatures and the colours handed in (all equal if absent)."""
+def _mol_graph(m, stereo=False):
+    """Adjacency {neighbour: order} per atom, the atoms' exact local signatures and the colours handed in (all equal if absent).
+    stereo: a bond's label is its order and its 'bond_label', an atom's own signature has its 'atom_label'."""
     n = len(m['element'])
     bi, bt = np.asarray(m['bond_index']).reshape(2, -1), np.asarray(m['bond_type']).reshape(-1)
+    al, bl = [0] * n, [0] * bt.size
+    if stereo:
+        if 'stereo' not in m:
+            raise ValueError("same_molecule: stereo=True needs molecules that carry 'stereo' (assemble(stereo=))")
+        al, bl = np.asarray(m['stereo']['atom_label']).reshape(-1).tolist(), np.asarray(m['stereo']['bond_label']).reshape(-1).tolist()
+        if len(al) != n or len(bl) != bt.size:
+            raise ValueError(f"same_molecule: {n} atoms and {bt.size} bonds, 'stereo' has {len(al)} and {len(bl)} labels")
     adj = [{} for _ in range(n)]
-    for a, b, t in zip(bi[0].tolist(), bi[1].tolist(), bt.tolist()):
-        adj[a][b] = adj[b][a] = int(t)
-    own = [(int(z), tuple(sorted(nb.values()))) for z, nb in zip(m['element'], adj)]
+    for a, b, t, l in zip(bi[0].tolist(), bi[1].tolist(), bt.tolist(), bl):
+        adj[a][b] = adj[b][a] = int(t) | (int(l) & 0xff) << 8
+    own = [(int(z), int(l), tuple(sorted(nb.values()))) for z, l, nb in zip(m['element'], al, adj)]
     col = m.get('atom_colour')
     col = [0] * n if col is None else [int(c) & _M64 for c in np.asarray(col).reshape(-1).tolist()]
     if len(col) != n:
@@ -1141,15 +1361,18 @@ def _component_matches(c1, adj1, sig1, c2, adj2, sig2):
     return extend(0)
 
 
-def same_molecule(m1, m2):
+def same_molecule(m1, m2, stereo=False):
     """Exact: do two assembled molecules have the same atoms and bonds up to a renumbering of the atoms (elements and bond orders as
     labels, 4 = aromatic its own label; coordinates play no part)?  'atom_colour', where both carry it, only narrows the search: with
-    any colours, all equal included, the answer is the same, as long as equal molecules were coloured by the same rule."""
+    any colours, all equal included, the answer is the same, as long as equal molecules were coloured by the same rule.
+    stereo=True (both must carry 'stereo', assemble(stereo=)): the renumbering must also keep every 'atom_label' and 'bond_label', so
+    two enantiomers, or a cis and a trans isomer, differ.  The labels are relative to the colours: this is exact as far as atoms
+    with equal colours are equivalent, and an undefined element (2) only equals an undefined one."""
     if len(m1['element']) != len(m2['element']) or np.asarray(m1['bond_type']).size != np.asarray(m2['bond_type']).size:
         return False
     if ('atom_colour' in m1) != ('atom_colour' in m2):                  # colours of one side only say nothing: drop them
         m1, m2 = ({k: v for k, v in m.items() if k != 'atom_colour'} for m in (m1, m2))
-    (adj1, sig1), (adj2, sig2) = _mol_graph(m1), _mol_graph(m2)
+    (adj1, sig1), (adj2, sig2) = _mol_graph(m1, stereo), _mol_graph(m2, stereo)
     if sorted(sig1) != sorted(sig2):
         return False
     comps1, comps2 = _components(adj1), _components(adj2)
@@ -1165,16 +1388,17 @@ def same_molecule(m1, m2):
     return True
 
 
-def unique_molecules(mols):
+def unique_molecules(mols, stereo=False):
     """The partition of assembled molecules into classes of `same_molecule`: (representatives, class_of) with the first member of
     every class as its representative, in order of appearance, and class_of[i] the index into `representatives` of mols[i].
     If every molecule carries 'key', a molecule is only compared inside its key's group (equal molecules have equal keys); the
-    answer is exact either way."""
+    answer is exact either way.  stereo=True: the classes of `same_molecule(stereo=True)`, grouped by 'stereo_key' -- stereoisomers
+    are separate molecules; every molecule must carry 'stereo'."""
     reps, class_of, by_key = [], [], {}
-    keyed = all('key' in m for m in mols)
+    keyed = all('key' in m for m in mols) and not stereo
     for m in mols:
-        group = by_key.setdefault(int(m['key']) & _M64 if keyed else None, [])
-        hit = next((r for r in group if same_molecule(reps[r], m)), None)
+        group = by_key.setdefault(int(m['stereo']['stereo_key']) & _M64 if stereo else int(m['key']) & _M64 if keyed else None, [])
+        hit = next((r for r in group if same_molecule(reps[r], m, stereo)), None)
         if hit is None:
             hit = len(reps)
             reps.append(m)
@@ -1188,7 +1412,8 @@ def duplicate_groups(keys):
     """Key-level census of a key vector on its own device, no host loop: (first, counts, group) with first[k] the index of the first
     occurrence of the k-th distinct key (ascending, so in order of appearance), counts[k] how often it occurs and group[i] the k of
     keys[i].  KEY-LEVEL ONLY: molecules with different keys differ, molecules with one key are very likely, not certainly, the same --
-    copy the representatives `keys[first]` points at and let `unique_molecules` confirm where that matters."""
+    copy the representatives `keys[first]` points at and let `unique_molecules` confirm where that matters.  Handed a `Stereo`'s
+    `stereo_key` instead of a `MolKeys`' `key`, the census counts stereoisomers separately."""
     keys = keys.reshape(-1)
     n, dev = keys.numel(), keys.device
     srt, perm = torch.sort(keys, stable=True)                          # stable: the first occurrence leads its run
@@ -1206,7 +1431,7 @@ def duplicate_groups(keys):
 
 # ---- the top-up loop of sample_all.py:79-84,172 ------------------------------------------------------------------------------
 def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, device='cuda', unique=False, geometry=None,
-                 rings=None, kekule=None, features=None, smiles=None, **sample_kwargs):
+                 rings=None, kekule=None, features=None, smiles=None, stereo=None, **sample_kwargs):
     """Sample until `num_samples` molecules have passed the screen, giving up once more than `max_failed_factor * num_samples` have
     failed (checked before every draw, as the reference does).  Every draw asks for min(batch_size, what is still missing) graphs,
     so never more than `num_samples` are finished.  `sample_kwargs` (fragment=, pos_guidance_opt=, rng=, seed=, ...) go to
@@ -1228,6 +1453,10 @@ def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, d
     smiles=True: a valid molecule is finished only if it is also 'smiles_ok' -- it has a Kekulé structure and its text was written;
     one that is not goes to 'failed'.  The molecules then carry 'smiles'.  The text needs the Kekulé form of the draw: it is computed
     (with kekule= if given, else with the default options) and carried, as 'kekule', only if asked for by its own argument.
+    stereo=a `StereoLimits`, or True for the default limits: a valid molecule is finished only if it is also 'stereo_ok'; one that is
+    not goes to 'failed'.  The molecules then carry 'stereo'; with smiles=True the text is isomeric; with unique=True stereoisomers
+    count as different molecules (looked up by 'stereo_key', confirmed by `same_molecule(stereo=True)`).  The Kekulé form and the
+    rings it needs are computed and carried as for features=.
     All of these share one screen per draw."""
     ring_limits = RingLimits() if rings is True else rings
     if ring_limits is not None and not isinstance(ring_limits, RingLimits):
@@ -1241,6 +1470,9 @@ def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, d
                              f'{features!r}')
     if smiles is not None and smiles is not True:
         raise ValueError(f'phoregen_amd.molecule.sample_valid: smiles= must be True, not {smiles!r}')
+    stereo_limits = StereoLimits() if stereo is True else stereo
+    if stereo_limits is not None and not isinstance(stereo_limits, StereoLimits):
+        raise ValueError(f'phoregen_amd.molecule.sample_valid: stereo= must be True or a StereoLimits, not {stereo!r}')
     finished, failed, duplicates, n_calls = [], [], [], 0
     by_key = {}                                                        # key -> finished molecules that have it
     while len(finished) < num_samples:
@@ -1268,25 +1500,34 @@ def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, d
                 feat = features_for(data, res, screen=sc, kekule=kek, rings=ring)
             else:
                 feat = _features(res, features[0], features[1], screen=sc, kekule=kek, rings=ring, limits=features[2])
+        ster = None
+        if stereo_limits is not None:
+            sc = next((x.screen for x in (geo, ring, kek, feat) if x is not None), None)
+            ster = _stereo(res, screen=sc, kekule=kek if kek is not None else feat.kekule if feat is not None else None,
+                           rings=ring if ring is not None else feat.rings if feat is not None else None, limits=stereo_limits)
         smi = None
         if smiles is not None:
-            sc = next((x.screen for x in (geo, ring, kek, feat) if x is not None), None)
-            smi = _smiles(res, screen=sc, kekule=kek if kek is not None else feat.kekule if feat is not None else None)
+            sc = next((x.screen for x in (geo, ring, kek, feat, ster) if x is not None), None)
+            smi = _smiles(res, screen=sc, stereo=ster,
+                          kekule=kek if kek is not None else feat.kekule if feat is not None else ster.kekule if ster is not None else None)
         mols = assemble(res, keys=unique, **{k: v for k, v in (('geometry', geo), ('rings', ring), ('kekule', kek), ('features', feat),
-                                                               ('smiles', smi)) if v is not None})
+                                                               ('smiles', smi), ('stereo', ster)) if v is not None})
         for m in mols:
             if (not m['valid'] or (geometry is not None and not m['geom']['geom_ok'])
                     or (ring_limits is not None and not m['rings']['rings_ok'])
                     or (kek_options is not None and not m['kekule']['kekule_ok'])
                     or (features is not None and not m['features']['features_ok'])
-                    or (smiles is not None and not m['smiles']['smiles_ok'])):
+                    or (smiles is not None and not m['smiles']['smiles_ok'])
+                    or (ster is not None and not m['stereo']['stereo_ok'])):
                 failed.append(m)
-            elif unique and any(same_molecule(m, other) for other in by_key.setdefault(m['key'], [])):
+                continue
+            key = m['stereo']['stereo_key'] if unique and ster is not None else m['key'] if unique else None
+            if unique and any(same_molecule(m, other, ster is not None) for other in by_key.setdefault(key, [])):
                 duplicates.append(m)
             else:
                 finished.append(m)
                 if unique:
-                    by_key[m['key']].append(m)
+                    by_key[key].append(m)
     out = {'finished': finished, 'failed': failed, 'n_calls': n_calls}
     if unique:
         out['duplicates'] = duplicates

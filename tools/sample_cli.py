@@ -28,7 +28,12 @@ carry the counts and the per-point matches as the data item PHOREGEN_FEATURES.  
 molecule as Kekulé-form OpenSMILES text (phoregen_amd.molecule.smiles; with --no_charged from the neutral-only Kekulé form, as with --kekule) and finishes a molecule only if it
 has a Kekulé structure to write from; <outdir>/{name}_SMILES_all.txt then holds one line per finished molecule, in the order of the
 .sdf files -- the file sample_all.py writes -- and the .sdf files carry the text as the data item PHOREGEN_SMILES.  The text is not
-canonical: a reader's own toolkit canonicalises it.  --num_steps shortens the reverse process (default: the model's).  Without them
+canonical: a reader's own toolkit canonicalises it.  --stereo (implies --valid_only) also reads the stereo of every molecule from its
+coordinates (phoregen_amd.molecule.stereo: tetrahedral centres, cis / trans double bonds outside rings) and finishes it only if it has a
+Kekulé structure and finite coordinates; with --smiles the lines are then isomeric SMILES ('@', '@@', '/', '\\'), with --unique
+stereoisomers count as different molecules and {name}_keys.txt lists the stereo keys, and the .sdf files carry the parities and labels
+as the data item PHOREGEN_STEREO; --stereo_limits '{"vol_min": 0.6, "planar_min": 0.3, "max_undefined": 0}' replaces single limits
+of phoregen_amd.molecule.StereoLimits.  --num_steps shortens the reverse process (default: the model's).  Without them
 nothing changes.
 """
 import argparse
@@ -45,7 +50,7 @@ from phoregen_amd.config import default_model_config, load_config  # noqa: E402
 from phoregen_amd.data import PHORETYPES1, parse_phore_file  # noqa: E402
 from phoregen_amd.fragment import load_fragment_json  # noqa: E402
 from phoregen_amd.models.diffusion import PhoreDiff  # noqa: E402
-from phoregen_amd.molecule import FeatureLimits, GeomLimits, KekuleOptions, RingLimits, STATUS_NONFINITE, assemble, point_kinds_of, sample_valid, write_sdf  # noqa: E402
+from phoregen_amd.molecule import FeatureLimits, GeomLimits, KekuleOptions, RingLimits, StereoLimits, STATUS_NONFINITE, assemble, point_kinds_of, sample_valid, write_sdf  # noqa: E402
 from phoregen_amd.utils.sample_utils import decode_batch  # noqa: E402
 from phoregen_amd.weights import init_deterministic_  # noqa: E402
 
@@ -86,6 +91,11 @@ def main():
                     help='JSON object replacing single limits of FeatureLimits (with --features), e.g. \'{"max_unmatched": 0}\'')
     ap.add_argument('--smiles', action='store_true',
                     help='implies --valid_only: a molecule without a Kekulé structure is not finished; writes <outdir>/<name>_SMILES_all.txt')
+    ap.add_argument('--stereo', action='store_true',
+                    help='implies --valid_only: reads centres and cis / trans double bonds from the coordinates; isomeric SMILES with --smiles, '
+                         'stereoisomers apart with --unique')
+    ap.add_argument('--stereo_limits', type=json.loads, default=None,
+                    help='JSON object replacing single limits of StereoLimits (with --stereo): vol_min, planar_min, max_undefined')
     ap.add_argument('--num_steps', type=int, default=None, help='reverse steps of the sampler (default: the model\'s)')
     ap.add_argument('--sdf', action='store_true', help='write one .sdf per molecule under <outdir>/sdf_results/')
     args = ap.parse_args()
@@ -97,7 +107,10 @@ def main():
         ap.error('--no_charged needs --kekule or --smiles')
     if args.feature_limits is not None and not args.features:
         ap.error('--feature_limits needs --features')
-    args.valid_only = args.valid_only or args.unique or args.geometry or args.rings or args.kekule or args.features or args.smiles
+    if args.stereo_limits is not None and not args.stereo:
+        ap.error('--stereo_limits needs --stereo')
+    args.valid_only = args.valid_only or args.unique or args.geometry or args.rings or args.kekule or args.features or args.smiles or args.stereo
+    stereo_limits = StereoLimits(**(args.stereo_limits or {})) if args.stereo else None
     feature_limits = FeatureLimits(**(args.feature_limits or {})) if args.features else None
     geom_limits = GeomLimits(**(args.geom_limits or {}))
     ring_limits = RingLimits(**(args.ring_limits or {})) if args.rings else None
@@ -138,12 +151,13 @@ def main():
                 ph = data['phore']
                 features = (ph.pos.float() + data.center.float(), point_kinds_of(ph.x, PHORETYPES1), feature_limits)
             out = sample_valid(model, data, args.num_samples, batch_size=args.batch_size, unique=args.unique, geometry=geometry,
-                               rings=ring_limits, kekule=kekule, features=features, smiles=True if args.smiles else None, **kw)
+                               rings=ring_limits, kekule=kekule, features=features, smiles=True if args.smiles else None,
+                               stereo=stereo_limits, **kw)
             done = out['finished']
             print(f"Finished {len(done)} | Failed {len(out['failed'])}" + (f" | Duplicates {len(out['duplicates'])}" if args.unique else ''))
             if args.unique:
                 with open(os.path.join(args.outdir, data.name + '_keys.txt'), 'w') as fh:
-                    fh.writelines('%016x\n' % m['key'] for m in done)
+                    fh.writelines('%016x\n' % (m['stereo']['stereo_key'] if args.stereo else m['key']) for m in done)
             if args.smiles:                                            # sample_all.py:157-159
                 with open(os.path.join(args.outdir, data.name + '_SMILES_all.txt'), 'w') as fh:
                     fh.writelines(m['smiles']['text'] + '\n' for m in done)
