@@ -695,6 +695,52 @@ int pg_mol_smiles_stereo(const int8_t* cls, const int8_t* kekule_order, const ui
                          const uint8_t* valences /*[11][4]*/, int capacity, uint8_t* text, int* length, int16_t* atom_rank, int* counts,
                          int* status, int* stereo_counts, void* stream);
 
+/* Circular fingerprints of the molecules the screen decoded, one wave per (frame, graph).  Definition: DESIGN.md 2.9 "Fingerprints and
+ * similarity".  Reads the screen's outputs cls [F][n_lig] and order [F][n_bond / 2] (frames dense) with the same offsets, exactly as
+ * pg_mol_key does: an atom is kept if its class is 0..10, a pair row is a bond if its order is 1..4 and both ends are kept; aromatic
+ * stays order 4 (no kekulisation).  With mix as in pg_mol_key: id_0[i] = mix(class | valence2 << 8 | degree << 24 | aromatic bonds
+ * << 32), the key's initial colour; for r = 1 .. radius, id_r[i] = mix(id_(r-1)[i] ^ mix(sum over the bonds i - j of mix(id_(r-1)[j] ^
+ * mix(order)))), sums wrapping at 64 bits.
+ *   fp [F][B][PG_FP_WORDS]: bit (b & 63) of word (b >> 6) is set for b = id_r[i] & (PG_FP_BITS - 1), every kept atom i and every r in
+ *     0 .. radius; all zero for a graph without a kept atom.  It does not depend on the numbering of the atoms, on dropped atoms,
+ *     their place in the row order or absorbing rows.
+ *   bits [F][B]: the set bits of the row
+ * Not RDKit's ECFP (no duplicate-environment removal, other invariants, another hash).  0 <= radius <= PG_FP_MAX_RADIUS.  max_n above
+ * PG_MOL_MAX_ATOMS, a negative size or a radius outside its range: error before anything is launched, outputs untouched.  Every word
+ * of every row is written (nothing needs zeroing); integer work only, so results are exact. */
+#define PG_FP_BITS 2048
+#define PG_FP_WORDS 32
+#define PG_FP_MAX_RADIUS 4
+int pg_mol_fp(const int8_t* cls, const int8_t* order, const int* g_lig_off /*[B+1]*/, const int* g_bond_off /*[B+1]*/, int B, int F,
+              int n_lig, int n_bond, int max_n, int radius, uint64_t* fp /*[F*B*32]*/, int* bits /*[F*B]*/, void* stream);
+
+/* Tanimoto similarity of fingerprint rows (PG_FP_WORDS 64-bit words each, 16-byte aligned).  For rows x, y: c = popcount(x & y),
+ * u = popcount(x) + popcount(y) - c; sim = the fp32 value nearest to c / u (IEEE round to nearest even, whatever the build's
+ * floating-point flags), and 1 if u = 0.  Popcounts are computed inside.  Every value is exact.
+ *   out [na][nb]: sim(a_i, b_j).  na * nb above 2^31 - 1 is an error.
+ * A negative size or a null pointer with a positive size: error before anything is launched. */
+#define PG_FP_TILE_A 256             /* rows a workgroup holds in registers, one per lane ...                  */
+#define PG_FP_TILE_B 64              /* ... and rows of one LDS tile of the other set                          */
+int pg_fp_tanimoto(const uint64_t* a, int na, const uint64_t* b, int nb, float* out /*[na*nb]*/, void* stream);
+
+/* For every row i of a against the rows j of b (no [na][nb] matrix in memory):
+ *   sim [na]: the largest sim(a_i, b_j); index [na]: the lowest j that attains it; sum [na]: the fp64 sum over j of the fp32 values.
+ * same != 0: a and b must be one set (one pointer, one size) and j = i is left out.  A row without a candidate (nb = 0, or same with
+ * one row) gets sim -1, index -1, sum 0.  sim and index are exact and do not depend on how the work is cut; sum is added in a fixed
+ * order for given sizes on a given device, within nb^2 * 2^-53 of the exact sum.  Where a has few rows and b many, b is cut into runs
+ * that are combined in a second launch; their parts live in stream-ordered memory (hipMallocAsync), no host synchronisation. */
+int pg_fp_nearest(const uint64_t* a, int na, const uint64_t* b, int nb, int same, float* sim /*[na]*/, int32_t* index /*[na]*/,
+                  double* sum /*[na]*/, void* stream);
+
+/* MaxMin diverse-subset picking over the n rows of fp: picked[0] = first, pick_sim[0] = -1; at step t >= 1 every unpicked row i has
+ * m[i] = the largest sim to the rows picked so far, and the pick is the i with the smallest (m[i], i) in lexicographic order;
+ * pick_sim[t] = that m[i].  A duplicate of a picked row has m = 1 and is picked last, lowest index first.  One launch per pick, each
+ * reading the pick before it from slots and reducing into the next with a 64-bit atomicMin: no host synchronisation between picks.
+ * work [n] and slots [k] are scratch the caller provides; their contents before and after the call mean nothing.  Exact.
+ * k < 0, k > n, n < 0, first outside 0 .. n - 1 with n > 0, or a null array with k > 0: error before anything is launched. */
+int pg_fp_maxmin(const uint64_t* fp, int n, int k, int first, int32_t* picked /*[k]*/, float* pick_sim /*[k]*/, float* work /*[n]*/,
+                 uint64_t* slots /*[k]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

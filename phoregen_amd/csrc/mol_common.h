@@ -85,6 +85,14 @@ PG_MOL_HD int mol_class(int k) { return (k >= 0 && k < 11) ? k : -1; }
 // a pair row's order that is a bond (4 = aromatic); the bond is kept if both its atoms are
 PG_MOL_HD bool mol_is_bond(int o) { return o >= 1 && o <= 4; }
 
+// the splitmix64 step of the identity key and the fingerprint (`mix` of DESIGN.md 2.9): add the golden gamma, then the finaliser
+PG_MOL_HD unsigned long long key_mix(unsigned long long x) {
+  x += 0x9E3779B97F4A7C15ull;
+  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
+  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
+  return x ^ (x >> 31);
+}
+
 #if defined(__HIPCC__)
 
 __device__ __forceinline__ bool mol_nonfinite(float x) { return (__float_as_uint(x) & 0x7f800000u) == 0x7f800000u; }

@@ -12,14 +12,6 @@ constexpr int kKeyRow = kKeyMax + 8;        // bytes per row of the pair table: 
 constexpr int kKeyRounds = 3;               // refinement rounds (KEY_ROUNDS of molecule.py)
 static_assert(kKeyMax % 64 == 0 && kKeyMax <= 128, "a pair code holds a hop distance below 128 or 128 + bond order in one byte");
 
-// the splitmix64 step: add the golden gamma, then the finaliser
-__device__ __forceinline__ unsigned long long key_mix(unsigned long long x) {
-  x += 0x9E3779B97F4A7C15ull;
-  x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
-  x = (x ^ (x >> 27)) * 0x94D049BB133111EBull;
-  return x ^ (x >> 31);
-}
-
 __global__ __launch_bounds__(64) void mol_key_kernel(const int8_t* __restrict__ cls_i, const int8_t* __restrict__ order_i,
                                                      const int* __restrict__ g_lig_off, const int* __restrict__ g_bond_off, int B,
                                                      int n_lig, int n_half, long long* __restrict__ key_o,

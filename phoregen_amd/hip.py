@@ -165,6 +165,10 @@ _PROTOS = {
                                 C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, C.c_void_p]),
     'pg_mol_smiles_stereo': (C.c_int, [c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_ip,
                                        C.c_int, c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, C.c_void_p]),
+    'pg_mol_fp': (C.c_int, [c_ip, c_ip, c_ip, c_ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_ip, c_ip, C.c_void_p]),
+    'pg_fp_tanimoto': (C.c_int, [c_ip, C.c_int, c_ip, C.c_int, c_fp, C.c_void_p]),
+    'pg_fp_nearest': (C.c_int, [c_ip, C.c_int, c_ip, C.c_int, C.c_int, c_fp, c_ip, c_fp, C.c_void_p]),
+    'pg_fp_maxmin': (C.c_int, [c_ip, C.c_int, C.c_int, C.c_int, c_ip, c_fp, c_fp, c_ip, C.c_void_p]),
 }
 
 EXPORTS = tuple(_PROTOS)

@@ -43,7 +43,14 @@ cis or trans (csrc/mol_stereo.hip; DESIGN.md 2.9 "Stereo"), gives each a label t
 a `stereo_key` that tells stereoisomers apart where the identity key cannot.  `smiles(stereo=)` writes them into the text ('@', '@@',
 '/', '\\': isomeric SMILES, csrc/mol_smiles.hip); `assemble(stereo=)`, `same_molecule(stereo=True)`, `unique_molecules(stereo=True)`,
 `sample_valid(stereo=)` and `write_sdf` carry them.  No CIP names (R / S, E / Z), no pseudo-asymmetric centres, no ring double bonds,
-allenes or atropisomers, no three-coordinate N, P or S; the two thresholds are design choices, not calibrated."""
+allenes or atropisomers, no three-coordinate N, P or S; the two thresholds are design choices, not calibrated.
+
+Fingerprints: `fingerprints` gives every decoded molecule a 2048-bit circular (Morgan-style) fingerprint (csrc/mol_fp.hip; DESIGN.md
+2.9 "Fingerprints and similarity"): one bit per (atom, radius 0..R) environment identifier, built from the identity key's initial
+colour and its `mix`, aromatic bonds as their own order.  `assemble(fingerprints=)`, `sample_valid(fingerprints=)` and `write_sdf` carry
+it; `phoregen_amd.similarity` compares sets of them on the device (Tanimoto matrix, nearest neighbour, internal diversity, MaxMin
+picks).  Exact and independent of the numbering of the atoms; NOT RDKit's ECFP (no duplicate-environment removal, other invariants,
+another hash) and not checked against RDKit."""
 import ctypes
 from dataclasses import astuple, dataclass
 
@@ -83,6 +90,13 @@ KEY_ROUNDS = 3
 KEY_NO_PATH = 255
 KEY_EMPTY = 0xE220A8397B1DCDAF
 _M64 = (1 << 64) - 1
+
+# The fingerprint (DESIGN.md 2.9 "Fingerprints and similarity"): bits and 64-bit words of a row (bit b is bit b & 63 of word b >> 6),
+# the largest and the default radius.  The kernel and the tests' restatement share these names and nothing else.
+FP_BITS = 2048
+FP_WORDS = FP_BITS // 64
+FP_MAX_RADIUS = 4
+FP_RADIUS = 2
 
 # The geometry screen (DESIGN.md 2.9 "Geometry"): status bits, and the names of the metric and count columns in the kernel's order
 GEOM_BOND_SHORT = 1              # a bond shorter than bond_min
@@ -431,6 +445,55 @@ def _launch_key(lib, cls, order, lig_off, bond_off, B, F, max_n, key, colour):
     _check_arrays('molecule_keys', cls.device, [(cls, torch.int8), (order, torch.int8), (lig_off, torch.int32), (bond_off, torch.int32)])
     hip.check(lib.pg_mol_key(cls.data_ptr(), order.data_ptr(), lig_off.data_ptr(), bond_off.data_ptr(), B, F, cls.size(-1),
                              2 * order.size(-1), max_n, key.data_ptr(), hip.ptr(colour), hip.stream_ptr()), 'pg_mol_key')
+
+
+@dataclass
+class Fingerprints:
+    """Device tensors of one `fingerprints` call.  The int64 values are 64-bit patterns: read them as unsigned (`& 2**64 - 1`)."""
+    fp: torch.Tensor             # int64 [F, B, 32] bit b of a row is bit b & 63 of word b >> 6
+    bits: torch.Tensor           # int32 [F, B]     set bits of the row
+    radius: int
+    screen: Screen = None        # the screen it was computed from
+
+
+def _check_radius(fn, radius):
+    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 0 <= radius <= FP_MAX_RADIUS:
+        raise ValueError(f'phoregen_amd.molecule.{fn}: radius must be an integer in 0 .. {FP_MAX_RADIUS}, not {radius!r}')
+    return int(radius)
+
+
+@torch.no_grad()
+def fingerprints(sc, radius=FP_RADIUS):
+    """Circular fingerprints of every (frame, graph) of a `Screen`, on its device, in one launch (pg_mol_fp; DESIGN.md 2.9
+    "Fingerprints and similarity"): FP_BITS bits per molecule, one for every kept atom's environment identifier of radius 0 .. radius
+    (the identity key's initial colour, then `radius` rounds over the atom's bonds).  It depends on the kept atoms' elements and the
+    bonds' orders alone (4 = aromatic is its own order: no kekulisation, so it does not depend on which Kekulé structure `kekulize`
+    returns), not on the numbering of the atoms, coordinates, dropped atoms or absorbing rows.  An empty graph has no bit set; a
+    disconnected one has one fingerprint.  `phoregen_amd.similarity` compares them.  This is NOT RDKit's ECFP: no duplicate-
+    environment removal, other atom invariants, another hash; not checked against RDKit."""
+    radius = _check_radius('fingerprints', radius)
+    dev = sc.cls.device
+    _need_cuda('fingerprints', 'the fingerprint', dev, 'screen')
+    F, B = sc.status.shape
+    with torch.cuda.device(dev):
+        lib = hip.lib()
+        fp = torch.empty(F, B, FP_WORDS, dtype=torch.int64, device=dev)
+        bits = torch.empty(F, B, dtype=torch.int32, device=dev)
+        _launch_fp(lib, sc.cls, sc.order, sc.lig_off, sc.bond_off, B, F, max(sc.num_atoms, default=0), radius, fp, bits)
+    return Fingerprints(fp=fp, bits=bits, radius=radius, screen=sc)
+
+
+def _launch_fp(lib, cls, order, lig_off, bond_off, B, F, max_n, radius, fp, bits):
+    """pg_mol_fp on the current stream.  A graph above MAX_ATOMS or a radius outside 0 .. FP_MAX_RADIUS is the library's error:
+    nothing is launched and the outputs are not written."""
+    _check_arrays('fingerprints', cls.device, [(cls, torch.int8), (order, torch.int8), (lig_off, torch.int32), (bond_off, torch.int32),
+                                               (fp, torch.int64), (bits, torch.int32)])
+    if (lig_off.numel() != B + 1 or bond_off.numel() != B + 1 or cls.numel() != F * cls.size(-1) or order.numel() != F * order.size(-1)
+            or fp.numel() != F * B * FP_WORDS or bits.numel() != F * B):
+        raise ValueError(f'phoregen_amd.molecule.fingerprints: sizes of the offsets, screen arrays and outputs do not fit {F} frames x '
+                         f'{B} graphs, {cls.size(-1)} atom rows, {order.size(-1)} pair rows')
+    hip.check(lib.pg_mol_fp(cls.data_ptr(), order.data_ptr(), lig_off.data_ptr(), bond_off.data_ptr(), B, F, cls.size(-1),
+                            2 * order.size(-1), max_n, radius, fp.data_ptr(), bits.data_ptr(), hip.stream_ptr()), 'pg_mol_fp')
 
 
 def _launch(lib, node, node_fs, edge, edge_fs, pos, pos_fs, lig_off, bond_off, B, F, N, E, max_n, out):
@@ -1001,6 +1064,7 @@ _kekulize = kekulize
 _features = features
 _smiles = smiles
 _stereo = stereo
+_fingerprints = fingerprints
 _PAIRS = {}
 
 
@@ -1014,7 +1078,7 @@ def _pairs(n):
 
 
 @torch.no_grad()
-def assemble(results, keys=False, geometry=None, rings=None, kekule=None, features=None, smiles=None, stereo=None):
+def assemble(results, keys=False, geometry=None, rings=None, kekule=None, features=None, smiles=None, stereo=None, fingerprints=None):
     """The final prediction as one dict per graph with `decode_data`'s keys and meaning -- 'element' (atomic numbers), 'atom_pos'
     (kept atoms, the tensor's own fp32 values), 'bond_index' [2, n_b] (indices among the kept atoms) and 'bond_type' [n_b] for
     a < b only, in row order -- plus 'status', 'valid', 'n_components' and 'valence' (per kept atom, halves allowed).  The screen runs
@@ -1046,8 +1110,14 @@ def assemble(results, keys=False, geometry=None, rings=None, kekule=None, featur
     STEREO_FAIL_MASK), the eight STEREO_COUNTS by name, 'atom_parity' and 'atom_label' (int8 per kept atom), 'bond_stereo' and
     'bond_label' (int8 per entry of 'bond_type', in its order; all four: 0 = not stereogenic, +1 / -1, 2 = undefined) and
     'stereo_key' (an unsigned Python int) -- in the same copy; its screen is reused, and it must have been computed from the screen of
-    the others."""
-    geom, pos_t = geometry, results['pred'][1]
+    the others.
+    fingerprints=a `Fingerprints` of this result's final frame: every dict also has 'fingerprint' (np.uint64 [FP_WORDS]), 'fp_bits'
+    (its set bits) and 'fp_radius' -- in the same copy; its screen is reused, and it must have been computed from the screen of the
+    others."""
+    geom, pos_t, fps = geometry, results['pred'][1], fingerprints
+    if fps is not None and (not isinstance(fps, Fingerprints) or fps.screen is None or fps.fp.size(0) != 1
+                            or fps.screen.cls.size(1) != pos_t.size(-2) or fps.fp.device != pos_t.device):
+        raise ValueError('phoregen_amd.molecule.assemble: fingerprints= must be a Fingerprints of the final frame of this result')
     given = [(what, x) for what, x in (('geometry', geom), ('rings', rings), ('kekule', kekule), ('features', features), ('smiles', smiles),
                                        ('stereo', stereo)) if x is not None]
     for what, x in given:
@@ -1056,7 +1126,9 @@ def assemble(results, keys=False, geometry=None, rings=None, kekule=None, featur
     for (what_a, xa), (what_b, xb) in zip(given, given[1:]):
         if not _same_screen(xa.screen, xb.screen):
             raise ValueError(f'phoregen_amd.molecule.assemble: {what_a}= and {what_b}= were computed from screens of different results')
-    sc = given[0][1].screen if given else screen(results, 'final')
+    if fps is not None and given and not _same_screen(given[-1][1].screen, fps.screen):
+        raise ValueError(f'phoregen_amd.molecule.assemble: {given[-1][0]}= and fingerprints= were computed from screens of different results')
+    sc = given[0][1].screen if given else fps.screen if fps is not None else screen(results, 'final')
     # the parts of the one blob, widest elements first so that every part stays aligned in it
     parts = []
     if keys:
@@ -1064,6 +1136,8 @@ def assemble(results, keys=False, geometry=None, rings=None, kekule=None, featur
         parts += [('key', mk.key[0], np.uint64), ('colour', mk.colour[0], np.uint64)]
     if stereo is not None:
         parts += [('t_key', stereo.stereo_key[0], np.uint64)]
+    if fps is not None:
+        parts += [('p_fp', fps.fp[0], np.uint64)]
     if rings is not None:
         parts += [('r_status', rings.status[0], np.int32), ('r_counts', rings.counts[0], np.int32)]
     if kekule is not None:
@@ -1081,6 +1155,8 @@ def assemble(results, keys=False, geometry=None, rings=None, kekule=None, featur
         parts += [('f_status', features.status[0], np.int32), ('f_counts', features.counts[0], np.int32),
                   ('f_dist', features.point_dist[0], np.float32), ('f_off', features.point_off, np.int32),
                   ('f_range', features.point_range, np.int32)]
+    if fps is not None:
+        parts += [('p_bits', fps.bits[0], np.int32)]
     parts += [('status', sc.status[0], np.int32), ('counts', sc.counts[0], np.int32), ('pos', pos_t, np.float32),
               ('compact', sc.compact[0], np.int16)]
     if geom is not None:
@@ -1180,6 +1256,9 @@ def assemble(results, keys=False, geometry=None, rings=None, kekule=None, featur
                                       atom_parity=v['t_parity'][n0:n0 + n][keep].copy(), atom_label=v['t_alabel'][n0:n0 + n][keep].copy(),
                                       bond_stereo=v['t_bond'][h0:h0 + h][nz].copy(), bond_label=v['t_blabel'][h0:h0 + h][nz].copy(),
                                       stereo_key=int(v['t_key'][g]))
+        if fps is not None:
+            mols[-1]['fingerprint'] = v['p_fp'].reshape(-1, FP_WORDS)[g].copy()
+            mols[-1]['fp_bits'], mols[-1]['fp_radius'] = int(v['p_bits'][g]), fps.radius
         n0, h0 = n0 + n, h0 + h
     return mols
 
@@ -1245,6 +1324,14 @@ def _stereo_item(m):
     return '\n'.join(lines) + '\n\n'
 
 
+def _fingerprint_item(m):
+    """The PHOREGEN_FINGERPRINT data item of a molecule that carries 'fingerprint' (`assemble`)."""
+    words = [int(w) & _M64 for w in np.asarray(m['fingerprint']).reshape(-1).tolist()]
+    if len(words) != FP_WORDS:
+        raise ValueError(f"write_sdf: 'fingerprint' has {len(words)} words, not {FP_WORDS}")
+    return '> <PHOREGEN_FINGERPRINT>\n%s\nradius %d\n\n' % (''.join('%016x' % w for w in words), int(m.get('fp_radius', FP_RADIUS)))
+
+
 def write_sdf(path, mols, names=None):
     """An SDF file: one mol block per molecule, each closed by a '$$$$' line.  A molecule that carries 'key' (assemble(keys=True))
     gets one data item `> <PHOREGEN_KEY>` with the key as 16 hex digits between its block and the '$$$$'.  A molecule that carries
@@ -1260,7 +1347,9 @@ def write_sdf(path, mols, names=None):
     that carries 'stereo' (assemble(stereo=)) gets `> <PHOREGEN_STEREO>`: the status as hex, 'stereo_key' as 16 hex digits, one 'name
     value' line per count (STEREO_COUNTS), then one line 'centre atom parity label' per stereogenic centre (atom 1-based) and one line
     'bond atom atom stereo label' per stereogenic double bond, values as '+', '-' or '?' (undefined).  The mol block itself does not
-    change: its 3D coordinates carry the stereo."""
+    change: its 3D coordinates carry the stereo.  A molecule that carries 'fingerprint' (assemble(fingerprints=)) gets
+    `> <PHOREGEN_FINGERPRINT>`: one line of 512 hex digits, word 0 first, each word as 16 digits, then 'radius R'.  A molecule without
+    one gets no such item: the text is as it always was."""
     names = names if names is not None else [''] * len(mols)
     if len(names) != len(mols):
         raise ValueError(f'write_sdf: {len(mols)} molecules, {len(names)} names')
@@ -1285,6 +1374,8 @@ def write_sdf(path, mols, names=None):
                 fh.write('> <PHOREGEN_SMILES>\n%s\n\n' % m['smiles']['text'])
             if 'stereo' in m:
                 fh.write(_stereo_item(m))
+            if 'fingerprint' in m:
+                fh.write(_fingerprint_item(m))
             fh.write('$$$$\n')
 
 
@@ -1431,7 +1522,7 @@ def duplicate_groups(keys):
 
 # ---- the top-up loop of sample_all.py:79-84,172 ------------------------------------------------------------------------------
 def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, device='cuda', unique=False, geometry=None,
-                 rings=None, kekule=None, features=None, smiles=None, stereo=None, **sample_kwargs):
+                 rings=None, kekule=None, features=None, smiles=None, stereo=None, fingerprints=None, **sample_kwargs):
     """Sample until `num_samples` molecules have passed the screen, giving up once more than `max_failed_factor * num_samples` have
     failed (checked before every draw, as the reference does).  Every draw asks for min(batch_size, what is still missing) graphs,
     so never more than `num_samples` are finished.  `sample_kwargs` (fragment=, pos_guidance_opt=, rng=, seed=, ...) go to
@@ -1457,7 +1548,12 @@ def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, d
     not goes to 'failed'.  The molecules then carry 'stereo'; with smiles=True the text is isomeric; with unique=True stereoisomers
     count as different molecules (looked up by 'stereo_key', confirmed by `same_molecule(stereo=True)`).  The Kekulé form and the
     rings it needs are computed and carried as for features=.
+    fingerprints=True for the default radius, or a radius 0 .. FP_MAX_RADIUS: the molecules then carry 'fingerprint', 'fp_bits' and
+    'fp_radius'; nothing is filtered on them.
     All of these share one screen per draw."""
+    fp_radius = None
+    if fingerprints is not None and fingerprints is not False:
+        fp_radius = _check_radius('sample_valid', FP_RADIUS if fingerprints is True else fingerprints)
     ring_limits = RingLimits() if rings is True else rings
     if ring_limits is not None and not isinstance(ring_limits, RingLimits):
         raise ValueError(f'phoregen_amd.molecule.sample_valid: rings= must be True or a RingLimits, not {rings!r}')
@@ -1510,8 +1606,12 @@ def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, d
             sc = next((x.screen for x in (geo, ring, kek, feat, ster) if x is not None), None)
             smi = _smiles(res, screen=sc, stereo=ster,
                           kekule=kek if kek is not None else feat.kekule if feat is not None else ster.kekule if ster is not None else None)
+        fps = None
+        if fp_radius is not None:
+            sc = next((x.screen for x in (geo, ring, kek, feat, ster, smi) if x is not None), None)
+            fps = _fingerprints(sc if sc is not None else _screen(res, 'final'), fp_radius)
         mols = assemble(res, keys=unique, **{k: v for k, v in (('geometry', geo), ('rings', ring), ('kekule', kek), ('features', feat),
-                                                               ('smiles', smi), ('stereo', ster)) if v is not None})
+                                                               ('smiles', smi), ('stereo', ster), ('fingerprints', fps)) if v is not None})
         for m in mols:
             if (not m['valid'] or (geometry is not None and not m['geom']['geom_ok'])
                     or (ring_limits is not None and not m['rings']['rings_ok'])

@@ -33,7 +33,14 @@ coordinates (phoregen_amd.molecule.stereo: tetrahedral centres, cis / trans doub
 Kekulé structure and finite coordinates; with --smiles the lines are then isomeric SMILES ('@', '@@', '/', '\\'), with --unique
 stereoisomers count as different molecules and {name}_keys.txt lists the stereo keys, and the .sdf files carry the parities and labels
 as the data item PHOREGEN_STEREO; --stereo_limits '{"vol_min": 0.6, "planar_min": 0.3, "max_undefined": 0}' replaces single limits
-of phoregen_amd.molecule.StereoLimits.  --num_steps shortens the reverse process (default: the model's).  Without them
+of phoregen_amd.molecule.StereoLimits.  --fingerprints (implies --valid_only) also gives every finished molecule its 2048-bit circular
+fingerprint (phoregen_amd.molecule.fingerprints; --fp_radius R, 0 .. 4, default 2; not RDKit's ECFP) and compares the finished set on the
+device (phoregen_amd.similarity): <outdir>/{name}_fingerprints.npy holds them as uint64 [n, 32] in the order of the finished molecules,
+<outdir>/{name}_similarity.txt one line 'n internal_diversity mean_nearest_similarity', and the .sdf files carry the bits as the data
+item PHOREGEN_FINGERPRINT.  --diverse K (implies --fingerprints) writes <outdir>/{name}_diverse.txt: the MaxMin picks from the first
+finished molecule on, one line 'index pick_sim' per pick in pick order (at most n of them).  --reference_fps FILE.npy (uint64 [m, 32],
+e.g. another run's {name}_fingerprints.npy; implies --fingerprints) writes <outdir>/{name}_nearest.txt: per finished molecule the
+largest similarity to that set and the row that attains it.  --num_steps shortens the reverse process (default: the model's).  Without them
 nothing changes.
 """
 import argparse
@@ -42,6 +49,7 @@ import os
 import sys
 import time
 
+import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -50,7 +58,8 @@ from phoregen_amd.config import default_model_config, load_config  # noqa: E402
 from phoregen_amd.data import PHORETYPES1, parse_phore_file  # noqa: E402
 from phoregen_amd.fragment import load_fragment_json  # noqa: E402
 from phoregen_amd.models.diffusion import PhoreDiff  # noqa: E402
-from phoregen_amd.molecule import FeatureLimits, GeomLimits, KekuleOptions, RingLimits, StereoLimits, STATUS_NONFINITE, assemble, point_kinds_of, sample_valid, write_sdf  # noqa: E402
+from phoregen_amd import similarity  # noqa: E402
+from phoregen_amd.molecule import FP_MAX_RADIUS, FP_RADIUS, FP_WORDS, FeatureLimits, GeomLimits, KekuleOptions, RingLimits, StereoLimits, STATUS_NONFINITE, assemble, point_kinds_of, sample_valid, write_sdf  # noqa: E402
 from phoregen_amd.utils.sample_utils import decode_batch  # noqa: E402
 from phoregen_amd.weights import init_deterministic_  # noqa: E402
 
@@ -96,6 +105,15 @@ def main():
                          'stereoisomers apart with --unique')
     ap.add_argument('--stereo_limits', type=json.loads, default=None,
                     help='JSON object replacing single limits of StereoLimits (with --stereo): vol_min, planar_min, max_undefined')
+    ap.add_argument('--fingerprints', action='store_true',
+                    help='implies --valid_only: writes <outdir>/<name>_fingerprints.npy and <name>_similarity.txt (n, internal diversity, '
+                         'mean nearest-neighbour similarity)')
+    ap.add_argument('--fp_radius', type=int, default=None, help=f'radius of the fingerprint, 0 .. {FP_MAX_RADIUS} (default {FP_RADIUS})')
+    ap.add_argument('--diverse', type=int, default=None, metavar='K',
+                    help='implies --fingerprints: writes <outdir>/<name>_diverse.txt, the MaxMin picks (index, pick_sim) in pick order')
+    ap.add_argument('--reference_fps', type=str, default=None, metavar='FILE.npy',
+                    help='implies --fingerprints: uint64 [m, 32]; writes <outdir>/<name>_nearest.txt, per finished molecule the nearest '
+                         'similarity to that set and the row that attains it')
     ap.add_argument('--num_steps', type=int, default=None, help='reverse steps of the sampler (default: the model\'s)')
     ap.add_argument('--sdf', action='store_true', help='write one .sdf per molecule under <outdir>/sdf_results/')
     args = ap.parse_args()
@@ -109,7 +127,20 @@ def main():
         ap.error('--feature_limits needs --features')
     if args.stereo_limits is not None and not args.stereo:
         ap.error('--stereo_limits needs --stereo')
-    args.valid_only = args.valid_only or args.unique or args.geometry or args.rings or args.kekule or args.features or args.smiles or args.stereo
+    args.fingerprints = args.fingerprints or args.diverse is not None or args.reference_fps is not None
+    if args.fp_radius is not None and not args.fingerprints:
+        ap.error('--fp_radius needs --fingerprints')
+    fp_radius = FP_RADIUS if args.fp_radius is None else args.fp_radius
+    if not 0 <= fp_radius <= FP_MAX_RADIUS:
+        ap.error(f'--fp_radius must be 0 .. {FP_MAX_RADIUS}')
+    if args.diverse is not None and args.diverse < 0:
+        ap.error('--diverse must not be negative')
+    reference = None
+    if args.reference_fps is not None:
+        reference = np.load(args.reference_fps)
+        if reference.dtype != np.uint64 or reference.ndim != 2 or reference.shape[1] != FP_WORDS:
+            ap.error(f'--reference_fps must hold uint64 [m, {FP_WORDS}], not {reference.dtype} {reference.shape}')
+    args.valid_only = args.valid_only or args.fingerprints or args.unique or args.geometry or args.rings or args.kekule or args.features or args.smiles or args.stereo
     stereo_limits = StereoLimits(**(args.stereo_limits or {})) if args.stereo else None
     feature_limits = FeatureLimits(**(args.feature_limits or {})) if args.features else None
     geom_limits = GeomLimits(**(args.geom_limits or {}))
@@ -152,7 +183,7 @@ def main():
                 features = (ph.pos.float() + data.center.float(), point_kinds_of(ph.x, PHORETYPES1), feature_limits)
             out = sample_valid(model, data, args.num_samples, batch_size=args.batch_size, unique=args.unique, geometry=geometry,
                                rings=ring_limits, kekule=kekule, features=features, smiles=True if args.smiles else None,
-                               stereo=stereo_limits, **kw)
+                               stereo=stereo_limits, **(dict(fingerprints=fp_radius) if args.fingerprints else {}), **kw)
             done = out['finished']
             print(f"Finished {len(done)} | Failed {len(out['failed'])}" + (f" | Duplicates {len(out['duplicates'])}" if args.unique else ''))
             if args.unique:
@@ -161,6 +192,22 @@ def main():
             if args.smiles:                                            # sample_all.py:157-159
                 with open(os.path.join(args.outdir, data.name + '_SMILES_all.txt'), 'w') as fh:
                     fh.writelines(m['smiles']['text'] + '\n' for m in done)
+            if args.fingerprints:
+                fps = similarity.stack(done, 'cuda')
+                np.save(os.path.join(args.outdir, data.name + '_fingerprints.npy'), fps.cpu().numpy().view(np.uint64))
+                near = similarity.nearest(fps)
+                n = len(done)
+                diversity = similarity._diversity(near.sum.sum().item(), n)
+                with open(os.path.join(args.outdir, data.name + '_similarity.txt'), 'w') as fh:
+                    fh.write('%d %.6f %.6f\n' % (n, diversity, near.sim.double().mean().item() if n >= 2 else float('nan')))
+                if args.diverse is not None:
+                    picks = similarity.maxmin_pick(fps, min(args.diverse, n))
+                    with open(os.path.join(args.outdir, data.name + '_diverse.txt'), 'w') as fh:
+                        fh.writelines('%d %.6f\n' % (i, s) for i, s in zip(picks.index.tolist(), picks.sim.tolist()))
+                if reference is not None:
+                    ref = similarity.nearest(fps, torch.from_numpy(reference.view(np.int64)).to('cuda').contiguous())
+                    with open(os.path.join(args.outdir, data.name + '_nearest.txt'), 'w') as fh:
+                        fh.writelines('%.6f %d\n' % (s, j) for s, j in zip(ref.sim.tolist(), ref.index.tolist()))
         while len(done) < args.num_samples and not args.valid_only:
             n = min(args.batch_size, args.num_samples - len(done))
             res = model.sample(data, n, 'cuda', return_traj=False, **kw)
