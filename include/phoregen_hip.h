@@ -109,10 +109,18 @@ typedef struct {
   const int* rows;           /* optional [M]: logical row r reads X/X2 row rows[r] and writes Y row rows[r] (row subset) */
   int add_rows;              /* rows of add1 / add2 (upper bound of idx1 / idx2 values + 1); 0 = unknown.  Lets pg_gemm pick the
                               * streaming kernel, which addresses the gathered rows with 32-bit byte offsets */
+  int row_extent;            /* with tile_rows: rows of the X / Y buffers (every window lies inside [0, row_extent)) */
+  const int* tile_rows;      /* optional [M / 64], device-accessible: row windows.  The product runs over M / 64 windows of 64 consecutive
+                              * rows; window t covers rows tile_rows[t] .. tile_rows[t] + 63 of X and of Y (row r of Y from row r of X, so
+                              * overlapping windows write the same bits) and M counts the rows computed.  Every first row must lie in
+                              * [0, row_extent - 64]: checked when the list is host-visible (pinned or managed memory), the caller's duty
+                              * for a device-only list.  Streaming kernel only: K1 = 128, K2 = 0, no added operand, no `rows`, act = 0, N a
+                              * multiple of 128 (plain or LayerNorm-on-load with N = 128); anything else is an error, not a slower path */
 } PgGemm;
 int pg_gemm(const PgGemm* p, void* stream);
 /* test hook (returns the old setting): 0 keeps every product on the tiled kernel (csrc/gemm.hip) instead of the streaming one
- * (csrc/gemm_stream.hip), so that the tests can hold the two against each other */
+ * (csrc/gemm_stream.hip), so that the tests can hold the two against each other (a product with row windows, `tile_rows`, has no tiled
+ * form and stays on the streaming kernel) */
 int pg_debug_gemm_streaming(int on);
 
 /* ---- graph topology of one batch ------------------------------------------------------------

@@ -258,6 +258,7 @@ __global__ __launch_bounds__(256) void rows_linear_mfma_kernel(const float* X, i
 
 namespace pg {   // gemm_stream.hip
 bool gemm_stream_eligible(const PgGemm* p);
+bool gemm_stream_windows_ok(const PgGemm* p);
 int launch_gemm_stream(const PgGemm* p, hipStream_t st);
 }
 
@@ -270,6 +271,32 @@ extern "C" int pg_gemm(const PgGemm* p, void* stream) {
   if (p->K2 > 0 && !p->X2) { pg::set_error("pg_gemm: K2 > 0 without X2"); return PG_ERR_ARG; }
   if (p->ln_gamma && !p->ln_beta) { pg::set_error("pg_gemm: ln_gamma without ln_beta"); return PG_ERR_ARG; }
   if (p->ln_gamma && (p->K2 != 0 || p->K1 != 128 || (p->ldx & 3) || ((size_t)p->X & 15))) { pg::set_error("pg_gemm: LayerNorm-on-load needs K1 == 128, K2 == 0, 16-byte aligned rows"); return PG_ERR_ARG; }
+  if (p->tile_rows) {
+    // row windows exist on the streaming kernel only: any other form is an error (the tiled kernel would give the saving back), and
+    // pg_debug_gemm_streaming(0) leaves these products where they are
+    if (!pg::gemm_stream_windows_ok(p)) {
+      pg::set_error("pg_gemm: tile_rows needs the streaming kernel's plain or LayerNorm-on-load form (K1 = 128, K2 = 0, no added operand, "
+                    "no rows, act = 0, N a multiple of 128), M = 64 x windows and row_extent >= 64 (M %d, N %d, K1 %d, K2 %d, row_extent %d)",
+                    p->M, p->N, p->K1, p->K2, p->row_extent);
+      return PG_ERR_ARG;
+    }
+    // a list the host can read (pinned or managed memory) is checked here; a device-only list is the caller's duty (BatchPlan.lig_windows)
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, p->tile_rows) != hipSuccess || at.type == hipMemoryTypeUnregistered) {
+      (void)hipGetLastError();
+      pg::set_error("pg_gemm: tile_rows is not device-accessible memory");
+      return PG_ERR_ARG;
+    }
+    if (at.type == hipMemoryTypeHost || at.type == hipMemoryTypeManaged) {      // (one address for host and device)
+      const int* o = p->tile_rows;
+      for (int t = 0; t < p->M / 64; ++t)
+        if (o[t] < 0 || o[t] > p->row_extent - 64) {
+          pg::set_error("pg_gemm: tile_rows[%d] = %d outside [0, row_extent - 64 = %d]", t, o[t], p->row_extent - 64);
+          return PG_ERR_ARG;
+        }
+    }
+    return pg::launch_gemm_stream(p, (hipStream_t)stream);
+  }
   // K = 128 (+ 20) / K = 20 products with a plain epilogue or LayerNorm-on-load: the streaming kernel (LDS-DMA tiles, no vector-ALU
   // work on the memory path; gemm_stream.hip); everything else (row subsets, odd K, two gathered operands): the tiled kernel
   if (g_gemm_stream && pg::gemm_stream_eligible(p)) return pg::launch_gemm_stream(p, (hipStream_t)stream);

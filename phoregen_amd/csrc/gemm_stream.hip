@@ -38,7 +38,8 @@ constexpr int ST_STAGE = ST_BM * 128 * 4;       // 32 KB
 
 template <int NW /* waves: 32 output columns each */, int NADD /* 0 | 1: rows add1[idx1[r]] | 2: rows add1[r] */, int K1 /* 128 | 0 */,
           int K2 /* 0 | 20 */, bool LN /* LayerNorm(128) + ReLU on the X rows (K1 = 128, NW = 4) */,
-          bool SSP = false /* shifted softplus on the result (the heads' first layers) */>
+          bool SSP = false /* shifted softplus on the result (the heads' first layers) */,
+          bool WIN = false /* row windows: tile t starts at row p.tile_rows[t] (K1 = 128, K2 = 0, NADD = 0) */>
 __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void gemm_stream_kernel(PgGemm p, int n_tiles) {
   extern __shared__ __attribute__((aligned(1024))) char st_lds[];     // the ONLY LDS object: stage s at byte s * 32 KB
   const int lane = threadIdx.x & 63;
@@ -97,8 +98,9 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void gemm_stream_kernel(P
 
   // ---- lane-fixed offsets ----
   const unsigned ldxb = (unsigned)p.ldx * 4u, ldyb = (unsigned)p.ldy * 4u;
-  const i4v descX = raw_buffer_desc(p.X, (unsigned)p.M * ldxb);
-  const __amdgpu_buffer_rsrc_t descY = __builtin_amdgcn_make_buffer_rsrc(p.Y, 0, (unsigned)p.M * ldyb, 0x00020000);
+  const unsigned n_rows = WIN ? (unsigned)p.row_extent : (unsigned)p.M;      // rows of the X / Y buffers
+  const i4v descX = raw_buffer_desc(p.X, n_rows * ldxb);
+  const __amdgpu_buffer_rsrc_t descY = __builtin_amdgcn_make_buffer_rsrc(p.Y, 0, n_rows * ldyb, 0x00020000);
   // DMA source of lane (row_sub, slot pp) in a piece: the slot holds k-group pp ^ ((row >> 1) & 7), row = 8 i + row_sub
   const unsigned row_sub = lane >> 3, pp = lane & 7;
   const unsigned voff_even = row_sub * ldxb + ((pp ^ ((row_sub >> 1) & 7u)) << 4);
@@ -123,6 +125,13 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void gemm_stream_kernel(P
   // every tile is a full tile: the last one starts at row M - 64 and recomputes a few rows of its neighbour (same values)
   const unsigned last_row0 = (unsigned)p.M - ST_BM;
   auto tile_row0 = [&](unsigned tl) { const unsigned r = tl * ST_BM; return r < last_row0 ? r : last_row0; };
+  // row windows: the tile's first row comes from the list instead.  One SCALAR load per tile (the index is uniform, the list is
+  // read through the constant address space): nothing joins the vector-memory queue the counted wait below counts.  Past the last
+  // tile: the last window once more (the trailing DMA, never consumed)
+  auto win_row0 = [&](unsigned tl) {
+    const unsigned t = tl < (unsigned)n_tiles ? tl : (unsigned)n_tiles - 1u;
+    return (unsigned)reinterpret_cast<const __attribute__((address_space(4))) int*>((uintptr_t)p.tile_rows)[t];
+  };
   // indices of the lane's 16 rows of block b: rows 32 b + 8 q + 4 kh + t -> one 16-byte load per (b, q)
   auto load_idx = [&](__amdgpu_buffer_rsrc_t dI, unsigned row0, i4v (&ix)[8]) {
 #pragma unroll
@@ -154,8 +163,8 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void gemm_stream_kernel(P
   const unsigned tile_step = gridDim.x;
   unsigned tile = blockIdx.x;
 
-  auto dma_tile = [&](unsigned tl, unsigned stage) {
-    const unsigned row0b = tile_row0(tl) * ldxb;
+  auto dma_tile = [&](unsigned row0, unsigned stage) {
+    const unsigned row0b = row0 * ldxb;
     if constexpr (NW == 4) {
 #pragma unroll
       for (int q = 0; q < 8; ++q) {
@@ -171,7 +180,10 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void gemm_stream_kernel(P
 
   // ---- prologue: first tile's DMA and gathers ----
   if constexpr (K2 > 0) load_x2(tile_row0(tile), xa);
-  if constexpr (K1 > 0) dma_tile(tile, 0);
+  // row windows: first rows of this tile and of the next, carried round the loop (each is loaded one tile before the DMA that uses it)
+  unsigned wrow = 0, wrow_next = 0;
+  if constexpr (WIN) { wrow = win_row0(tile); wrow_next = win_row0(tile + tile_step); }
+  if constexpr (K1 > 0) dma_tile(WIN ? wrow : tile_row0(tile), 0);
   if constexpr (NADD == 1) { i4v ix[8]; load_idx(descI1, tile_row0(tile), ix); gather(descA1, ld1b, ix, g1); }
   if constexpr (NADD == 2) gather_plain(tile_row0(tile), g1);
 
@@ -191,7 +203,9 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void gemm_stream_kernel(P
     i4v ix1[8];
     if constexpr (NADD == 1) load_idx(descI1, tile_row0(next), ix1);
     if constexpr (K2 > 0) load_x2(tile_row0(next), xn);
-    if constexpr (K1 > 0) dma_tile(next, stage ^ 1u);   // past the last tile: the clamped last tile once more, never consumed
+    unsigned wrow_after = 0;
+    if constexpr (WIN) wrow_after = win_row0(next + tile_step);
+    if constexpr (K1 > 0) dma_tile(WIN ? wrow_next : tile_row0(next), stage ^ 1u);   // past the last tile: the clamped last tile once more, never consumed
 
     if constexpr (LN) {
       // normalise the landed tile in place: 4 threads per row, each its 128-byte piece row, read in k order (slot q ^ sw holds
@@ -283,7 +297,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void gemm_stream_kernel(P
       if constexpr (NADD == 2) gather_plain(tile_row0(next), g1);
     }
 
-    const unsigned row0 = tile_row0(tile);
+    const unsigned row0 = WIN ? wrow : tile_row0(tile);
 #pragma unroll
     for (int b = 0; b < 2; ++b)
 #pragma unroll
@@ -295,6 +309,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void gemm_stream_kernel(P
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(int, v), descY, voffY[r & 3], soff, 0);
       }
     tile = next;
+    if constexpr (WIN) { wrow = wrow_next; wrow_next = wrow_after; }
   };
 
   body(std::integral_constant<unsigned, 0>{}, std::true_type{});
@@ -306,17 +321,17 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void gemm_stream_kernel(P
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // the trailing (out-of-range) DMA must not outlive the workgroup's LDS
 }
 
-template <int NW, int NADD, int K1, int K2, bool LN = false, bool SSP = false>
+template <int NW, int NADD, int K1, int K2, bool LN = false, bool SSP = false, bool WIN = false>
 static int launch_stream_t(const PgGemm* p, hipStream_t st) {
-  const void* k = reinterpret_cast<const void*>(gemm_stream_kernel<NW, NADD, K1, K2, LN, SSP>);
+  const void* k = reinterpret_cast<const void*>(gemm_stream_kernel<NW, NADD, K1, K2, LN, SSP, WIN>);
   const size_t lds = K1 ? 2 * ST_STAGE + (LN ? 1024 : 0) : 0;
   if (lds) if (int rc = reserve_lds(k, lds, "pg_gemm(stream)")) return rc;
-  const int n_tiles = (p->M + ST_BM - 1) / ST_BM;
+  const int n_tiles = (p->M + ST_BM - 1) / ST_BM;      // (row windows: M = 64 x windows)
   const int n_cb = p->N / (NW * 32);
   int per_cb = (NW == 4 ? 2 : 1) * kNumCU / n_cb;
   if (per_cb < 1) per_cb = 1;
   if (per_cb > n_tiles) per_cb = n_tiles;
-  hipLaunchKernelGGL((gemm_stream_kernel<NW, NADD, K1, K2, LN, SSP>), dim3(per_cb, n_cb), dim3(NW * 64), lds, st, *p, n_tiles);
+  hipLaunchKernelGGL((gemm_stream_kernel<NW, NADD, K1, K2, LN, SSP, WIN>), dim3(per_cb, n_cb), dim3(NW * 64), lds, st, *p, n_tiles);
   return check_launch("pg_gemm(stream)");
 }
 
@@ -355,7 +370,19 @@ static int launch_stream_k(const PgGemm* p, hipStream_t st) {
   return launch_stream_t<4, 2, K1, K2>(p, st);
 }
 
+// row windows (PgGemm.tile_rows): the forms the engine's ligand-only products take, and no other
+bool gemm_stream_windows_ok(const PgGemm* p) {
+  if (p->K1 != 128 || p->K2 || p->add1 || p->add2 || p->rows || p->act != 0 || (p->N & 127)) return false;
+  if (p->M < ST_BM || (p->M % ST_BM) || p->row_extent < ST_BM) return false;
+  if ((size_t)p->row_extent * p->ldx * 4 >= 0xfffff000ull || (size_t)p->row_extent * p->ldy * 4 >= 0xfffff000ull) return false;
+  return gemm_stream_eligible(p);        // (alignment, LayerNorm-on-load form; its size checks on M hold for the smaller of the two)
+}
+
 int launch_gemm_stream(const PgGemm* p, hipStream_t st) {
+  if (p->tile_rows) {
+    if (p->ln_gamma) return launch_stream_t<4, 0, 128, 0, true, false, true>(p, st);
+    return (p->N & 255) == 0 ? launch_stream_t<8, 0, 128, 0, false, false, true>(p, st) : launch_stream_t<4, 0, 128, 0, false, false, true>(p, st);
+  }
   if (p->ln_gamma) return launch_stream_t<4, 0, 128, 0, true>(p, st);
   if (p->act == 1) return launch_stream_t<4, 0, 128, 0, false, true>(p, st);
   if (p->K1 == 20) {                             // K = 20 alone: the X operand takes the X2 (register) path

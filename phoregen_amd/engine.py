@@ -86,6 +86,10 @@ class Engine:
         self.step_ahead = o['step_ahead']
         self.pos_tiled, self.pos_tiled_below = o['pos_tiled'], o['pos_tiled_below']
         self.tri_grid = o['tri_grid']                  # persistent triplet workgroups (-1: by batch size)
+        # products that only ligand rows are read from run over the plan's 64-row windows around the ligand runs (PgGemm.tile_rows);
+        # 2: lane 0 also waits for what it reads alone (the first of the three Y2 launches; the first-layer blocks in front of P).
+        # A plan of fewer than 64 context rows has no windows
+        self.lig_windows = o['lig_windows'] if plan.lig_windows is not None else 0
         self._lane = 0
         self._n_points = 0       # order points of this engine's launch lists
         self._points = {}        # ... their events in the Python runner (created at first use)
@@ -235,7 +239,9 @@ class Engine:
         return [a.elapsed_time(b) for (sa, a), (sb, b) in zip(evs[0::2], evs[1::2]) if sa and not sb]
 
     def _gemm(self, prog, X, K1, W, Y, M, N, bias=None, X2=None, K2=0, ln=None, add1=None, idx1=None, add2=None,
-              idx2=None, scale=1.0, act=hip.ACT_NONE, rows=None):
+              idx2=None, scale=1.0, act=hip.ACT_NONE, rows=None, lig_only=False):
+        """lig_only: only ligand rows of Y are read -- with options.lig_windows the product runs over the plan's row windows (M = the rows
+        it computes; X and Y keep their M rows)."""
         g = hip.PgGemm()
         g.X, g.ldx, g.K1 = X.data_ptr(), X.stride(0), K1
         g.X2, g.ldx2, g.K2 = (X2.data_ptr(), X2.stride(0), K2) if X2 is not None else (None, 0, 0)
@@ -248,6 +254,8 @@ class Engine:
         g.Y, g.ldy, g.M, g.N = Y.data_ptr(), Y.stride(0), M, N
         g.rows = hip.ptr(rows)
         g.add_rows = add1.size(0) if add1 is not None else 0      # the gathered operands are whole [rows, ld] tensors
+        if lig_only and self.lig_windows:
+            g.tile_rows, g.row_extent, g.M = self.plan.lig_windows.data_ptr(), M, 64 * self.plan.n_lig_windows
         self._keep += [g, X, W, Y, bias, X2, ln, add1, idx1, add2, idx2, rows]
         self._call(prog, self.lib.pg_gemm, C.byref(g))
 
@@ -266,7 +274,9 @@ class Engine:
         """q = W2q . ReLU(LN(q_hid)) + b2q, scaled by 1/sqrt(head_dim); q_hid = block 4 of the sub-layer's first-layer columns."""
         n, wq = self.plan.n_ctx, self.ws.q[buf]
         qh = Y[:, col0 + 4 * 128: col0 + 5 * 128]
-        self._gemm(prog, qh, 128, a.W2q, wq, n, 128, bias=a.b2q, ln=(a.q_ln_g, a.q_ln_b), scale=HEAD_SCALE)
+        # ligand targets only (bond-node, knn-pos, bond-pos): the rows of the ligand windows, like the launch that wrote q_hid there
+        lig_only = all(is_lig for _, _, is_lig in h_dst_lists)
+        self._gemm(prog, qh, 128, a.W2q, wq, n, 128, bias=a.b2q, ln=(a.q_ln_g, a.q_ln_b), scale=HEAD_SCALE, lig_only=lig_only)
 
     def _node_attention(self, prog, mode, a, Y, col0, x, h_dst_lists, out=None, dx=None, csrc=None, buf=0, extra=None,
                         query_done=False, qbuf=None):
@@ -444,7 +454,11 @@ class Engine:
         # first-layer blocks: knn-node blocks for every ctx node, bond-node / triplet blocks only where they are read
         # (ligand atoms: targets and sources of bond edges)
         p, n = self.plan, self.plan.n_ctx
-        self._gemm(prog, h_in, 128, L.W_node1, Y1, n, 1920, bias=L.b_node1)
+        if not self.lig_windows:
+            self._gemm(prog, h_in, 128, L.W_node1, Y1, n, 1920, bias=L.b_node1)
+            return
+        self._gemm(prog, h_in, 128, L.W_node1[:640], Y1[:, :640], n, 640, bias=L.b_node1[:640])
+        self._gemm(prog, h_in, 128, L.W_node1[640:], Y1[:, 640:], n, 1280, bias=L.b_node1[640:], lig_only=True)
 
     def _triplet_queries(self, prog, L, hb_in, Y1):
         w, p, E = self.ws, self.plan, self.plan.n_bond
@@ -531,7 +545,15 @@ class Engine:
             if li == 0:
                 self._call(prog, lib.pg_layer_geom, t, xc.data_ptr(), None, None, w.nrm_phore_ctx.data_ptr(), None,
                            w.nrm.data_ptr(), w.G.data_ptr())
-            if (pre and not v2) or pre0:
+            # lig_windows == 2: lane 0 no longer stands behind Y2 and the knn position update (below), so by the end of the position phase
+            # lane 2 is the longer chain (first-layer blocks, triplet queries, knn-node query): P and the Q rows wait for the first-layer
+            # blocks alone, the triplet kernel and the knn-node attention for the rest of lane 2 where they read it (128 graphs, alternating
+            # runs: 18.15 -> 17.91 ms per step; profiles/r08_lig_windows_ab.md).  Layer 0 of a pipelined step keeps the whole-lane wait: its
+            # products come from another program, whose events this one cannot wait for
+            late2 = self.lig_windows == 2 and pre and not v2 and not pre0
+            if late2:
+                self._wait(prog, 0, y1_done)
+            elif (pre and not v2) or pre0:
                 # lane 2 carried this layer's first-layer blocks and triplet queries through the previous layer's position updates
                 # (pipelined step, layer 0: through the end of the previous step)
                 self._sync(prog, 0, (2,))
@@ -580,7 +602,7 @@ class Engine:
                     self._wait(prog, 0, q3_done)   # (lane 3 goes on with the bond-node attention: not joined)
                 else:
                     self._join(prog, (3,))
-            if pre and v2 and not pre0:            # (pre0: lane 0 has waited for lane 2 at the layer's start)
+            if (pre and v2 and not pre0) or late2:   # (pre0: lane 0 has waited for lane 2 at the layer's start)
                 self._sync(prog, 0, (2,))          # this layer's triplet queries (lane 2, launched one layer ahead)
             a = L.TB
             self._event(prog, 'triplet', True)
@@ -633,6 +655,8 @@ class Engine:
                 self._sync(prog, 1, (2,))              # this layer's first-layer blocks and knn-node query (lane 2, `prog_ahead`)
             elif pre and v2:
                 self._wait(prog, 1, ne_done)           # this layer's knn-node query (lane 3, launched one layer ahead)
+            elif late2:
+                self._sync(prog, 1, (2,))              # this layer's knn-node query (lane 2, launched one layer ahead)
             self._event(prog, 'knn_node', True)       # (the launches of the sub-layer: ligand targets, pharmacophore targets)
             self._node_attention(prog, hip.SEG_KNN_NODE, L.NE, Y1c, 0, xc1, both, out=w.aggE, buf=0, query_done=True,
                                  qbuf=3 if pre else None)
@@ -652,13 +676,32 @@ class Engine:
             # ---- position updates from h', h_bond' and the OLD geometry (:291-296)
             # knn-pos k/v source halves for every node (cols 256:512); target halves, queries and the bond-pos blocks
             # only for ligand atoms
-            self._gemm(prog, hn, 128, L.W_node2, w.Y2, n, 1280, bias=L.b_node2)
-            if v2:
+            y2_done = None
+            if self.lig_windows:
+                # what lane 0 waits for first (the knn-pos query block and all of bond-pos), then the source halves every node's
+                # neighbours read, then the knn-pos target halves
+                y2 = lambda c0, c1, lig_only: self._gemm(prog, hn, 128, L.W_node2[c0:c1], w.Y2[:, c0:c1], n, c1 - c0, bias=L.b_node2[c0:c1],
+                                                         lig_only=lig_only)
+                y2(512, 1280, True)
+                if v2:
+                    self._query_gemm(prog, L.PB, w.Y2, 5 * 128, lig, 1)
+                if self.lig_windows == 2:
+                    y2_done = self._record(prog, 1)
+                y2(256, 512, False)
+                y2(0, 256, True)
+            else:
+                self._gemm(prog, hn, 128, L.W_node2, w.Y2, n, 1280, bias=L.b_node2)
+            if v2 and not self.lig_windows:
                 # the bond position update's query right behind Y2 on the node chain's lane (Y2 is out well before the triplet kernel ends):
                 # the one event lane 0 waits for below then covers it, instead of a second cross-lane hop in front of the attention
                 self._query_gemm(prog, L.PB, w.Y2, 5 * 128, lig, 1)
             more_ahead = ahead and li + 1 < n_layers and not last
-            self._sync(prog, 0, (1,))                  # lane 0 continues after the triplet kernel AND Y2 (which implies lane 2)
+            if y2_done is not None:
+                # lane 0 continues after the triplet kernel and the FIRST Y2 launch (behind h', which implies lane 2): the bond-pos rows and
+                # everything forked from lane 0 below read h' and the bond-pos blocks only; the knn position update stays on lane 1
+                self._wait(prog, 0, y2_done)
+            else:
+                self._sync(prog, 0, (1,))              # lane 0 continues after the triplet kernel AND Y2 (which implies lane 2)
             if v2 and more_ahead:
                 # h' is final and Y2 is out: the next layer's first-layer blocks follow on lane 1 (beside the triplet kernel / the bond
                 # position update), so that the position phase's side lanes start with the triplet queries right away and the next P

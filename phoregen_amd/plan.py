@@ -85,6 +85,15 @@ class BatchPlan:
         bond_off = torch.zeros(B + 1, dtype=torch.long)
         bond_off[1:] = torch.bincount(be, minlength=B).cumsum(0)
         self.g_bond_off = i32(bond_off)                 # first bond row of each graph (graph-keyed device RNG)
+        # row windows of the products that only ligand rows are read from (PgGemm.tile_rows; engine: options.lig_windows): a graph's
+        # ligand run [s, s + n) of the context rows as ceil(n / 64) windows of 64 rows, the k-th starting at min(s + 64 k, n_ctx - 64).
+        # A window may reach into the rows behind the run (or, at the end of the context, in front of it): those are computed from
+        # their own inputs like every other row.  No list below 64 context rows (not one full window)
+        self.lig_windows, self.n_lig_windows = None, 0
+        if self.n_ctx >= 64 and self.n_lig:
+            first = (g_ctx_off[:-1] + nph).tolist()
+            wins = [min(s + 64 * k, self.n_ctx - 64) for s, n_ in zip(first, nlig.tolist()) for k in range((n_ + 63) // 64)]
+            self.lig_windows, self.n_lig_windows = torch.tensor(wins, dtype=torch.int32).to(device), len(wins)
         self.batch_node, self.batch_edge, self.edge_index = bn.to(device), be.to(device), ei_ref.to(device)     # caller's order
         self.edge_ref, self.edge_int = i32(order), i32(inv)            # internal -> caller's row, caller's -> internal row
         self.edge_ref_long, self.edge_int_long = order.to(device), inv.to(device)
