@@ -749,6 +749,75 @@ int pg_fp_nearest(const uint64_t* a, int na, const uint64_t* b, int nb, int same
 int pg_fp_maxmin(const uint64_t* fp, int n, int k, int first, int32_t* picked /*[k]*/, float* pick_sim /*[k]*/, float* work /*[n]*/,
                  uint64_t* slots /*[k]*/, void* stream);
 
+/* Substructure search: for every (frame, graph) the screen decoded and every pattern of a table, the embeddings of the pattern in the
+ * molecule, one wave per (frame, graph, pattern).  Definition: DESIGN.md 2.9 "Substructure".
+ * Target: the kept atoms (class 0..10) in the screen's compact numbering (compact [F][n_lig]) and the pair rows a < b with order 1..4
+ * whose two ends are kept; order 4 (aromatic) is its own order.  An atom's properties: its class, its degree (kept bonds), hcount and
+ * charge (pg_mol_kekule's), in a ring (atom_ring > 0), aromatic (it has a bond of order 4); a bond's: its order and whether it is a
+ * ring bond (ring_size > 0).  ring_size [F][n_bond / 2] and atom_ring [F][n_lig] are pg_mol_rings' outputs, hcount, charge [F][n_lig]
+ * and kekule_status [F][B] pg_mol_kekule's.
+ * Pattern: a connected graph of 1 <= k <= PG_SUB_MAX_ATOMS query atoms, one table row of PG_SUB_PATTERN_BYTES bytes:
+ *   PG_SUB_OFF_K       1 byte   k
+ *   PG_SUB_OFF_MIN     int32    (little endian) the lower bound on `anchors`, >= 0
+ *   PG_SUB_OFF_MAX     int32    the upper bound, -1 = none
+ *   PG_SUB_OFF_ORDER   16 bytes the matching order: the query atom at position d, a permutation of 0 .. k - 1 that starts with atom
+ *                               0 (the anchor) in which every later atom has a bond to an earlier one
+ *   PG_SUB_OFF_ATOMS   16 records of PG_SUB_ATOM_BYTES bytes, query atom q at q: the element set as 11 bits (2 bytes, little endian),
+ *                               degree lo, hi, hcount lo, hi (a byte each, inclusive; 0, 255 = any), flags = charge | ring << 2 |
+ *                               aromatic << 4 with PG_SUB_ANY / PG_SUB_YES / PG_SUB_NO each (charge: YES = +1, NO = 0), one byte 0
+ *   PG_SUB_OFF_BONDS   16 x 16 bytes, symmetric, byte [a][b] = 0 for no query bond, else the accepted orders as bits 0..3 (order o is
+ *                               bit o - 1) | ring << 4 (PG_SUB_YES: a ring bond, PG_SUB_NO: a bridge)
+ * Bytes that belong to atoms beyond k are not read.  An embedding is an injective map of the query atoms to kept atoms with every
+ * atom record met at its image and every query bond on a target bond of an accepted order and ring flag; further target bonds between
+ * images are allowed (a monomorphism).  A pattern that constrains hcount or charge has no embedding on a graph whose kekule_status
+ * has bit 1 (failed) and gets PG_SUB_NO_KEKULE; other patterns do not read hcount, charge or kekule_status.
+ * Outputs, frames dense, [F][B][P] plus the trailing dimension; every element is written:
+ *   embeddings  the number of embeddings, saturating at 2^31 - 1
+ *   anchors     the number of distinct atoms that are the image of query atom 0 in an embedding
+ *   atom_mask   [2] bit c of word c >> 6: the atom with compact index c is in the image of an embedding
+ *   first       [PG_SUB_MAX_ATOMS] the embedding whose images, listed in matching order, are lexicographically smallest, per query
+ *               atom in the table's atom order; -1 beyond k, all -1 without an embedding
+ *   status      PG_SUB_* bits; PG_SUB_OUT_OF_BOUNDS: anchors outside [min, max], or the row has a bound (min > 0 or max >= 0) and
+ *               PG_SUB_TRUNCATED is set
+ * Work bound: a step is one way to go on along the matching order: a partial embedding (the first d - 1 >= 1 query atoms of the order
+ * mapped with every constraint among them met) and an unused atom that meets the d-th query atom's record and is joined to the image
+ * of its walk parent (the earliest atom of the order it has a bond to) by a bond that query bond accepts; its other bonds to earlier
+ * atoms are tested afterwards.  steps(r) = the number of steps whose anchor is the atom r.  A root with
+ * steps(r) > max_steps is abandoned and PG_SUB_TRUNCATED set; then embeddings and anchors are lower bounds, atom_mask a subset and
+ * first some embedding or -1.  Without the bit every output is exact.  1 <= max_steps <= PG_SUB_MAX_STEPS.
+ * table [P][PG_SUB_PATTERN_BYTES] is device memory, table_host the same bytes in host memory: the rows are checked from it before
+ * anything is launched (the library does not synchronise).  1 <= P <= PG_SUB_MAX_PATTERNS; F * B * P must fit one launch.
+ * max_n above PG_MOL_MAX_ATOMS, a negative size, P or max_steps out of range, a malformed row (k outside 1..16, an empty element or
+ * order set, lo > hi, a flag outside any / yes / no, an asymmetric bond byte, an order that is no such permutation, bad bounds) or a
+ * null array with B, F > 0: error before anything is launched, outputs untouched.  Integer work only, so results are exact. */
+#define PG_SUB_MAX_ATOMS 16
+#define PG_SUB_MAX_PATTERNS 256
+#define PG_SUB_MAX_STEPS 1073741824
+#define PG_SUB_PATTERN_BYTES 416
+#define PG_SUB_OFF_K 0
+#define PG_SUB_OFF_MIN 4
+#define PG_SUB_OFF_MAX 8
+#define PG_SUB_OFF_ORDER 16
+#define PG_SUB_OFF_ATOMS 32
+#define PG_SUB_OFF_BONDS 160
+#define PG_SUB_ATOM_BYTES 8
+#define PG_SUB_ATOM_ELEMENTS 0
+#define PG_SUB_ATOM_DEGREE 2
+#define PG_SUB_ATOM_HCOUNT 4
+#define PG_SUB_ATOM_FLAGS 6
+#define PG_SUB_ANY 0
+#define PG_SUB_YES 1
+#define PG_SUB_NO 2
+#define PG_SUB_MATCHED 1
+#define PG_SUB_NO_KEKULE 2
+#define PG_SUB_TRUNCATED 4
+#define PG_SUB_OUT_OF_BOUNDS 8
+int pg_mol_sub(const int8_t* cls, const int8_t* order, const int16_t* compact, const uint8_t* ring_size, const uint8_t* atom_ring,
+               const uint8_t* hcount, const int8_t* charge, const int* kekule_status /*[F][B]*/, const int* g_lig_off /*[B+1]*/,
+               const int* g_bond_off /*[B+1]*/, int B, int F, int n_lig, int n_bond, int max_n, const uint8_t* table /*device*/,
+               const uint8_t* table_host, int P, int max_steps, int* embeddings /*[F*B*P]*/, int* anchors /*[F*B*P]*/,
+               int64_t* atom_mask /*[F*B*P*2]*/, int16_t* first /*[F*B*P*16]*/, int* status /*[F*B*P]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

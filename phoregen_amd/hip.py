@@ -81,6 +81,11 @@ ACT_NONE, ACT_SSP, ACT_RELU = 0, 1, 2
 
 ABI_VERSION = 11
 PG_MOL_MAX_ATOMS = 128          # include/phoregen_hip.h (the library refuses a larger graph before it launches anything)
+# the substructure search (pg_mol_sub): the limits and the layout of a pattern row, as the PG_SUB_* macros of include/phoregen_hip.h
+PG_SUB_MAX_ATOMS, PG_SUB_MAX_PATTERNS, PG_SUB_MAX_STEPS, PG_SUB_PATTERN_BYTES = 16, 256, 1 << 30, 416
+PG_SUB_OFF_K, PG_SUB_OFF_MIN, PG_SUB_OFF_MAX, PG_SUB_OFF_ORDER, PG_SUB_OFF_ATOMS, PG_SUB_OFF_BONDS = 0, 4, 8, 16, 32, 160
+PG_SUB_ATOM_BYTES, PG_SUB_ATOM_ELEMENTS, PG_SUB_ATOM_DEGREE, PG_SUB_ATOM_HCOUNT, PG_SUB_ATOM_FLAGS = 8, 0, 2, 4, 6
+PG_SUB_ANY, PG_SUB_YES, PG_SUB_NO = 0, 1, 2
 _lib = None
 
 _PROTOS = {
@@ -170,6 +175,7 @@ _PROTOS = {
     'pg_fp_tanimoto': (C.c_int, [c_ip, C.c_int, c_ip, C.c_int, c_fp, C.c_void_p]),
     'pg_fp_nearest': (C.c_int, [c_ip, C.c_int, c_ip, C.c_int, C.c_int, c_fp, c_ip, c_fp, C.c_void_p]),
     'pg_fp_maxmin': (C.c_int, [c_ip, C.c_int, C.c_int, C.c_int, c_ip, c_fp, c_fp, c_ip, C.c_void_p]),
+    'pg_mol_sub': (C.c_int, [c_ip] * 10 + [C.c_int] * 5 + [c_ip, c_ip, C.c_int, C.c_int] + [c_ip] * 5 + [C.c_void_p]),
 }
 
 EXPORTS = tuple(_PROTOS)

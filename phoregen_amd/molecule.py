@@ -50,7 +50,10 @@ Fingerprints: `fingerprints` gives every decoded molecule a 2048-bit circular (M
 colour and its `mix`, aromatic bonds as their own order.  `assemble(fingerprints=)`, `sample_valid(fingerprints=)` and `write_sdf` carry
 it; `phoregen_amd.similarity` compares sets of them on the device (Tanimoto matrix, nearest neighbour, internal diversity, MaxMin
 picks).  Exact and independent of the numbering of the atoms; NOT RDKit's ECFP (no duplicate-environment removal, other invariants,
-another hash) and not checked against RDKit."""
+another hash) and not checked against RDKit.
+
+Substructure: `phoregen_amd.substructure` answers whether, how often and where a decoded molecule contains a pattern (csrc/mol_sub.hip;
+DESIGN.md 2.9 "Substructure"); `assemble(substructure=)`, `sample_valid(substructure=)` and `write_sdf` carry it."""
 import ctypes
 from dataclasses import astuple, dataclass
 
@@ -1078,7 +1081,8 @@ def _pairs(n):
 
 
 @torch.no_grad()
-def assemble(results, keys=False, geometry=None, rings=None, kekule=None, features=None, smiles=None, stereo=None, fingerprints=None):
+def assemble(results, keys=False, geometry=None, rings=None, kekule=None, features=None, smiles=None, stereo=None, fingerprints=None,
+             substructure=None):
     """The final prediction as one dict per graph with `decode_data`'s keys and meaning -- 'element' (atomic numbers), 'atom_pos'
     (kept atoms, the tensor's own fp32 values), 'bond_index' [2, n_b] (indices among the kept atoms) and 'bond_type' [n_b] for
     a < b only, in row order -- plus 'status', 'valid', 'n_components' and 'valence' (per kept atom, halves allowed).  The screen runs
@@ -1113,8 +1117,17 @@ def assemble(results, keys=False, geometry=None, rings=None, kekule=None, featur
     the others.
     fingerprints=a `Fingerprints` of this result's final frame: every dict also has 'fingerprint' (np.uint64 [FP_WORDS]), 'fp_bits'
     (its set bits) and 'fp_radius' -- in the same copy; its screen is reused, and it must have been computed from the screen of the
-    others."""
-    geom, pos_t, fps = geometry, results['pred'][1], fingerprints
+    others.
+    substructure=a `Substructure` (phoregen_amd.substructure) of this result's final frame: every dict also has 'substructure' -- per
+    pattern name 'embeddings', 'anchors', 'atoms' (the atoms that lie in an embedding, indices into this dict's atoms), 'first' (the
+    first embedding per query atom, None without one), 'status' (SUB_* bits) and 'status_names' -- and 'substructure_ok' (no pattern
+    is SUB_OUT_OF_BOUNDS), in the same copy; its screen is reused, and it must have been computed from the screen of the others."""
+    geom, pos_t, fps, sub = geometry, results['pred'][1], fingerprints, substructure
+    if sub is not None:
+        from . import substructure as _sub
+        if (not isinstance(sub, _sub.Substructure) or sub.status.size(0) != 1 or sub.screen.cls.size(1) != pos_t.size(-2)
+                or sub.status.device != pos_t.device):
+            raise ValueError('phoregen_amd.molecule.assemble: substructure= must be a Substructure of the final frame of this result')
     if fps is not None and (not isinstance(fps, Fingerprints) or fps.screen is None or fps.fp.size(0) != 1
                             or fps.screen.cls.size(1) != pos_t.size(-2) or fps.fp.device != pos_t.device):
         raise ValueError('phoregen_amd.molecule.assemble: fingerprints= must be a Fingerprints of the final frame of this result')
@@ -1128,7 +1141,9 @@ def assemble(results, keys=False, geometry=None, rings=None, kekule=None, featur
             raise ValueError(f'phoregen_amd.molecule.assemble: {what_a}= and {what_b}= were computed from screens of different results')
     if fps is not None and given and not _same_screen(given[-1][1].screen, fps.screen):
         raise ValueError(f'phoregen_amd.molecule.assemble: {given[-1][0]}= and fingerprints= were computed from screens of different results')
-    sc = given[0][1].screen if given else fps.screen if fps is not None else screen(results, 'final')
+    if sub is not None and (given or fps is not None) and not _same_screen(given[-1][1].screen if given else fps.screen, sub.screen):
+        raise ValueError('phoregen_amd.molecule.assemble: substructure= and the others were computed from screens of different results')
+    sc = given[0][1].screen if given else fps.screen if fps is not None else sub.screen if sub is not None else screen(results, 'final')
     # the parts of the one blob, widest elements first so that every part stays aligned in it
     parts = []
     if keys:
@@ -1138,6 +1153,9 @@ def assemble(results, keys=False, geometry=None, rings=None, kekule=None, featur
         parts += [('t_key', stereo.stereo_key[0], np.uint64)]
     if fps is not None:
         parts += [('p_fp', fps.fp[0], np.uint64)]
+    if sub is not None:
+        parts += [('u_mask', sub.atom_mask[0], np.int64), ('u_emb', sub.embeddings[0], np.int32), ('u_anchors', sub.anchors[0], np.int32),
+                  ('u_status', sub.status[0], np.int32)]
     if rings is not None:
         parts += [('r_status', rings.status[0], np.int32), ('r_counts', rings.counts[0], np.int32)]
     if kekule is not None:
@@ -1159,6 +1177,8 @@ def assemble(results, keys=False, geometry=None, rings=None, kekule=None, featur
         parts += [('p_bits', fps.bits[0], np.int32)]
     parts += [('status', sc.status[0], np.int32), ('counts', sc.counts[0], np.int32), ('pos', pos_t, np.float32),
               ('compact', sc.compact[0], np.int16)]
+    if sub is not None:
+        parts += [('u_first', sub.first[0], np.int16)]
     if geom is not None:
         parts += [('g_atom', geom.point_atom[0], np.int16)]
     if rings is not None:
@@ -1259,6 +1279,12 @@ def assemble(results, keys=False, geometry=None, rings=None, kekule=None, featur
         if fps is not None:
             mols[-1]['fingerprint'] = v['p_fp'].reshape(-1, FP_WORDS)[g].copy()
             mols[-1]['fp_bits'], mols[-1]['fp_radius'] = int(v['p_bits'][g]), fps.radius
+        if sub is not None:
+            n_pat = len(sub.patterns)
+            mols[-1]['substructure'] = _sub.molecule_entries(sub.patterns, v['u_emb'].reshape(-1, n_pat)[g], v['u_anchors'].reshape(-1, n_pat)[g],
+                                                             v['u_mask'].reshape(-1, n_pat, 2)[g], v['u_first'].reshape(-1, n_pat, _sub.MAX_ATOMS)[g],
+                                                             v['u_status'].reshape(-1, n_pat)[g])
+            mols[-1]['substructure_ok'] = _sub.entries_ok(mols[-1]['substructure'])
         n0, h0 = n0 + n, h0 + h
     return mols
 
@@ -1348,8 +1374,11 @@ def write_sdf(path, mols, names=None):
     value' line per count (STEREO_COUNTS), then one line 'centre atom parity label' per stereogenic centre (atom 1-based) and one line
     'bond atom atom stereo label' per stereogenic double bond, values as '+', '-' or '?' (undefined).  The mol block itself does not
     change: its 3D coordinates carry the stereo.  A molecule that carries 'fingerprint' (assemble(fingerprints=)) gets
-    `> <PHOREGEN_FINGERPRINT>`: one line of 512 hex digits, word 0 first, each word as 16 digits, then 'radius R'.  A molecule without
-    one gets no such item: the text is as it always was."""
+    `> <PHOREGEN_FINGERPRINT>`: one line of 512 hex digits, word 0 first, each word as 16 digits, then 'radius R'.  A molecule that
+    carries 'substructure' (assemble(substructure=)) gets `> <PHOREGEN_SUBSTRUCTURE>`: one line per pattern with its name, embeddings,
+    anchors, the status as hex, the atoms that lie in an embedding and the first embedding (1-based, comma-separated, '-' if empty;
+    `phoregen_amd.substructure.parse_sdf_item` reads it back).  A molecule without one gets no such item: the text is as it always
+    was."""
     names = names if names is not None else [''] * len(mols)
     if len(names) != len(mols):
         raise ValueError(f'write_sdf: {len(mols)} molecules, {len(names)} names')
@@ -1376,6 +1405,9 @@ def write_sdf(path, mols, names=None):
                 fh.write(_stereo_item(m))
             if 'fingerprint' in m:
                 fh.write(_fingerprint_item(m))
+            if 'substructure' in m:
+                from .substructure import sdf_item
+                fh.write(sdf_item(m['substructure']))
             fh.write('$$$$\n')
 
 
@@ -1522,7 +1554,7 @@ def duplicate_groups(keys):
 
 # ---- the top-up loop of sample_all.py:79-84,172 ------------------------------------------------------------------------------
 def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, device='cuda', unique=False, geometry=None,
-                 rings=None, kekule=None, features=None, smiles=None, stereo=None, fingerprints=None, **sample_kwargs):
+                 rings=None, kekule=None, features=None, smiles=None, stereo=None, fingerprints=None, substructure=None, **sample_kwargs):
     """Sample until `num_samples` molecules have passed the screen, giving up once more than `max_failed_factor * num_samples` have
     failed (checked before every draw, as the reference does).  Every draw asks for min(batch_size, what is still missing) graphs,
     so never more than `num_samples` are finished.  `sample_kwargs` (fragment=, pos_guidance_opt=, rng=, seed=, ...) go to
@@ -1550,7 +1582,16 @@ def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, d
     rings it needs are computed and carried as for features=.
     fingerprints=True for the default radius, or a radius 0 .. FP_MAX_RADIUS: the molecules then carry 'fingerprint', 'fp_bits' and
     'fp_radius'; nothing is filtered on them.
+    substructure=a list of `Pattern`s (phoregen_amd.substructure), or (patterns, max_steps): a valid molecule is finished only if it is
+    also 'substructure_ok' -- for every pattern `anchors` lies within the pattern's min / max, and no bounded pattern was truncated;
+    one that is not goes to 'failed'.  The molecules then carry 'substructure'.  The rings and the Kekulé form it needs are computed
+    and carried as for features=.
     All of these share one screen per draw."""
+    sub_patterns = sub_steps = None
+    if substructure is not None:
+        from . import substructure as _sub
+        sub_patterns, sub_steps = substructure if isinstance(substructure, tuple) else (substructure, _sub.DEFAULT_STEPS)
+        sub_patterns, sub_steps = _sub._checked(sub_patterns), _sub._check_steps('sample_valid', sub_steps)
     fp_radius = None
     if fingerprints is not None and fingerprints is not False:
         fp_radius = _check_radius('sample_valid', FP_RADIUS if fingerprints is True else fingerprints)
@@ -1610,15 +1651,23 @@ def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, d
         if fp_radius is not None:
             sc = next((x.screen for x in (geo, ring, kek, feat, ster, smi) if x is not None), None)
             fps = _fingerprints(sc if sc is not None else _screen(res, 'final'), fp_radius)
+        subs = None
+        if sub_patterns is not None:
+            sc = next((x.screen for x in (geo, ring, kek, feat, ster, smi, fps) if x is not None), None)
+            subs = _sub.substructure(res, sub_patterns, screen=sc, max_steps=sub_steps,
+                                     rings=ring if ring is not None else feat.rings if feat is not None else ster.rings if ster is not None else None,
+                                     kekule=next((x for x in (kek, feat and feat.kekule, ster and ster.kekule, smi and smi.kekule) if x is not None), None))
         mols = assemble(res, keys=unique, **{k: v for k, v in (('geometry', geo), ('rings', ring), ('kekule', kek), ('features', feat),
-                                                               ('smiles', smi), ('stereo', ster), ('fingerprints', fps)) if v is not None})
+                                                               ('smiles', smi), ('stereo', ster), ('fingerprints', fps),
+                                                               ('substructure', subs)) if v is not None})
         for m in mols:
             if (not m['valid'] or (geometry is not None and not m['geom']['geom_ok'])
                     or (ring_limits is not None and not m['rings']['rings_ok'])
                     or (kek_options is not None and not m['kekule']['kekule_ok'])
                     or (features is not None and not m['features']['features_ok'])
                     or (smiles is not None and not m['smiles']['smiles_ok'])
-                    or (ster is not None and not m['stereo']['stereo_ok'])):
+                    or (ster is not None and not m['stereo']['stereo_ok'])
+                    or (subs is not None and not m['substructure_ok'])):
                 failed.append(m)
                 continue
             key = m['stereo']['stereo_key'] if unique and ster is not None else m['key'] if unique else None

@@ -40,7 +40,11 @@ device (phoregen_amd.similarity): <outdir>/{name}_fingerprints.npy holds them as
 item PHOREGEN_FINGERPRINT.  --diverse K (implies --fingerprints) writes <outdir>/{name}_diverse.txt: the MaxMin picks from the first
 finished molecule on, one line 'index pick_sim' per pick in pick order (at most n of them).  --reference_fps FILE.npy (uint64 [m, 32],
 e.g. another run's {name}_fingerprints.npy; implies --fingerprints) writes <outdir>/{name}_nearest.txt: per finished molecule the
-largest similarity to that set and the row that attains it.  --num_steps shortens the reverse process (default: the model's).  Without them
+largest similarity to that set and the row that attains it.  --substructure patterns.json (implies --valid_only; the format is that
+of tools/patterns/example_patterns.json, phoregen_amd.substructure.Pattern.from_dict) searches every pattern in every molecule on the
+device and finishes a molecule only if, for every pattern, the number of anchors lies within the pattern's min / max;
+<outdir>/{name}_substructure.txt holds one line 'index name embeddings anchors status' per finished molecule and pattern and the .sdf
+files carry the data item PHOREGEN_SUBSTRUCTURE; --substructure_steps N replaces the work bound per root (default 65536).  --num_steps shortens the reverse process (default: the model's).  Without them
 nothing changes.
 """
 import argparse
@@ -59,6 +63,7 @@ from phoregen_amd.data import PHORETYPES1, parse_phore_file  # noqa: E402
 from phoregen_amd.fragment import load_fragment_json  # noqa: E402
 from phoregen_amd.models.diffusion import PhoreDiff  # noqa: E402
 from phoregen_amd import similarity  # noqa: E402
+from phoregen_amd import substructure as substruct  # noqa: E402
 from phoregen_amd.molecule import FP_MAX_RADIUS, FP_RADIUS, FP_WORDS, FeatureLimits, GeomLimits, KekuleOptions, RingLimits, StereoLimits, STATUS_NONFINITE, assemble, point_kinds_of, sample_valid, write_sdf  # noqa: E402
 from phoregen_amd.utils.sample_utils import decode_batch  # noqa: E402
 from phoregen_amd.weights import init_deterministic_  # noqa: E402
@@ -114,6 +119,11 @@ def main():
     ap.add_argument('--reference_fps', type=str, default=None, metavar='FILE.npy',
                     help='implies --fingerprints: uint64 [m, 32]; writes <outdir>/<name>_nearest.txt, per finished molecule the nearest '
                          'similarity to that set and the row that attains it')
+    ap.add_argument('--substructure', type=str, default=None, metavar='patterns.json',
+                    help='implies --valid_only: a molecule whose anchors of a pattern lie outside its min / max is not finished; writes '
+                         '<outdir>/<name>_substructure.txt')
+    ap.add_argument('--substructure_steps', type=int, default=None, metavar='N',
+                    help=f'with --substructure: the work bound per root, 1 .. 2**30 (default {substruct.DEFAULT_STEPS})')
     ap.add_argument('--num_steps', type=int, default=None, help='reverse steps of the sampler (default: the model\'s)')
     ap.add_argument('--sdf', action='store_true', help='write one .sdf per molecule under <outdir>/sdf_results/')
     args = ap.parse_args()
@@ -140,7 +150,15 @@ def main():
         reference = np.load(args.reference_fps)
         if reference.dtype != np.uint64 or reference.ndim != 2 or reference.shape[1] != FP_WORDS:
             ap.error(f'--reference_fps must hold uint64 [m, {FP_WORDS}], not {reference.dtype} {reference.shape}')
-    args.valid_only = args.valid_only or args.fingerprints or args.unique or args.geometry or args.rings or args.kekule or args.features or args.smiles or args.stereo
+    if args.substructure_steps is not None and args.substructure is None:
+        ap.error('--substructure_steps needs --substructure')
+    patterns = None
+    if args.substructure is not None:
+        steps = substruct.DEFAULT_STEPS if args.substructure_steps is None else args.substructure_steps
+        if not 1 <= steps <= substruct.MAX_STEPS:
+            ap.error('--substructure_steps must be 1 .. 2**30')
+        patterns = (substruct.load_patterns_json(args.substructure), steps)
+    args.valid_only = args.valid_only or patterns is not None or args.fingerprints or args.unique or args.geometry or args.rings or args.kekule or args.features or args.smiles or args.stereo
     stereo_limits = StereoLimits(**(args.stereo_limits or {})) if args.stereo else None
     feature_limits = FeatureLimits(**(args.feature_limits or {})) if args.features else None
     geom_limits = GeomLimits(**(args.geom_limits or {}))
@@ -183,7 +201,8 @@ def main():
                 features = (ph.pos.float() + data.center.float(), point_kinds_of(ph.x, PHORETYPES1), feature_limits)
             out = sample_valid(model, data, args.num_samples, batch_size=args.batch_size, unique=args.unique, geometry=geometry,
                                rings=ring_limits, kekule=kekule, features=features, smiles=True if args.smiles else None,
-                               stereo=stereo_limits, **(dict(fingerprints=fp_radius) if args.fingerprints else {}), **kw)
+                               stereo=stereo_limits, **(dict(fingerprints=fp_radius) if args.fingerprints else {}),
+                               **(dict(substructure=patterns) if patterns is not None else {}), **kw)
             done = out['finished']
             print(f"Finished {len(done)} | Failed {len(out['failed'])}" + (f" | Duplicates {len(out['duplicates'])}" if args.unique else ''))
             if args.unique:
@@ -192,6 +211,10 @@ def main():
             if args.smiles:                                            # sample_all.py:157-159
                 with open(os.path.join(args.outdir, data.name + '_SMILES_all.txt'), 'w') as fh:
                     fh.writelines(m['smiles']['text'] + '\n' for m in done)
+            if patterns is not None:
+                with open(os.path.join(args.outdir, data.name + '_substructure.txt'), 'w') as fh:
+                    fh.writelines('%d %s %d %d 0x%02x\n' % (i, name, e['embeddings'], e['anchors'], e['status'])
+                                  for i, m in enumerate(done) for name, e in m['substructure'].items())
             if args.fingerprints:
                 fps = similarity.stack(done, 'cuda')
                 np.save(os.path.join(args.outdir, data.name + '_fingerprints.npy'), fps.cpu().numpy().view(np.uint64))
