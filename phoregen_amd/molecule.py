@@ -56,6 +56,7 @@ Substructure: `phoregen_amd.substructure` answers whether, how often and where a
 DESIGN.md 2.9 "Substructure"); `assemble(substructure=)`, `sample_valid(substructure=)` and `write_sdf` carry it."""
 import ctypes
 from dataclasses import astuple, dataclass
+from functools import cached_property, lru_cache
 
 import numpy as np
 import torch
@@ -206,6 +207,23 @@ ATOMIC_WEIGHT = {1: 1.008, 5: 10.81, 6: 12.011, 7: 14.007, 8: 15.999, 9: 18.998,
                  35: 79.904, 53: 126.904}
 
 
+_BOUND_TEXT = {0x7fffffff: '2**31 - 1', 1 << 30: '2**30'}
+
+
+def _check_int(fn, name, v, lo, hi):
+    """v as an int if it is an integer (no bool) in lo .. hi, else the ValueError of `fn`."""
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+        raise ValueError(f'{fn}: {name} must be an integer in {lo} .. {_BOUND_TEXT.get(hi, hi)}, not {v!r}')
+    return int(v)
+
+
+def _check_number(fn, name, v, positive):
+    """A finite number (no bool) >= 0, or > 0 with `positive`, else the ValueError of `fn`."""
+    if (isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or v < 0
+            or (positive and v == 0)):
+        raise ValueError(f'{fn}: {name} must be a finite number {">" if positive else ">="} 0, not {v!r}')
+
+
 @dataclass(frozen=True)
 class KekuleOptions:
     """allow_charged: if the neutral pass has no Kekulé structure, try again with N+ / P+ / S+ carrying a ring double bond."""
@@ -228,8 +246,7 @@ class RingLimits:
 
     def __post_init__(self):
         for k, v in zip(('ring_min', 'ring_max', 'system_max', 'rotatable_max'), astuple(self)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= v <= 0x7fffffff:
-                raise ValueError(f'RingLimits: {k} must be an integer in 0 .. 2**31 - 1, not {v!r}')
+            _check_int('RingLimits', k, v, 0, 0x7fffffff)
 
 
 @dataclass(frozen=True)
@@ -242,11 +259,8 @@ class FeatureLimits:
     max_unmatched: int = 2 ** 31 - 1
 
     def __post_init__(self):
-        c, m = self.feat_cut, self.max_unmatched
-        if isinstance(c, bool) or not isinstance(c, (int, float, np.integer, np.floating)) or not np.isfinite(c) or c < 0:
-            raise ValueError(f'FeatureLimits: feat_cut must be a finite number >= 0, not {c!r}')
-        if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not 0 <= m <= 0x7fffffff:
-            raise ValueError(f'FeatureLimits: max_unmatched must be an integer in 0 .. 2**31 - 1, not {m!r}')
+        _check_number('FeatureLimits', 'feat_cut', self.feat_cut, False)
+        _check_int('FeatureLimits', 'max_unmatched', self.max_unmatched, 0, 0x7fffffff)
 
 
 @dataclass(frozen=True)
@@ -276,45 +290,37 @@ class StereoLimits:
 
     def __post_init__(self):
         for k in ('vol_min', 'planar_min'):
-            x = getattr(self, k)
-            if isinstance(x, bool) or not isinstance(x, (int, float, np.integer, np.floating)) or not np.isfinite(x) or x <= 0:
-                raise ValueError(f'StereoLimits: {k} must be a finite number > 0, not {x!r}')
-        m = self.max_undefined
-        if isinstance(m, bool) or not isinstance(m, (int, np.integer)) or not 0 <= m <= 0x7fffffff:
-            raise ValueError(f'StereoLimits: max_undefined must be an integer in 0 .. 2**31 - 1, not {m!r}')
+            _check_number('StereoLimits', k, getattr(self, k), True)
+        _check_int('StereoLimits', 'max_undefined', self.max_undefined, 0, 0x7fffffff)
 
 
-_max_valence2 = {}               # device -> uint8 [11], twice MAX_VALENCE in class order
+def _pad4(table):
+    return [list(table[z]) + [0] * (4 - len(table[z])) for z in ATOM_TYPES]
+
+
+# The tables the kernels are handed, as rows of uint8 in class order: twice MAX_VALENCE [11]; KEKULE_DBL_NEUTRAL, KEKULE_DBL_CHARGED,
+# KEKULE_MUST [11] and H_VALENCES [11, 4]; SMILES_VALENCES [11, 4]
+_TABLE_ROWS = {'valence': ([2 * MAX_VALENCE[z] for z in ATOM_TYPES],),
+               'kekule': tuple([d[z] for z in ATOM_TYPES] for d in (KEKULE_DBL_NEUTRAL, KEKULE_DBL_CHARGED, KEKULE_MUST)) + (_pad4(H_VALENCES),),
+               'smiles': (_pad4(SMILES_VALENCES),)}
+
+
+@lru_cache(maxsize=None)
+def _tables(name, device):
+    """The tensors of _TABLE_ROWS[name] on `device`, made once per device."""
+    return tuple(torch.tensor(r, dtype=torch.uint8, device=device) for r in _TABLE_ROWS[name])
 
 
 def _valence_table(device):
-    t = _max_valence2.get(device)
-    if t is None:
-        t = _max_valence2[device] = torch.tensor([2 * MAX_VALENCE[z] for z in ATOM_TYPES], dtype=torch.uint8, device=device)
-    return t
-
-
-_kekule_tables = {}              # device -> (uint8 [11] x 3, uint8 [11, 4])
+    return _tables('valence', device)[0]
 
 
 def _kekule_table(device):
-    t = _kekule_tables.get(device)
-    if t is None:
-        rows = [[d[z] for z in ATOM_TYPES] for d in (KEKULE_DBL_NEUTRAL, KEKULE_DBL_CHARGED, KEKULE_MUST)]
-        rows.append([list(H_VALENCES[z]) + [0] * (4 - len(H_VALENCES[z])) for z in ATOM_TYPES])
-        t = _kekule_tables[device] = tuple(torch.tensor(r, dtype=torch.uint8, device=device) for r in rows)
-    return t
-
-
-_smiles_tables = {}              # device -> uint8 [11, 4]
+    return _tables('kekule', device)
 
 
 def _smiles_table(device):
-    t = _smiles_tables.get(device)
-    if t is None:
-        rows = [list(SMILES_VALENCES[z]) + [0] * (4 - len(SMILES_VALENCES[z])) for z in ATOM_TYPES]
-        t = _smiles_tables[device] = torch.tensor(rows, dtype=torch.uint8, device=device)
-    return t
+    return _tables('smiles', device)[0]
 
 
 @dataclass
@@ -359,6 +365,26 @@ def _screen_of(fn, screen, results, frames, F, N, E, dev):
     if tuple(sc.status.shape) != (F, len(sc.num_atoms)) or sc.cls.size(1) != N or sc.cls.device != dev or 2 * sc.order.size(1) != E:
         raise ValueError(f'phoregen_amd.molecule.{fn}: the screen ({tuple(sc.status.shape)} frames x graphs, {sc.cls.size(1)} atom '
                          f'rows) is not one of this result and frames ({F} frames, {N} atom rows)')
+    return sc
+
+
+def _same_screen(a, b):
+    return a is b or not (a.num_atoms != b.num_atoms or a.status.shape != b.status.shape or a.cls.shape != b.cls.shape
+                          or a.order.shape != b.order.shape or a.cls.device != b.cls.device)
+
+
+def _resolve(fn, results, frames, screen, where='phoregen_amd.molecule', **given):
+    """The one `Screen` a function and the results it was handed (name=result, None: not handed in) work on: screen= if given, else
+    the first result's, else a new one.  It must be one of this result and frames, and every result must have been computed from
+    it.  A `MolKeys` (keys=) carries no screen: its shapes are held against it."""
+    node, _, edge, F, _ = _frames(results, frames)
+    given = {what: x for what, x in given.items() if x is not None}
+    first = next((x.screen for what, x in given.items() if what != 'keys'), None)
+    sc = _screen_of(fn, screen if screen is not None else first, results, frames, F, node.size(-2), edge.size(-2), node.device)
+    for what, x in given.items():
+        if (what == 'keys' and (x.key.shape != sc.status.shape or x.colour.shape != sc.cls.shape or x.key.device != sc.cls.device)
+                or what != 'keys' and not _same_screen(sc, x.screen)):
+            raise ValueError(f'{where}.{fn}: screen= and {what}= were computed from screens of different results')
     return sc
 
 
@@ -460,9 +486,7 @@ class Fingerprints:
 
 
 def _check_radius(fn, radius):
-    if isinstance(radius, bool) or not isinstance(radius, (int, np.integer)) or not 0 <= radius <= FP_MAX_RADIUS:
-        raise ValueError(f'phoregen_amd.molecule.{fn}: radius must be an integer in 0 .. {FP_MAX_RADIUS}, not {radius!r}')
-    return int(radius)
+    return _check_int(f'phoregen_amd.molecule.{fn}', 'radius', radius, 0, FP_MAX_RADIUS)
 
 
 @torch.no_grad()
@@ -747,11 +771,6 @@ class Features:
     rings: Rings                 # the rings it typed from
 
 
-def _same_screen(a, b):
-    return a is b or not (a.num_atoms != b.num_atoms or a.status.shape != b.status.shape or a.cls.shape != b.cls.shape
-                          or a.order.shape != b.order.shape or a.cls.device != b.cls.device)
-
-
 @torch.no_grad()
 def features(results, point_pos, point_kind, point_batch=None, frames='final', screen=None, kekule=None, rings=None,
              limits=FeatureLimits()):
@@ -774,13 +793,8 @@ def features(results, point_pos, point_kind, point_batch=None, frames='final', s
     if not torch.is_tensor(point_kind) or point_kind.numel() != P or point_kind.dtype.is_floating_point or point_kind.dtype == torch.bool:
         raise ValueError(f'phoregen_amd.molecule.features: {P} points, point_kind must hold one integer kind per point, it has '
                          f'{getattr(point_kind, "shape", None)} of {getattr(point_kind, "dtype", None)}')
-    given = [(what, x.screen) for what, x in (('kekule', kekule), ('rings', rings)) if x is not None]
-    sc = _screen_of('features', screen if screen is not None or not given else given[0][1], results, frames, F, pos.size(-2),
-                    edge.size(-2), dev)
+    sc = _resolve('features', results, frames, screen, kekule=kekule, rings=rings)
     B, N = len(sc.num_atoms), pos.size(-2)
-    for what, other in given:
-        if not _same_screen(sc, other):
-            raise ValueError(f'phoregen_amd.molecule.features: screen= and {what}= were computed from screens of different results')
     _check_rows('features', pos, F, 3, 'coordinates', dev)
     kek = kekule if kekule is not None else _kekulize(results, frames, screen=sc)
     rg = rings if rings is not None else _rings(results, frames, screen=sc)
@@ -887,13 +901,7 @@ def stereo(results, frames='final', screen=None, kekule=None, rings=None, keys=N
     _need_cuda('stereo', 'the stereo perception', dev)
     if not isinstance(limits, StereoLimits):
         raise ValueError(f'phoregen_amd.molecule.stereo: limits must be a StereoLimits, not {limits!r}')
-    given = [(what, x.screen) for what, x in (('kekule', kekule), ('rings', rings)) if x is not None]
-    sc = _screen_of('stereo', screen if screen is not None or not given else given[0][1], results, frames, F, pos.size(-2), edge.size(-2), dev)
-    for what, other in given:
-        if not _same_screen(sc, other):
-            raise ValueError(f'phoregen_amd.molecule.stereo: screen= and {what}= were computed from screens of different results')
-    if keys is not None and (keys.key.shape != sc.status.shape or keys.colour.shape != sc.cls.shape or keys.key.device != dev):
-        raise ValueError('phoregen_amd.molecule.stereo: screen= and keys= were computed from screens of different results')
+    sc = _resolve('stereo', results, frames, screen, kekule=kekule, rings=rings, keys=keys)
     _check_rows('stereo', pos, F, 3, 'coordinates', dev)
     kek = kekule if kekule is not None else _kekulize(results, frames, screen=sc)
     rg = rings if rings is not None else _rings(results, frames, screen=sc)
@@ -983,16 +991,11 @@ def smiles(results, frames='final', screen=None, kekule=None, capacity=None, ste
     _need_cuda('smiles', 'the SMILES writer', dev)
     if stereo is not None and not isinstance(stereo, Stereo):
         raise ValueError(f'phoregen_amd.molecule.smiles: stereo= must be a Stereo, not {stereo!r}')
-    first = next((x.screen for x in (kekule, stereo) if x is not None), None)
-    sc = _screen_of('smiles', screen if screen is not None or first is None else first, results, frames, F, node.size(-2), edge.size(-2), dev)
-    for what, x in (('kekule', kekule), ('stereo', stereo)):
-        if x is not None and not _same_screen(sc, x.screen):
-            raise ValueError(f'phoregen_amd.molecule.smiles: screen= and {what}= were computed from screens of different results')
+    sc = _resolve('smiles', results, frames, screen, kekule=kekule, stereo=stereo)
     kek = kekule if kekule is not None else stereo.kekule if stereo is not None else _kekulize(results, frames, screen=sc)
     B, N, max_n = len(sc.num_atoms), node.size(-2), max(sc.num_atoms, default=0)
-    cap = (8 if stereo is None else 12) * max(max_n, 8) if capacity is None else capacity
-    if isinstance(cap, bool) or not isinstance(cap, (int, np.integer)) or not 1 <= cap <= 0x7fffffff:
-        raise ValueError(f'phoregen_amd.molecule.smiles: capacity must be an integer in 1 .. 2**31 - 1, not {capacity!r}')
+    cap = _check_int('phoregen_amd.molecule.smiles', 'capacity', (8 if stereo is None else 12) * max(max_n, 8) if capacity is None else capacity,
+                     1, 0x7fffffff)
     with torch.cuda.device(dev):
         lib = hip.lib()
         out = dict(status=torch.empty(F, B, dtype=torch.int32, device=dev),
@@ -1358,6 +1361,29 @@ def _fingerprint_item(m):
     return '> <PHOREGEN_FINGERPRINT>\n%s\nradius %d\n\n' % (''.join('%016x' % w for w in words), int(m.get('fp_radius', FP_RADIUS)))
 
 
+def _substructure_item(m):
+    from .substructure import sdf_item
+    return sdf_item(m['substructure'])
+
+
+# The data items of `write_sdf`, in the order they are written: (the key a molecule must carry, molecule -> the item's text)
+_SDF_ITEMS = [
+    ('key', lambda m: '> <PHOREGEN_KEY>\n%016x\n\n' % (int(m['key']) & _M64)),
+    ('geom', lambda m: '> <PHOREGEN_GEOM>\nstatus 0x%02x\n' % int(m['geom']['status'])
+     + ''.join('%s %.4f\n' % (k, m['geom'][k]) for k in GEOM_METRICS[:7]) + '\n'),
+    ('rings', lambda m: '> <PHOREGEN_RINGS>\nstatus 0x%02x\n' % int(m['rings']['status'])
+     + ''.join('%s %d\n' % (k, m['rings'][k]) for k in RING_COUNTS) + '\n'),
+    ('kekule', lambda m: '> <PHOREGEN_KEKULE>\nstatus 0x%02x\nformula %s\nmol_weight %.3f\n'
+     % (int(m['kekule']['status']), m['kekule']['formula'], m['kekule']['mol_weight'])
+     + ''.join('%s %d\n' % (k, m['kekule'][_KEKULE_KEYS[k]]) for k in KEKULE_COUNTS) + '\n'),
+    ('features', lambda m: _features_item(m['features'])),
+    ('smiles', lambda m: '> <PHOREGEN_SMILES>\n%s\n\n' % m['smiles']['text'] if m['smiles'].get('smiles_ok') else ''),
+    ('stereo', _stereo_item),
+    ('fingerprint', _fingerprint_item),
+    ('substructure', _substructure_item),
+]
+
+
 def write_sdf(path, mols, names=None):
     """An SDF file: one mol block per molecule, each closed by a '$$$$' line.  A molecule that carries 'key' (assemble(keys=True))
     gets one data item `> <PHOREGEN_KEY>` with the key as 16 hex digits between its block and the '$$$$'.  A molecule that carries
@@ -1385,29 +1411,7 @@ def write_sdf(path, mols, names=None):
     with open(path, 'w') as fh:
         for m, nm in zip(mols, names):
             fh.write(mol_block(m, nm))
-            if 'key' in m:
-                fh.write('> <PHOREGEN_KEY>\n%016x\n\n' % (int(m['key']) & _M64))
-            if 'geom' in m:
-                fh.write('> <PHOREGEN_GEOM>\nstatus 0x%02x\n' % int(m['geom']['status'])
-                         + ''.join('%s %.4f\n' % (k, m['geom'][k]) for k in GEOM_METRICS[:7]) + '\n')
-            if 'rings' in m:
-                fh.write('> <PHOREGEN_RINGS>\nstatus 0x%02x\n' % int(m['rings']['status'])
-                         + ''.join('%s %d\n' % (k, m['rings'][k]) for k in RING_COUNTS) + '\n')
-            if 'kekule' in m:
-                fh.write('> <PHOREGEN_KEKULE>\nstatus 0x%02x\nformula %s\nmol_weight %.3f\n'
-                         % (int(m['kekule']['status']), m['kekule']['formula'], m['kekule']['mol_weight'])
-                         + ''.join('%s %d\n' % (k, m['kekule'][_KEKULE_KEYS[k]]) for k in KEKULE_COUNTS) + '\n')
-            if 'features' in m:
-                fh.write(_features_item(m['features']))
-            if 'smiles' in m and m['smiles'].get('smiles_ok'):
-                fh.write('> <PHOREGEN_SMILES>\n%s\n\n' % m['smiles']['text'])
-            if 'stereo' in m:
-                fh.write(_stereo_item(m))
-            if 'fingerprint' in m:
-                fh.write(_fingerprint_item(m))
-            if 'substructure' in m:
-                from .substructure import sdf_item
-                fh.write(sdf_item(m['substructure']))
+            fh.write(''.join(item(m) for key, item in _SDF_ITEMS if key in m))
             fh.write('$$$$\n')
 
 
@@ -1553,6 +1557,30 @@ def duplicate_groups(keys):
 
 
 # ---- the top-up loop of sample_all.py:79-84,172 ------------------------------------------------------------------------------
+class _Draw:
+    """What the analyses of one draw share: its screen, rings, Kekulé form and keys, each computed on first demand and at most once,
+    the rings and the Kekulé form with the user's limits / options if given, else with the defaults."""
+
+    def __init__(self, res, ring_limits, kek_options):
+        self.res, self.ring_limits, self.kek_options = res, ring_limits or RingLimits(), kek_options or KekuleOptions()
+
+    @cached_property
+    def screen(self):
+        return _screen(self.res, 'final')
+
+    @cached_property
+    def rings(self):
+        return _rings(self.res, screen=self.screen, limits=self.ring_limits)
+
+    @cached_property
+    def kekule(self):
+        return _kekulize(self.res, screen=self.screen, options=self.kek_options)
+
+    @cached_property
+    def keys(self):
+        return molecule_keys(self.screen)
+
+
 def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, device='cuda', unique=False, geometry=None,
                  rings=None, kekule=None, features=None, smiles=None, stereo=None, fingerprints=None, substructure=None, **sample_kwargs):
     """Sample until `num_samples` molecules have passed the screen, giving up once more than `max_failed_factor * num_samples` have
@@ -1618,45 +1646,19 @@ def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, d
         n = min(batch_size, num_samples - len(finished))
         res = model.sample(data, n, device, return_traj=False, **sample_kwargs)
         n_calls += 1
-        geo = None
-        if geometry is True:
-            geo = geometry_for(data, res, ex_col=getattr(model, 'ex_col', 12))
-        elif geometry is not None:
-            point_pos, point_is_ex, limits = geometry
-            geo = _geometry(res, point_pos, point_is_ex, limits=limits)
-        ring = None
-        if ring_limits is not None:
-            ring = _rings(res, screen=geo.screen if geo is not None else None, limits=ring_limits)
-        kek = None
-        if kek_options is not None:
-            kek = _kekulize(res, screen=geo.screen if geo is not None else ring.screen if ring is not None else None, options=kek_options)
-        feat = None
-        if features is not None:
-            sc = next((x.screen for x in (geo, ring, kek) if x is not None), None)
-            if features is True:
-                feat = features_for(data, res, screen=sc, kekule=kek, rings=ring)
-            else:
-                feat = _features(res, features[0], features[1], screen=sc, kekule=kek, rings=ring, limits=features[2])
-        ster = None
-        if stereo_limits is not None:
-            sc = next((x.screen for x in (geo, ring, kek, feat) if x is not None), None)
-            ster = _stereo(res, screen=sc, kekule=kek if kek is not None else feat.kekule if feat is not None else None,
-                           rings=ring if ring is not None else feat.rings if feat is not None else None, limits=stereo_limits)
-        smi = None
-        if smiles is not None:
-            sc = next((x.screen for x in (geo, ring, kek, feat, ster) if x is not None), None)
-            smi = _smiles(res, screen=sc, stereo=ster,
-                          kekule=kek if kek is not None else feat.kekule if feat is not None else ster.kekule if ster is not None else None)
-        fps = None
-        if fp_radius is not None:
-            sc = next((x.screen for x in (geo, ring, kek, feat, ster, smi) if x is not None), None)
-            fps = _fingerprints(sc if sc is not None else _screen(res, 'final'), fp_radius)
-        subs = None
-        if sub_patterns is not None:
-            sc = next((x.screen for x in (geo, ring, kek, feat, ster, smi, fps) if x is not None), None)
-            subs = _sub.substructure(res, sub_patterns, screen=sc, max_steps=sub_steps,
-                                     rings=ring if ring is not None else feat.rings if feat is not None else ster.rings if ster is not None else None,
-                                     kekule=next((x for x in (kek, feat and feat.kekule, ster and ster.kekule, smi and smi.kekule) if x is not None), None))
+        draw = _Draw(res, ring_limits, kek_options)
+        geo = (None if geometry is None else geometry_for(data, res, screen=draw.screen, ex_col=getattr(model, 'ex_col', 12)) if geometry is True
+               else _geometry(res, geometry[0], geometry[1], screen=draw.screen, limits=geometry[2]))
+        ring = draw.rings if ring_limits is not None else None
+        kek = draw.kekule if kek_options is not None else None
+        feat = (None if features is None else features_for(data, res, screen=draw.screen, kekule=draw.kekule, rings=draw.rings) if features is True
+                else _features(res, features[0], features[1], screen=draw.screen, kekule=draw.kekule, rings=draw.rings, limits=features[2]))
+        ster = None if stereo_limits is None else _stereo(res, screen=draw.screen, kekule=draw.kekule, rings=draw.rings, keys=draw.keys,
+                                                          limits=stereo_limits)
+        smi = None if smiles is None else _smiles(res, screen=draw.screen, kekule=draw.kekule, stereo=ster)
+        fps = None if fp_radius is None else _fingerprints(draw.screen, fp_radius)
+        subs = None if sub_patterns is None else _sub.substructure(res, sub_patterns, screen=draw.screen, rings=draw.rings, kekule=draw.kekule,
+                                                                   max_steps=sub_steps)
         mols = assemble(res, keys=unique, **{k: v for k, v in (('geometry', geo), ('rings', ring), ('kekule', kek), ('features', feat),
                                                                ('smiles', smi), ('stereo', ster), ('fingerprints', fps),
                                                                ('substructure', subs)) if v is not None})

@@ -401,9 +401,7 @@ class Substructure:
 
 
 def _check_steps(fn, max_steps):
-    if isinstance(max_steps, bool) or not isinstance(max_steps, (int, np.integer)) or not 1 <= max_steps <= MAX_STEPS:
-        raise ValueError(f'phoregen_amd.substructure.{fn}: max_steps must be an integer in 1 .. 2**30, not {max_steps!r}')
-    return int(max_steps)
+    return M._check_int(f'phoregen_amd.substructure.{fn}', 'max_steps', max_steps, 1, MAX_STEPS)
 
 
 @torch.no_grad()
@@ -414,15 +412,10 @@ def substructure(results, patterns, frames='final', screen=None, rings=None, kek
     tried per root; a (graph, pattern) that exceeds it gets SUB_TRUNCATED and lower bounds, every other row is exact."""
     patterns = _checked(patterns)
     max_steps = _check_steps('substructure', max_steps)
-    node, _, edge, F, _ = M._frames(results, frames)
+    node, _, _, F, _ = M._frames(results, frames)
     dev = node.device
     M._need_cuda('substructure', 'the substructure search', dev)
-    given = [(what, x.screen) for what, x in (('rings', rings), ('kekule', kekule)) if x is not None]
-    sc = M._screen_of('substructure', screen if screen is not None or not given else given[0][1], results, frames, F, node.size(-2),
-                      edge.size(-2), dev)
-    for what, other in given:
-        if not M._same_screen(sc, other):
-            raise ValueError(f'phoregen_amd.substructure.substructure: screen= and {what}= were computed from screens of different results')
+    sc = M._resolve('substructure', results, frames, screen, 'phoregen_amd.substructure', rings=rings, kekule=kekule)
     rg = rings if rings is not None else M.rings(results, frames, screen=sc)
     kek = kekule if kekule is not None else M.kekulize(results, frames, screen=sc)
     B, P = len(sc.num_atoms), len(patterns)

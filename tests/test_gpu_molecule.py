@@ -179,6 +179,90 @@ def test_assemble_with_a_fragment(model):
             assert have.get((a, b)) == t, (g, a, b, t)
 
 
+def _same_entry(a, b):
+    """Equal in type and value: dicts key by key in their order, arrays and tensors with their dtype, a NaN equal to a NaN."""
+    if type(a) is not type(b):
+        return False
+    if isinstance(a, dict):
+        return list(a) == list(b) and all(_same_entry(a[k], b[k]) for k in a)
+    if isinstance(a, np.ndarray):
+        return a.dtype == b.dtype and a.shape == b.shape and np.array_equal(a, b, equal_nan=a.dtype.kind == 'f')
+    if torch.is_tensor(a):
+        return a.dtype == b.dtype and torch.equal(a, b)
+    if isinstance(a, (list, tuple)):
+        return len(a) == len(b) and all(_same_entry(x, y) for x, y in zip(a, b))
+    return a == b or (isinstance(a, float) and a != a and b != b)
+
+
+def test_assemble_with_every_carrier_equals_each_carrier_alone():
+    """The one blob of `assemble`: with every carrier at once (and keys) each carrier's entries are those of `assemble` with that carrier
+    alone, and the base keys those of the plain call.  The batch makes the byte counts odd wherever they can be -- 23 atom rows, 3
+    points (15 point outputs, 3 point kinds), text rows of 33 bytes, one pattern -- so a part that is cut at the wrong place or lies
+    misaligned behind a narrower one shows.  Graphs of 0, 1, 2, 7 (a pyridine-like ring with a methyl group) and 13 atoms (a ring and
+    two chains, atom 5 of the dropped class 11)."""
+    from phoregen_amd import substructure as S
+    C_, N_, O_ = 1, 2, 3
+    ring = {(0, 1): 4, (1, 2): 4, (2, 3): 4, (3, 4): 4, (4, 5): 4, (0, 5): 4}
+    graphs = [([], {}), ([C_], {}), ([C_, O_], {(0, 1): 2}), ([N_] + [C_] * 6, {**ring, (1, 6): 1}),
+              ([C_, C_, O_, C_, C_, 11, C_, C_, C_, N_, C_, C_, O_],
+               {(0, 1): 1, (1, 2): 1, (1, 3): 2, (3, 4): 1, (4, 5): 1, (4, 6): 1, (6, 7): 1, (7, 8): 1, (8, 9): 1, (9, 10): 1, (10, 11): 1, (6, 11): 1,
+                (11, 12): 1})]
+    sizes = [len(c) for c, _ in graphs]
+    assert sizes == [0, 1, 2, 7, 13]
+    rows = [R.scores_from_classes(c, b) for c, b in graphs]
+    res = _result(*(torch.cat([r[i] for r in rows]) for i in range(3)), sizes)
+    pts = torch.tensor([[0.25, 0.5, 0.75], [3.0, 3.25, 3.5], [1.0, 1.0, 1.0]])
+    is_ex, kinds = torch.tensor([0, 0, 1]), torch.tensor([3, 4, M.POINT_IGNORED], dtype=torch.int8)
+    pattern = S.Pattern.from_dict({'name': 'C-O', 'atoms': [{'elements': ['C']}, {'elements': ['O']}], 'bonds': [{'a': 0, 'b': 1, 'orders': [1, 2]}]})
+    sc = M.screen(res)
+    rg, kk = M.rings(res, screen=sc), M.kekulize(res, screen=sc)
+    st = M.stereo(res, screen=sc, kekule=kk, rings=rg)
+    carriers = dict(geometry=M.geometry(res, pts, is_ex, screen=sc), rings=rg, kekule=kk,
+                    features=M.features(res, pts, kinds, screen=sc, kekule=kk, rings=rg), smiles=M.smiles(res, screen=sc, kekule=kk, capacity=33, stereo=st),
+                    stereo=st, fingerprints=M.fingerprints(sc, 1), substructure=S.substructure(res, [pattern], screen=sc, rings=rg, kekule=kk))
+    entries = dict(geometry=['geom'], rings=['rings'], kekule=['kekule'], features=['features'], smiles=['smiles'], stereo=['stereo'],
+                   fingerprints=['fingerprint', 'fp_bits', 'fp_radius'], substructure=['substructure', 'substructure_ok'])
+    every, plain = M.assemble(res, keys=True, **carriers), M.assemble(res)
+    base = list(plain[0])
+    assert len(every) == len(plain) == 5 and base == ['element', 'atom_pos', 'bond_index', 'bond_type', 'status', 'valid', 'n_components', 'valence']
+    for m, p in zip(every, plain):
+        assert list(m) == base + ['key', 'atom_colour'] + [k for what in carriers for k in entries[what]]
+        assert all(_same_entry(m[k], p[k]) for k in base)
+    for m, k in zip(every, M.assemble(res, keys=True)):
+        assert _same_entry(m['key'], k['key']) and _same_entry(m['atom_colour'], k['atom_colour'])
+    for what, x in carriers.items():
+        alone = M.assemble(res, **{what: x})
+        for g, (m, a) in enumerate(zip(every, alone)):
+            assert list(a) == base + entries[what], (what, g)
+            assert all(_same_entry(m[k], a[k]) for k in base + entries[what]), (what, g)
+    # what the batch was built to hold: the decoded graphs, a dropped atom, texts that fit their 33 bytes, a pattern that is found
+    assert [len(m['element']) for m in every] == [0, 1, 2, 7, 12] and every[4]['status'] & M.STATUS_HAD_MASKED_ATOM and every[3]['valid']
+    assert [m['smiles']['smiles_ok'] for m in every] == [True] * 5 and every[2]['smiles']['text'] == 'C=O' and every[0]['smiles']['text'] == ''
+    assert every[3]['kekule']['formula'] == 'C6H7N' and every[3]['rings']['rings'] == 1 and every[4]['rings']['rings'] == 1
+    assert [m['substructure']['C-O']['anchors'] for m in every] == [0, 0, 1, 0, 2] and every[3]['fp_radius'] == 1
+    assert all(m['geom']['point_dist'].shape == (3,) and m['features']['point_kind'].tolist() == [3, 4, -2] for m in every)
+    # the graph without atoms: empty arrays of the right dtype in every carrier
+    e = every[0]
+    empty = {'atom_colour': (e['atom_colour'], np.uint64), 'valence': (e['valence'], np.float64),
+             'bond_ring_size': (e['rings']['bond_ring_size'], np.uint8), 'atom_ring': (e['rings']['atom_ring'], np.uint8),
+             'ring_sys': (e['rings']['ring_sys'], np.int16), 'hcount': (e['kekule']['hcount'], np.uint8), 'charge': (e['kekule']['charge'], np.int8),
+             'atom_fp': (e['features']['atom_fp'], np.uint8), 'atom_rank': (e['smiles']['atom_rank'], np.int16),
+             **{k: (e['stereo'][k], np.int8) for k in ('atom_parity', 'atom_label', 'bond_stereo', 'bond_label')}}
+    for k, (arr, dt) in empty.items():
+        assert isinstance(arr, np.ndarray) and arr.dtype == dt and arr.shape == (0,), k
+    assert e['element'] == [] and e['atom_pos'].shape == (0, 3) and e['bond_index'].shape == (2, 0) and e['kekule']['bond_type'].dtype == torch.int64
+    assert e['kekule']['bond_type'].shape == (0,) and e['features']['atom_types'] == [] and e['kekule']['formula'] == ''
+    assert e['geom']['point_dist'].dtype == np.float32 and e['geom']['point_atom'].dtype == np.int16 and e['geom']['point_atom'].tolist() == [-1] * 3
+    assert e['features']['point_dist'].dtype == np.float32 and e['features']['point_matched'].dtype == np.bool_
+    assert e['fingerprint'].dtype == np.uint64 and e['fingerprint'].shape == (M.FP_WORDS,) and not e['fingerprint'].any() and e['fp_bits'] == 0
+    assert e['substructure']['C-O'] == {'embeddings': 0, 'anchors': 0, 'atoms': [], 'first': None, 'status': 0, 'status_names': ()}
+    assert e['key'] == M.KEY_EMPTY and type(e['stereo']['stereo_key']) is int and e['status'] == M.STATUS_NO_ATOMS
+    # every status is a Python int
+    for m in every:
+        assert type(m['status']) is int and type(m['substructure']['C-O']['status']) is int
+        assert all(type(m[k]['status']) is int for k in ('geom', 'rings', 'kekule', 'features', 'smiles', 'stereo'))
+
+
 class _Rota:
     """Test double for the network: `.sample` returns device tensors that encode a fixed rota of three-atom molecules."""
     KINDS = {'valid': ([1, 1, 3], {(0, 1): 1, (1, 2): 1}), 'disconnected': ([1, 1, 3], {(0, 1): 1}),
