@@ -470,6 +470,29 @@ int pg_mol_screen(const float* node_scores, int64_t node_fs, const float* edge_s
                   int n_bond, int max_n, const uint8_t* max_valence2 /*[11]*/, int* status, int* counts, int8_t* cls,
                   int16_t* compact, uint8_t* valence2, int16_t* comp, int8_t* order, void* stream);
 
+/* The same screen with the bonds perceived from the coordinates instead of the edge scores (phoregen_amd/molecule.py
+ * screen(bonds='distance'); the rule of the reference's utils/predict_bonds.py, DESIGN.md 2.9 "Distance bonds").  Atom classes are
+ * the argmax of node_scores as above.  For the pair a < b of two kept atoms whose coordinates are finite, with d100 = 100.0f *
+ * sqrtf(dx*dx + dy*dy + dz*dz) in fp32 and t = thresholds[class a][class b]: order 0 unless d100 < t[0]; then 2 if d100 < t[1], and 3
+ * if also d100 < t[2]; else 1.  All compares are strict, so an entry of 0 means "no such bond".  thresholds [11][11][3] fp32 (bond
+ * length + margin in pm; the caller hands in a symmetric table).  Any other pair has order 0.  There is no aromatic order and no
+ * absorbing class: PG_MOL_HAD_ABSORBING_BOND is never set.  PG_MOL_DIST_UNMAPPED_ELEMENT (informational) marks a graph with a kept atom
+ * of class 0 (B) or 5 (Si), the two elements the reference's rule cannot name.  The seven outputs are pg_mol_screen's, in the same
+ * layouts, every element written.
+ * edge_scores may be NULL.  If not (edge_fs as above; only the first half of a graph's rows is read), agree [F][B][6] is written: over
+ * the pairs a < b of kept atoms with finite coordinates, with p = the argmax of the pair's scores (0 and 5: no bond) and o = the
+ * distance order, the number of pairs with p = o in 1..3; p = 4 and o in 1..2; both bonded otherwise; p only; o only; neither.
+ * With edge_scores NULL agree is not touched.
+ * node_scores and node_fs 16-byte, counts 16-byte, a non-null edge_scores and edge_fs 8-byte aligned.  max_n above PG_MOL_MAX_ATOMS,
+ * a negative size, a null table, or edge_scores without agree: error before anything is launched, outputs untouched.  Compares and
+ * integer counts only (no floating-point sum), so a graph's rows do not depend on its batch. */
+#define PG_MOL_DIST_UNMAPPED_ELEMENT 64 /* informational: a kept B or Si atom                                  */
+int pg_mol_screen_dist(const float* node_scores, int64_t node_fs, const float* pos, int64_t pos_fs, const float* edge_scores,
+                       int64_t edge_fs, const int* g_lig_off /*[B+1]*/, const int* g_bond_off /*[B+1]*/, int B, int F, int n_lig,
+                       int n_bond, int max_n, const uint8_t* max_valence2 /*[11]*/, const float* thresholds /*[11][11][3]*/,
+                       int* status, int* counts, int8_t* cls, int16_t* compact, uint8_t* valence2, int16_t* comp, int8_t* order,
+                       int* agree /*[F][B][6]*/, void* stream);
+
 /* Identity keys of the molecules the screen decoded, one wave per (frame, graph).  Reads the screen's outputs cls [F][n_lig] and
  * order [F][n_bond / 2] (frames are dense: frame f starts at f * n_lig / f * n_bond / 2) with the same offsets; an atom is kept if
  * its class is 0..10, a pair row is a bond if its order is 1..4 and both ends are kept.  key [F][B]: a 64-bit value that does not

@@ -155,6 +155,8 @@ _PROTOS = {
                                    C.c_int, c_fp, C.c_int, c_fp, c_fp, c_fp, C.c_void_p]),
     'pg_mol_screen': (C.c_int, [c_fp, C.c_int64, c_fp, C.c_int64, c_fp, C.c_int64, c_ip, c_ip, C.c_int, C.c_int, C.c_int, C.c_int,
                                 C.c_int, c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, C.c_void_p]),
+    'pg_mol_screen_dist': (C.c_int, [c_fp, C.c_int64, c_fp, C.c_int64, c_fp, C.c_int64, c_ip, c_ip, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     C.c_int, c_ip, c_fp, c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, c_ip, C.c_void_p]),
     'pg_mol_key': (C.c_int, [c_ip, c_ip, c_ip, c_ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_ip, c_ip, C.c_void_p]),
     'pg_mol_geom': (C.c_int, [c_fp, C.c_int64, c_ip, c_ip, c_ip, c_ip, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_fp, c_ip, C.c_int,
                               c_ip, c_ip, C.c_int, C.POINTER(C.c_float), c_fp, c_ip, c_fp, c_ip, c_ip, C.c_void_p]),

@@ -52,10 +52,15 @@ it; `phoregen_amd.similarity` compares sets of them on the device (Tanimoto matr
 picks).  Exact and independent of the numbering of the atoms; NOT RDKit's ECFP (no duplicate-environment removal, other invariants,
 another hash) and not checked against RDKit.
 
+Distance bonds: `screen(bonds='distance')` perceives the bonds from the coordinates with the reference's `--add_edge distance` rule
+(csrc/mol_screen_dist.hip; DESIGN.md 2.9 "Distance bonds") and returns the same `Screen`, so everything above works on them unchanged;
+`bond_agreement` also counts how they agree with the predicted bonds.  `assemble(screen=)`, `sample_valid(add_edge=)` and `write_sdf`
+carry it.  Orders 1..3 only: no aromatic order, no hydrogens, no `openbabel` mode.
+
 Substructure: `phoregen_amd.substructure` answers whether, how often and where a decoded molecule contains a pattern (csrc/mol_sub.hip;
 DESIGN.md 2.9 "Substructure"); `assemble(substructure=)`, `sample_valid(substructure=)` and `write_sdf` carry it."""
 import ctypes
-from dataclasses import astuple, dataclass
+from dataclasses import astuple, dataclass, replace
 from functools import cached_property, lru_cache
 
 import numpy as np
@@ -75,6 +80,17 @@ STATUS_NAMES = {STATUS_NO_ATOMS: 'NO_ATOMS', STATUS_DISCONNECTED: 'DISCONNECTED'
                 STATUS_NONFINITE: 'NONFINITE', STATUS_HAD_MASKED_ATOM: 'HAD_MASKED_ATOM',
                 STATUS_HAD_ABSORBING_BOND: 'HAD_ABSORBING_BOND'}
 
+# `screen(bonds='distance')` only (DESIGN.md 2.9 "Distance bonds"; kept out of STATUS_NAMES / FAIL_MASK, which describe pg_mol_screen)
+STATUS_DIST_UNMAPPED_ELEMENT = 64  # informational: a kept B or Si atom, for which the reference's `predict_bonds` raises KeyError
+DISTANCE_STATUS_NAMES = {**{b: n for b, n in STATUS_NAMES.items() if b != STATUS_HAD_ABSORBING_BOND},
+                         STATUS_DIST_UNMAPPED_ELEMENT: 'DIST_UNMAPPED_ELEMENT'}
+BOND_MODES = ('predicted', 'distance')
+# columns of `Screen.agree`: the pairs a < b of kept atoms with finite coordinates by (predicted order p, distance order o)
+BOND_AGREE_COUNTS = ('both_same',        # p = o in 1..3
+                     'both_aromatic',    # p = 4 and o in 1..2
+                     'both_differ',      # both bonded, neither of the above
+                     'predicted_only', 'distance_only', 'neither')
+
 # Largest explicit valence an atom may carry, by atomic number: the largest entry of each element's default valence list as RDKit has
 # it, with N raised to 4 because the reference turns a four-valent N into N+ instead of failing (utils/sample_utils.py:437-440).
 # CAVEAT: written from memory; RDKit is not a dependency of this project and the table has not been checked against it.  The rule is
@@ -82,6 +98,58 @@ STATUS_NAMES = {STATUS_NO_ATOMS: 'NO_ATOMS', STATUS_DISCONNECTED: 'DISCONNECTED'
 # This is the table's only copy: the kernel and the tests' restatement are handed it.
 MAX_VALENCE = {5: 3, 6: 4, 7: 4, 8: 2, 9: 1, 14: 4, 15: 7, 16: 6, 17: 1, 35: 1, 53: 5}
 assert list(MAX_VALENCE) == ATOM_TYPES
+
+# Typical bond lengths in pm by element pair, in ATOM_TYPES order (B C N O F Si P S Cl Br I): single, double, triple; 0 = no entry.
+# From the two public tables the reference's utils/predict_bonds.py cites (wiredchemist.com bond energies and lengths;
+# chemistry-reference.com bond lengths and enthalpies), as that file's lookup (lower atomic number first) reads them: so C=S has its
+# 160 although the table lists it from carbon's side only, fifteen pairs have no single-bond length and never bond (ten of boron's
+# eleven -- only B-Cl has one -- and N-Si, Si-P, P-I, Cl-I, Br-I).  tests/test_molbonds_host.py pins every entry to values recorded
+# from the reference.  This is the table's only copy: the kernel is handed `length + margin`, the tests' restatement reads this.
+BOND_LENGTHS_PM = (
+    (   # single
+     #        B    C    N    O    F   Si    P    S   Cl   Br    I
+        (  0,   0,   0,   0,   0,   0,   0,   0, 175,   0,   0),   # B
+        (  0, 154, 147, 143, 135, 185, 184, 182, 177, 194, 214),   # C
+        (  0, 147, 145, 140, 136,   0, 177, 168, 175, 214, 222),   # N
+        (  0, 143, 140, 148, 142, 163, 163, 151, 164, 172, 194),   # O
+        (  0, 135, 136, 142, 142, 160, 156, 158, 166, 178, 187),   # F
+        (  0, 185,   0, 163, 160, 233,   0, 200, 202, 215, 243),   # Si
+        (  0, 184, 177, 163, 156,   0, 221, 210, 203, 222,   0),   # P
+        (  0, 182, 168, 151, 158, 200, 210, 204, 207, 225, 234),   # S
+        (175, 177, 175, 164, 166, 202, 203, 207, 199, 214,   0),   # Cl
+        (  0, 194, 214, 172, 178, 215, 222, 225, 214, 228,   0),   # Br
+        (  0, 214, 222, 194, 187, 243,   0, 234,   0,   0, 266),   # I
+    ),
+    (   # double
+     #        B    C    N    O    F   Si    P    S   Cl   Br    I
+        (  0,   0,   0,   0,   0,   0,   0,   0,   0,   0,   0),   # B
+        (  0, 134, 129, 120,   0,   0,   0, 160,   0,   0,   0),   # C
+        (  0, 129, 125, 121,   0,   0,   0,   0,   0,   0,   0),   # N
+        (  0, 120, 121, 121,   0,   0, 150,   0,   0,   0,   0),   # O
+        (  0,   0,   0,   0,   0,   0,   0,   0,   0,   0,   0),   # F
+        (  0,   0,   0,   0,   0,   0,   0,   0,   0,   0,   0),   # Si
+        (  0,   0,   0, 150,   0,   0,   0, 186,   0,   0,   0),   # P
+        (  0, 160,   0,   0,   0,   0, 186,   0,   0,   0,   0),   # S
+        (  0,   0,   0,   0,   0,   0,   0,   0,   0,   0,   0),   # Cl
+        (  0,   0,   0,   0,   0,   0,   0,   0,   0,   0,   0),   # Br
+        (  0,   0,   0,   0,   0,   0,   0,   0,   0,   0,   0),   # I
+    ),
+    (   # triple
+     #        B    C    N    O    F   Si    P    S   Cl   Br    I
+        (  0,   0,   0,   0,   0,   0,   0,   0,   0,   0,   0),   # B
+        (  0, 120, 116, 113,   0,   0,   0,   0,   0,   0,   0),   # C
+        (  0, 116, 110,   0,   0,   0,   0,   0,   0,   0,   0),   # N
+        (  0, 113,   0,   0,   0,   0,   0,   0,   0,   0,   0),   # O
+        (  0,   0,   0,   0,   0,   0,   0,   0,   0,   0,   0),   # F
+        (  0,   0,   0,   0,   0,   0,   0,   0,   0,   0,   0),   # Si
+        (  0,   0,   0,   0,   0,   0,   0,   0,   0,   0,   0),   # P
+        (  0,   0,   0,   0,   0,   0,   0,   0,   0,   0,   0),   # S
+        (  0,   0,   0,   0,   0,   0,   0,   0,   0,   0,   0),   # Cl
+        (  0,   0,   0,   0,   0,   0,   0,   0,   0,   0,   0),   # Br
+        (  0,   0,   0,   0,   0,   0,   0,   0,   0,   0,   0),   # I
+    ),
+)
+assert all(len(m) == len(ATOM_TYPES) and all(len(r) == len(ATOM_TYPES) for r in m) for m in BOND_LENGTHS_PM)
 ELEMENT_SYMBOL = {5: 'B', 6: 'C', 7: 'N', 8: 'O', 9: 'F', 14: 'Si', 15: 'P', 16: 'S', 17: 'Cl', 35: 'Br', 53: 'I'}
 MAX_ATOMS = hip.PG_MOL_MAX_ATOMS
 
@@ -294,6 +362,20 @@ class StereoLimits:
         _check_int('StereoLimits', 'max_undefined', self.max_undefined, 0, 0x7fffffff)
 
 
+@dataclass(frozen=True)
+class BondMargins:
+    """Margins of the distance bond rule in pm (the reference's margin1 / margin2 / margin3): a pair is bonded iff 100 d < single +
+    `single`, then double iff 100 d < double + `double`, then triple iff 100 d < triple + `triple`; every comparison is strict and in
+    fp32.  A pair without a table entry never takes that order, whatever the margin."""
+    single: float = 10
+    double: float = 5
+    triple: float = 3
+
+    def __post_init__(self):
+        for k in ('single', 'double', 'triple'):
+            _check_number('BondMargins', k, getattr(self, k), False)
+
+
 def _pad4(table):
     return [list(table[z]) + [0] * (4 - len(table[z])) for z in ATOM_TYPES]
 
@@ -309,6 +391,20 @@ _TABLE_ROWS = {'valence': ([2 * MAX_VALENCE[z] for z in ATOM_TYPES],),
 def _tables(name, device):
     """The tensors of _TABLE_ROWS[name] on `device`, made once per device."""
     return tuple(torch.tensor(r, dtype=torch.uint8, device=device) for r in _TABLE_ROWS[name])
+
+
+def bond_thresholds(margins=None):
+    """The distance rule's thresholds as the kernel takes them: fp32 [11, 11, 3] in ATOM_TYPES order, `length + margin` in pm, 0 where
+    the table has no entry (no distance is below 0, so such a pair never takes that order)."""
+    margins = BondMargins() if margins is None else margins
+    length = np.asarray(BOND_LENGTHS_PM, dtype=np.float64).transpose(1, 2, 0)
+    return np.ascontiguousarray(np.where(length > 0, length + np.asarray(astuple(margins), dtype=np.float64), 0.0), dtype=np.float32)
+
+
+@lru_cache(maxsize=None)
+def _bond_threshold_table(margins, device):
+    """`bond_thresholds(margins)` on `device`, made once per margins and device."""
+    return torch.from_numpy(bond_thresholds(margins)).to(device)
 
 
 def _valence_table(device):
@@ -337,6 +433,8 @@ class Screen:
     lig_off: torch.Tensor        # int32 [B + 1]
     bond_off: torch.Tensor       # int32 [B + 1]  (directed rows, both halves)
     num_atoms: list              # B ints
+    bonds: str = 'predicted'     # where `order` comes from: 'predicted' (argmax of the edge scores) or 'distance' (the coordinates)
+    agree: torch.Tensor = None   # int32 [F, B, 6] BOND_AGREE_COUNTS; `bond_agreement` only
 
 
 def _need_cuda(fn, noun, dev, holder='result'):
@@ -370,7 +468,7 @@ def _screen_of(fn, screen, results, frames, F, N, E, dev):
 
 def _same_screen(a, b):
     return a is b or not (a.num_atoms != b.num_atoms or a.status.shape != b.status.shape or a.cls.shape != b.cls.shape
-                          or a.order.shape != b.order.shape or a.cls.device != b.cls.device)
+                          or a.order.shape != b.order.shape or a.cls.device != b.cls.device or a.bonds != b.bonds)
 
 
 def _resolve(fn, results, frames, screen, where='phoregen_amd.molecule', **given):
@@ -409,10 +507,23 @@ def _frames(results, frames):
 
 
 @torch.no_grad()
-def screen(results, frames='final'):
+def screen(results, frames='final', bonds='predicted', margins=BondMargins()):
     """Decode and screen every graph of a `sample` / `sample_batch` result on the device its tensors live on.
     frames='final': the final prediction (`results['pred']`, F = 1); 'traj': every frame of the saved trajectory.
+    bonds='predicted': the order of a pair is the argmax of its edge scores (pg_mol_screen).  bonds='distance': it is perceived from
+    the coordinates with the reference's `--add_edge distance` rule (pg_mol_screen_dist; BOND_LENGTHS_PM, `margins`; DESIGN.md 2.9
+    "Distance bonds"): orders 1..3 only, the edge scores are not read, the status may carry STATUS_DIST_UNMAPPED_ELEMENT and never
+    STATUS_HAD_ABSORBING_BOND.  The `Screen` has the same arrays either way, so everything that takes one works on either.
     `results` is only read."""
+    return _screen_any(results, frames, bonds, margins, False)
+
+
+def _screen_any(results, frames, bonds, margins, _agree):
+    """`screen`; _agree: with bonds='distance', also read the edge scores and fill `Screen.agree`."""
+    if bonds not in BOND_MODES:
+        raise ValueError(f'phoregen_amd.molecule.screen: bonds must be one of {BOND_MODES}, not {bonds!r}')
+    if not isinstance(margins, BondMargins):
+        raise ValueError(f'phoregen_amd.molecule.screen: margins must be a BondMargins, not {margins!r}')
     node, pos, edge, F, (node_fs, edge_fs, pos_fs) = _frames(results, frames)
     dev = node.device
     _need_cuda('screen', 'the screen', dev)
@@ -438,8 +549,22 @@ def screen(results, frames='final'):
                    cls=torch.empty(F, N, dtype=torch.int8, device=dev), compact=torch.empty(F, N, dtype=torch.int16, device=dev),
                    valence2=torch.empty(F, N, dtype=torch.uint8, device=dev), comp=torch.empty(F, N, dtype=torch.int16, device=dev),
                    order=torch.empty(F, H, dtype=torch.int8, device=dev))
-        _launch(lib, node, node_fs, edge, edge_fs, pos, pos_fs, lig_off, bond_off, B, F, N, E, max(num_atoms, default=0), out)
-    return Screen(valid=(out['status'] & FAIL_MASK) == 0, lig_off=lig_off, bond_off=bond_off, num_atoms=num_atoms, **out)
+        agree = None
+        if bonds == 'predicted':
+            _launch(lib, node, node_fs, edge, edge_fs, pos, pos_fs, lig_off, bond_off, B, F, N, E, max(num_atoms, default=0), out)
+        else:
+            agree = torch.empty(F, B, len(BOND_AGREE_COUNTS), dtype=torch.int32, device=dev) if _agree else None
+            _launch_dist(lib, node, node_fs, pos, pos_fs, edge if _agree else None, edge_fs, lig_off, bond_off, B, F, N, E,
+                         max(num_atoms, default=0), _bond_threshold_table(margins, dev), out, agree)
+    return Screen(valid=(out['status'] & FAIL_MASK) == 0, lig_off=lig_off, bond_off=bond_off, num_atoms=num_atoms, bonds=bonds,
+                  agree=agree, **out)
+
+
+def bond_agreement(results, frames='final', margins=BondMargins()):
+    """The distance `Screen` of `screen(bonds='distance')` with `agree` filled: int32 [F, B, 6], per (frame, graph) the pairs a < b of
+    kept atoms with finite coordinates counted by how the predicted bond (argmax of the pair's edge scores; class 5 is no bond) and
+    the distance bond agree (BOND_AGREE_COUNTS).  One launch; the reversed half of the edge rows is not read."""
+    return _screen_any(results, frames, 'distance', margins, True)
 
 
 _screen = screen                 # (functions below take a `screen=` argument)
@@ -531,6 +656,20 @@ def _launch(lib, node, node_fs, edge, edge_fs, pos, pos_fs, lig_off, bond_off, B
                                 out['status'].data_ptr(), out['counts'].data_ptr(), out['cls'].data_ptr(),
                                 out['compact'].data_ptr(), out['valence2'].data_ptr(), out['comp'].data_ptr(),
                                 out['order'].data_ptr(), hip.stream_ptr()), 'pg_mol_screen')
+
+
+def _launch_dist(lib, node, node_fs, pos, pos_fs, edge, edge_fs, lig_off, bond_off, B, F, N, E, max_n, thresholds, out, agree):
+    """pg_mol_screen_dist on the current stream; edge / agree: None, or the edge scores and the [F, B, 6] output of the agreement
+    counts.  A graph above MAX_ATOMS is the library's error (RuntimeError with its message): nothing is launched and `out` is not
+    written."""
+    _check_arrays('screen', node.device, [(thresholds, torch.float32)] + ([] if agree is None else [(agree, torch.int32)]))
+    if thresholds.numel() != 3 * len(ATOM_TYPES) ** 2 or (agree is not None and agree.numel() != F * B * len(BOND_AGREE_COUNTS)):
+        raise ValueError('phoregen_amd.molecule.screen: the threshold table must be [11, 11, 3], the agreement counts [F, B, 6]')
+    hip.check(lib.pg_mol_screen_dist(node.data_ptr(), node_fs, pos.data_ptr(), pos_fs, hip.ptr(edge), edge_fs, lig_off.data_ptr(),
+                                     bond_off.data_ptr(), B, F, N, E, max_n, _valence_table(node.device).data_ptr(),
+                                     thresholds.data_ptr(), out['status'].data_ptr(), out['counts'].data_ptr(), out['cls'].data_ptr(),
+                                     out['compact'].data_ptr(), out['valence2'].data_ptr(), out['comp'].data_ptr(),
+                                     out['order'].data_ptr(), hip.ptr(agree), hip.stream_ptr()), 'pg_mol_screen_dist')
 
 
 @dataclass
@@ -1085,7 +1224,7 @@ def _pairs(n):
 
 @torch.no_grad()
 def assemble(results, keys=False, geometry=None, rings=None, kekule=None, features=None, smiles=None, stereo=None, fingerprints=None,
-             substructure=None):
+             substructure=None, screen=None):
     """The final prediction as one dict per graph with `decode_data`'s keys and meaning -- 'element' (atomic numbers), 'atom_pos'
     (kept atoms, the tensor's own fp32 values), 'bond_index' [2, n_b] (indices among the kept atoms) and 'bond_type' [n_b] for
     a < b only, in row order -- plus 'status', 'valid', 'n_components' and 'valence' (per kept atom, halves allowed).  The screen runs
@@ -1124,8 +1263,16 @@ def assemble(results, keys=False, geometry=None, rings=None, kekule=None, featur
     substructure=a `Substructure` (phoregen_amd.substructure) of this result's final frame: every dict also has 'substructure' -- per
     pattern name 'embeddings', 'anchors', 'atoms' (the atoms that lie in an embedding, indices into this dict's atoms), 'first' (the
     first embedding per query atom, None without one), 'status' (SUB_* bits) and 'status_names' -- and 'substructure_ok' (no pattern
-    is SUB_OUT_OF_BOUNDS), in the same copy; its screen is reused, and it must have been computed from the screen of the others."""
+    is SUB_OUT_OF_BOUNDS), in the same copy; its screen is reused, and it must have been computed from the screen of the others.
+    screen=a `Screen` of this result's final frame: its `order` becomes 'bond_index' / 'bond_type' (so with a `screen(bonds='distance')`
+    the molecules have the distance-perceived bonds); every other result handed in must have been computed from it or from one of the
+    same bond source.  Every dict then also has 'bonds' (the screen's mode) and, with a `bond_agreement` screen, 'bond_agreement':
+    the six BOND_AGREE_COUNTS by name."""
     geom, pos_t, fps, sub = geometry, results['pred'][1], fingerprints, substructure
+    sc_in = screen
+    if sc_in is not None and (not isinstance(sc_in, Screen) or sc_in.status.size(0) != 1 or sc_in.cls.size(1) != pos_t.size(-2)
+                              or sc_in.cls.device != pos_t.device):
+        raise ValueError('phoregen_amd.molecule.assemble: screen= must be a Screen of the final frame of this result')
     if sub is not None:
         from . import substructure as _sub
         if (not isinstance(sub, _sub.Substructure) or sub.status.size(0) != 1 or sub.screen.cls.size(1) != pos_t.size(-2)
@@ -1146,7 +1293,13 @@ def assemble(results, keys=False, geometry=None, rings=None, kekule=None, featur
         raise ValueError(f'phoregen_amd.molecule.assemble: {given[-1][0]}= and fingerprints= were computed from screens of different results')
     if sub is not None and (given or fps is not None) and not _same_screen(given[-1][1].screen if given else fps.screen, sub.screen):
         raise ValueError('phoregen_amd.molecule.assemble: substructure= and the others were computed from screens of different results')
-    sc = given[0][1].screen if given else fps.screen if fps is not None else sub.screen if sub is not None else screen(results, 'final')
+    others = [(what, x.screen) for what, x in given] + [(what, x.screen) for what, x in (('fingerprints', fps), ('substructure', sub))
+                                                        if x is not None]
+    for what, x_sc in others if sc_in is not None else ():
+        if not _same_screen(sc_in, x_sc):
+            raise ValueError(f'phoregen_amd.molecule.assemble: screen= and {what}= were computed from screens of different results or '
+                             f'bond sources ({sc_in.bonds!r}, {x_sc.bonds!r})')
+    sc = sc_in if sc_in is not None else others[0][1] if others else _screen(results, 'final')
     # the parts of the one blob, widest elements first so that every part stays aligned in it
     parts = []
     if keys:
@@ -1178,6 +1331,8 @@ def assemble(results, keys=False, geometry=None, rings=None, kekule=None, featur
                   ('f_range', features.point_range, np.int32)]
     if fps is not None:
         parts += [('p_bits', fps.bits[0], np.int32)]
+    if sc_in is not None and sc.agree is not None:
+        parts += [('agree', sc.agree[0], np.int32)]
     parts += [('status', sc.status[0], np.int32), ('counts', sc.counts[0], np.int32), ('pos', pos_t, np.float32),
               ('compact', sc.compact[0], np.int16)]
     if sub is not None:
@@ -1233,6 +1388,10 @@ def assemble(results, keys=False, geometry=None, rings=None, kekule=None, featur
                      'bond_type': torch.from_numpy(o[nz].astype(np.int64)),
                      'status': int(status[g]), 'valid': (int(status[g]) & FAIL_MASK) == 0, 'n_components': int(counts[g, 2]),
                      'valence': valence2[n0:n0 + n][keep].astype(np.float64) / 2.0})
+        if sc_in is not None:
+            mols[-1]['bonds'] = sc.bonds
+            if sc.agree is not None:
+                mols[-1]['bond_agreement'] = {k: int(x) for k, x in zip(BOND_AGREE_COUNTS, v['agree'].reshape(-1, len(BOND_AGREE_COUNTS))[g])}
         if keys:
             mols[-1]['key'], mols[-1]['atom_colour'] = int(v['key'][g]), v['colour'][n0:n0 + n][keep].copy()
         if geom is not None:
@@ -1367,7 +1526,14 @@ def _substructure_item(m):
 
 
 # The data items of `write_sdf`, in the order they are written: (the key a molecule must carry, molecule -> the item's text)
+def _bonds_item(m):
+    """The PHOREGEN_BONDS data item of a molecule that carries 'bonds' (`assemble(screen=)`)."""
+    ag = m.get('bond_agreement')
+    return '> <PHOREGEN_BONDS>\nmode %s\n' % m['bonds'] + ('' if ag is None else ''.join('%s %d\n' % (k, ag[k]) for k in BOND_AGREE_COUNTS)) + '\n'
+
+
 _SDF_ITEMS = [
+    ('bonds', _bonds_item),
     ('key', lambda m: '> <PHOREGEN_KEY>\n%016x\n\n' % (int(m['key']) & _M64)),
     ('geom', lambda m: '> <PHOREGEN_GEOM>\nstatus 0x%02x\n' % int(m['geom']['status'])
      + ''.join('%s %.4f\n' % (k, m['geom'][k]) for k in GEOM_METRICS[:7]) + '\n'),
@@ -1403,8 +1569,9 @@ def write_sdf(path, mols, names=None):
     `> <PHOREGEN_FINGERPRINT>`: one line of 512 hex digits, word 0 first, each word as 16 digits, then 'radius R'.  A molecule that
     carries 'substructure' (assemble(substructure=)) gets `> <PHOREGEN_SUBSTRUCTURE>`: one line per pattern with its name, embeddings,
     anchors, the status as hex, the atoms that lie in an embedding and the first embedding (1-based, comma-separated, '-' if empty;
-    `phoregen_amd.substructure.parse_sdf_item` reads it back).  A molecule without one gets no such item: the text is as it always
-    was."""
+    `phoregen_amd.substructure.parse_sdf_item` reads it back).  A molecule that carries 'bonds' (assemble(screen=)) gets `> <PHOREGEN_BONDS>`:
+    'mode predicted' or 'mode distance', then, if it also carries 'bond_agreement', one 'name value' line per count
+    (BOND_AGREE_COUNTS).  A molecule without one gets no such item: the text is as it always was."""
     names = names if names is not None else [''] * len(mols)
     if len(names) != len(mols):
         raise ValueError(f'write_sdf: {len(mols)} molecules, {len(names)} names')
@@ -1561,12 +1728,19 @@ class _Draw:
     """What the analyses of one draw share: its screen, rings, Kekulé form and keys, each computed on first demand and at most once,
     the rings and the Kekulé form with the user's limits / options if given, else with the defaults."""
 
-    def __init__(self, res, ring_limits, kek_options):
+    def __init__(self, res, ring_limits, kek_options, add_edge='predicted', margins=None, agreement=False):
         self.res, self.ring_limits, self.kek_options = res, ring_limits or RingLimits(), kek_options or KekuleOptions()
+        self.add_edge, self.margins, self.agreement = add_edge, margins or BondMargins(), agreement
 
     @cached_property
     def screen(self):
-        return _screen(self.res, 'final')
+        """The draw's screen in its bond mode; with `agreement` it carries the counts of `bond_agreement` in either mode."""
+        if self.add_edge == 'predicted':
+            sc = _screen(self.res, 'final')
+            return replace(sc, agree=bond_agreement(self.res, 'final', self.margins).agree) if self.agreement else sc
+        if self.agreement:
+            return bond_agreement(self.res, 'final', self.margins)
+        return _screen(self.res, 'final', bonds=self.add_edge, margins=self.margins)
 
     @cached_property
     def rings(self):
@@ -1582,7 +1756,8 @@ class _Draw:
 
 
 def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, device='cuda', unique=False, geometry=None,
-                 rings=None, kekule=None, features=None, smiles=None, stereo=None, fingerprints=None, substructure=None, **sample_kwargs):
+                 rings=None, kekule=None, features=None, smiles=None, stereo=None, fingerprints=None, substructure=None,
+                 add_edge='predicted', bond_margins=None, bond_agreement=False, **sample_kwargs):
     """Sample until `num_samples` molecules have passed the screen, giving up once more than `max_failed_factor * num_samples` have
     failed (checked before every draw, as the reference does).  Every draw asks for min(batch_size, what is still missing) graphs,
     so never more than `num_samples` are finished.  `sample_kwargs` (fragment=, pos_guidance_opt=, rng=, seed=, ...) go to
@@ -1614,7 +1789,16 @@ def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, d
     also 'substructure_ok' -- for every pattern `anchors` lies within the pattern's min / max, and no bounded pattern was truncated;
     one that is not goes to 'failed'.  The molecules then carry 'substructure'.  The rings and the Kekulé form it needs are computed
     and carried as for features=.
+    add_edge='predicted' (the reference driver's `--add_edge` spelling): the bonds are the argmax of the edge scores.  'distance': they
+    are perceived from the sampled coordinates (`screen(bonds='distance')`, with bond_margins= a `BondMargins` or the defaults);
+    validity and every analysis above then run on that screen, and the molecules carry 'bonds'.  'openbabel' is not supported.
+    bond_agreement=True: the molecules also carry 'bonds' and 'bond_agreement' (the six BOND_AGREE_COUNTS of the predicted against the
+    distance bonds, `bond_agreement`), in either mode; nothing is filtered on them.
     All of these share one screen per draw."""
+    if add_edge not in BOND_MODES:
+        raise ValueError(f'phoregen_amd.molecule.sample_valid: add_edge must be one of {BOND_MODES}, not {add_edge!r}')
+    if bond_margins is not None and not isinstance(bond_margins, BondMargins):
+        raise ValueError(f'phoregen_amd.molecule.sample_valid: bond_margins= must be a BondMargins, not {bond_margins!r}')
     sub_patterns = sub_steps = None
     if substructure is not None:
         from . import substructure as _sub
@@ -1646,7 +1830,7 @@ def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, d
         n = min(batch_size, num_samples - len(finished))
         res = model.sample(data, n, device, return_traj=False, **sample_kwargs)
         n_calls += 1
-        draw = _Draw(res, ring_limits, kek_options)
+        draw = _Draw(res, ring_limits, kek_options, add_edge, bond_margins, bool(bond_agreement))
         geo = (None if geometry is None else geometry_for(data, res, screen=draw.screen, ex_col=getattr(model, 'ex_col', 12)) if geometry is True
                else _geometry(res, geometry[0], geometry[1], screen=draw.screen, limits=geometry[2]))
         ring = draw.rings if ring_limits is not None else None
@@ -1661,7 +1845,9 @@ def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, d
                                                                    max_steps=sub_steps)
         mols = assemble(res, keys=unique, **{k: v for k, v in (('geometry', geo), ('rings', ring), ('kekule', kek), ('features', feat),
                                                                ('smiles', smi), ('stereo', ster), ('fingerprints', fps),
-                                                               ('substructure', subs)) if v is not None})
+                                                               ('substructure', subs),
+                                                               ('screen', draw.screen if add_edge != 'predicted' or bond_agreement else None))
+                                          if v is not None})
         for m in mols:
             if (not m['valid'] or (geometry is not None and not m['geom']['geom_ok'])
                     or (ring_limits is not None and not m['rings']['rings_ok'])

@@ -8,7 +8,8 @@ profiles/mol_screen_timing.md.
 tiled 32 x to 4096 graphs (the atom-count distribution of BASELINE config 4).  Kernel times are HIP events around the launch alone
 (outputs allocated before), warm, median of repeats; next to them the wall time of what a caller pays today: `decode_batch` for (a)
 and (c), and for (b) a frame-by-frame loop, both as one launch per frame and as `decode_batch` per frame (a few frames timed,
-scaled to all)."""
+scaled to all).  Next to every kernel time stands the distance bond screen's (pg_mol_screen_dist, csrc/mol_screen_dist.hip;
+`screen(bonds='distance')`, without the agreement counts) on the same tensors in the same process, and the ratio of the two medians."""
 import argparse
 import json
 import os
@@ -35,14 +36,21 @@ def _buffers(F, B, N, E, dev):
                 order=torch.empty(F, E // 2, dtype=torch.int8, device=dev))
 
 
-def kernel_ms(node, pos, edge, F, strides, sc, repeats, warmup=3):
-    """Median / min / max of `repeats` event-timed launches over F frames (strides in elements), after `warmup` launches."""
+def kernel_ms(node, pos, edge, F, strides, sc, repeats, warmup=3, dist=False):
+    """Median / min / max of `repeats` event-timed launches over F frames (strides in elements), after `warmup` launches.
+    dist: pg_mol_screen_dist (no edge scores, no agreement counts) instead of pg_mol_screen."""
     B, N, E = len(sc.num_atoms), node.size(-2), edge.size(-2)
     out = _buffers(F, B, N, E, node.device)
     lib = hip.lib()
 
+    thresholds = M._bond_threshold_table(M.BondMargins(), node.device)
+
     def go():
-        M._launch(lib, node, strides[0], edge, strides[1], pos, strides[2], sc.lig_off, sc.bond_off, B, F, N, E, max(sc.num_atoms), out)
+        if dist:
+            M._launch_dist(lib, node, strides[0], pos, strides[2], None, 0, sc.lig_off, sc.bond_off, B, F, N, E, max(sc.num_atoms),
+                           thresholds, out, None)
+        else:
+            M._launch(lib, node, strides[0], edge, strides[1], pos, strides[2], sc.lig_off, sc.bond_off, B, F, N, E, max(sc.num_atoms), out)
     for _ in range(warmup):
         go()
     torch.cuda.synchronize()
@@ -97,6 +105,8 @@ def main():
     sc = M.screen(res)
     node, pos, edge = res['pred']
     k = kernel_ms(node, pos, edge, 1, (0, 0, 0), sc, 50)
+    dist_ms = [kernel_ms(node, pos, edge, 1, (0, 0, 0), sc, 50, dist=True)]
+    assert torch.equal(dist_ms[0][3]['order'], M.screen(res, bonds='distance').order)
     rows.append(('(a) final frame, %d graphs' % args.graphs, 1, k[:3], traffic_bytes(sc, 1),
                  wall_ms(lambda: M.screen(res), 10), wall_ms(lambda: M.assemble(res), 10), wall_ms(lambda: decode_batch(res), 10)))
     valid_final = int(sc.valid.sum())
@@ -106,6 +116,7 @@ def main():
     F = tn.size(0)
     strides = (tn.stride(0), te.stride(0), tp.stride(0))
     kb = kernel_ms(tn, tp, te, F, strides, sc, 7, warmup=2)
+    dist_ms.append(kernel_ms(tn, tp, te, F, strides, sc, 7, warmup=2, dist=True))
     sct = M.screen(res, frames='traj')
     assert torch.equal(sct.status, kb[3]['status']) and torch.equal(sct.order, kb[3]['order'])
     first_valid = [int(v) for v in (sct.valid.int().argmax(0) + F * (~sct.valid.any(0)).int()).tolist()]    # F = never
@@ -136,15 +147,18 @@ def main():
     big['lig_info'][2] = make_edge_data(big['lig_info'][0].cpu())[0].to(dev)
     scc = M.screen(big)
     kc = kernel_ms(*big['pred'], 1, (0, 0, 0), scc, 30)
+    dist_ms.append(kernel_ms(*big['pred'], 1, (0, 0, 0), scc, 30, dist=True))
     assert torch.equal(scc.status[0, :args.graphs], sc.status[0])
     rows.append(('(c) final frame, %d graphs' % (args.graphs * args.tile), 1, kc[:3], traffic_bytes(scc, 1),
                  wall_ms(lambda: M.screen(big), 5), wall_ms(lambda: M.assemble(big), 5), wall_ms(lambda: decode_batch(big), 5)))
 
     fmt = lambda t: '-' if t is None else '%.3f (%.3f - %.3f)' % t   # noqa: E731
-    lines = ['| case | kernel ms, median (min - max) | GB/s of needed traffic | `screen()` wall ms | `assemble()` wall ms | `decode_batch()` wall ms |',
-             '|---|---|---|---|---|---|']
-    for name, _, k3, nbytes, ws, wa, wd in rows:
-        lines.append('| %s | %s | %.0f | %s | %s | %s |' % (name, fmt(k3), nbytes / k3[0] / 1e6, fmt(ws), fmt(wa), fmt(wd)))
+    lines = ['| case | kernel ms, median (min - max) | GB/s of needed traffic | `screen()` wall ms | `assemble()` wall ms | `decode_batch()` wall ms '
+             '| `pg_mol_screen_dist` kernel ms | dist / screen |',
+             '|---|---|---|---|---|---|---|---|']
+    for (name, _, k3, nbytes, ws, wa, wd), d in zip(rows, dist_ms):
+        lines.append('| %s | %s | %.0f | %s | %s | %s | %s | %.2f |' % (name, fmt(k3), nbytes / k3[0] / 1e6, fmt(ws), fmt(wa), fmt(wd), fmt(d[:3]),
+                                                                     d[0] / k3[0]))
     lines += ['',
               'Trajectory frame by frame instead of one launch (scaled to %d frames): one launch per frame %.1f ms wall (%d frames timed: %.3f ms); '
               '`decode_batch` per frame %.0f ms wall (%d frames timed: %.1f ms).' %
@@ -155,7 +169,7 @@ def main():
               (t_sample, valid_final, args.graphs, sum(v < F for v in first_valid))]
     text = '\n'.join(lines) + '\n'
     print(text)
-    print(json.dumps({'kernel_ms_final': rows[0][2][0], 'kernel_ms_traj': rows[1][2][0], 'kernel_ms_4096': rows[2][2][0], 'frames': F,
+    print(json.dumps({'dist_kernel_ms': [d[0] for d in dist_ms], 'kernel_ms_final': rows[0][2][0], 'kernel_ms_traj': rows[1][2][0], 'kernel_ms_4096': rows[2][2][0], 'frames': F,
                       'per_frame_launch_ms_scaled': pf[0] * F / nf, 'per_frame_decode_ms_scaled': pd[0] * F / len(frames3)}))
     if args.out:
         with open(args.out, 'w') as fh:

@@ -44,7 +44,12 @@ largest similarity to that set and the row that attains it.  --substructure patt
 of tools/patterns/example_patterns.json, phoregen_amd.substructure.Pattern.from_dict) searches every pattern in every molecule on the
 device and finishes a molecule only if, for every pattern, the number of anchors lies within the pattern's min / max;
 <outdir>/{name}_substructure.txt holds one line 'index name embeddings anchors status' per finished molecule and pattern and the .sdf
-files carry the data item PHOREGEN_SUBSTRUCTURE; --substructure_steps N replaces the work bound per root (default 65536).  --num_steps shortens the reverse process (default: the model's).  Without them
+files carry the data item PHOREGEN_SUBSTRUCTURE; --substructure_steps N replaces the work bound per root (default 65536).
+--add_edge distance (the reference driver's spelling; implies --valid_only) takes the bonds from the sampled coordinates instead of the
+bond scores (phoregen_amd.molecule.screen(bonds='distance')): validity and every analysis above then run on those bonds; 'openbabel' is
+refused.  --bond_agreement (implies --valid_only) writes <outdir>/{name}_bond_agreement.txt, one line 'index mode both_same
+both_aromatic both_differ predicted_only distance_only neither' per finished molecule, and the .sdf files carry the data item
+PHOREGEN_BONDS.  --num_steps shortens the reverse process (default: the model's).  Without them
 nothing changes.
 """
 import argparse
@@ -64,7 +69,7 @@ from phoregen_amd.fragment import load_fragment_json  # noqa: E402
 from phoregen_amd.models.diffusion import PhoreDiff  # noqa: E402
 from phoregen_amd import similarity  # noqa: E402
 from phoregen_amd import substructure as substruct  # noqa: E402
-from phoregen_amd.molecule import FP_MAX_RADIUS, FP_RADIUS, FP_WORDS, FeatureLimits, GeomLimits, KekuleOptions, RingLimits, StereoLimits, STATUS_NONFINITE, assemble, point_kinds_of, sample_valid, write_sdf  # noqa: E402
+from phoregen_amd.molecule import BOND_AGREE_COUNTS, FP_MAX_RADIUS, FP_RADIUS, FP_WORDS, FeatureLimits, GeomLimits, KekuleOptions, RingLimits, StereoLimits, STATUS_NONFINITE, assemble, point_kinds_of, sample_valid, write_sdf  # noqa: E402
 from phoregen_amd.utils.sample_utils import decode_batch  # noqa: E402
 from phoregen_amd.weights import init_deterministic_  # noqa: E402
 
@@ -124,9 +129,18 @@ def main():
                          '<outdir>/<name>_substructure.txt')
     ap.add_argument('--substructure_steps', type=int, default=None, metavar='N',
                     help=f'with --substructure: the work bound per root, 1 .. 2**30 (default {substruct.DEFAULT_STEPS})')
+    ap.add_argument('--add_edge', type=str, default='predicted', choices=['predicted', 'distance', 'openbabel'],
+                    help="where the bonds come from (the reference driver's spelling): 'predicted' = argmax of the bond scores; 'distance' "
+                         "(implies --valid_only) = perceived from the sampled coordinates, every screen and analysis then runs on those "
+                         "bonds; 'openbabel' is not supported")
+    ap.add_argument('--bond_agreement', action='store_true',
+                    help='implies --valid_only: writes <outdir>/<name>_bond_agreement.txt, per finished molecule how the predicted and the '
+                         'distance bonds agree, and the .sdf files carry the counts as the data item PHOREGEN_BONDS')
     ap.add_argument('--num_steps', type=int, default=None, help='reverse steps of the sampler (default: the model\'s)')
     ap.add_argument('--sdf', action='store_true', help='write one .sdf per molecule under <outdir>/sdf_results/')
     args = ap.parse_args()
+    if args.add_edge == 'openbabel':
+        ap.error("--add_edge openbabel is not supported: this project has no OpenBabel; use 'predicted' or 'distance'")
     if args.geom_limits is not None and not args.geometry:
         ap.error('--geom_limits needs --geometry')
     if args.ring_limits is not None and not args.rings:
@@ -158,7 +172,7 @@ def main():
         if not 1 <= steps <= substruct.MAX_STEPS:
             ap.error('--substructure_steps must be 1 .. 2**30')
         patterns = (substruct.load_patterns_json(args.substructure), steps)
-    args.valid_only = args.valid_only or patterns is not None or args.fingerprints or args.unique or args.geometry or args.rings or args.kekule or args.features or args.smiles or args.stereo
+    args.valid_only = args.valid_only or args.add_edge != 'predicted' or args.bond_agreement or patterns is not None or args.fingerprints or args.unique or args.geometry or args.rings or args.kekule or args.features or args.smiles or args.stereo
     stereo_limits = StereoLimits(**(args.stereo_limits or {})) if args.stereo else None
     feature_limits = FeatureLimits(**(args.feature_limits or {})) if args.features else None
     geom_limits = GeomLimits(**(args.geom_limits or {}))
@@ -202,12 +216,19 @@ def main():
             out = sample_valid(model, data, args.num_samples, batch_size=args.batch_size, unique=args.unique, geometry=geometry,
                                rings=ring_limits, kekule=kekule, features=features, smiles=True if args.smiles else None,
                                stereo=stereo_limits, **(dict(fingerprints=fp_radius) if args.fingerprints else {}),
-                               **(dict(substructure=patterns) if patterns is not None else {}), **kw)
+                               **(dict(substructure=patterns) if patterns is not None else {}),
+                               **(dict(add_edge=args.add_edge) if args.add_edge != 'predicted' else {}),
+                               **(dict(bond_agreement=True) if args.bond_agreement else {}), **kw)
             done = out['finished']
             print(f"Finished {len(done)} | Failed {len(out['failed'])}" + (f" | Duplicates {len(out['duplicates'])}" if args.unique else ''))
             if args.unique:
                 with open(os.path.join(args.outdir, data.name + '_keys.txt'), 'w') as fh:
                     fh.writelines('%016x\n' % (m['stereo']['stereo_key'] if args.stereo else m['key']) for m in done)
+            if args.bond_agreement:
+                with open(os.path.join(args.outdir, data.name + '_bond_agreement.txt'), 'w') as fh:
+                    fh.write('# index mode ' + ' '.join(BOND_AGREE_COUNTS) + '\n')
+                    fh.writelines('%d %s %s\n' % (i, m['bonds'], ' '.join(str(m['bond_agreement'][k]) for k in BOND_AGREE_COUNTS))
+                                  for i, m in enumerate(done))
             if args.smiles:                                            # sample_all.py:157-159
                 with open(os.path.join(args.outdir, data.name + '_SMILES_all.txt'), 'w') as fh:
                     fh.writelines(m['smiles']['text'] + '\n' for m in done)
