@@ -841,6 +841,54 @@ int pg_mol_sub(const int8_t* cls, const int8_t* order, const int16_t* compact, c
                const uint8_t* table_host, int P, int max_steps, int* embeddings /*[F*B*P]*/, int* anchors /*[F*B*P]*/,
                int64_t* atom_mask /*[F*B*P*2]*/, int16_t* first /*[F*B*P*16]*/, int* status /*[F*B*P]*/, void* stream);
 
+/* 3D positions for the hydrogens pg_mol_kekule counted, one wave per (frame, graph).  Definition: DESIGN.md 2.9 "Hydrogens".  Reads the
+ * coordinates (pos, pos_fs as pg_mol_geom takes them), the screen's cls [F][n_lig] and order [F][n_bond / 2] and pg_mol_kekule's
+ * kekule_order [F][n_bond / 2], hcount, charge [F][n_lig] and status [F][B] (frames dense, the same offsets; charge is not read: the
+ * hydrogen count already carries it).  An atom is kept if its class is 0..10; its heavy neighbours are the kept atoms joined to it by a
+ * pair row of Kekulé order 1..3, in ascending local index, d of them; u_k is the fp32 unit vector to the k-th.
+ * A site is a kept atom with 1 <= hcount <= PG_HYD_MAX_PER_ATOM and finite coordinates at it and at every heavy neighbour.  Its shape:
+ * linear if it has a bond of Kekulé order 3 or two of order 2; else trigonal if it has a bond of Kekulé order 2 or of the screen's
+ * order 4, or is class N with d + hcount = 3 and a heavy neighbour that has such a bond; else tetrahedral.  Hydrogen k stands at
+ * p + xh_length[class] * dir_k, dir_k by (shape, d, hcount) as DESIGN.md tabulates: opposite the neighbours' sum (3, 1), astride
+ * it (tetrahedral 2, 1..2), on the cone around the one bond with the torsion set by the neighbour's lowest-index other neighbour or, without
+ * one, by the coordinate axis most across the bond, negated for the higher of the two atoms (d = 1), the fixed vertices (1,1,1), (1,-1,-1), (-1,1,-1), (-1,-1,1) / sqrt(3)
+ * (d = 0).  Every other combination, a neighbour at zero or non-finite distance (it is left out) and a vector to normalise with squared norm below
+ * PG_HYD_DEG_EPS^2 take the generic rule: the first hydrogen opposite the neighbours' sum if that has a direction, every further one on
+ * the fixed vertex whose largest dot product with the directions so far is smallest, first minimum.
+ *   h_pos [F][n_lig][PG_HYD_MAX_PER_ATOM][3]: the hydrogens of the atom row, slot by slot; unused slots 0.  16-byte aligned.
+ *   h_placed [F][n_lig]: the hydrogens placed at the atom, 0 or its hcount
+ *   site_shape [F][n_lig]: 0 no site, else PG_HYD_SHAPE_* of the rule that placed them
+ *   min_contact [F][B]: the smallest distance of a hydrogen to a kept atom other than its parent or to a hydrogen of another parent, fp32
+ *     sqrtf of the squared distance as in pg_mol_geom; +inf without such a pair
+ *   counts [F][B][PG_HYD_N_COUNTS]: 0 hydrogens placed, 1 sites, 2 .. 5 sites per shape (tetrahedral, trigonal, linear, generic), 6
+ *     contacts: the pairs above closer than clash_min (strict), 7 kept atoms
+ *   status [F][B]: PG_HYD_* bits.  With NO_KEKULE every other output of the graph is 0; with TOO_MANY (a kept atom with more than
+ *     PG_HYD_MAX_PER_ATOM hydrogens) nothing is placed in the graph.
+ * xh_length [11] is device memory, in class order; the library does not read it on the host, so the caller answers for finite lengths
+ * of at least 0 (phoregen_amd.hydrogens.HydrogenOptions checks them).  A graph's rows do not depend on its batch.  max_n above
+ * PG_MOL_MAX_ATOMS, a negative size, clash_min not finite or below 0, max_contacts below 0, a null table, a misaligned h_pos or (with
+ * B, F > 0) a null array that has elements: error before anything is launched, outputs untouched.  Every element of every output is written (nothing
+ * needs zeroing). */
+#define PG_HYD_NO_KEKULE 1           /* the graph's Kekulé status has PG_KEKULE_FAILED: no hydrogen counts to place */
+#define PG_HYD_NONFINITE 2           /* a kept atom with a non-finite coordinate: nothing placed at or next to it   */
+#define PG_HYD_TOO_MANY 4            /* a kept atom with more than PG_HYD_MAX_PER_ATOM hydrogens                   */
+#define PG_HYD_CONTACTS 8            /* more than max_contacts contacts                                        */
+#define PG_HYD_GENERIC 16            /* informational: at least one site placed by the generic rule            */
+#define PG_HYD_HAS_HYDROGEN 32       /* informational: at least one hydrogen placed                            */
+#define PG_HYD_N_COUNTS 8
+#define PG_HYD_MAX_PER_ATOM 4
+#define PG_HYD_SHAPE_TETRAHEDRAL 1
+#define PG_HYD_SHAPE_TRIGONAL 2
+#define PG_HYD_SHAPE_LINEAR 3
+#define PG_HYD_SHAPE_GENERIC 4
+#define PG_HYD_DEG_EPS 1e-3f
+int pg_mol_hydrogens(const float* pos, int64_t pos_fs, const int8_t* cls, const int8_t* order, const int8_t* kekule_order,
+                     const uint8_t* hcount, const int8_t* charge, const int* kekule_status /*[F][B]*/, const int* g_lig_off /*[B+1]*/,
+                     const int* g_bond_off /*[B+1]*/, int B, int F, int n_lig, int n_bond, int max_n, const float* xh_length /*[11] device*/,
+                     float clash_min, int max_contacts, float* h_pos /*[F][n_lig][4][3]*/, uint8_t* h_placed /*[F][n_lig]*/,
+                     uint8_t* site_shape /*[F][n_lig]*/, float* min_contact /*[F][B]*/, int* counts /*[F][B][PG_HYD_N_COUNTS]*/,
+                     int* status /*[F][B]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

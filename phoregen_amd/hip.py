@@ -86,6 +86,8 @@ PG_SUB_MAX_ATOMS, PG_SUB_MAX_PATTERNS, PG_SUB_MAX_STEPS, PG_SUB_PATTERN_BYTES = 
 PG_SUB_OFF_K, PG_SUB_OFF_MIN, PG_SUB_OFF_MAX, PG_SUB_OFF_ORDER, PG_SUB_OFF_ATOMS, PG_SUB_OFF_BONDS = 0, 4, 8, 16, 32, 160
 PG_SUB_ATOM_BYTES, PG_SUB_ATOM_ELEMENTS, PG_SUB_ATOM_DEGREE, PG_SUB_ATOM_HCOUNT, PG_SUB_ATOM_FLAGS = 8, 0, 2, 4, 6
 PG_SUB_ANY, PG_SUB_YES, PG_SUB_NO = 0, 1, 2
+# the hydrogen placement (pg_mol_hydrogens): slots per atom, count columns and the degeneracy threshold, as the PG_HYD_* macros
+PG_HYD_MAX_PER_ATOM, PG_HYD_N_COUNTS, PG_HYD_DEG_EPS = 4, 8, 1e-3
 _lib = None
 
 _PROTOS = {
@@ -178,6 +180,8 @@ _PROTOS = {
     'pg_fp_nearest': (C.c_int, [c_ip, C.c_int, c_ip, C.c_int, C.c_int, c_fp, c_ip, c_fp, C.c_void_p]),
     'pg_fp_maxmin': (C.c_int, [c_ip, C.c_int, C.c_int, C.c_int, c_ip, c_fp, c_fp, c_ip, C.c_void_p]),
     'pg_mol_sub': (C.c_int, [c_ip] * 10 + [C.c_int] * 5 + [c_ip, c_ip, C.c_int, C.c_int] + [c_ip] * 5 + [C.c_void_p]),
+    'pg_mol_hydrogens': (C.c_int, [c_fp, C.c_int64] + [c_ip] * 8 + [C.c_int] * 5 + [c_fp, C.c_float, C.c_int, c_fp, c_ip, c_ip, c_fp, c_ip, c_ip,
+                                   C.c_void_p]),
 }
 
 EXPORTS = tuple(_PROTOS)

@@ -58,7 +58,13 @@ Distance bonds: `screen(bonds='distance')` perceives the bonds from the coordina
 carry it.  Orders 1..3 only: no aromatic order, no hydrogens, no `openbabel` mode.
 
 Substructure: `phoregen_amd.substructure` answers whether, how often and where a decoded molecule contains a pattern (csrc/mol_sub.hip;
-DESIGN.md 2.9 "Substructure"); `assemble(substructure=)`, `sample_valid(substructure=)` and `write_sdf` carry it."""
+DESIGN.md 2.9 "Substructure"); `assemble(substructure=)`, `sample_valid(substructure=)` and `write_sdf` carry it.
+
+Hydrogens: `phoregen_amd.hydrogens` gives every hydrogen `kekulize` counted its coordinates (csrc/mol_hydrogens.hip; DESIGN.md 2.9
+"Hydrogens"): the shape of each site by an integer rule over the Kekulé orders, the directions from the unit vectors to its heavy
+neighbours, and a count of the contacts the hydrogens make.  `assemble(hydrogens=)`, `sample_valid(hydrogens=)`, `mol_block` (an
+all-atom block) and `write_sdf` carry it.  Ideal local geometry only: no force field, no rotor search; lengths and thresholds are
+design choices, not checked against RDKit / OpenBabel."""
 import ctypes
 from dataclasses import astuple, dataclass, replace
 from functools import cached_property, lru_cache
@@ -1224,7 +1230,7 @@ def _pairs(n):
 
 @torch.no_grad()
 def assemble(results, keys=False, geometry=None, rings=None, kekule=None, features=None, smiles=None, stereo=None, fingerprints=None,
-             substructure=None, screen=None):
+             substructure=None, screen=None, hydrogens=None):
     """The final prediction as one dict per graph with `decode_data`'s keys and meaning -- 'element' (atomic numbers), 'atom_pos'
     (kept atoms, the tensor's own fp32 values), 'bond_index' [2, n_b] (indices among the kept atoms) and 'bond_type' [n_b] for
     a < b only, in row order -- plus 'status', 'valid', 'n_components' and 'valence' (per kept atom, halves allowed).  The screen runs
@@ -1267,8 +1273,12 @@ def assemble(results, keys=False, geometry=None, rings=None, kekule=None, featur
     screen=a `Screen` of this result's final frame: its `order` becomes 'bond_index' / 'bond_type' (so with a `screen(bonds='distance')`
     the molecules have the distance-perceived bonds); every other result handed in must have been computed from it or from one of the
     same bond source.  Every dict then also has 'bonds' (the screen's mode) and, with a `bond_agreement` screen, 'bond_agreement':
-    the six BOND_AGREE_COUNTS by name."""
-    geom, pos_t, fps, sub = geometry, results['pred'][1], fingerprints, substructure
+    the six BOND_AGREE_COUNTS by name.
+    hydrogens=a `Hydrogens` (phoregen_amd.hydrogens) of this result's final frame: every dict also has 'hydrogens' -- 'status' (HYD_*
+    bits), 'hydrogens_ok' (no bit of HYD_FAIL_MASK), the eight HYD_COUNTS by name, 'min_contact', 'h_pos' (fp32 [n_h, 3], the placed
+    hydrogens in (parent, slot) order), 'h_parent' (per hydrogen an index into this dict's atoms) and 'site_shape' (per kept atom) --
+    in the same copy; its screen is reused, and it must have been computed from the screen of the others."""
+    geom, pos_t, fps, sub, hyd = geometry, results['pred'][1], fingerprints, substructure, hydrogens
     sc_in = screen
     if sc_in is not None and (not isinstance(sc_in, Screen) or sc_in.status.size(0) != 1 or sc_in.cls.size(1) != pos_t.size(-2)
                               or sc_in.cls.device != pos_t.device):
@@ -1278,6 +1288,11 @@ def assemble(results, keys=False, geometry=None, rings=None, kekule=None, featur
         if (not isinstance(sub, _sub.Substructure) or sub.status.size(0) != 1 or sub.screen.cls.size(1) != pos_t.size(-2)
                 or sub.status.device != pos_t.device):
             raise ValueError('phoregen_amd.molecule.assemble: substructure= must be a Substructure of the final frame of this result')
+    if hyd is not None:
+        from . import hydrogens as _hyd
+        if (not isinstance(hyd, _hyd.Hydrogens) or hyd.status.size(0) != 1 or hyd.screen.cls.size(1) != pos_t.size(-2)
+                or hyd.status.device != pos_t.device):
+            raise ValueError('phoregen_amd.molecule.assemble: hydrogens= must be a Hydrogens of the final frame of this result')
     if fps is not None and (not isinstance(fps, Fingerprints) or fps.screen is None or fps.fp.size(0) != 1
                             or fps.screen.cls.size(1) != pos_t.size(-2) or fps.fp.device != pos_t.device):
         raise ValueError('phoregen_amd.molecule.assemble: fingerprints= must be a Fingerprints of the final frame of this result')
@@ -1295,6 +1310,10 @@ def assemble(results, keys=False, geometry=None, rings=None, kekule=None, featur
         raise ValueError('phoregen_amd.molecule.assemble: substructure= and the others were computed from screens of different results')
     others = [(what, x.screen) for what, x in given] + [(what, x.screen) for what, x in (('fingerprints', fps), ('substructure', sub))
                                                         if x is not None]
+    if hyd is not None:
+        if others and not _same_screen(others[-1][1], hyd.screen):
+            raise ValueError(f'phoregen_amd.molecule.assemble: {others[-1][0]}= and hydrogens= were computed from screens of different results')
+        others.append(('hydrogens', hyd.screen))
     for what, x_sc in others if sc_in is not None else ():
         if not _same_screen(sc_in, x_sc):
             raise ValueError(f'phoregen_amd.molecule.assemble: screen= and {what}= were computed from screens of different results or '
@@ -1333,6 +1352,9 @@ def assemble(results, keys=False, geometry=None, rings=None, kekule=None, featur
         parts += [('p_bits', fps.bits[0], np.int32)]
     if sc_in is not None and sc.agree is not None:
         parts += [('agree', sc.agree[0], np.int32)]
+    if hyd is not None:
+        parts += [('h_status', hyd.status[0], np.int32), ('h_counts', hyd.counts[0], np.int32), ('h_min', hyd.min_contact[0], np.float32),
+                  ('h_pos', hyd.h_pos[0], np.float32)]
     parts += [('status', sc.status[0], np.int32), ('counts', sc.counts[0], np.int32), ('pos', pos_t, np.float32),
               ('compact', sc.compact[0], np.int16)]
     if sub is not None:
@@ -1357,6 +1379,8 @@ def assemble(results, keys=False, geometry=None, rings=None, kekule=None, featur
     if stereo is not None:
         parts += [('t_parity', stereo.atom_parity[0], np.int8), ('t_alabel', stereo.atom_label[0], np.int8),
                   ('t_bond', stereo.bond_stereo[0], np.int8), ('t_blabel', stereo.bond_label[0], np.int8)]
+    if hyd is not None:
+        parts += [('h_placed', hyd.h_placed[0], np.uint8), ('h_shape', hyd.site_shape[0], np.uint8)]
     sizes = [t.numel() * t.element_size() for _, t, _ in parts]
     blob = torch.cat([t.reshape(-1).view(torch.uint8) for _, t, _ in parts]).cpu().numpy()
     cut = np.cumsum([0] + sizes)
@@ -1447,6 +1471,10 @@ def assemble(results, keys=False, geometry=None, rings=None, kekule=None, featur
                                                              v['u_mask'].reshape(-1, n_pat, 2)[g], v['u_first'].reshape(-1, n_pat, _sub.MAX_ATOMS)[g],
                                                              v['u_status'].reshape(-1, n_pat)[g])
             mols[-1]['substructure_ok'] = _sub.entries_ok(mols[-1]['substructure'])
+        if hyd is not None:
+            mols[-1]['hydrogens'] = _hyd.molecule_entry(v['h_status'][g], v['h_counts'].reshape(-1, len(_hyd.HYD_COUNTS))[g], v['h_min'][g],
+                                                        v['h_pos'].reshape(-1, _hyd.MAX_PER_ATOM, 3)[n0:n0 + n][keep],
+                                                        v['h_placed'][n0:n0 + n][keep], v['h_shape'][n0:n0 + n][keep])
         n0, h0 = n0 + n, h0 + h
     return mols
 
@@ -1458,7 +1486,10 @@ def mol_block(mol, name=''):
     A molecule that carries 'kekule' (assemble(kekule=)) with 'kekule_ok' is written in Kekulé form: bond types 1 / 2 / 3 from
     kekule['bond_type'], a charged atom's charge in the atom line's `ccc` field (3 = +1, 2 = +2, 1 = +3, 5 = -1, 6 = -2, 7 = -3) and in
     'M  CHG' lines of at most eight entries before 'M  END'.  Hydrogens stay implicit.  Without 'kekule', or with a failed one, the
-    block is as it always was."""
+    block is as it always was.
+    A molecule that also carries 'hydrogens' (assemble(hydrogens=)) with 'hydrogens_ok' -- and 'kekule' with 'kekule_ok' -- is written
+    as an all-atom block: after the heavy atoms one 'H' line per placed hydrogen in (parent, slot) order, after the heavy bonds one
+    type-1 bond line per hydrogen from its parent.  In every other case the block is byte for byte what it is without 'hydrogens'."""
     elements, pos = mol['element'], np.asarray(mol['atom_pos'], dtype=np.float64).reshape(-1, 3)
     bi, bt = np.asarray(mol['bond_index']).reshape(2, -1), np.asarray(mol['bond_type']).reshape(-1)
     kek = mol.get('kekule')
@@ -1469,16 +1500,28 @@ def mol_block(mol, name=''):
         if bt.size != bi.shape[1] or len(charge) != len(elements) or any(abs(q) > 3 for q in charge):
             raise ValueError(f"mol_block: 'kekule' has {bt.size} bond types and {len(charge)} charges for {bi.shape[1]} bonds and "
                              f'{len(elements)} atoms (charges within -3 .. 3)')
-    if len(elements) > 999 or bt.size > 999:
-        raise ValueError(f'mol_block: {len(elements)} atoms / {bt.size} bonds do not fit the 3-digit counts of a V2000 block')
-    if not np.isfinite(pos).all():
+    hyd = mol.get('hydrogens') if kek is not None else None
+    hyd = hyd if hyd is not None and hyd.get('hydrogens_ok') else None
+    h_pos, h_parent = np.zeros((0, 3)), []
+    if hyd is not None:
+        h_pos, h_parent = np.asarray(hyd['h_pos'], dtype=np.float64).reshape(-1, 3), np.asarray(hyd['h_parent']).reshape(-1).tolist()
+        if len(h_parent) != len(h_pos) or any(not 0 <= a < len(elements) for a in h_parent):
+            raise ValueError(f"mol_block: 'hydrogens' has {len(h_pos)} positions and {len(h_parent)} parents among {len(elements)} atoms")
+    n_all, n_bonds = len(elements) + len(h_parent), bt.size + len(h_parent)
+    if n_all > 999 or n_bonds > 999:
+        raise ValueError(f'mol_block: {n_all} atoms / {n_bonds} bonds do not fit the 3-digit counts of a V2000 block')
+    if not (np.isfinite(pos).all() and np.isfinite(h_pos).all()):
         raise ValueError('mol_block: non-finite coordinates')
     lines = [str(name).split('\n')[0], '  PhoreGen' + ' ' * 10 + '3D', '',
-             '%3d%3d  0  0  0  0  0  0  0  0999 V2000' % (len(elements), bt.size)]
+             '%3d%3d  0  0  0  0  0  0  0  0999 V2000' % (n_all, n_bonds)]
     for z, (x, y, zc), q in zip(elements, pos.tolist(), charge):
         lines.append('%10.4f%10.4f%10.4f %-3s 0%3d  0  0  0  0  0  0  0  0  0  0' % (x, y, zc, ELEMENT_SYMBOL[int(z)], (4 - q) if q else 0))
+    for x, y, zc in h_pos.tolist():
+        lines.append('%10.4f%10.4f%10.4f %-3s 0%3d  0  0  0  0  0  0  0  0  0  0' % (x, y, zc, 'H', 0))
     for (a, b), t in zip(bi.T.tolist(), bt.tolist()):
         lines.append('%3d%3d%3d  0' % (a + 1, b + 1, t))
+    for k, a in enumerate(h_parent):
+        lines.append('%3d%3d%3d  0' % (a + 1, len(elements) + k + 1, 1))
     charged = [(i + 1, q) for i, q in enumerate(charge) if q]
     for k in range(0, len(charged), 8):
         lines.append('M  CHG%3d' % len(charged[k:k + 8]) + ''.join(' %3d %3d' % e for e in charged[k:k + 8]))
@@ -1525,6 +1568,11 @@ def _substructure_item(m):
     return sdf_item(m['substructure'])
 
 
+def _hydrogens_item(m):
+    from .hydrogens import sdf_item
+    return sdf_item(m['hydrogens'])
+
+
 # The data items of `write_sdf`, in the order they are written: (the key a molecule must carry, molecule -> the item's text)
 def _bonds_item(m):
     """The PHOREGEN_BONDS data item of a molecule that carries 'bonds' (`assemble(screen=)`)."""
@@ -1547,6 +1595,7 @@ _SDF_ITEMS = [
     ('stereo', _stereo_item),
     ('fingerprint', _fingerprint_item),
     ('substructure', _substructure_item),
+    ('hydrogens', _hydrogens_item),
 ]
 
 
@@ -1571,7 +1620,10 @@ def write_sdf(path, mols, names=None):
     anchors, the status as hex, the atoms that lie in an embedding and the first embedding (1-based, comma-separated, '-' if empty;
     `phoregen_amd.substructure.parse_sdf_item` reads it back).  A molecule that carries 'bonds' (assemble(screen=)) gets `> <PHOREGEN_BONDS>`:
     'mode predicted' or 'mode distance', then, if it also carries 'bond_agreement', one 'name value' line per count
-    (BOND_AGREE_COUNTS).  A molecule without one gets no such item: the text is as it always was."""
+    (BOND_AGREE_COUNTS).  A molecule that carries 'hydrogens' (assemble(hydrogens=)) is written as an all-atom block if that and its
+    Kekulé form are ok (`mol_block`) and gets `> <PHOREGEN_HYDROGENS>`: the status as hex, one 'name value' line per count (HYD_COUNTS of
+    phoregen_amd.hydrogens) and 'min_contact' with four decimals ('inf' without a pair).  A molecule without one gets no such item: the
+    text is as it always was."""
     names = names if names is not None else [''] * len(mols)
     if len(names) != len(mols):
         raise ValueError(f'write_sdf: {len(mols)} molecules, {len(names)} names')
@@ -1757,7 +1809,7 @@ class _Draw:
 
 def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, device='cuda', unique=False, geometry=None,
                  rings=None, kekule=None, features=None, smiles=None, stereo=None, fingerprints=None, substructure=None,
-                 add_edge='predicted', bond_margins=None, bond_agreement=False, **sample_kwargs):
+                 add_edge='predicted', bond_margins=None, bond_agreement=False, hydrogens=None, **sample_kwargs):
     """Sample until `num_samples` molecules have passed the screen, giving up once more than `max_failed_factor * num_samples` have
     failed (checked before every draw, as the reference does).  Every draw asks for min(batch_size, what is still missing) graphs,
     so never more than `num_samples` are finished.  `sample_kwargs` (fragment=, pos_guidance_opt=, rng=, seed=, ...) go to
@@ -1794,6 +1846,10 @@ def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, d
     validity and every analysis above then run on that screen, and the molecules carry 'bonds'.  'openbabel' is not supported.
     bond_agreement=True: the molecules also carry 'bonds' and 'bond_agreement' (the six BOND_AGREE_COUNTS of the predicted against the
     distance bonds, `bond_agreement`), in either mode; nothing is filtered on them.
+    hydrogens=a `HydrogenOptions` (phoregen_amd.hydrogens), or True for the default options: a valid molecule is finished only if it is
+    also 'hydrogens_ok' -- it has a Kekulé structure, finite coordinates and no more contacts than the options allow; one that is not
+    goes to 'failed'.  The molecules then carry 'hydrogens' and, since an all-atom block needs it, the Kekulé form of the draw as
+    'kekule' (computed with kekule= if given, else with the default options), so `write_sdf` writes all-atom blocks.
     All of these share one screen per draw."""
     if add_edge not in BOND_MODES:
         raise ValueError(f'phoregen_amd.molecule.sample_valid: add_edge must be one of {BOND_MODES}, not {add_edge!r}')
@@ -1822,6 +1878,12 @@ def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, d
     stereo_limits = StereoLimits() if stereo is True else stereo
     if stereo_limits is not None and not isinstance(stereo_limits, StereoLimits):
         raise ValueError(f'phoregen_amd.molecule.sample_valid: stereo= must be True or a StereoLimits, not {stereo!r}')
+    hyd_options = None
+    if hydrogens is not None and hydrogens is not False:
+        from . import hydrogens as _hyd
+        hyd_options = _hyd.HydrogenOptions() if hydrogens is True else hydrogens
+        if not isinstance(hyd_options, _hyd.HydrogenOptions):
+            raise ValueError(f'phoregen_amd.molecule.sample_valid: hydrogens= must be True or a HydrogenOptions, not {hydrogens!r}')
     finished, failed, duplicates, n_calls = [], [], [], 0
     by_key = {}                                                        # key -> finished molecules that have it
     while len(finished) < num_samples:
@@ -1834,7 +1896,8 @@ def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, d
         geo = (None if geometry is None else geometry_for(data, res, screen=draw.screen, ex_col=getattr(model, 'ex_col', 12)) if geometry is True
                else _geometry(res, geometry[0], geometry[1], screen=draw.screen, limits=geometry[2]))
         ring = draw.rings if ring_limits is not None else None
-        kek = draw.kekule if kek_options is not None else None
+        kek = draw.kekule if kek_options is not None or hyd_options is not None else None
+        hyds = None if hyd_options is None else _hyd.hydrogens(res, screen=draw.screen, kekule=draw.kekule, options=hyd_options)
         feat = (None if features is None else features_for(data, res, screen=draw.screen, kekule=draw.kekule, rings=draw.rings) if features is True
                 else _features(res, features[0], features[1], screen=draw.screen, kekule=draw.kekule, rings=draw.rings, limits=features[2]))
         ster = None if stereo_limits is None else _stereo(res, screen=draw.screen, kekule=draw.kekule, rings=draw.rings, keys=draw.keys,
@@ -1845,17 +1908,18 @@ def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, d
                                                                    max_steps=sub_steps)
         mols = assemble(res, keys=unique, **{k: v for k, v in (('geometry', geo), ('rings', ring), ('kekule', kek), ('features', feat),
                                                                ('smiles', smi), ('stereo', ster), ('fingerprints', fps),
-                                                               ('substructure', subs),
+                                                               ('substructure', subs), ('hydrogens', hyds),
                                                                ('screen', draw.screen if add_edge != 'predicted' or bond_agreement else None))
                                           if v is not None})
         for m in mols:
             if (not m['valid'] or (geometry is not None and not m['geom']['geom_ok'])
                     or (ring_limits is not None and not m['rings']['rings_ok'])
-                    or (kek_options is not None and not m['kekule']['kekule_ok'])
+                    or (kek is not None and not m['kekule']['kekule_ok'])
                     or (features is not None and not m['features']['features_ok'])
                     or (smiles is not None and not m['smiles']['smiles_ok'])
                     or (ster is not None and not m['stereo']['stereo_ok'])
-                    or (subs is not None and not m['substructure_ok'])):
+                    or (subs is not None and not m['substructure_ok'])
+                    or (hyds is not None and not m['hydrogens']['hydrogens_ok'])):
                 failed.append(m)
                 continue
             key = m['stereo']['stereo_key'] if unique and ster is not None else m['key'] if unique else None

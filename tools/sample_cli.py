@@ -49,7 +49,11 @@ files carry the data item PHOREGEN_SUBSTRUCTURE; --substructure_steps N replaces
 bond scores (phoregen_amd.molecule.screen(bonds='distance')): validity and every analysis above then run on those bonds; 'openbabel' is
 refused.  --bond_agreement (implies --valid_only) writes <outdir>/{name}_bond_agreement.txt, one line 'index mode both_same
 both_aromatic both_differ predicted_only distance_only neither' per finished molecule, and the .sdf files carry the data item
-PHOREGEN_BONDS.  --num_steps shortens the reverse process (default: the model's).  Without them
+PHOREGEN_BONDS.  --hydrogens (implies --valid_only and the Kekulé form) also gives every hydrogen its coordinates
+(phoregen_amd.hydrogens: ideal local geometry, no force field) and finishes a molecule only if it has a Kekulé structure, finite
+coordinates and no more contacts than allowed; with --sdf the blocks are then all-atom blocks and carry the counts as the data item
+PHOREGEN_HYDROGENS; --hydrogen_options '{"clash_min": 1.2, "max_contacts": 0}' replaces single options of
+phoregen_amd.hydrogens.HydrogenOptions.  --num_steps shortens the reverse process (default: the model's).  Without them
 nothing changes.
 """
 import argparse
@@ -69,6 +73,7 @@ from phoregen_amd.fragment import load_fragment_json  # noqa: E402
 from phoregen_amd.models.diffusion import PhoreDiff  # noqa: E402
 from phoregen_amd import similarity  # noqa: E402
 from phoregen_amd import substructure as substruct  # noqa: E402
+from phoregen_amd.hydrogens import HydrogenOptions  # noqa: E402
 from phoregen_amd.molecule import BOND_AGREE_COUNTS, FP_MAX_RADIUS, FP_RADIUS, FP_WORDS, FeatureLimits, GeomLimits, KekuleOptions, RingLimits, StereoLimits, STATUS_NONFINITE, assemble, point_kinds_of, sample_valid, write_sdf  # noqa: E402
 from phoregen_amd.utils.sample_utils import decode_batch  # noqa: E402
 from phoregen_amd.weights import init_deterministic_  # noqa: E402
@@ -136,6 +141,10 @@ def main():
     ap.add_argument('--bond_agreement', action='store_true',
                     help='implies --valid_only: writes <outdir>/<name>_bond_agreement.txt, per finished molecule how the predicted and the '
                          'distance bonds agree, and the .sdf files carry the counts as the data item PHOREGEN_BONDS')
+    ap.add_argument('--hydrogens', action='store_true',
+                    help='implies --valid_only: places the hydrogens of the Kekulé form in 3D; .sdf blocks are written as all-atom blocks')
+    ap.add_argument('--hydrogen_options', type=json.loads, default=None,
+                    help='JSON object replacing single options of HydrogenOptions (with --hydrogens): xh_length, clash_min, max_contacts')
     ap.add_argument('--num_steps', type=int, default=None, help='reverse steps of the sampler (default: the model\'s)')
     ap.add_argument('--sdf', action='store_true', help='write one .sdf per molecule under <outdir>/sdf_results/')
     args = ap.parse_args()
@@ -145,12 +154,14 @@ def main():
         ap.error('--geom_limits needs --geometry')
     if args.ring_limits is not None and not args.rings:
         ap.error('--ring_limits needs --rings')
-    if args.no_charged and not (args.kekule or args.smiles):
-        ap.error('--no_charged needs --kekule or --smiles')
+    if args.no_charged and not (args.kekule or args.smiles or args.hydrogens):
+        ap.error('--no_charged needs --kekule, --smiles or --hydrogens')
     if args.feature_limits is not None and not args.features:
         ap.error('--feature_limits needs --features')
     if args.stereo_limits is not None and not args.stereo:
         ap.error('--stereo_limits needs --stereo')
+    if args.hydrogen_options is not None and not args.hydrogens:
+        ap.error('--hydrogen_options needs --hydrogens')
     args.fingerprints = args.fingerprints or args.diverse is not None or args.reference_fps is not None
     if args.fp_radius is not None and not args.fingerprints:
         ap.error('--fp_radius needs --fingerprints')
@@ -172,13 +183,14 @@ def main():
         if not 1 <= steps <= substruct.MAX_STEPS:
             ap.error('--substructure_steps must be 1 .. 2**30')
         patterns = (substruct.load_patterns_json(args.substructure), steps)
-    args.valid_only = args.valid_only or args.add_edge != 'predicted' or args.bond_agreement or patterns is not None or args.fingerprints or args.unique or args.geometry or args.rings or args.kekule or args.features or args.smiles or args.stereo
+    args.valid_only = args.valid_only or args.add_edge != 'predicted' or args.bond_agreement or patterns is not None or args.fingerprints or args.unique or args.geometry or args.rings or args.kekule or args.features or args.smiles or args.stereo or args.hydrogens
     stereo_limits = StereoLimits(**(args.stereo_limits or {})) if args.stereo else None
+    hydrogen_options = HydrogenOptions(**(args.hydrogen_options or {})) if args.hydrogens else None
     feature_limits = FeatureLimits(**(args.feature_limits or {})) if args.features else None
     geom_limits = GeomLimits(**(args.geom_limits or {}))
     ring_limits = RingLimits(**(args.ring_limits or {})) if args.rings else None
     # (--smiles --no_charged: the text is written from the neutral-only Kekulé form, which the molecules then carry as with --kekule)
-    kekule = KekuleOptions(allow_charged=not args.no_charged) if args.kekule or (args.smiles and args.no_charged) else None
+    kekule = KekuleOptions(allow_charged=not args.no_charged) if args.kekule or ((args.smiles or args.hydrogens) and args.no_charged) else None
     torch.manual_seed(args.seed)
     cfg = default_model_config()
     if args.config:
@@ -218,7 +230,8 @@ def main():
                                stereo=stereo_limits, **(dict(fingerprints=fp_radius) if args.fingerprints else {}),
                                **(dict(substructure=patterns) if patterns is not None else {}),
                                **(dict(add_edge=args.add_edge) if args.add_edge != 'predicted' else {}),
-                               **(dict(bond_agreement=True) if args.bond_agreement else {}), **kw)
+                               **(dict(bond_agreement=True) if args.bond_agreement else {}),
+                               **(dict(hydrogens=hydrogen_options) if args.hydrogens else {}), **kw)
             done = out['finished']
             print(f"Finished {len(done)} | Failed {len(out['failed'])}" + (f" | Duplicates {len(out['duplicates'])}" if args.unique else ''))
             if args.unique:
@@ -264,7 +277,8 @@ def main():
             os.makedirs(sdf_dir, exist_ok=True)
             n_sdf = 0
             for i, m in enumerate(done):
-                if m['status'] & STATUS_NONFINITE or m['bond_type'].numel() > 999:      # non-finite coordinates / more bonds than a V2000 block counts
+                n_h = len(m['hydrogens']['h_parent']) if 'hydrogens' in m else 0         # (an all-atom block has a bond per hydrogen)
+                if m['status'] & STATUS_NONFINITE or m['bond_type'].numel() + n_h > 999:      # non-finite coordinates / more bonds than a V2000 block counts
                     continue
                 write_sdf(os.path.join(sdf_dir, f'{pidx}_{data.name}_{i}.sdf'), [m], names=[f'{data.name}_{i}'])
                 n_sdf += 1
