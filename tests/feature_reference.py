@@ -4,19 +4,19 @@ pattern of rule 6 enumerated atom by atom with distinct atoms, distances in floa
 kernel but the named constants of phoregen_amd.molecule.  The Kekulé form and the ring sizes are inputs: on the CPU they come from
 kekule_reference / ring_reference, on the GPU from the kernels that the feature kernel reads (which Kekulé structure a graph gets
 is not canonical, so the typing is always restated for the structure at hand).  Also here: the named molecules with their
-hand-written answers, the random family, and the driver of tools/feature_host_check.cpp."""
+hand-written answers, the random family, and the case format of tools/feature_host_check.cpp."""
 import itertools
 import os
-import subprocess
 
 import numpy as np
 
 import kekule_reference as K
 import mol_reference as R
+import mol_support as MS
 import ring_reference as G
+from mol_support import B_, C_, N_, O_, F_, SI_, P_, S_, CL_, BR_, I_  # noqa: F401
 from phoregen_amd import molecule as M
 
-B_, C_, N_, O_, F_, SI_, P_, S_, CL_, BR_, I_ = range(11)
 ONPS = (O_, N_, P_, S_)
 T = M.FEATURE_TYPES
 
@@ -25,16 +25,10 @@ T = M.FEATURE_TYPES
 def _graph(cls, order, kek_order, hcount, charge, ring_size):
     cls = [int(c) for c in cls]
     n = len(cls)
-    kept = [0 <= c <= 10 for c in cls]
+    kept, _, rows, order = MS.pair_walk(cls, order)
     nbr = [dict() for _ in range(n)]                                   # neighbour -> (Kekulé order, screen order is 4, ring bond)
-    row = 0
-    for a in range(n):
-        for b in range(a + 1, n):
-            o = int(order[row])
-            if 1 <= o <= 4 and kept[a] and kept[b]:
-                nbr[a][b] = nbr[b][a] = (int(kek_order[row]), o == 4, int(ring_size[row]) > 0)
-            row += 1
-    assert row == len(order)
+    for (a, b), row in rows.items():
+        nbr[a][b] = nbr[b][a] = (int(kek_order[row]), order[row] == 4, int(ring_size[row]) > 0)
     h = [int(hcount[i]) if kept[i] else 0 for i in range(n)]
     q = [int(charge[i]) if kept[i] else 0 for i in range(n)]
     arom = [any(a4 and ring for _, a4, ring in nbr[i].values()) for i in range(n)]
@@ -238,10 +232,8 @@ def graphs_from_generator(n_graphs=40, seed=R.GEN_SEED):
     node, pos, edge, sizes = R.generate_batch(seed, n_graphs)
     out = []
     for r in R.screen_batch(node, pos, edge, sizes):
-        n = len(r['cls'])
-        a, b = np.triu_indices(n, 1)
-        rows = np.nonzero(r['order'])[0]
-        out.append(([int(c) if c >= 0 else 11 for c in r['cls']], {(int(a[k]), int(b[k])): int(r['order'][k]) for k in rows}))
+        rows, a, b = MS.listed_pairs(len(r['cls']), r['order'])
+        out.append(([int(c) if c >= 0 else 11 for c in r['cls']], {(int(x), int(y)): int(r['order'][k]) for x, y, k in zip(a, b, rows)}))
     return out
 
 
@@ -348,17 +340,6 @@ def restate_case(case, inputs=None, limits=None):
 
 
 # ---- tools/feature_host_check.cpp: the kernel's rules compiled for the host ---------------------------------------------------------------
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def build_host_check(out_dir, sanitize=True):
-    """Compile tools/feature_host_check.cpp with g++ (ASan + UBSan unless sanitize=False); returns the program's path."""
-    exe = os.path.join(str(out_dir), 'feature_host_check')
-    flags = ['-fsanitize=address,undefined', '-fno-sanitize-recover=all'] if sanitize else []
-    subprocess.run(['g++', '-std=c++17', '-O1', '-g', *flags, os.path.join(ROOT, 'tools', 'feature_host_check.cpp'), '-o', exe], check=True)
-    return exe
-
-
 def run_host_check(exe, cases, work_dir):
     """cases: [(cls, order, kek_order, hcount, charge, kekule_ok, ring_size)] of graphs WITH a Kekulé structure -> one uint8 array of
     atom bytes per case."""
@@ -367,9 +348,8 @@ def run_host_check(exe, cases, work_dir):
         for cls, order, kek, h, q, ok, rs in cases:
             assert ok
             n = len(cls)
-            a, b = np.triu_indices(n, 1)
-            rows = np.nonzero(np.asarray(order))[0]
+            rows, a, b = MS.listed_pairs(n, order)
             fh.write('%d %d\n' % (n, rows.size) + ' '.join('%d %d %d' % (cls[i], h[i], q[i]) for i in range(n)) + '\n'
-                     + ' '.join('%d %d %d %d %d' % (a[r], b[r], order[r], kek[r], rs[r]) for r in rows) + '\n')
-    out = subprocess.run([exe, path], check=True, capture_output=True, text=True).stdout.split('\n')
+                     + ' '.join('%d %d %d %d %d' % (x, y, order[r], kek[r], rs[r]) for x, y, r in zip(a, b, rows)) + '\n')
+    out = MS.run_program(exe, path)
     return [np.array([int(v) for v in out[c].split()], dtype=np.uint8) for c in range(len(cases))]

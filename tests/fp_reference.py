@@ -1,18 +1,16 @@
 """Plain restatement of the fingerprints and the similarity of sets of them (DESIGN.md 2.9 "Fingerprints and similarity";
 phoregen_amd/molecule.py, phoregen_amd/similarity.py, csrc/mol_fp.hip, csrc/fp_sim.hip) for the tests, written from the text: Python
 ints masked to 64 bits, sets of bit positions, np.float32 division, no device code.  It shares nothing with the kernels but the
-named constants of phoregen_amd.molecule.  Also here: the build and the calls of the host program tools/fp_host_check.cpp."""
+named constants of phoregen_amd.molecule.  Also here: the calls of the host program tools/fp_host_check.cpp."""
 import os
-import subprocess
 
 import numpy as np
 
 import molkey_reference as K
+from mol_support import M64, compact_bonds, run_program
 from phoregen_amd import molecule as M
 from phoregen_amd.utils.sample_utils import ATOM_TYPES
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-M64 = K.M64
 mix = K.mix
 
 
@@ -58,18 +56,8 @@ def words_of(bits):
 def bits_of_rows(cls, order, radius=M.FP_RADIUS):
     """One graph as the screen wrote it (molkey_reference.key_of_rows' conventions): cls int8 [n] (-1 = dropped), order int8 for the
     pairs a < b in row-major order.  The set of bit positions."""
-    cls, order = [int(v) for v in cls], [int(v) for v in order]
-    n = len(cls)
-    kept = [i for i in range(n) if 0 <= cls[i] <= 10]
-    compact = {i: k for k, i in enumerate(kept)}
-    bonds, row = {}, 0
-    for a in range(n):
-        for b in range(a + 1, n):
-            if 1 <= order[row] <= 4 and a in compact and b in compact:
-                bonds[(compact[a], compact[b])] = order[row]
-            row += 1
-    assert row == len(order)
-    return bit_set([cls[i] for i in kept], bonds, radius)
+    kept, bonds = compact_bonds(cls, order)
+    return bit_set([int(cls[i]) for i in kept], bonds, radius)
 
 
 def bits_of_mol(m, radius=M.FP_RADIUS):
@@ -202,14 +190,6 @@ def split_runs(n_a, n_b, target, tile_a, tile_b):
 
 
 # ---- the host program -----------------------------------------------------------------------------------------------------------------
-def build_host_check(out_dir, sanitize=True):
-    """Compile tools/fp_host_check.cpp with g++ (ASan + UBSan unless sanitize=False); returns the program's path."""
-    exe = os.path.join(str(out_dir), 'fp_host_check')
-    flags = ['-fsanitize=address,undefined', '-fno-sanitize-recover=all'] if sanitize else []
-    subprocess.run(['g++', '-std=c++17', '-O1', '-g', *flags, os.path.join(ROOT, 'tools', 'fp_host_check.cpp'), '-o', exe], check=True)
-    return exe
-
-
 def run_host_check(exe, mode, work_dir, lines=None):
     """Runs one mode; `lines`: the input file's lines.  Returns the output file's path."""
     out = os.path.join(str(work_dir), mode + '.out')
@@ -219,5 +199,5 @@ def run_host_check(exe, mode, work_dir, lines=None):
         with open(src, 'w') as fh:
             fh.write('\n'.join(lines) + '\n')
         args.append(src)
-    subprocess.run(args + [out], check=True)
+    run_program(*args, out)
     return out

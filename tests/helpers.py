@@ -164,59 +164,10 @@ class Oracle64:
             torch.set_default_dtype(old)
 
 
-# ---- builders shared by the molecule kernels' GPU tests (test_gpu_mol*.py, test_gpu_fragment.py) -----------------------------------------
+# ---- the model of the GPU tests (the molecule tests' own builders are in tests/mol_support.py) ------------------------------------------
 def default_model(dev):
     """The zinc_300 model with the deterministic weights of seed 0, in eval mode on dev."""
     from phoregen_amd.config import default_model_config
     from phoregen_amd.models.diffusion import PhoreDiff
     from phoregen_amd.weights import init_deterministic_
     return init_deterministic_(PhoreDiff(default_model_config(), 'zinc_300'), 0).eval().to(dev)
-
-
-def mol_result(node, pos, edge, sizes, traj=(None, None, None), dev='cuda'):
-    """A sampler-shaped result dict on the device; traj: the three trajectory tensors (a tensor already on the device is kept as it
-    is, strides included) or None."""
-    from phoregen_amd.plan import make_edge_data
-    na = torch.tensor(sizes, dtype=torch.long)
-    ei, eb = make_edge_data(na)
-    return {'pred': [node.to(dev), pos.to(dev), edge.to(dev)], 'traj': [None if t is None else t.to(dev) for t in traj],
-            'lig_info': [na.to(dev), torch.repeat_interleave(torch.arange(len(sizes)), na).to(dev), ei.to(dev), eb.to(dev)]}
-
-
-def permute_batch(node, pos, edge, sizes, seed):
-    """Every graph's atoms renumbered at random (atom i becomes perms[g][i]) and both halves of its bond rows moved to the rows of
-    the renumbered pairs.  The kernel reads the first half only, so the pair's first-half scores stay in the first half whichever
-    of its ends now has the smaller index."""
-    rng = np.random.default_rng(seed)
-    node2, pos2, edge2, perms = node.clone(), pos.clone(), edge.clone(), []
-    n0, e0 = 0, 0
-    for n in sizes:
-        h = n * (n - 1) // 2
-        p = rng.permutation(n)
-        perms.append(p)
-        dst = torch.from_numpy(n0 + p)
-        node2[dst], pos2[dst] = node[n0:n0 + n], pos[n0:n0 + n]
-        if h:
-            a, b = np.triu_indices(n, 1)
-            pa, pb = p[a], p[b]
-            lo, hi = np.minimum(pa, pb), np.maximum(pa, pb)
-            rows = torch.from_numpy(lo * n - lo * (lo + 1) // 2 + (hi - lo - 1))
-            assert sorted(rows.tolist()) == list(range(h))
-            edge2[e0 + rows] = edge[e0:e0 + h]
-            edge2[e0 + h + rows] = edge[e0 + h:e0 + 2 * h]
-        n0, e0 = n0 + n, e0 + 2 * h
-    return node2, pos2, edge2, perms
-
-
-def onehot_graph(atom_cls, et_half):
-    """One graph from atom classes [n] and first-half bond classes [h] (written to both halves), one-hot scores."""
-    n, h = len(atom_cls), len(et_half)
-    node = torch.zeros(n, 12)
-    node[torch.arange(n), torch.as_tensor(atom_cls, dtype=torch.long)] = 1.0
-    edge = torch.zeros(2 * h, 6)
-    edge[torch.arange(2 * h), torch.as_tensor(np.concatenate([et_half, et_half]), dtype=torch.long)] = 1.0
-    return node, torch.arange(3 * n, dtype=torch.float32).reshape(n, 3) * 0.25, edge
-
-
-def cat_graphs(parts):
-    return tuple(torch.cat([p[k] for p in parts]) for k in range(3))

@@ -3,7 +3,8 @@ csrc/hydrogen_core.h) for the tests: numpy vectors, Python lists and dicts, one 
 document and the core and nothing else.  Besides the outputs it returns, per hydrogen, the smallest norm `s` of any vector it
 normalised on the way to that hydrogen, and every quantity a float comparison decided (`decisions`), so that the tests can keep their
 inputs away from the thresholds by the restatement alone.  Also here: the hand examples with ideal float64 skeletons, the generator
-of the family, the position bound, and the driver of tools/hydrogen_host_check.cpp.  Nothing here holds device code.
+of the family, the position bound, and the case format of tools/hydrogen_host_check.cpp.  Nothing here holds device code.  What the
+kernel reads for one graph comes from stereo_reference.all_rows, without the keys and rings that this kernel does not read.
 
 The position bound.  A hydrogen is p + L dir.  With e = 2^-24 (round to nearest, fp32; the build's divisions and square roots are
 correctly rounded) and the fp32 coordinates taken as exact, count the roundings of the longest path, the d = 1 rule, to first order:
@@ -21,21 +22,19 @@ so |error| <= e (max|coordinate| + L (32 + 34 / s)) <= K e (max|coordinate| + L 
 leaves the second-order terms a sixth.  The other rules are shorter: (3, 1) and trigonal (2, 1) normalise one sum of unit vectors,
 tetrahedral (2, h) a sum and a cross product, a vertex of the generic rule nothing at all.  `s` here is the smallest norm of ANY
 vector normalised for the hydrogen, bond vectors included, which can only widen the bound where a bond is shorter than the sum."""
+import functools
 import math
 import os
-import subprocess
 
 import numpy as np
-import torch
 
 import kekule_reference as K
-import mol_reference as R
+import mol_support as MS
+import stereo_reference
+from mol_support import B_, C_, N_, O_, F_, SI_, P_, S_, CL_, BR_, I_, batch_from, mirrored  # noqa: F401  (read from here by the tests)
 from phoregen_amd import hydrogens as HY
 from phoregen_amd import molecule as M
-from phoregen_amd.utils.sample_utils import ATOM_TYPES
 
-B_, C_, N_, O_, F_, SI_, P_, S_, CL_, BR_, I_ = range(11)
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 K_BOUND = 40                     # 34 roundings on the longest path (module docstring), the rest for second-order terms
 EPS32 = 2.0 ** -24
 TET, TRIG, LIN, GEN = HY.SHAPE_TETRAHEDRAL, HY.SHAPE_TRIGONAL, HY.SHAPE_LINEAR, HY.SHAPE_GENERIC
@@ -53,23 +52,17 @@ def graph_of_rows(cls, kekule_order, order):
     """kept [n]; heavy neighbours [n] ascending (pair rows of Kekulé order 1..3 between kept atoms); per atom the number of Kekulé
     double bonds, whether it has a triple bond, whether it has a bond of the screen's order 4."""
     n = len(cls)
-    kept = [0 <= int(c) <= 10 for c in cls]
-    nbrs, ndbl, triple, arom, row = [[] for _ in range(n)], [0] * n, [False] * n, [False] * n, 0
-    for a in range(n):
-        for b in range(a + 1, n):
-            if kept[a] and kept[b]:
-                ko = int(kekule_order[row])
-                if 1 <= ko <= 3:
-                    nbrs[a].append(b), nbrs[b].append(a)
-                if ko == 2:
-                    ndbl[a], ndbl[b] = ndbl[a] + 1, ndbl[b] + 1
-                if ko == 3:
-                    triple[a] = triple[b] = True
-                if int(order[row]) == 4:
-                    arom[a] = arom[b] = True
-            row += 1
-    assert row == len(order) == len(kekule_order)
-    return kept, [sorted(x) for x in nbrs], ndbl, triple, arom
+    assert len(order) == len(kekule_order)
+    w = MS.pair_walk(cls, kekule_order, (1, 2, 3))
+    ndbl, triple, arom = [0] * n, [False] * n, [False] * n
+    for (a, b), row in w.rows.items():
+        if w.order[row] == 2:
+            ndbl[a], ndbl[b] = ndbl[a] + 1, ndbl[b] + 1
+        if w.order[row] == 3:
+            triple[a] = triple[b] = True
+    for a, b in MS.pair_walk(cls, order, (4,)).rows:                   # (the screen's order 4, whatever the Kekulé order of the pair)
+        arom[a] = arom[b] = True
+    return w.kept, w.nbrs, ndbl, triple, arom
 
 
 def shape_of(cls, ndbl, triple, arom, d, h, conj):
@@ -237,20 +230,18 @@ def hydrogens_of_rows(cls, order, kekule_order, hcount, kekule_status, pos, opti
     return out
 
 
-def all_rows(classes, bonds, pos, allow_charged=True):
-    """Everything the kernel reads for one (classes, {(a, b): bond class}, coordinates) graph, the Kekulé form by its own restatement:
-    (cls, order, kekule_order, hcount, charge, kekule_status, pos as the float64 of its fp32 rounding)."""
-    cls, order = K.rows_of(classes, bonds)
-    k = K.kekule_of_rows(cls, order, allow_charged)
-    return (cls, order, k['kekule_order'], k['hcount'], k['charge'], int(k['status']),
-            np.asarray(pos, dtype=np.float32).astype(np.float64).reshape(len(classes), 3))
+# everything the kernel reads for one (classes, {(a, b): bond class}, coordinates) graph, the Kekulé form by its own restatement
+all_rows = functools.partial(stereo_reference.all_rows, with_keys_and_rings=False)
+
+
+def restate(rows, options=None, pos=None):
+    """`hydrogens_of_rows` on an `all_rows` record; pos: other coordinates than the record's."""
+    return hydrogens_of_rows(rows.cls, rows.order, rows.kekule_order, rows.hcount, rows.kekule_status, rows.pos if pos is None else pos, options)
 
 
 def hydrogens_of(classes, bonds, pos, options=None, exact=False):
     """The restatement on a graph; exact: on the float64 coordinates as they are, not on their fp32 rounding."""
-    r = all_rows(classes, bonds, pos)
-    p = np.asarray(pos, dtype=np.float64).reshape(-1, 3) if exact else r[6]
-    return hydrogens_of_rows(r[0], r[1], r[2], r[3], r[5], p, options)
+    return restate(all_rows(classes, bonds, pos), options, np.asarray(pos, dtype=np.float64).reshape(-1, 3) if exact else None)
 
 
 def is_safe(result, options=None):
@@ -292,11 +283,6 @@ def compare(got, want, pos, options=None, where=''):
     else:
         assert mc == wc, (where, 'min_contact', mc, wc)
     return worst
-
-
-def restate(rows, options=None):
-    """`hydrogens_of_rows` on an `all_rows` tuple."""
-    return hydrogens_of_rows(rows[0], rows[1], rows[2], rows[3], rows[5], rows[6], options)
 
 
 # ---- the hand examples: ideal skeletons in float64 ------------------------------------------------------------------------------------------
@@ -359,11 +345,6 @@ EXAMPLE_CLASH = (0.4, 16.0)
 def example_graphs():
     """[(classes, bonds, pos float32)] of EXAMPLES, in its order."""
     return [(c, b, np.array(p, dtype=np.float32)) for c, b, p, _ in EXAMPLES.values()]
-
-
-def mirrored(pos):
-    """The mirror image: x -> -x."""
-    return np.asarray(pos) * np.array([-1.0, 1.0, 1.0], dtype=np.asarray(pos).dtype)
 
 
 def angle(a, b, c):
@@ -451,8 +432,8 @@ def census(graphs, options=None):
     rows = {}
     for classes, bonds, pos in graphs:
         r = all_rows(classes, bonds, pos)
-        got = hydrogens_of_rows(r[0], r[1], r[2], r[3], r[5], r[6], options)
-        _, nbrs, _, _, _ = graph_of_rows(r[0], r[2], r[1])
+        got = restate(r, options)
+        _, nbrs, _, _, _ = graph_of_rows(r.cls, r.kekule_order, r.order)
         for i, (h, s) in enumerate(zip(got['h_placed'].tolist(), got['site_shape'].tolist())):
             if h:
                 rows[(s, len(nbrs[i]), h)] = rows.get((s, len(nbrs[i]), h), 0) + 1
@@ -464,41 +445,26 @@ TABLE_ROWS = ([(TET, 3, 1), (TET, 2, 2), (TET, 2, 1), (TRIG, 2, 1), (LIN, 1, 1)]
               + [(TET, 0, h) for h in (1, 2, 3, 4)])
 
 
-def batch_from(graphs):
-    """(node, pos, edge, sizes) as CPU tensors in the sampler's layout from [(classes, bonds, pos)], one-hot scores."""
-    parts = [R.scores_from_classes(list(c), b, pos=torch.as_tensor(np.asarray(p, dtype=np.float32)).reshape(-1, 3)) for c, b, p in graphs]
-    return (torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts]), torch.cat([p[2] for p in parts]), [len(c) for c, _, _ in graphs])
-
-
 # ---- tools/hydrogen_host_check.cpp: the core compiled for the host --------------------------------------------------------------------------
-def build_host_check(out_dir, sanitize=True):
-    """Compile tools/hydrogen_host_check.cpp with g++ (ASan + UBSan unless sanitize=False); returns the program's path."""
-    exe = os.path.join(str(out_dir), 'hydrogen_host_check')
-    flags = ['-fsanitize=address,undefined', '-fno-sanitize-recover=all'] if sanitize else []
-    subprocess.run(['g++', '-std=c++17', '-O1', '-g', *flags, os.path.join(ROOT, 'tools', 'hydrogen_host_check.cpp'), '-o', exe], check=True)
-    return exe
-
-
 def run_host_check(exe, cases, work_dir, options=None):
-    """cases: [`all_rows` tuples].  Returns per case the dict `compare` takes."""
+    """cases: [`all_rows` records].  Returns per case the dict `compare` takes."""
     opt = HY.HydrogenOptions() if options is None else options
     path = os.path.join(str(work_dir), 'hydrogen_cases.txt')
     with open(path, 'w') as fh:
-        fh.write(' '.join(float(np.float32(v)).hex() for v in opt.xh_length) + '\n')
-        fh.write('%s %d\n' % (float(np.float32(opt.clash_min)).hex(), opt.max_contacts))
-        for cls, order, kek, h, q, kstatus, pos in cases:
-            n = len(cls)
-            a, b = np.triu_indices(n, 1)
-            rows = [r for r in range(len(order)) if order[r] or kek[r]]
-            fh.write('%d %d %d\n' % (n, kstatus, len(rows)))
+        fh.write(' '.join(MS.hex32(v) for v in opt.xh_length) + '\n')
+        fh.write('%s %d\n' % (MS.hex32(opt.clash_min), opt.max_contacts))
+        for m in cases:
+            n = len(m.cls)
+            rows, a, b = MS.listed_pairs(n, m.order, m.kekule_order)
+            fh.write('%d %d %d\n' % (n, m.kekule_status, len(rows)))
             for i in range(n):
-                fh.write('%d %d %s %s %s\n' % (cls[i], h[i], *(float(np.float32(x)).hex() for x in pos[i])))
-            for r in rows:
-                fh.write('%d %d %d %d\n' % (a[r], b[r], order[r], kek[r]))
-    out = subprocess.run([exe, path], check=True, capture_output=True, text=True).stdout.split('\n')
+                fh.write('%d %d %s %s %s\n' % (m.cls[i], m.hcount[i], *(MS.hex32(x) for x in m.pos[i])))
+            for x, y, r in zip(a, b, rows):
+                fh.write('%d %d %d %d\n' % (x, y, m.order[r], m.kekule_order[r]))
+    out = MS.run_program(exe, path)
     got = []
     for c, case in enumerate(cases):
-        n = len(case[0])
+        n = len(case.cls)
         head, atoms, coords = (out[3 * c + k].split() for k in range(3))
         got.append({'status': int(head[0]), 'min_contact': float.fromhex(head[1]) if head[1] not in ('inf', 'nan') else float(head[1]),
                     'counts': np.array([int(v) for v in head[2:]], dtype=np.int32),

@@ -3,18 +3,18 @@ written from the text in another form than the kernel: classification and per-at
 cardinality by exhaustive search over the allowed graph, memoised on the set of atoms still free -- no augmenting paths, no blossoms.
 A matching the kernel returns is validated by its properties (`check_assignment`), not compared with the restatement's own.  No
 device code; it shares nothing with the kernel but the named constants and tables of phoregen_amd.molecule.  Also here: the named
-molecules of the tests with their hand-written answers, the random family, and the driver of tools/kekule_host_check.cpp."""
+molecules of the tests with their hand-written answers, the random family, and the case format of tools/kekule_host_check.cpp.  The
+graph builders (here with the aromatic order as the default), `rows_of` and the walk over the pair rows are tests/mol_support.py's."""
 import os
-import subprocess
 import sys
 
 import numpy as np
 
-import mol_reference as R
+import mol_support as MS
+from mol_support import B_, C_, N_, O_, F_, SI_, P_, S_, CL_, BR_, I_, rows_of  # noqa: F401  (read from here by other modules)
 from phoregen_amd import molecule as M
 from phoregen_amd.utils.sample_utils import ATOM_TYPES
 
-B_, C_, N_, O_, F_, SI_, P_, S_, CL_, BR_, I_ = range(11)
 NONE, NOT, MAY, MUST = 'none', 'not', 'may', 'must'
 
 
@@ -24,24 +24,19 @@ def _table(d):
 
 def graph_of_rows(cls, order):
     """One graph as the screen wrote it -> kept flags, s and a per atom, the aromatic bonds [(a, b, row)]."""
-    cls, order = [int(v) for v in cls], [int(v) for v in order]
-    n = len(cls)
-    kept = [0 <= c <= 10 for c in cls]
-    s, a, arom, row = [0] * n, [0] * n, [], 0
-    for i in range(n):
-        for j in range(i + 1, n):
-            o = order[row]
-            if 1 <= o <= 4 and kept[i] and kept[j]:
-                if o == 4:
-                    a[i] += 1
-                    a[j] += 1
-                    arom.append((i, j, row))
-                else:
-                    s[i] += o
-                    s[j] += o
-            row += 1
-    assert row == len(order)
-    return {'n': n, 'cls': cls, 'order': order, 'kept': kept, 's': s, 'a': a, 'arom': arom}
+    w = MS.pair_walk(cls, order)
+    n = len(w.kept)
+    s, a, arom = [0] * n, [0] * n, []
+    for (i, j), row in w.rows.items():
+        o = w.order[row]
+        if o == 4:
+            a[i] += 1
+            a[j] += 1
+            arom.append((i, j, row))
+        else:
+            s[i] += o
+            s[j] += o
+    return {'n': n, 'cls': [int(c) for c in cls], 'order': w.order, 'kept': w.kept, 's': s, 'a': a, 'arom': arom}
 
 
 def classify(g, pas):
@@ -216,23 +211,11 @@ def has_odd_cycle(n, edges):
 
 # ---- building inputs ------------------------------------------------------------------------------------------------------------
 def cycle(n, order=4, off=0):
-    return {(min(off + i, off + (i + 1) % n), max(off + i, off + (i + 1) % n)): order for i in range(n)}
+    return MS.cycle(n, order, off)
 
 
 def chain(n, order=4, off=0):
-    return {(off + i, off + i + 1): order for i in range(n - 1)}
-
-
-def rows_of(classes, bonds):
-    """(cls, order) rows of one graph, as the screen would write them, from classes 0..11 and {(a, b): bond class 1..5}."""
-    n = len(classes)
-    cls = np.array([c if c <= 10 else -1 for c in classes], dtype=np.int8)
-    order = np.zeros(n * (n - 1) // 2, dtype=np.int8)
-    for (a, b), t in bonds.items():
-        assert a < b
-        if 1 <= t <= 4 and cls[a] >= 0 and cls[b] >= 0:
-            order[R.pair_row(a, b, n)] = t
-    return cls, order
+    return MS.chain(n, order, off)
 
 
 def ladder(rungs, order=4):
@@ -361,33 +344,20 @@ def outcome(sol):
 
 
 # ---- tools/kekule_host_check.cpp: the kernel's core compiled for the host ------------------------------------------------------------
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def build_host_check(out_dir, sanitize=True):
-    """Compile tools/kekule_host_check.cpp with g++ (ASan + UBSan unless sanitize=False); returns the program's path."""
-    exe = os.path.join(str(out_dir), 'kekule_host_check')
-    flags = ['-fsanitize=address,undefined', '-fno-sanitize-recover=all'] if sanitize else []
-    subprocess.run(['g++', '-std=c++17', '-O1', '-g', *flags, os.path.join(ROOT, 'tools', 'kekule_host_check.cpp'), '-o', exe], check=True)
-    return exe
-
-
 def run_host_check(exe, cases, work_dir):
     """cases: [(cls, order, allow_charged)] as rows -> one dict per case in `check_assignment`'s form."""
     path = os.path.join(str(work_dir), 'kekule_cases.txt')
-    hval = [list(M.H_VALENCES[z]) + [0] * (4 - len(M.H_VALENCES[z])) for z in ATOM_TYPES]
     listed = []
     with open(path, 'w') as fh:
-        for t in (_table(M.KEKULE_DBL_NEUTRAL), _table(M.KEKULE_DBL_CHARGED), _table(M.KEKULE_MUST), sum(hval, [])):
+        for t in (_table(M.KEKULE_DBL_NEUTRAL), _table(M.KEKULE_DBL_CHARGED), _table(M.KEKULE_MUST), MS.padded_valences(M.H_VALENCES)):
             fh.write(' '.join(str(int(v)) for v in t) + '\n')
         for cls, order, allow in cases:
             n = len(cls)
-            a, b = np.triu_indices(n, 1)
-            rows = np.nonzero(np.asarray(order))[0]
+            rows, a, b = MS.listed_pairs(n, order)
             listed.append(rows)
             fh.write('%d %d %d\n' % (n, int(allow), rows.size) + ' '.join(str(int(c)) for c in cls) + '\n'
-                     + ' '.join('%d %d %d' % (a[r], b[r], order[r]) for r in rows) + '\n')
-    out = subprocess.run([exe, path], check=True, capture_output=True, text=True).stdout.split('\n')
+                     + ' '.join('%d %d %d' % (x, y, order[r]) for x, y, r in zip(a, b, rows)) + '\n')
+    out = MS.run_program(exe, path)
     got = []
     for c, ((cls, order, _), rows) in enumerate(zip(cases, listed)):
         head, kek_rows, hq = ([int(v) for v in out[3 * c + k].split()] for k in range(3))

@@ -5,10 +5,9 @@ for identity, networkx's labelled graph isomorphism (tests only; the product doe
 import numpy as np
 import torch
 
+from mol_support import C_, N_, O_, M64, compact_bonds, cycle
 from phoregen_amd import molecule as M
 from phoregen_amd.utils.sample_utils import ATOM_TYPES
-
-M64 = (1 << 64) - 1
 
 
 def mix(x):
@@ -69,19 +68,9 @@ def key_of(classes, bonds):
 def key_of_rows(cls, order):
     """One graph as the screen wrote it: cls int8 [n] (-1 = dropped), order int8 [n (n - 1) / 2] for the pairs a < b in row-major
     order.  Returns (key, colours [n] with 0 for a dropped atom)."""
-    cls, order = [int(v) for v in cls], [int(v) for v in order]
-    n = len(cls)
-    kept = [i for i in range(n) if 0 <= cls[i] <= 10]
-    compact = {i: k for k, i in enumerate(kept)}
-    bonds, row = {}, 0
-    for a in range(n):
-        for b in range(a + 1, n):
-            if 1 <= order[row] <= 4 and a in compact and b in compact:
-                bonds[(compact[a], compact[b])] = order[row]
-            row += 1
-    assert row == len(order)
-    key, c = key_of([cls[i] for i in kept], bonds)
-    colour = [0] * n
+    kept, bonds = compact_bonds(cls, order)
+    key, c = key_of([int(cls[i]) for i in kept], bonds)
+    colour = [0] * len(cls)
     for k, i in enumerate(kept):
         colour[i] = c[k]
     return key, colour
@@ -159,22 +148,17 @@ CORPUS_RANDOM_BASES = 40
 CORPUS_MAX_ATOMS = 40
 
 
-def _ring(n, order=1, off=0):
-    return {(min(off + i, off + (i + 1) % n), max(off + i, off + (i + 1) % n)): order for i in range(n)}
-
-
 def named_bases():
     """Small molecules the identity tests name: (name, classes, bonds)."""
-    C_, N_, O_ = 1, 2, 3
-    decalin = _ring(6)
+    decalin = cycle(6, 1)
     decalin.update({(0, 6): 1, (6, 7): 1, (7, 8): 1, (8, 9): 1, (1, 9): 1})
-    bicyclopentyl = _ring(5)
-    bicyclopentyl.update(_ring(5, off=5))
+    bicyclopentyl = cycle(5, 1)
+    bicyclopentyl.update(cycle(5, 1, off=5))
     bicyclopentyl[(0, 5)] = 1
     kekule = {p: 1 + (i % 2) for i, p in enumerate([(0, 1), (1, 2), (2, 3), (3, 4), (4, 5), (0, 5)])}
-    pyridine = _ring(6, order=4)
+    pyridine = cycle(6, 4)
     return [('decalin', [C_] * 10, decalin), ('bicyclopentyl', [C_] * 10, bicyclopentyl),
-            ('benzene', [C_] * 6, _ring(6, order=4)), ('cyclohexane', [C_] * 6, _ring(6)), ('benzene_kekule', [C_] * 6, kekule),
+            ('benzene', [C_] * 6, cycle(6, 4)), ('cyclohexane', [C_] * 6, cycle(6, 1)), ('benzene_kekule', [C_] * 6, kekule),
             ('pyridine', [N_] + [C_] * 5, pyridine), ('ethanol_water', [C_, C_, O_, O_], {(0, 1): 1, (1, 2): 1})]
 
 

@@ -1,13 +1,15 @@
 """Plain restatement of the ring screen (DESIGN.md 2.9 "Rings"; phoregen_amd/molecule.py, csrc/mol_rings.hip) for the tests, written
 from the text in another form than the kernel: adjacency lists, a queue breadth-first search per bond on a copy of the graph with that
 bond taken out, union-find for ring systems and components.  No device code; it shares nothing with the kernel but the named
-constants of phoregen_amd.molecule.  Also here: the named molecules of the ring tests with their hand-written answers."""
+constants of phoregen_amd.molecule.  Also here: the named molecules of the ring tests with their hand-written answers, and the
+networkx graph of a graph's rows.  The graph builders, `rows_of`, `batch_from` and the walk over the pair rows are
+tests/mol_support.py's."""
 from collections import deque
 
 import numpy as np
-import torch
 
-import mol_reference as R
+import mol_support as MS
+from mol_support import C_, batch_from, pair_walk, rows_of  # noqa: F401  (batch_from and rows_of are read from here by the tests)
 from phoregen_amd import molecule as M
 
 
@@ -46,19 +48,9 @@ def rings_of_rows(cls, order, limits=None):
     order.  Returns the kernel's outputs for it: 'ring_size' uint8 [h], 'atom_ring' uint8 [n], 'ring_sys' int16 [n], 'counts'
     int32 [10] (M.RING_COUNTS), 'status', 'ok'."""
     limits = M.RingLimits() if limits is None else limits
-    cls, order = [int(v) for v in cls], [int(v) for v in order]
     n = len(cls)
-    kept = [0 <= c <= 10 for c in cls]
-    bonds, row = [], 0                                                 # (a, b, order, row)
-    for a in range(n):
-        for b in range(a + 1, n):
-            if 1 <= order[row] <= 4 and kept[a] and kept[b]:
-                bonds.append((a, b, order[row], row))
-            row += 1
-    assert row == len(order)
-    nbrs = [[] for _ in range(n)]
-    for a, b, _, _ in bonds:
-        nbrs[a].append(b), nbrs[b].append(a)
+    kept, nbrs, rows, order = pair_walk(cls, order)
+    bonds = [(a, b, order[row], row) for (a, b), row in rows.items()]
     degree = [len(x) for x in nbrs]
     aromatic = [0] * n
     ring_size = np.zeros(len(order), dtype=np.uint8)
@@ -116,34 +108,14 @@ def rings_of_batch(refs, limits=None):
 
 # ---- building inputs ------------------------------------------------------------------------------------------------------------
 def cycle(n, order=1, off=0):
-    return {(min(off + i, off + (i + 1) % n), max(off + i, off + (i + 1) % n)): order for i in range(n)}
+    return MS.cycle(n, order, off)
 
 
 def chain(n, order=1, off=0):
-    return {(off + i, off + i + 1): order for i in range(n - 1)}
-
-
-def batch_from(graphs):
-    """(node, pos, edge, sizes) as CPU tensors in the sampler's layout from [(atom classes 0..11, {(a, b): bond class 1..5})],
-    one-hot scores."""
-    parts = [R.scores_from_classes(list(c), b) for c, b in graphs]
-    return (torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts]), torch.cat([p[2] for p in parts]),
-            [len(c) for c, _ in graphs])
-
-
-def rows_of(classes, bonds):
-    """(cls, order) rows of one graph, as the screen would write them, from classes 0..11 and {(a, b): bond class 1..5}."""
-    n = len(classes)
-    cls = np.array([c if c <= 10 else -1 for c in classes], dtype=np.int8)
-    order = np.zeros(n * (n - 1) // 2, dtype=np.int8)
-    for (a, b), t in bonds.items():
-        if 1 <= t <= 4 and cls[a] >= 0 and cls[b] >= 0:
-            order[R.pair_row(a, b, n)] = t
-    return cls, order
+    return MS.chain(n, order, off)
 
 
 def _named():
-    C_ = 1
     naphthalene = cycle(6, 4)
     naphthalene.update({(0, 6): 4, (6, 7): 4, (7, 8): 4, (8, 9): 4, (1, 9): 4})
     biphenyl = {**cycle(6, 4), **cycle(6, 4, off=6)}
@@ -177,13 +149,8 @@ FILTER = dict(ring_min=5, ring_max=8, system_max=9, rotatable_max=0)     # the l
 def nx_graph(cls, order):
     """networkx graph of one graph's rows (kept atoms as nodes, bonds as edges)."""
     import networkx as nx
-    n = len(cls)
+    w = pair_walk(cls, order)
     g = nx.Graph()
-    g.add_nodes_from(i for i in range(n) if 0 <= cls[i] <= 10)
-    row = 0
-    for a in range(n):
-        for b in range(a + 1, n):
-            if 1 <= order[row] <= 4 and a in g and b in g:
-                g.add_edge(a, b)
-            row += 1
+    g.add_nodes_from(i for i, k in enumerate(w.kept) if k)
+    g.add_edges_from(w.rows)
     return g

@@ -5,20 +5,19 @@ The writer is written from the definition's text in another form than the kernel
 the definition's `visit(v)` joins them -- no stack, no bit masks, no prefix sum.  The reader parses the emitted subset of OpenSMILES
 (bare and bracket atoms, '=', '#', branches, ring-closure labels with '%nn', '.', implicit hydrogens by the notation's own valence
 rule) and knows nothing of the writer.  Neither holds device code; they share nothing with the kernel but the named constants and
-tables of phoregen_amd.molecule.  Also here: the hand-checked examples, and the driver of tools/smiles_host_check.cpp."""
+tables of phoregen_amd.molecule.  Also here: the hand-checked examples, and the case format of tools/smiles_host_check.cpp."""
 import os
-import subprocess
 import sys
 
 import numpy as np
 
 import kekule_reference as K
+import mol_support as MS
+from mol_support import C_, N_, O_, SI_, I_
 from phoregen_amd import molecule as M
 from phoregen_amd.utils.sample_utils import ATOM_TYPES
 
-B_, C_, N_, O_, F_, SI_, P_, S_, CL_, BR_, I_ = range(11)
 BOND_SYMBOL = {1: '', 2: '=', 3: '#'}
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 class RingLabels(Exception):
@@ -114,13 +113,7 @@ def smiles_of_rows(cls, kekule_order, hcount, charge, kekule_status=0, capacity=
     if kekule_status & M.KEKULE_FAILED:
         return failed(M.SMILES_NO_KEKULE)
     elements = {i: ATOM_TYPES[c] for i, c in enumerate(cls) if 0 <= c <= 10}
-    bonds, row = {}, 0
-    for a in range(n):
-        for b in range(a + 1, n):
-            if kek[row] in (1, 2, 3) and a in elements and b in elements:
-                bonds[(a, b)] = kek[row]
-            row += 1
-    assert row == len(kek)
+    bonds = {p: kek[row] for p, row in MS.pair_walk(cls, kek, (1, 2, 3)).rows.items()}
     try:
         w = write_graph(elements, bonds, {i: int(hcount[i]) for i in elements}, {i: int(charge[i]) for i in elements})
     except RingLabels:
@@ -250,14 +243,8 @@ def molecule_in_text_order(cls, kekule_order, hcount, charge, atom_rank):
     assert sorted(rank[i] for i in kept) == list(range(len(kept))) and all(rank[i] == -1 for i in range(n) if i not in kept), rank
     by_rank = sorted(kept, key=lambda i: rank[i])
     atoms = [(ATOM_TYPES[cls[i]], int(hcount[i]), int(charge[i])) for i in by_rank]
-    bonds, row = {}, 0
-    for a in range(n):
-        for b in range(a + 1, n):
-            o = int(kekule_order[row])
-            if o in (1, 2, 3) and a in kept and b in kept:
-                bonds[(min(rank[a], rank[b]), max(rank[a], rank[b]))] = o
-            row += 1
-    return atoms, bonds
+    w = MS.pair_walk(cls, kekule_order, (1, 2, 3))
+    return atoms, {(min(rank[a], rank[b]), max(rank[a], rank[b])): w.order[row] for (a, b), row in w.rows.items()}
 
 
 def check_read_back(text, cls, kekule_order, hcount, charge, atom_rank, where=''):
@@ -277,7 +264,7 @@ def formula_of_text(text):
 # ---- inputs --------------------------------------------------------------------------------------------------------------------------------
 def kekule_rows(classes, bonds, allow_charged=True):
     """(cls, kekule_order, hcount, charge, kekule_status) of one (classes, {(a, b): bond class}) graph by the Kekulé restatement."""
-    cls, order = K.rows_of(classes, bonds)
+    cls, order = MS.rows_of(classes, bonds)
     r = K.kekule_of_rows(cls, order, allow_charged)
     return cls, r['kekule_order'], r['hcount'], r['charge'], int(r['status'])
 
@@ -311,29 +298,19 @@ def label_boundary(extra):
 
 
 # ---- tools/smiles_host_check.cpp: the kernel's core compiled for the host ----------------------------------------------------------------
-def build_host_check(out_dir, sanitize=True):
-    """Compile tools/smiles_host_check.cpp with g++ (ASan + UBSan unless sanitize=False); returns the program's path."""
-    exe = os.path.join(str(out_dir), 'smiles_host_check')
-    flags = ['-fsanitize=address,undefined', '-fno-sanitize-recover=all'] if sanitize else []
-    subprocess.run(['g++', '-std=c++17', '-O1', '-g', *flags, os.path.join(ROOT, 'tools', 'smiles_host_check.cpp'), '-o', exe], check=True)
-    return exe
-
-
 def run_host_check(exe, cases, work_dir):
     """cases: [(cls, kekule_order, hcount, charge, kekule_status, capacity or None)] -> one dict per case in `smiles_of_rows`' form."""
     path = os.path.join(str(work_dir), 'smiles_cases.txt')
-    table = sum((list(M.SMILES_VALENCES[z]) + [0] * (4 - len(M.SMILES_VALENCES[z])) for z in ATOM_TYPES), [])
     with open(path, 'w') as fh:
-        fh.write(' '.join(str(v) for v in table) + '\n')
+        fh.write(' '.join(str(v) for v in MS.padded_valences(M.SMILES_VALENCES)) + '\n')
         for cls, kek, h, q, kstatus, capacity in cases:
             n = len(cls)
-            a, b = np.triu_indices(n, 1)
-            rows = np.nonzero(np.asarray(kek))[0]
+            rows, a, b = MS.listed_pairs(n, kek)
             fh.write('%d %d %d %d\n' % (n, 8 * max(n, 8) if capacity is None else capacity, kstatus, rows.size))
             for arr in (cls, h, q):
                 fh.write(' '.join(str(int(x)) for x in arr) + '\n')
-            fh.write(' '.join('%d %d %d' % (a[r], b[r], kek[r]) for r in rows) + '\n')
-    out = subprocess.run([exe, path], check=True, capture_output=True, text=True).stdout.split('\n')
+            fh.write(' '.join('%d %d %d' % (x, y, kek[r]) for x, y, r in zip(a, b, rows)) + '\n')
+    out = MS.run_program(exe, path)
     got = []
     for c in range(len(cases)):
         head, text, ranks = [int(v) for v in out[3 * c].split()], out[3 * c + 1], [int(v) for v in out[3 * c + 2].split()]

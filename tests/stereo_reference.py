@@ -6,28 +6,26 @@ tests/molkey_reference.py.  The writer is recursive over dicts, as tests/smiles_
 a union-find with parities instead of the kernel's breadth-first walk.  The reader parses the text by the OpenSMILES definition alone
 -- the order in which a chiral atom's neighbours stand in the text, '@' = counter-clockwise seen from the first, '/' and '\\' as
 "above" and "below" an end of a double bond -- and knows nothing of the writer's rules; `check_text_against_geometry` holds what it
-reads against the coordinates.  Also here: the generator of the size family, the hand examples with their coordinates, and the
-driver of tools/stereo_host_check.cpp.  Nothing here holds device code."""
+reads against the coordinates.  Also here: `all_rows`, which gathers everything the kernels read for one graph from the other
+restatements (tests/hydrogen_reference.py uses it too), the generator of the size family, the hand examples with their coordinates,
+and the case format of tools/stereo_host_check.cpp.  Nothing here holds device code."""
 import math
 import os
-import subprocess
 import sys
 
 import numpy as np
 import torch
 
 import kekule_reference as K
-import mol_reference as R
+import mol_support as MS
 import molkey_reference as KEY
 import ring_reference as G
 import smiles_reference as S
+from mol_support import C_, N_, O_, F_, SI_, P_, S_, CL_, BR_, M64, batch_from, mirrored  # noqa: F401  (read from here by the tests)
 from phoregen_amd import molecule as M
 from phoregen_amd.utils.sample_utils import ATOM_TYPES
 
-B_, C_, N_, O_, F_, SI_, P_, S_, CL_, BR_, I_ = range(11)
-M64 = (1 << 64) - 1
 UNDEF = M.STEREO_UNDEFINED_VALUE
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CENTRE_CLASSES = tuple(ATOM_TYPES.index(z) for z in M.STEREO_CENTRE_CLASSES)
 MARGIN = 1e-4                    # no generated |V| or |t| lies closer than this to its threshold; fp32 moves either by about 1e-6
 
@@ -49,18 +47,7 @@ def perm_sign(seq):
 # ---- section 1: perception ----------------------------------------------------------------------------------------------------------------
 def graph_of_rows(cls, order):
     """kept [n], nbrs [n] (ascending) and the bond rows {(a, b): row} of a graph as the ring screen reads it."""
-    cls, order = [int(c) for c in cls], [int(o) for o in order]
-    n = len(cls)
-    kept = [0 <= c <= 10 for c in cls]
-    nbrs, rows, row = [[] for _ in range(n)], {}, 0
-    for a in range(n):
-        for b in range(a + 1, n):
-            if 1 <= order[row] <= 4 and kept[a] and kept[b]:
-                nbrs[a].append(b), nbrs[b].append(a)
-                rows[(a, b)] = row
-            row += 1
-    assert row == len(order)
-    return kept, [sorted(x) for x in nbrs], rows
+    return MS.pair_walk(cls, order)[:3]
 
 
 def _unit(c, p):
@@ -168,17 +155,16 @@ def stereo_of_rows(cls, order, kekule_order, hcount, kekule_status, ring_size, c
 
 
 def numbering_proof(rows, limits=None):
-    """Does no renumbering of the atoms move an answer of this graph (an `all_rows` tuple)?  A centre's |V| is the same for every order
+    """Does no renumbering of the atoms move an answer of this graph (an `all_rows` record)?  A centre's |V| is the same for every order
     of its neighbours, but a double bond is judged on its LOWEST-INDEX substituents: on a distorted geometry another pair of
     substituents can give another |t|, on the other side of planar_min, or a sign that does not go with it.  True iff, for every
     stereogenic double bond, all choices of substituents give |t| >= planar_min + MARGIN with the signs of a planar bond, or all give
     |t| < planar_min - MARGIN; and no |V| lies within MARGIN of vol_min."""
     limits = M.StereoLimits() if limits is None else limits
-    cls, order, kek, hc, _, kstatus, ring, colour, key, pos = rows
-    r = stereo_of_rows(cls, order, kek, hc, kstatus, ring, colour, key, pos, limits)
+    r, pos = restate(rows, limits), rows.pos
     if any(v is None or abs(abs(v) - limits.vol_min) <= MARGIN for v in r['volumes'].values()):
         return False
-    _, nbrs, at = graph_of_rows(cls, order)
+    _, nbrs, at = graph_of_rows(rows.cls, rows.order)
     for (a, b), row in at.items():
         if r['bond_stereo'][row] == 0:
             continue
@@ -193,19 +179,26 @@ def numbering_proof(rows, limits=None):
     return True
 
 
-def all_rows(classes, bonds, pos, allow_charged=True):
-    """Everything the stereo kernel reads for one (classes, {(a, b): bond class}, coordinates) graph, by the other restatements:
-    (cls, order, kekule_order, hcount, charge, kekule_status, ring_size, colour, key, pos)."""
-    cls, order = K.rows_of(classes, bonds)
+def all_rows(classes, bonds, pos, allow_charged=True, with_keys_and_rings=True):
+    """Everything the kernels read for one (classes, {(a, b): bond class}, coordinates) graph, by the other restatements, as a
+    `mol_support.MolRows`: the rows, the Kekulé form, pos as the float64 of its fp32 rounding and, with_keys_and_rings, the ring
+    sizes, the colours and the key (None without)."""
+    cls, order = MS.rows_of(classes, bonds)
     k = K.kekule_of_rows(cls, order, allow_charged)
-    key, colour = KEY.key_of_rows(cls, order)
-    return (cls, order, k['kekule_order'], k['hcount'], k['charge'], int(k['status']), G.rings_of_rows(cls, order)['ring_size'], colour, key,
-            np.asarray(pos, dtype=np.float32).astype(np.float64).reshape(len(classes), 3))
+    key, colour = KEY.key_of_rows(cls, order) if with_keys_and_rings else (None, None)
+    return MS.MolRows(cls, order, k['kekule_order'], k['hcount'], k['charge'], int(k['status']),
+                      G.rings_of_rows(cls, order)['ring_size'] if with_keys_and_rings else None, colour, key,
+                      np.asarray(pos, dtype=np.float32).astype(np.float64).reshape(len(classes), 3))
+
+
+def restate(rows, limits=None):
+    """`stereo_of_rows` on an `all_rows` record."""
+    return stereo_of_rows(rows.cls, rows.order, rows.kekule_order, rows.hcount, rows.kekule_status, rows.ring_size, rows.colour, rows.key,
+                          rows.pos, limits)
 
 
 def stereo_of(classes, bonds, pos, limits=None):
-    r = all_rows(classes, bonds, pos)
-    return stereo_of_rows(r[0], r[1], r[2], r[3], r[5], r[6], r[7], r[8], r[9], limits)
+    return restate(all_rows(classes, bonds, pos), limits)
 
 
 def same_stereo(got, want, where=''):
@@ -365,13 +358,8 @@ def smiles_of_rows(cls, kekule_order, hcount, charge, kekule_status, atom_parity
     if kekule_status & M.KEKULE_FAILED:
         return failed(M.SMILES_NO_KEKULE)
     elements = {i: ATOM_TYPES[c] for i, c in enumerate(cls) if 0 <= c <= 10}
-    bonds, stereo, row = {}, {}, 0
-    for a in range(n):
-        for b in range(a + 1, n):
-            if kek[row] in (1, 2, 3) and a in elements and b in elements:
-                bonds[(a, b)] = kek[row]
-                stereo[(a, b)] = int(bond_stereo[row])
-            row += 1
+    at = MS.pair_walk(cls, kek, (1, 2, 3)).rows
+    bonds, stereo = {p: kek[row] for p, row in at.items()}, {p: int(bond_stereo[row]) for p, row in at.items()}
     try:
         w = write_graph(elements, bonds, {i: int(hcount[i]) for i in elements}, {i: int(charge[i]) for i in elements},
                         {i: int(atom_parity[i]) for i in elements}, stereo)
@@ -660,8 +648,7 @@ def census(graphs, limits=None):
     at, around = set(), False
     for classes, bonds, pos in graphs:
         r = stereo_of(classes, bonds, pos, limits)
-        rows = all_rows(classes, bonds, pos)
-        _, nbrs, _ = graph_of_rows(rows[0], rows[1])
+        _, nbrs, _ = graph_of_rows(*MS.rows_of(classes, bonds))
         c['no_kekule'] += r['status'] == M.STEREO_NO_KEKULE
         for i, p in enumerate(r['atom_parity'].tolist()):
             c['centres+'] += p == 1
@@ -678,21 +665,10 @@ def census(graphs, limits=None):
     return c, at, around
 
 
-def batch_from(graphs):
-    """(node, pos, edge, sizes) as CPU tensors in the sampler's layout from [(classes, bonds, pos)], one-hot scores."""
-    parts = [R.scores_from_classes(list(c), b, pos=torch.as_tensor(np.asarray(p, dtype=np.float32)).reshape(-1, 3)) for c, b, p in graphs]
-    return (torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts]), torch.cat([p[2] for p in parts]), [len(c) for c, _, _ in graphs])
-
-
 # ---- the hand examples: name: (classes, bonds, coordinates in Angstrom, isomeric text) -------------------------------------------------------
 # The first three sets of coordinates were written by hand (a tetrahedron's corners; a planar sp2 skeleton), the others come from a
 # distance-geometry embedding of ideal bond lengths and angles, rounded to three decimals.  The texts were checked by hand against the
 # coordinates: `check_text_against_geometry` repeats that check for every one of them.
-def mirrored(pos):
-    """The mirror image: x -> -x."""
-    return [[-x, y, z] for x, y, z in pos]
-
-
 _TARTARIC = ([C_, O_, O_, C_, O_, C_, O_, C_, O_, O_],
              {(0, 1): 2, (0, 2): 1, (0, 3): 1, (3, 4): 1, (3, 5): 1, (5, 6): 1, (5, 7): 1, (7, 8): 2, (7, 9): 1})
 _DIFLUORO = ([F_, C_, C_, F_], {(0, 1): 1, (1, 2): 2, (2, 3): 1})
@@ -744,7 +720,7 @@ def assembled(classes, bonds, pos, limits=None):
     assert all(c <= 10 for c in classes)
     r = stereo_of(classes, bonds, pos, limits)
     m = KEY.with_key(KEY.mol_from(classes, bonds))
-    _, _, rows = graph_of_rows(*K.rows_of(classes, bonds))
+    _, _, rows = graph_of_rows(*MS.rows_of(classes, bonds))
     at = [rows[(int(a), int(b))] for a, b in m['bond_index'].T.tolist()]
     m['atom_pos'] = torch.as_tensor(np.asarray(pos, dtype=np.float32)).reshape(-1, 3)
     m['stereo'] = dict({'status': r['status'], 'stereo_ok': r['ok'], 'stereo_key': r['stereo_key']}, **dict(zip(M.STEREO_COUNTS, r['counts'].tolist())),
@@ -753,42 +729,32 @@ def assembled(classes, bonds, pos, limits=None):
 
 
 # ---- tools/stereo_host_check.cpp: the cores compiled for the host ---------------------------------------------------------------------------
-def build_host_check(out_dir, sanitize=True):
-    """Compile tools/stereo_host_check.cpp with g++ (ASan + UBSan unless sanitize=False); returns the program's path."""
-    exe = os.path.join(str(out_dir), 'stereo_host_check')
-    flags = ['-fsanitize=address,undefined', '-fno-sanitize-recover=all'] if sanitize else []
-    subprocess.run(['g++', '-std=c++17', '-O1', '-g', *flags, os.path.join(ROOT, 'tools', 'stereo_host_check.cpp'), '-o', exe], check=True)
-    return exe
-
-
 def run_host_check(exe, cases, work_dir, limits=None, stereo_in=None):
-    """cases: [`all_rows` tuples].  The program perceives every case and writes its isomeric text from what it perceived -- or, for the
-    cases of stereo_in {case: (atom_parity, bond_stereo)}, from those values.  Returns one (stereo, text) pair of dicts per case in
+    """cases: [`all_rows` records].  The program perceives every case and writes its isomeric text from what it perceived -- or, for
+    the cases of stereo_in {case: (atom_parity, bond_stereo)}, from those values.  Returns one (stereo, text) pair of dicts per case in
     `stereo_of_rows`' and `smiles_of_rows`' forms."""
     limits = M.StereoLimits() if limits is None else limits
     stereo_in = stereo_in or {}
     path = os.path.join(str(work_dir), 'stereo_cases.txt')
-    table = sum((list(M.SMILES_VALENCES[z]) + [0] * (4 - len(M.SMILES_VALENCES[z])) for z in ATOM_TYPES), [])
     listed = []
     with open(path, 'w') as fh:
-        fh.write(' '.join(str(v) for v in table) + '\n')
+        fh.write(' '.join(str(v) for v in MS.padded_valences(M.SMILES_VALENCES)) + '\n')
         fh.write('%s %s %d\n' % (float(limits.vol_min).hex(), float(limits.planar_min).hex(), limits.max_undefined))
-        for c, (cls, order, kek, h, q, kstatus, ring, colour, key, pos) in enumerate(cases):
-            n = len(cls)
-            a, b = np.triu_indices(n, 1)
-            rows = np.nonzero(np.asarray(order))[0]
+        for c, m in enumerate(cases):
+            n = len(m.cls)
+            rows, a, b = MS.listed_pairs(n, m.order)
             listed.append(rows)
             given = stereo_in.get(c)
-            fh.write('%d %d %d %d %d %d\n' % (n, 12 * max(n, 8), kstatus, rows.size, int(key) & M64, given is not None))
+            fh.write('%d %d %d %d %d %d\n' % (n, 12 * max(n, 8), m.kekule_status, rows.size, int(m.key) & M64, given is not None))
             for i in range(n):
-                fh.write('%d %d %d %d %s %s %s %d\n' % (cls[i], h[i], q[i], int(colour[i]) & M64, *(float(np.float32(x)).hex() for x in pos[i]),
+                fh.write('%d %d %d %d %s %s %s %d\n' % (m.cls[i], m.hcount[i], m.charge[i], int(m.colour[i]) & M64, *(MS.hex32(x) for x in m.pos[i]),
                                                          given[0][i] if given is not None else 0))
-            for r in rows:
-                fh.write('%d %d %d %d %d %d\n' % (a[r], b[r], order[r], kek[r], ring[r], given[1][r] if given is not None else 0))
-    out = subprocess.run([exe, path], check=True, capture_output=True, text=True).stdout.split('\n')
+            for x, y, r in zip(a, b, rows):
+                fh.write('%d %d %d %d %d %d\n' % (x, y, m.order[r], m.kekule_order[r], m.ring_size[r], given[1][r] if given is not None else 0))
+    out = MS.run_program(exe, path)
     got = []
     for c, (case, rows) in enumerate(zip(cases, listed)):
-        n, hh = len(case[0]), len(case[1])
+        n, hh = len(case.cls), len(case.order)
         head, atoms, pairs, shead, text, ranks = (out[6 * c + k] for k in range(6))
         head, atoms, pairs, shead = ([int(v) for v in x.split()] for x in (head, atoms, pairs, shead))
         st = {'status': head[0], 'stereo_key': head[1], 'counts': np.array(head[2:], dtype=np.int32),

@@ -10,6 +10,7 @@ from phoregen_amd import substructure as S
 from phoregen_amd.utils.sample_utils import ATOM_TYPES
 
 import kekule_reference as K
+import mol_support as MS
 import molkey_reference as Q
 import ring_reference as G
 
@@ -21,30 +22,25 @@ STEP_LIMIT = 5_000_000               # the restatement gives up (raises) beyond 
 def target_of_rows(cls, order, ring_size, atom_ring, hcount=None, charge=None, kekule_status=0):
     """One graph as the screen, the ring screen and the Kekulé kernel wrote it -> {'atoms': [property dict per kept atom, in compact
     numbering], 'bonds': {(a, b): (order, ring bond)} both ways, 'nbr': sorted neighbours per atom, 'kekule_failed', 'local': local index per compact index}."""
-    cls, order = [int(v) for v in cls], [int(v) for v in order]
-    n = len(cls)
-    kept = [i for i in range(n) if 0 <= cls[i] <= 10]
+    w = MS.pair_walk(cls, order)
+    kept = [i for i, k in enumerate(w.kept) if k]
     compact = {i: c for c, i in enumerate(kept)}
-    atoms = [{'cls': cls[i], 'degree': 0, 'hcount': int(hcount[i]) if hcount is not None else 0,
+    atoms = [{'cls': int(cls[i]), 'degree': 0, 'hcount': int(hcount[i]) if hcount is not None else 0,
               'charge': int(charge[i]) if charge is not None else 0, 'ring': int(atom_ring[i]) > 0, 'aromatic': False} for i in kept]
-    bonds, row = {}, 0
-    for a in range(n):
-        for b in range(a + 1, n):
-            if 1 <= order[row] <= 4 and a in compact and b in compact:
-                ca, cb = compact[a], compact[b]
-                bonds[(ca, cb)] = bonds[(cb, ca)] = (order[row], int(ring_size[row]) > 0)
-                for x in (ca, cb):
-                    atoms[x]['degree'] += 1
-                    atoms[x]['aromatic'] = atoms[x]['aromatic'] or order[row] == 4
-            row += 1
-    assert row == len(order)
+    bonds = {}
+    for (a, b), row in w.rows.items():
+        ca, cb = compact[a], compact[b]
+        bonds[(ca, cb)] = bonds[(cb, ca)] = (w.order[row], int(ring_size[row]) > 0)
+        for x in (ca, cb):
+            atoms[x]['degree'] += 1
+            atoms[x]['aromatic'] = atoms[x]['aromatic'] or w.order[row] == 4
     nbr = [sorted(b for (a, b) in bonds if a == c) for c in range(len(kept))]
     return {'atoms': atoms, 'bonds': bonds, 'nbr': nbr, 'kekule_failed': bool(int(kekule_status) & M.KEKULE_FAILED), 'local': kept}
 
 
 def target_of_classes(classes, bonds, kekule=True):
     """A target from atom classes 0..11 and {(a, b): bond class 1..5}, properties from ring_reference / kekule_reference."""
-    cls, order = G.rows_of(list(classes), dict(bonds))
+    cls, order = MS.rows_of(list(classes), dict(bonds))
     rings = G.rings_of_rows(cls, order)
     if not kekule:
         return target_of_rows(cls, order, rings['ring_size'], rings['atom_ring'])
@@ -196,11 +192,11 @@ def nx_count(target, p):
 
 # ---- the tests' pattern lists ---------------------------------------------------------------------------------------------------------
 def _path(n):
-    return [{'a': i, 'b': i + 1} for i in range(n - 1)]
+    return [{'a': a, 'b': b} for a, b in MS.chain(n, 0)]
 
 
 def _cycle(n, **kw):
-    return [dict({'a': min(i, (i + 1) % n), 'b': max(i, (i + 1) % n)}, **kw) for i in range(n)]
+    return [dict({'a': a, 'b': b}, **kw) for a, b in MS.cycle(n, 0)]
 
 
 _DECALIN = _cycle(6) + [{'a': 0, 'b': 6}, {'a': 6, 'b': 7}, {'a': 7, 'b': 8}, {'a': 8, 'b': 9}, {'a': 1, 'b': 9}]

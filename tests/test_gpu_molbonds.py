@@ -9,7 +9,7 @@ import pytest
 import torch
 
 import bonds_reference as BR
-from helpers import mol_result as _result, permute_batch
+from mol_support import split_frame, mol_result as _result, permute_batch
 from phoregen_amd import molecule as M
 from phoregen_amd.utils.sample_utils import ATOM_TYPES
 
@@ -28,22 +28,18 @@ def batch():
 
 def _compare_frame(sc, f, refs, sizes, agree=True):
     """Frame f of a Screen against the restated graphs: every output array, every graph."""
-    status, counts, valid = sc.status[f].cpu().numpy(), sc.counts[f].cpu().numpy(), sc.valid[f].cpu().numpy()
-    per_row = {k: getattr(sc, k)[f].cpu().numpy() for k in ('cls', 'compact', 'valence2', 'comp', 'order')}
-    ag = sc.agree[f].cpu().numpy() if agree else None
-    n0, h0 = 0, 0
-    for g, (n, r) in enumerate(zip(sizes, refs)):
-        h = n * (n - 1) // 2
-        assert status[g] == r['status'], (f, g, n, status[g], r['status'])
-        assert counts[g].tolist() == r['counts'].tolist(), (f, g, n, counts[g].tolist(), r['counts'].tolist())
-        assert bool(valid[g]) == r['valid']
-        for k, v in per_row.items():
-            got = v[h0:h0 + h] if k == 'order' else v[n0:n0 + n]
-            assert got.dtype == r[k].dtype and np.array_equal(got, r[k]), (f, g, n, k)
+    got = split_frame(sizes, f, per_atom={k: getattr(sc, k) for k in ('cls', 'compact', 'valence2', 'comp')}, per_pair={'order': sc.order},
+                      per_graph=dict({'status': sc.status, 'counts': sc.counts, 'valid': sc.valid}, **({'agree': sc.agree} if agree else {})))
+    for g, (n, x, r) in enumerate(zip(sizes, got, refs)):
+        assert x['status'] == r['status'], (f, g, n, x['status'], r['status'])
+        assert x['counts'].tolist() == r['counts'].tolist(), (f, g, n, x['counts'].tolist(), r['counts'].tolist())
+        assert bool(x['valid']) == r['valid']
+        for k in ('cls', 'compact', 'valence2', 'comp', 'order'):
+            assert x[k].dtype == r[k].dtype and np.array_equal(x[k], r[k]), (f, g, n, k)
         if agree:
-            assert ag.dtype == r['agree'].dtype and ag[g].tolist() == r['agree'].tolist(), (f, g, n, ag[g].tolist(), r['agree'].tolist())
-            assert int(ag[g].sum()) == int(r['counts'][0]) * (int(r['counts'][0]) - 1) // 2 or r['status'] & M.STATUS_NONFINITE
-        n0, h0 = n0 + n, h0 + h
+            ag = x['agree']
+            assert ag.dtype == r['agree'].dtype and ag.tolist() == r['agree'].tolist(), (f, g, n, ag.tolist(), r['agree'].tolist())
+            assert int(ag.sum()) == int(r['counts'][0]) * (int(r['counts'][0]) - 1) // 2 or r['status'] & M.STATUS_NONFINITE
 
 
 def _same(a, b, names=ARRAYS):

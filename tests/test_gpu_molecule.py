@@ -7,7 +7,8 @@ import pytest
 import torch
 
 import mol_reference as R
-from helpers import default_model, mol_result as _result
+from helpers import default_model
+from mol_support import split_frame, mol_result as _result
 from phoregen_amd import molecule as M
 
 pytestmark = pytest.mark.gpu
@@ -22,18 +23,14 @@ def model():
 
 def _compare_frame(sc, f, refs, sizes):
     """Frame f of a Screen against the restated graphs: every output array, every graph."""
-    status, counts, valid = sc.status[f].cpu().numpy(), sc.counts[f].cpu().numpy(), sc.valid[f].cpu().numpy()
-    per_row = {k: getattr(sc, k)[f].cpu().numpy() for k in ('cls', 'compact', 'valence2', 'comp', 'order')}
-    n0, h0 = 0, 0
-    for g, (n, r) in enumerate(zip(sizes, refs)):
-        h = n * (n - 1) // 2
-        assert status[g] == r['status'], (f, g, n, status[g], r['status'])
-        assert counts[g].tolist() == r['counts'].tolist(), (f, g, n, counts[g].tolist(), r['counts'].tolist())
-        assert bool(valid[g]) == r['valid']
-        for k, v in per_row.items():
-            got = v[h0:h0 + h] if k == 'order' else v[n0:n0 + n]
-            assert got.dtype == r[k].dtype and np.array_equal(got, r[k]), (f, g, n, k)
-        n0, h0 = n0 + n, h0 + h
+    got = split_frame(sizes, f, per_atom={k: getattr(sc, k) for k in ('cls', 'compact', 'valence2', 'comp')}, per_pair={'order': sc.order},
+                      per_graph={'status': sc.status, 'counts': sc.counts, 'valid': sc.valid})
+    for g, (n, x, r) in enumerate(zip(sizes, got, refs)):
+        assert x['status'] == r['status'], (f, g, n, x['status'], r['status'])
+        assert x['counts'].tolist() == r['counts'].tolist(), (f, g, n, x['counts'].tolist(), r['counts'].tolist())
+        assert bool(x['valid']) == r['valid']
+        for k in ('cls', 'compact', 'valence2', 'comp', 'order'):
+            assert x[k].dtype == r[k].dtype and np.array_equal(x[k], r[k]), (f, g, n, k)
 
 
 def test_kernel_equals_restatement_on_ragged_batches():

@@ -17,7 +17,7 @@ import feature_reference as FR
 import kekule_reference as K
 import mol_reference as R
 from phoregen_amd import hip
-from helpers import mol_result as _result
+from mol_support import batch_from, renumbered_rows, split_frame, mol_result as _result
 from phoregen_amd import molecule as M
 
 pytestmark = pytest.mark.gpu
@@ -28,27 +28,20 @@ CI = M.FEATURE_COUNTS.index
 
 def _batch(cases):
     """(node, pos, edge, sizes) of cases {'classes', 'bonds', 'pos'} as CPU tensors, one-hot scores."""
-    parts = [R.scores_from_classes(c['classes'], c['bonds'], pos=torch.from_numpy(np.asarray(c['pos'], dtype=np.float32)).reshape(-1, 3)) for c in cases]
-    return (torch.cat([p[0] for p in parts]), torch.cat([p[1] for p in parts]), torch.cat([p[2] for p in parts]), [len(c['classes']) for c in cases])
+    return batch_from([(c['classes'], c['bonds'], c['pos']) for c in cases])
 
 
 def _split(ft, sizes, f=0):
     """Frame f of a `Features` as one dict of numpy arrays per graph, with the inputs the kernel read."""
-    sc, kk, rg = ft.screen, ft.kekule, ft.rings
-    cls, order = sc.cls[f].cpu().numpy(), sc.order[f].cpu().numpy()
-    kek, h, q, kst = kk.kekule_order[f].cpu().numpy(), kk.hcount[f].cpu().numpy(), kk.charge[f].cpu().numpy(), kk.status[f].cpu().tolist()
-    rs = rg.ring_size[f].cpu().numpy()
-    fp, dist, atom = ft.atom_fp[f].cpu().numpy(), ft.point_dist[f].cpu().numpy(), ft.point_atom[f].cpu().numpy()
-    counts, status, ok, off = ft.counts[f].cpu().numpy(), ft.status[f].cpu().tolist(), ft.ok[f].cpu().tolist(), ft.point_off.cpu().tolist()
-    out, n0, h0 = [], 0, 0
-    for g, n in enumerate(sizes):
-        hh = n * (n - 1) // 2
-        out.append({'atom_fp': fp[n0:n0 + n], 'point_dist': dist[off[g]:off[g + 1]], 'point_atom': atom[off[g]:off[g + 1]], 'counts': counts[g],
-                    'status': status[g], 'ok': ok[g],
-                    'inputs': (cls[n0:n0 + n], order[h0:h0 + hh], kek[h0:h0 + hh], h[n0:n0 + n], q[n0:n0 + n],
-                               kst[g] & M.KEKULE_FAILED == 0, rs[h0:h0 + hh])})
-        n0, h0 = n0 + n, h0 + hh
-    return out
+    sc, kk = ft.screen, ft.kekule
+    parts = split_frame(sizes, f, per_atom={'atom_fp': ft.atom_fp, 'cls': sc.cls, 'hcount': kk.hcount, 'charge': kk.charge},
+                        per_pair={'order': sc.order, 'kekule_order': kk.kekule_order, 'ring_size': ft.rings.ring_size},
+                        per_graph={'counts': ft.counts, 'status': ft.status, 'ok': ft.ok, 'kekule_status': kk.status})
+    dist, atom, off = ft.point_dist[f].cpu().numpy(), ft.point_atom[f].cpu().numpy(), ft.point_off.cpu().tolist()
+    return [{'atom_fp': r['atom_fp'], 'point_dist': dist[off[g]:off[g + 1]], 'point_atom': atom[off[g]:off[g + 1]], 'counts': r['counts'],
+             'status': r['status'], 'ok': r['ok'],
+             'inputs': (r['cls'], r['order'], r['kekule_order'], r['hcount'], r['charge'], r['kekule_status'] & M.KEKULE_FAILED == 0, r['ring_size'])}
+            for g, r in enumerate(parts)]
 
 
 def _same(r, w, where):
@@ -252,11 +245,7 @@ def test_renumbered_graphs(family):
 
 def _same_structure(a, b, p):
     """Did both numberings get the same Kekulé structure (double bonds, hydrogens and charges atom for atom)?"""
-    n = len(p)
-    ia, ib = np.triu_indices(n, 1)
-    lo, hi = np.minimum(p[ia], p[ib]), np.maximum(p[ia], p[ib])
-    rows_b = lo * n - lo * (lo + 1) // 2 + (hi - lo - 1)
-    return (np.array_equal(b['inputs'][2][rows_b], a['inputs'][2]) and np.array_equal(b['inputs'][3][p], a['inputs'][3])
+    return (np.array_equal(b['inputs'][2][renumbered_rows(p)], a['inputs'][2]) and np.array_equal(b['inputs'][3][p], a['inputs'][3])
             and np.array_equal(b['inputs'][4][p], a['inputs'][4]))
 
 

@@ -13,14 +13,14 @@ import torch
 
 import fp_reference as P
 import mol_reference as R
-from helpers import default_model, mol_result as _result, permute_batch as _permute_batch
+from helpers import default_model
+from mol_support import M64, mol_result as _result, permute_batch as _permute_batch
 from phoregen_amd import molecule as M
 from phoregen_amd import similarity as S
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-M64 = (1 << 64) - 1
 
 
 @pytest.fixture(scope='module')

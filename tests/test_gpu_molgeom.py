@@ -17,7 +17,8 @@ import torch
 import geom_reference as G
 import mol_reference as R
 from phoregen_amd import hip
-from helpers import default_model, mol_result as _result
+from helpers import default_model
+from mol_support import bits as _bits, mol_result as _result
 from phoregen_amd import molecule as M
 
 pytestmark = pytest.mark.gpu
@@ -66,11 +67,6 @@ def _buffers(F, B, Q, fill=None):
     shapes = {'status': ((F, B), torch.int32), 'counts': ((F, B, 6), torch.int32), 'metrics': ((F, B, 8), torch.float32),
               'point_dist': ((F, Q), torch.float32), 'point_atom': ((F, Q), torch.int16)}
     return {k: (torch.empty(s, dtype=dt, device=DEV) if fill is None else torch.full(s, fill, dtype=dt, device=DEV)) for k, (s, dt) in shapes.items()}
-
-
-def _bits(t):
-    """A tensor as integers of its own width: equality of these is equality bit for bit (NaNs included)."""
-    return t.contiguous().view(torch.int32) if t.dtype == torch.float32 else t
 
 
 def _same(a, b):

@@ -13,7 +13,7 @@ import pytest
 import torch
 
 import hydrogen_reference as H
-from helpers import mol_result as _result, permute_batch as _permute_batch
+from mol_support import MolRows, bits, read_mol_block, split_frame, mol_result as _result, permute_batch as _permute_batch
 from phoregen_amd import hip, hydrogens as HY, molecule as M
 
 pytestmark = pytest.mark.gpu
@@ -30,19 +30,14 @@ def family():
 
 
 def _split(hy, pos, sizes, f=0):
-    """Frame f of a `Hydrogens` as one dict of host values per graph, with 'rows' = the `all_rows` tuple of the device's own inputs."""
-    cpu = lambda t: t[f].cpu().numpy()                                 # noqa: E731
-    status, counts, h_pos, placed, shape, minc = (cpu(getattr(hy, k)) for k in NAMES)
-    cls, order, kek, hc, ch, kst = (cpu(x) for x in (hy.screen.cls, hy.screen.order, hy.kekule.kekule_order, hy.kekule.hcount,
-                                                     hy.kekule.charge, hy.kekule.status))
-    out, n0, h0 = [], 0, 0
-    for g, n in enumerate(sizes):
-        h = n * (n - 1) // 2
-        a, hh = slice(n0, n0 + n), slice(h0, h0 + h)
-        out.append({'status': int(status[g]), 'counts': counts[g], 'h_pos': h_pos[a], 'h_placed': placed[a], 'site_shape': shape[a],
-                    'min_contact': float(minc[g]),
-                    'rows': (cls[a], order[hh], kek[hh], hc[a], ch[a], int(kst[g]), np.asarray(pos[n0:n0 + n], dtype=np.float64))})
-        n0, h0 = n0 + n, h0 + h
+    """Frame f of a `Hydrogens` as one dict of host values per graph, with 'rows' = the `all_rows` record of the device's own inputs."""
+    sc, kk = hy.screen, hy.kekule
+    out = split_frame(sizes, f, per_atom={'h_pos': hy.h_pos, 'h_placed': hy.h_placed, 'site_shape': hy.site_shape},
+                      per_graph={'status': hy.status, 'counts': hy.counts, 'min_contact': hy.min_contact})
+    rows = split_frame(sizes, f, per_atom={'cls': sc.cls, 'hcount': kk.hcount, 'charge': kk.charge},
+                       per_pair={'order': sc.order, 'kekule_order': kk.kekule_order}, per_graph={'kekule_status': kk.status})
+    for r, m, p in zip(out, rows, np.split(np.asarray(pos, dtype=np.float64), np.cumsum(sizes, dtype=int)[:-1])):
+        r['rows'] = MolRows(pos=p, **m)
     return out
 
 
@@ -65,11 +60,11 @@ def _validate(r, options=None, where='', safe_only=False):
     want = H.restate(r['rows'], options)
     if safe_only and not H.is_safe(want, options):
         return None, None
-    return H.compare(r, want, r['rows'][6], options, where=where), want
+    return H.compare(r, want, r['rows'].pos, options, where=where), want
 
 
 def _bits(r):
-    return {k: np.asarray(r[k]).tobytes() if isinstance(r[k], np.ndarray) else r[k] for k in NAMES}
+    return {k: bits(r[k]) for k in NAMES}
 
 
 def _examples_and_mirrors():
@@ -127,8 +122,8 @@ def test_renumbered_graphs(family):
         _, want_b = _validate(b, FAMILY_OPT, where='renumbered %d' % g, safe_only=True)
         if want_b is None:
             continue                                                   # (an argmin that the new numbering decides by less than the margin)
-        _, nbrs, _, _, _ = H.graph_of_rows(a['rows'][0], a['rows'][2], a['rows'][1])
-        p, pa = perms[g], a['rows'][6]
+        _, nbrs, _, _, _ = H.graph_of_rows(a['rows'].cls, a['rows'].kekule_order, a['rows'].order)
+        p, pa = perms[g], a['rows'].pos
         for i in range(sizes[g]):
             h, shape = int(a['h_placed'][i]), int(a['site_shape'][i])
             assert int(b['h_placed'][p[i]]) == h, (g, i)
@@ -147,11 +142,11 @@ def test_renumbered_graphs(family):
                 same += 1
             elif h and len(nbrs[i]) == 1 and shape in (H.TET, H.TRIG):
                 want = {H.TET: H.TET_COS, H.TRIG: -0.5}[shape]
-                for r, q, at in ((a, pa, i), (b, b['rows'][6], p[i])):
-                    j = H.graph_of_rows(r['rows'][0], r['rows'][2], r['rows'][1])[1][at][0]
+                for r, q, at in ((a, pa, i), (b, b['rows'].pos, p[i])):
+                    j = H.graph_of_rows(r['rows'].cls, r['rows'].kekule_order, r['rows'].order)[1][at][0]
                     for k in range(h):
                         v, u = r['h_pos'][at, k] - q[at], q[j] - q[at]
-                        assert abs(np.linalg.norm(v) - FAMILY_OPT.xh_length[int(r['rows'][0][at])]) < 1e-5
+                        assert abs(np.linalg.norm(v) - FAMILY_OPT.xh_length[int(r['rows'].cls[at])]) < 1e-5
                         assert abs(float(np.dot(v, u) / (np.linalg.norm(v) * np.linalg.norm(u))) - want) < 1e-5, (g, i, k)
                 cone += 1
     assert same >= 100 and cone >= 50
@@ -172,8 +167,8 @@ def test_rotation_and_translation_move_the_hydrogens_with_the_molecule(family):
         _, wb = _validate(b, FAMILY_OPT, where='after %d' % g, safe_only=True)
         if wb is None:
             continue                                                   # (the rotation brought an axis or vertex choice within the margin)
-        _, nbrs, _, _, _ = H.graph_of_rows(a['rows'][0], a['rows'][2], a['rows'][1])
-        pa, pb = a['rows'][6], b['rows'][6]
+        _, nbrs, _, _, _ = H.graph_of_rows(a['rows'].cls, a['rows'].kekule_order, a['rows'].order)
+        pa, pb = a['rows'].pos, b['rows'].pos
         for i in range(len(pa)):
             h = int(a['h_placed'][i])
             axis_free = len(nbrs[i]) >= 2 or (len(nbrs[i]) == 1 and len(nbrs[nbrs[i][0]]) >= 2)
@@ -288,9 +283,9 @@ def test_too_many_oversize_and_cpu_results_are_refused():
 
 
 def _read_block(text):
-    lines = text.split('\n')
-    na, nb = int(lines[3][0:3]), int(lines[3][3:6])
-    return [ln[31:34].strip() for ln in lines[4:4 + na]], [(int(ln[0:3]) - 1, int(ln[3:6]) - 1, int(ln[6:9])) for ln in lines[4 + na:4 + na + nb]]
+    """(element symbols, bonds) of a V2000 block."""
+    atoms, bonds = read_mol_block(text)
+    return [a[0] for a in atoms], bonds
 
 
 def test_assemble_sdf_sample_valid_and_cli_carry_the_hydrogens(tmp_path):

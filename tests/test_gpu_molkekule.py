@@ -12,7 +12,8 @@ import torch
 import kekule_reference as K
 import mol_reference as R
 import ring_reference as G
-from helpers import default_model, mol_result as _result, permute_batch as _permute_batch
+from helpers import default_model
+from mol_support import renumbered_rows, split_frame, mol_result as _result, permute_batch as _permute_batch
 from phoregen_amd import molecule as M
 
 pytestmark = pytest.mark.gpu
@@ -36,16 +37,9 @@ def family():
 
 def _split(kk, sizes, f=0):
     """Frame f of a `Kekule` as one dict of numpy arrays per graph, in the restatement's form, plus the screen's rows."""
-    ko, hc, ch = kk.kekule_order[f].cpu().numpy(), kk.hcount[f].cpu().numpy(), kk.charge[f].cpu().numpy()
-    cls, order = kk.screen.cls[f].cpu().numpy(), kk.screen.order[f].cpu().numpy()
-    counts, status, ok = kk.counts[f].cpu().numpy(), kk.status[f].cpu().tolist(), kk.ok[f].cpu().tolist()
-    out, n0, h0 = [], 0, 0
-    for g, n in enumerate(sizes):
-        h = n * (n - 1) // 2
-        out.append({'kekule_order': ko[h0:h0 + h], 'hcount': hc[n0:n0 + n], 'charge': ch[n0:n0 + n], 'counts': counts[g],
-                    'status': status[g], 'ok': ok[g], 'cls': cls[n0:n0 + n], 'order': order[h0:h0 + h]})
-        n0, h0 = n0 + n, h0 + h
-    return out
+    return split_frame(sizes, f, per_atom={'hcount': kk.hcount, 'charge': kk.charge, 'cls': kk.screen.cls},
+                       per_pair={'kekule_order': kk.kekule_order, 'order': kk.screen.order},
+                       per_graph={'counts': kk.counts, 'status': kk.status, 'ok': kk.ok})
 
 
 def _run(node, pos, edge, sizes, allow=True):
@@ -140,12 +134,8 @@ def test_renumbered_graphs(family):
         if not (a['charge'] != 0).any() and not (b['charge'] != 0).any():
             assert a['counts'][CI('hydrogens')] == b['counts'][CI('hydrogens')], g
         # what is not aromatic is carried over as it is
-        n = sizes[g]
-        ia, ib = np.triu_indices(n, 1)
-        lo, hi = np.minimum(p[ia], p[ib]), np.maximum(p[ia], p[ib])
-        rows_b = lo * n - lo * (lo + 1) // 2 + (hi - lo - 1)
         plain = a['order'] != 4
-        assert np.array_equal(b['kekule_order'][rows_b][plain], a['kekule_order'][plain])
+        assert np.array_equal(b['kekule_order'][renumbered_rows(p)][plain], a['kekule_order'][plain])
 
 
 def test_large_graphs_with_known_answers():

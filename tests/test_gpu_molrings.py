@@ -9,13 +9,13 @@ import torch
 
 import mol_reference as R
 import ring_reference as G
-from helpers import default_model, mol_result as _result, permute_batch as _permute_batch, onehot_graph as _onehot, cat_graphs as _cat
+from helpers import default_model
+from mol_support import C_, renumbered_rows, split_frame, mol_result as _result, permute_batch as _permute_batch, onehot_graph as _onehot, cat_graphs as _cat
 from phoregen_amd import molecule as M
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-C_ = 1
 
 
 @pytest.fixture(scope='module')
@@ -25,15 +25,8 @@ def model():
 
 def _split(rg, sizes, f=0):
     """Frame f of a `Rings` as one dict of numpy arrays per graph, in the restatement's form."""
-    rs, ar, sy = rg.ring_size[f].cpu().numpy(), rg.atom_ring[f].cpu().numpy(), rg.ring_sys[f].cpu().numpy()
-    counts, status, ok = rg.counts[f].cpu().numpy(), rg.status[f].cpu().tolist(), rg.ok[f].cpu().tolist()
-    out, n0, h0 = [], 0, 0
-    for g, n in enumerate(sizes):
-        h = n * (n - 1) // 2
-        out.append({'ring_size': rs[h0:h0 + h], 'atom_ring': ar[n0:n0 + n], 'ring_sys': sy[n0:n0 + n], 'counts': counts[g],
-                    'status': status[g], 'ok': ok[g]})
-        n0, h0 = n0 + n, h0 + h
-    return out
+    return split_frame(sizes, f, per_atom={'atom_ring': rg.atom_ring, 'ring_sys': rg.ring_sys}, per_pair={'ring_size': rg.ring_size},
+                       per_graph={'counts': rg.counts, 'status': rg.status, 'ok': rg.ok})
 
 
 def _same(got, want, where=''):
@@ -209,9 +202,7 @@ def test_renumbered_batch():
     for g, (a, b, p) in enumerate(zip(_split(rg, sizes), _split(rg2, sizes), perms)):
         n = sizes[g]
         assert [int(b['atom_ring'][p[i]]) for i in range(n)] == a['atom_ring'].tolist()
-        ia, ib = np.triu_indices(n, 1)
-        lo, hi = np.minimum(p[ia], p[ib]), np.maximum(p[ia], p[ib])
-        assert np.array_equal(b['ring_size'][lo * n - lo * (lo + 1) // 2 + (hi - lo - 1)], a['ring_size'])
+        assert np.array_equal(b['ring_size'][renumbered_rows(p)], a['ring_size'])
         part = lambda sys, img: {frozenset(int(img[i]) for i in range(n) if sys[i] == s) for s in set(sys.tolist()) - {-1}}   # noqa: E731
         assert part(a['ring_sys'], p) == part(b['ring_sys'], np.arange(n))
         assert all(int(b['ring_sys'][i]) == min(s) for s in part(b['ring_sys'], np.arange(n)) for i in s)

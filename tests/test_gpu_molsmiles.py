@@ -16,7 +16,8 @@ import kekule_reference as K
 import mol_reference as R
 import ring_reference as G
 import smiles_reference as S
-from helpers import default_model, mol_result as _result, permute_batch as _permute_batch
+from helpers import default_model
+from mol_support import split_frame, mol_result as _result, permute_batch as _permute_batch
 from phoregen_amd import molecule as M
 
 pytestmark = pytest.mark.gpu
@@ -38,20 +39,15 @@ def family():
 
 def _split(sm, sizes, f=0):
     """Frame f of a `Smiles` as one dict of host values per graph, in the restatement's form, plus the rows it was written from."""
-    text, length = sm.text[f].cpu().numpy(), sm.length[f].cpu().tolist()
-    rank, counts, status, ok = sm.atom_rank[f].cpu().numpy(), sm.counts[f].cpu().numpy(), sm.status[f].cpu().tolist(), sm.ok[f].cpu().tolist()
-    cls, kek = sm.screen.cls[f].cpu().numpy(), sm.kekule.kekule_order[f].cpu().numpy()
-    hc, ch, kst = sm.kekule.hcount[f].cpu().numpy(), sm.kekule.charge[f].cpu().numpy(), sm.kekule.status[f].cpu().tolist()
-    strings = sm.strings(f)
-    out, n0, h0 = [], 0, 0
-    for g, n in enumerate(sizes):
-        h = n * (n - 1) // 2
-        row = text[g]
-        assert row.shape == (sm.capacity,) and not row[length[g]:].any() and (row[:length[g]] > 0x20).all() and (row[:length[g]] < 0x7f).all()
-        assert strings[g] == row[:length[g]].tobytes().decode('ascii')
-        out.append({'text': strings[g], 'length': length[g], 'atom_rank': rank[n0:n0 + n], 'counts': counts[g], 'status': status[g], 'ok': ok[g],
-                    'rows': (cls[n0:n0 + n], kek[h0:h0 + h], hc[n0:n0 + n], ch[n0:n0 + n], kst[g])})
-        n0, h0 = n0 + n, h0 + h
+    kk = sm.kekule
+    out = split_frame(sizes, f, per_atom={'atom_rank': sm.atom_rank, 'cls': sm.screen.cls, 'hcount': kk.hcount, 'charge': kk.charge},
+                      per_pair={'kekule_order': kk.kekule_order},
+                      per_graph={'text': sm.text, 'length': sm.length, 'counts': sm.counts, 'status': sm.status, 'ok': sm.ok, 'kekule_status': kk.status})
+    for r, string in zip(out, sm.strings(f)):
+        row, n = r['text'], r['length']
+        assert row.shape == (sm.capacity,) and not row[n:].any() and (row[:n] > 0x20).all() and (row[:n] < 0x7f).all()
+        assert string == row[:n].tobytes().decode('ascii')
+        r.update(text=string, rows=tuple(r.pop(k) for k in ('cls', 'kekule_order', 'hcount', 'charge', 'kekule_status')))
     return out
 
 

@@ -17,13 +17,12 @@ import torch
 import kekule_reference as K
 import smiles_reference as S
 import stereo_reference as T
-from helpers import mol_result as _result, permute_batch as _permute_batch
+from mol_support import M64, MolRows, split_frame, mol_result as _result, permute_batch as _permute_batch
 from phoregen_amd import molecule as M
 
 pytestmark = pytest.mark.gpu
 DEV = 'cuda'
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-M64 = (1 << 64) - 1
 
 
 @pytest.fixture(scope='module')
@@ -34,26 +33,23 @@ def family():
 
 def _split(st, sm, pos, sizes, f=0):
     """Frame f of a `Stereo` and of the `Smiles` written with it as one dict of host values per graph: 'stereo' and 'text' in the
-    restatement's forms, 'rows' = the `all_rows` tuple of the device's own inputs."""
-    cpu = lambda t: t[f].cpu().numpy()                                 # noqa: E731
-    par, lab, bst, bla, key, cnt, status = (cpu(x) for x in (st.atom_parity, st.atom_label, st.bond_stereo, st.bond_label, st.stereo_key,
-                                                             st.counts, st.status))
-    cls, order, kek, hc, ch = cpu(st.screen.cls), cpu(st.screen.order), cpu(st.kekule.kekule_order), cpu(st.kekule.hcount), cpu(st.kekule.charge)
-    kst, ring, col, idk = cpu(st.kekule.status), cpu(st.rings.ring_size), cpu(st.keys.colour), cpu(st.keys.key)
-    text, length, rank, scnt, sst, stc = (cpu(x) for x in (sm.text, sm.length, sm.atom_rank, sm.counts, sm.status, sm.stereo_counts))
-    strings = sm.strings(f)
-    out, n0, h0 = [], 0, 0
-    for g, n in enumerate(sizes):
-        h = n * (n - 1) // 2
-        a, hh = slice(n0, n0 + n), slice(h0, h0 + h)
-        assert not text[g][length[g]:].any() and strings[g] == text[g][:length[g]].tobytes().decode('ascii')
-        out.append({'stereo': {'atom_parity': par[a], 'atom_label': lab[a], 'bond_stereo': bst[hh], 'bond_label': bla[hh],
-                               'stereo_key': int(key[g]) & M64, 'counts': cnt[g], 'status': int(status[g])},
-                    'text': {'text': strings[g], 'status': int(sst[g]), 'ok': int(sst[g]) & M.SMILES_FAIL_MASK == 0, 'length': int(length[g]),
-                             'counts': scnt[g], 'atom_rank': rank[a], 'stereo_counts': stc[g]},
-                    'rows': (cls[a], order[hh], kek[hh], hc[a], ch[a], int(kst[g]), ring[hh], [int(c) & M64 for c in col[a]], int(idk[g]) & M64,
-                             np.asarray(pos[n0:n0 + n], dtype=np.float64))})
-        n0, h0 = n0 + n, h0 + h
+    restatement's forms, 'rows' = the `all_rows` record of the device's own inputs."""
+    sc, kk = st.screen, st.kekule
+    stereo = split_frame(sizes, f, per_atom={'atom_parity': st.atom_parity, 'atom_label': st.atom_label},
+                         per_pair={'bond_stereo': st.bond_stereo, 'bond_label': st.bond_label},
+                         per_graph={'stereo_key': st.stereo_key, 'counts': st.counts, 'status': st.status})
+    texts = split_frame(sizes, f, per_atom={'atom_rank': sm.atom_rank},
+                        per_graph={'bytes': sm.text, 'status': sm.status, 'length': sm.length, 'counts': sm.counts, 'stereo_counts': sm.stereo_counts})
+    rows = split_frame(sizes, f, per_atom={'cls': sc.cls, 'hcount': kk.hcount, 'charge': kk.charge, 'colour': st.keys.colour},
+                       per_pair={'order': sc.order, 'kekule_order': kk.kekule_order, 'ring_size': st.rings.ring_size},
+                       per_graph={'kekule_status': kk.status, 'key': st.keys.key})
+    out = []
+    for s, t, m, p, string in zip(stereo, texts, rows, np.split(np.asarray(pos, dtype=np.float64), np.cumsum(sizes, dtype=int)[:-1]), sm.strings(f)):
+        row = t.pop('bytes')
+        assert not row[t['length']:].any() and string == row[:t['length']].tobytes().decode('ascii')
+        s['stereo_key'] &= M64
+        m.update(colour=[int(c) & M64 for c in m['colour']], key=m['key'] & M64)
+        out.append({'stereo': s, 'text': dict(t, text=string, ok=t['status'] & M.SMILES_FAIL_MASK == 0), 'rows': MolRows(pos=p, **m)})
     return out
 
 
@@ -76,13 +72,12 @@ def _run(graphs, limits=M.StereoLimits(), capacity=None):
 def _validate(r, limits=None, capacity=None, where=''):
     """One graph: every output `==` the restatement's on the device's own inputs; the text agrees with the coordinates."""
     rows = r['rows']
-    want = T.stereo_of_rows(rows[0], rows[1], rows[2], rows[3], rows[5], rows[6], rows[7], rows[8], rows[9], limits)
+    want = T.restate(rows, limits)
     T.same_stereo(r['stereo'], want, where=where)
-    T.same_text(r['text'], T.smiles_of_rows(rows[0], rows[2], rows[3], rows[4], rows[5], want['atom_parity'], want['bond_stereo'],
-                                            capacity=capacity), where=where)
+    T.same_text(r['text'], T.smiles_of_rows(*rows.smiles_inputs(), want['atom_parity'], want['bond_stereo'], capacity=capacity), where=where)
     if r['text']['ok']:
-        _, _, at = T.graph_of_rows(rows[0], rows[1])
-        return T.check_text_against_geometry(r['text']['text'], r['text']['atom_rank'], rows[9], want, at, limits, where=where)
+        _, _, at = T.graph_of_rows(rows.cls, rows.order)
+        return T.check_text_against_geometry(r['text']['text'], r['text']['atom_rank'], rows.pos, want, at, limits, where=where)
     return 0, 0, 0
 
 
@@ -100,7 +95,7 @@ def test_examples_by_hand_their_mirror_images_twice_into_recycled_memory():
     assert [r['text']['text'] for r in got[:n]] == [t for _, _, _, t in T.EXAMPLES.values()]
     assert mirror['CHFClBr skeleton']['text']['text'] == '[C@@H](F)(Cl)Br' and mirror['cis-1,2-difluoroethene skeleton']['text']['text'] == 'F/C=C\\F'
     for name in ('ring double bond', 'allene'):
-        assert not by[name]['stereo']['counts'].any() and by[name]['stereo']['stereo_key'] == by[name]['rows'][8]
+        assert not by[name]['stereo']['counts'].any() and by[name]['stereo']['stereo_key'] == by[name]['rows'].key
     assert by['conjugated triene']['stereo']['counts'].tolist() == [0, 0, 0, 0, 3, 3, 3, 0]
     assert by['quaternary N+']['text']['text'].startswith('[N@+]') and by['quaternary N+']['stereo']['status'] == M.STEREO_HAS_CENTRE
     assert by['oxime']['stereo']['status'] == M.STEREO_HAS_BOND and by['oxime']['text']['stereo_counts'].tolist() == [0, 0, 2, 1]
@@ -112,7 +107,7 @@ def test_examples_by_hand_their_mirror_images_twice_into_recycled_memory():
         chiral = name in ('CHFClBr skeleton', 'quaternary N+', 'chiral tartaric skeleton', 'centre that is a ring-closure atom')
         assert (a['stereo_key'] != b['stereo_key']) == chiral, name
     assert by['meso-tartaric skeleton']['stereo']['stereo_key'] != by['chiral tartaric skeleton']['stereo']['stereo_key']
-    assert by['meso-tartaric skeleton']['rows'][8] == by['chiral tartaric skeleton']['rows'][8]
+    assert by['meso-tartaric skeleton']['rows'].key == by['chiral tartaric skeleton']['rows'].key
     # the outputs do not depend on what their buffers held: a call into recycled memory agrees
     first = [_facts(r) for r in got]
     del res, st, sm, got
@@ -133,7 +128,7 @@ def test_generated_family_and_plain_text_without_stereo(family):
         if r['stereo']['status'] == M.STEREO_NO_KEKULE:
             s = r['stereo']
             assert not (s['atom_parity'].any() or s['atom_label'].any() or s['bond_stereo'].any() or s['bond_label'].any() or s['counts'].any())
-            assert s['stereo_key'] == r['rows'][8] and r['text']['status'] == M.SMILES_NO_KEKULE and not r['text']['stereo_counts'].any()
+            assert s['stereo_key'] == r['rows'].key and r['text']['status'] == M.SMILES_NO_KEKULE and not r['text']['stereo_counts'].any()
     # with all-zero stereo inputs the new entry point writes pg_mol_smiles' bytes
     zero = dataclasses.replace(st, atom_parity=torch.zeros_like(st.atom_parity), bond_stereo=torch.zeros_like(st.bond_stereo))
     plain, blank = M.smiles(res, kekule=st.kekule, capacity=sm.capacity), M.smiles(res, stereo=zero)

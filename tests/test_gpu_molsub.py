@@ -12,7 +12,8 @@ import mol_reference as MR
 import molkey_reference as Q
 import ring_reference as G
 import sub_reference as R
-from helpers import default_model, mol_result as _result, permute_batch as _permute_batch
+from helpers import default_model
+from mol_support import M64, split_frame, mol_result as _result, permute_batch as _permute_batch
 from phoregen_amd import hip
 from phoregen_amd import molecule as M
 from phoregen_amd import substructure as S
@@ -23,7 +24,6 @@ DEV = 'cuda'
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 DICTS = R.PATTERNS + R.PROPERTY_PATTERNS
 PATTERNS = [S.Pattern.from_dict(p) for p in DICTS]
-M64 = (1 << 64) - 1
 
 
 @pytest.fixture(scope='module')
@@ -33,15 +33,9 @@ def model():
 
 def _targets(sc, rg, kek, f=0):
     """The restatement's targets of frame f from the device's screen, ring and Kekulé outputs."""
-    cls, order, ring_size, atom_ring = (t[f].cpu().numpy() for t in (sc.cls, sc.order, rg.ring_size, rg.atom_ring))
-    hcount, charge, status = kek.hcount[f].cpu().numpy(), kek.charge[f].cpu().numpy(), kek.status[f].cpu().tolist()
-    out, n0, h0 = [], 0, 0
-    for g, n in enumerate(sc.num_atoms):
-        h = n * (n - 1) // 2
-        out.append(R.target_of_rows(cls[n0:n0 + n], order[h0:h0 + h], ring_size[h0:h0 + h], atom_ring[n0:n0 + n], hcount[n0:n0 + n],
-                                    charge[n0:n0 + n], status[g]))
-        n0, h0 = n0 + n, h0 + h
-    return out
+    parts = split_frame(sc.num_atoms, f, per_atom={'cls': sc.cls, 'atom_ring': rg.atom_ring, 'hcount': kek.hcount, 'charge': kek.charge},
+                        per_pair={'order': sc.order, 'ring_size': rg.ring_size}, per_graph={'kekule_status': kek.status})
+    return [R.target_of_rows(**r) for r in parts]
 
 
 def _rows(sub, f=0):

@@ -10,6 +10,7 @@ import torch
 
 import bonds_reference as BR
 import mol_reference as R
+from mol_support import arg_count, header_macro, header_text, listed_pairs
 import molkey_reference as K
 from phoregen_amd import hip, molecule as M
 from phoregen_amd.utils.sample_utils import ATOM_TYPES
@@ -85,10 +86,9 @@ def test_restatement_reproduces_the_reference(golden):
     t = M.bond_thresholds()
     for cls, pos, bi, bt in golden_molecules(golden):
         order = BR.distance_orders(cls, pos, t)
-        a, b = np.triu_indices(len(cls), 1)
-        nz = np.nonzero(order)[0]
+        nz, a, b = listed_pairs(len(cls), order)
         # the reference appends (i, j) then (j, i) for every bonded pair i < j in row-major order
-        want_index = np.stack([np.stack([a[nz], b[nz]]), np.stack([b[nz], a[nz]])], axis=2).reshape(2, -1)
+        want_index = np.stack([np.stack([a, b]), np.stack([b, a])], axis=2).reshape(2, -1)
         assert np.array_equal(bi, want_index) and np.array_equal(bt, np.repeat(order[nz], 2))
 
 
@@ -136,15 +136,15 @@ def test_agreement_counts_by_hand():
 
 def test_binding_declares_the_distance_screen():
     lib = hip.load_library()
-    header = open(os.path.join(ROOT, 'include', 'phoregen_hip.h')).read()
+    header = header_text()
     assert re.search(r'\bint pg_mol_screen_dist\s*\(', header)
     assert 'pg_mol_screen_dist' in hip.EXPORTS and hasattr(lib, 'pg_mol_screen_dist')
-    assert len(hip._PROTOS['pg_mol_screen_dist'][1]) == 24 == header.split('int pg_mol_screen_dist(')[1].split(');')[0].count(',') + 1
-    assert len(hip._PROTOS['pg_mol_screen'][1]) == 22 == header.split('int pg_mol_screen(')[1].split(');')[0].count(',') + 1
+    assert len(hip._PROTOS['pg_mol_screen_dist'][1]) == 24 == arg_count('pg_mol_screen_dist')
+    assert len(hip._PROTOS['pg_mol_screen'][1]) == 22 == arg_count('pg_mol_screen')
     assert hip.ABI_VERSION == 11 == lib.pg_abi_version()
     makefile = open(os.path.join(ROOT, 'phoregen_amd', 'csrc', 'Makefile')).read()
     assert 'mol_screen_dist.hip' in makefile and re.search(r'mol_screen_dist\.o[^\n]*: mol_common\.h', makefile)
-    assert re.search(r'#define PG_MOL_DIST_UNMAPPED_ELEMENT %d\b' % M.STATUS_DIST_UNMAPPED_ELEMENT, header)
+    assert header_macro('PG_MOL_DIST_UNMAPPED_ELEMENT') == str(M.STATUS_DIST_UNMAPPED_ELEMENT)
     # argument errors are refused before any launch, without a GPU: oversize, negative sizes, missing tables, scores without agree
     val, thr, cnt = (hip.C.c_ubyte * 16)(), (hip.C.c_float * 363)(), (hip.C.c_int * 8)()
     scores, misaligned = 64, 68                                                  # (addresses that are never read)

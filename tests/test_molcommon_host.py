@@ -5,10 +5,11 @@ point-range guards against expectations written out here.
 The kernels themselves are held against their restatements in tests/test_gpu_mol*.py."""
 import os
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
+
+from mol_support import build_host_check, run_program
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 MAX_ATOMS = 128
@@ -17,15 +18,12 @@ pytestmark = pytest.mark.skipif(shutil.which('g++') is None, reason='no g++ to c
 
 @pytest.fixture(scope='module')
 def exe(tmp_path_factory):
-    path = os.path.join(str(tmp_path_factory.mktemp('mol_common')), 'mol_common_host_check')
-    subprocess.run(['g++', '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all',
-                    os.path.join(ROOT, 'tools', 'mol_common_host_check.cpp'), '-o', path], check=True)
-    return path
+    return build_host_check('mol_common_host_check', tmp_path_factory.mktemp('mol_common'))
 
 
 def test_pair_walk_visits_its_lane_share_in_row_major_order(exe):
-    out = subprocess.run([exe, 'pairs', str(MAX_ATOMS)], check=True, capture_output=True, text=True).stdout
-    got = np.array(out.split(), dtype=np.int64).reshape(-1, 5)                    # n, lane, p, a, b in the order visited
+    out = run_program(exe, 'pairs', MAX_ATOMS)
+    got = np.array(' '.join(out).split(), dtype=np.int64).reshape(-1, 5)                    # n, lane, p, a, b in the order visited
     want = []
     for n in range(MAX_ATOMS + 1):
         a, b = np.triu_indices(n, 1)                                             # row-major: pair p is (a[p], b[p])
@@ -63,7 +61,7 @@ def _run(exe, cases, tmp_path):
             fh.write('%d %d %d %d %d %d\n' % tuple(c[k] for k in ('F', 'B', 'n_lig', 'n_half', 'n_point', 'n_out')))
             for k in ('lig_off', 'bond_off', 'range', 'out_off'):
                 fh.write(' '.join(str(int(v)) for v in c[k]) + '\n')
-    lines = iter(subprocess.run([exe, 'frames', path], check=True, capture_output=True, text=True).stdout.strip().split('\n'))
+    lines = iter(run_program(exe, 'frames', path)[:-1])               # (without the empty piece after the last newline)
     got = []
     for c in cases:
         rows = []

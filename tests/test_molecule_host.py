@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import mol_reference as R
+from mol_support import header_text
 from phoregen_amd import hip
 from phoregen_amd import molecule as M
 
@@ -29,7 +30,7 @@ def test_constants_and_table():
     assert list(M.MAX_VALENCE) == ATOM_TYPES == list(M.ELEMENT_SYMBOL)
     assert [M.MAX_VALENCE[z] for z in ATOM_TYPES] == [3, 4, 4, 2, 1, 4, 7, 6, 1, 1, 5]
     # the header's constants and the Python mirrors
-    header = open(os.path.join(ROOT, 'include', 'phoregen_hip.h')).read()
+    header = header_text()
     defs = dict(re.findall(r'#define (PG_MOL_[A-Z_]+) (\d+)', header))
     assert int(defs['PG_MOL_MAX_ATOMS']) == M.MAX_ATOMS == hip.PG_MOL_MAX_ATOMS >= 128
     for bit, name in M.STATUS_NAMES.items():

@@ -14,6 +14,7 @@ import torch
 import feature_reference as FR
 import kekule_reference as K
 import mol_reference as R
+from mol_support import arg_count, build_host_check, header_macro, header_text
 from phoregen_amd import hip
 from phoregen_amd import molecule as M
 
@@ -124,7 +125,7 @@ def test_rules_on_the_host_under_sanitizers(family, tmp_path):
     """The text the kernel compiles (csrc/feature_core.h), built as a stand-alone host program with ASan + UBSan, on the named
     molecules, the random family and six hundred further random graphs."""
     cases, inputs, want, _ = family
-    exe = FR.build_host_check(tmp_path)
+    exe = build_host_check('feature_host_check', tmp_path)
     named = [k for k in FR.NAMED if k != 'indene-like']
     todo = [(FR.cpu_inputs(*FR.NAMED[k][:2]), FR.fp_of(FR.named_answer(k))) for k in named]
     todo += [(i, w['atom_fp']) for i, w in zip(inputs, want) if i[5]]
@@ -177,15 +178,15 @@ def test_features_needs_the_device():
 
 def test_binding_declares_the_feature_kernel():
     lib = hip.load_library()
-    header = open(os.path.join(ROOT, 'include', 'phoregen_hip.h')).read()
+    header = header_text()
     assert re.search(r'\bint pg_mol_feat\s*\(', header)
     assert 'pg_mol_feat' in hip.EXPORTS and hasattr(lib, 'pg_mol_feat')
-    assert len(hip._PROTOS['pg_mol_feat'][1]) == 31 == re.sub(r'/\*.*?\*/', '', header.split('int pg_mol_feat(')[1].split(');')[0]).count(',') + 1
+    assert len(hip._PROTOS['pg_mol_feat'][1]) == 31 == arg_count('pg_mol_feat')
     csrc = os.path.join(ROOT, 'phoregen_amd', 'csrc')
     assert 'mol_feat.hip' in open(os.path.join(csrc, 'Makefile')).read() and os.path.exists(os.path.join(csrc, 'feature_core.h'))
     for bit, name in M.FEAT_NAMES.items():
-        assert re.search(r'#define PG_FEAT_%s %d\b' % (name, bit), header), name
-    assert re.search(r'#define PG_FEAT_N_COUNTS %d\b' % len(M.FEATURE_COUNTS), header)
+        assert header_macro('PG_FEAT_' + name) == str(bit), name
+    assert header_macro('PG_FEAT_N_COUNTS') == str(len(M.FEATURE_COUNTS))
     # argument errors are refused before any launch, without a GPU: oversize, negative sizes, null arrays
     buf = hip.C.cast((hip.C.c_uint8 * 64)(), hip.C.c_void_p)
 

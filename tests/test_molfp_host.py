@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import fp_reference as P
+from mol_support import arg_count, build_host_check, cycle, header_macro, header_text
 import molkey_reference as K
 from phoregen_amd import hip
 from phoregen_amd import molecule as M
@@ -23,15 +24,14 @@ NAMES = ('pg_mol_fp', 'pg_fp_tanimoto', 'pg_fp_nearest', 'pg_fp_maxmin')
 
 @pytest.fixture(scope='module')
 def exe(tmp_path_factory):
-    return P.build_host_check(tmp_path_factory.mktemp('fp_host'))
+    return build_host_check('fp_host_check', tmp_path_factory.mktemp('fp_host'))
 
 
 def test_constants():
     assert M.FP_BITS == 2048 and M.FP_WORDS == 32 and M.FP_MAX_RADIUS == 4 and M.FP_RADIUS == 2
-    header = open(os.path.join(ROOT, 'include', 'phoregen_hip.h')).read()
     for name, v in (('PG_FP_BITS', M.FP_BITS), ('PG_FP_WORDS', M.FP_WORDS), ('PG_FP_MAX_RADIUS', M.FP_MAX_RADIUS),
                     ('PG_FP_TILE_A', S.TILE_A), ('PG_FP_TILE_B', S.TILE_B)):
-        assert re.search(r'#define %s %d\b' % (name, v), header), name
+        assert header_macro(name) == str(v), name
     assert 'not RDKit' in M.fingerprints.__doc__.replace('NOT', 'not')
 
 
@@ -79,8 +79,8 @@ def test_hand_cases():
         levels = [P.bit_set(classes, bonds, r) for r in range(M.FP_MAX_RADIUS + 1)]
         assert all(a <= b for a, b in zip(levels, levels[1:])), name
         assert len(levels[0]) <= len(set(P.identifiers(classes, bonds, 0)[0])), name
-    benzene, cyclohexane = P.bit_set([1] * 6, K._ring(6, order=4)), P.bit_set([1] * 6, K._ring(6))
-    assert len(P.bit_set([1] * 6, K._ring(6, order=4), 0)) == 1 and len(benzene) == 3      # one environment per radius
+    benzene, cyclohexane = P.bit_set([1] * 6, cycle(6, 4)), P.bit_set([1] * 6, cycle(6, 1))
+    assert len(P.bit_set([1] * 6, cycle(6, 4), 0)) == 1 and len(benzene) == 3      # one environment per radius
     kekule = {p: 1 + (i % 2) for i, p in enumerate([(0, 1), (1, 2), (2, 3), (3, 4), (4, 5), (0, 5)])}
     assert P.bit_set([1] * 6, kekule) != benzene != cyclohexane
     # a disconnected graph has one fingerprint: the union of its parts' bits
@@ -153,17 +153,13 @@ def test_core_on_the_host_under_sanitizers(exe, tmp_path):
 
 
 # ---- the binding ---------------------------------------------------------------------------------------------------------------------
-def _arg_count(header, name):
-    return re.sub(r'/\*.*?\*/', '', header.split('int %s(' % name)[1].split(');')[0]).count(',') + 1
-
-
 def test_binding_declares_the_entry_points():
     lib = hip.load_library()
-    header = open(os.path.join(ROOT, 'include', 'phoregen_hip.h')).read()
+    header = header_text()
     assert lib.pg_abi_version() == 11 == hip.ABI_VERSION
     for name, n_args in zip(NAMES, (13, 6, 9, 9)):
         assert re.search(r'\bint %s\s*\(' % name, header) and name in hip.EXPORTS and hasattr(lib, name)
-        assert len(hip._PROTOS[name][1]) == n_args == _arg_count(header, name), name
+        assert len(hip._PROTOS[name][1]) == n_args == arg_count(name), name
     makefile = open(os.path.join(ROOT, 'phoregen_amd', 'csrc', 'Makefile')).read()
     assert 'mol_fp.hip' in makefile and 'fp_sim.hip' in makefile and re.search(r'mol_fp\.o.*fp_sim\.o: fp_core\.h', makefile)
     assert re.search(r'mol_fp\.o: mol_common\.h', makefile)
@@ -218,7 +214,7 @@ def _with_fp(m, radius=M.FP_RADIUS):
 
 
 def test_stack_and_diversity_arithmetic():
-    mols = [_with_fp(K.mol_from([1, 1, 3], {(0, 1): 1, (1, 2): 1})), _with_fp(K.mol_from([1] * 6, K._ring(6, order=4)))]
+    mols = [_with_fp(K.mol_from([1, 1, 3], {(0, 1): 1, (1, 2): 1})), _with_fp(K.mol_from([1] * 6, cycle(6, 4)))]
     rows = S.stack(mols, 'cpu')
     assert rows.shape == (2, M.FP_WORDS) and rows.dtype == torch.int64
     assert np.array_equal(rows.numpy().view(np.uint64), P.rows_array([P.bits_of_mol(m) for m in mols]))

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import geom_reference as G
+from mol_support import arg_count, header_macro, header_text
 from phoregen_amd import hip
 from phoregen_amd import molecule as M
 
@@ -125,14 +126,14 @@ def test_geometry_needs_the_device():
 
 def test_binding_declares_the_geometry_screen():
     lib = hip.load_library()
-    header = open(os.path.join(ROOT, 'include', 'phoregen_hip.h')).read()
+    header = header_text()
     assert re.search(r'\bint pg_mol_geom\s*\(', header)
     assert 'pg_mol_geom' in hip.EXPORTS and hasattr(lib, 'pg_mol_geom')
-    assert len(hip._PROTOS['pg_mol_geom'][1]) == 24 == header.split('int pg_mol_geom(')[1].split(');')[0].count(',') + 1
+    assert len(hip._PROTOS['pg_mol_geom'][1]) == 24 == arg_count('pg_mol_geom')
     assert hip.ABI_VERSION == 11 == lib.pg_abi_version()
     assert 'mol_geom.hip' in open(os.path.join(ROOT, 'phoregen_amd', 'csrc', 'Makefile')).read()
     for bit, name in M.GEOM_NAMES.items():
-        assert re.search(r'#define PG_GEOM_%s %d\b' % (name, bit), header), name
+        assert header_macro('PG_GEOM_' + name) == str(bit), name
     # argument errors are refused before any launch, without a GPU: oversize, negative sizes, no limits
     lim = (hip.C.c_float * 5)(1.2, 2.8, 1.2, 3.0, 2.0)
     args = lambda B, n_lig, n_bond, max_n, n_point=0, limits=lim: (None, 0, None, None, None, None, B, 1, n_lig, n_bond, max_n, None, None,   # noqa: E731

@@ -11,7 +11,7 @@ import pytest
 import torch
 
 import hydrogen_reference as H
-from helpers import mol_result
+from mol_support import build_host_check, header_macro as macro, header_text, mol_result, read_mol_block as _read_block
 from phoregen_amd import hip, hydrogens as HY, molecule as M
 from phoregen_amd.utils.sample_utils import ATOM_TYPES
 
@@ -27,7 +27,7 @@ def family():
 
 @pytest.fixture(scope='module')
 def host_check(tmp_path_factory):
-    return H.build_host_check(tmp_path_factory.mktemp('hydrogen_host_check'))
+    return build_host_check('hydrogen_host_check', tmp_path_factory.mktemp('hydrogen_host_check'))
 
 
 def _exact(name, options=None):
@@ -35,12 +35,10 @@ def _exact(name, options=None):
     c, b, p, _ = H.EXAMPLES[name]
     r = H.hydrogens_of(c, b, p, options, exact=True)
     rows = H.all_rows(c, b, p)
-    return r, np.asarray(p, dtype=np.float64), H.graph_of_rows(rows[0], rows[2], rows[1])[1]
+    return r, np.asarray(p, dtype=np.float64), H.graph_of_rows(rows.cls, rows.kekule_order, rows.order)[1]
 
 
 def test_constants_options_and_header_agree():
-    header = open(os.path.join(ROOT, 'include', 'phoregen_hip.h')).read()
-    macro = lambda name: re.search(r'#define %s (\S+)' % name, header).group(1)   # noqa: E731
     for bit, name in HY.HYD_NAMES.items():
         assert int(macro('PG_HYD_' + name)) == bit
     assert HY.HYD_FAIL_MASK == 1 | 2 | 4 | 8 and len(HY.HYD_COUNTS) == int(macro('PG_HYD_N_COUNTS')) == hip.PG_HYD_N_COUNTS == 8
@@ -68,7 +66,7 @@ def test_restatement_lengths_counts_and_shapes_on_the_hand_examples():
         r, pos, nbrs = _exact(name)
         rows = H.all_rows(c, b, p)
         assert {i: (int(r['h_placed'][i]), int(r['site_shape'][i])) for i in range(len(c)) if r['h_placed'][i]} == sites, name
-        assert r['counts'][0] == sum(int(x) for x in rows[3]) == sum(h for h, _ in sites.values()), name   # every counted hydrogen is placed
+        assert r['counts'][0] == sum(int(x) for x in rows.hcount) == sum(h for h, _ in sites.values()), name   # every counted hydrogen is placed
         assert r['counts'][1] == len(sites) and r['counts'][2:6].sum() == len(sites) and r['counts'][7] == len(c), name
         assert r['ok'] and r['status'] & HY.HYD_HAS_HYDROGEN and bool(r['status'] & HY.HYD_GENERIC) == any(s == H.GEN for _, s in sites.values())
         for i, (h, _) in sites.items():
@@ -148,14 +146,14 @@ def test_host_core_against_the_restatement(host_check, family, tmp_path):
         cases = [H.all_rows(*g) for g in graphs]
         got = H.run_host_check(host_check, cases, tmp_path, opt)
         for g, (x, rows) in enumerate(zip(got, cases)):
-            worst = max(worst, H.compare(x, H.restate(rows, opt), rows[6], opt, where='example %d clash %g' % (g, clash)))
+            worst = max(worst, H.compare(x, H.restate(rows, opt), rows.pos, opt, where='example %d clash %g' % (g, clash)))
         contacts = [int(x['counts'][6]) for x in got]
         assert (max(contacts) == 0) if clash < 1 else (min(c for c, g in zip(contacts, graphs) if len(g[0]) > 1) > 0)
         assert any(x['status'] & HY.HYD_CONTACTS for x in got) == (clash > 1)
     opt = HY.HydrogenOptions(clash_min=H.FAMILY_CLASH)
     cases = [H.all_rows(*g) for g in family[0]]
     got = H.run_host_check(host_check, cases, tmp_path, opt)
-    ratios = [H.compare(x, H.restate(rows, opt), rows[6], opt, where='family %d' % g) for g, (x, rows) in enumerate(zip(got, cases))]
+    ratios = [H.compare(x, H.restate(rows, opt), rows.pos, opt, where='family %d' % g) for g, (x, rows) in enumerate(zip(got, cases))]
     worst = max(worst, max(ratios))
     print('host core, worst error / bound: %.4f' % worst)
     assert 0.0 < worst <= 1.0
@@ -165,11 +163,10 @@ def test_host_core_against_the_restatement(host_check, family, tmp_path):
     nan = np.array(p, dtype=np.float32)
     nan[0, 1] = np.nan
     dropped = ([c[0], 11, c[1], c[2]], {(0, 2): 1, (2, 3): 1, (0, 1): 1}, [p[0], [9.0, 9.0, 9.0], p[1], p[2]])
-    cases = [H.all_rows(c, b, nan), H.all_rows(*dropped), list(H.all_rows(c, b, p))]
-    cases[2][3] = [3, 5, 3]
+    cases = [H.all_rows(c, b, nan), H.all_rows(*dropped), H.all_rows(c, b, p)._replace(hcount=[3, 5, 3])]
     got = H.run_host_check(host_check, cases, tmp_path)
     for g, (x, rows) in enumerate(zip(got, cases)):
-        H.compare({**x, 'min_contact': H.restate(rows)['min_contact']}, H.restate(rows), rows[6], where='special %d' % g)
+        H.compare({**x, 'min_contact': H.restate(rows)['min_contact']}, H.restate(rows), rows.pos, where='special %d' % g)
     # (nothing at the atom or next to it; the far methyl's torsion reference is the NaN atom, so it takes the generic rule)
     assert got[0]['status'] == HY.HYD_NONFINITE | HY.HYD_GENERIC | HY.HYD_HAS_HYDROGEN
     assert got[0]['h_placed'].tolist() == [0, 0, 3] and got[0]['site_shape'].tolist() == [0, 0, H.GEN]
@@ -189,23 +186,14 @@ def _assembled(name, options=None):
     m = {'element': [ATOM_TYPES[k] for k in c], 'atom_pos': torch.as_tensor(np.asarray(p, dtype=np.float32)),
          'bond_index': torch.tensor(pairs, dtype=torch.long).reshape(-1, 2).T, 'bond_type': torch.tensor([b[k] for k in pairs], dtype=torch.long),
          'status': 0, 'valid': True}
-    formula, weight = M.formula_of(m['element'], rows[3], int(sum(rows[4])))
-    m['kekule'] = dict({'status': rows[5], 'kekule_ok': not rows[5] & M.KEKULE_FAILED, 'bond_type': torch.tensor([int(rows[2][k]) for k in at]),
-                        'hcount': np.asarray(rows[3], dtype=np.uint8), 'charge': np.asarray(rows[4], dtype=np.int8), 'formula': formula,
+    formula, weight = M.formula_of(m['element'], rows.hcount, int(sum(rows.charge)))
+    m['kekule'] = dict({'status': rows.kekule_status, 'kekule_ok': not rows.kekule_status & M.KEKULE_FAILED,
+                        'bond_type': torch.tensor([int(rows.kekule_order[k]) for k in at]),
+                        'hcount': np.asarray(rows.hcount, dtype=np.uint8), 'charge': np.asarray(rows.charge, dtype=np.int8), 'formula': formula,
                         'mol_weight': weight},
-                       **{M._KEKULE_KEYS[k]: int(x) for k, x in zip(M.KEKULE_COUNTS, K.kekule_of_rows(rows[0], rows[1])['counts'])})
+                       **{M._KEKULE_KEYS[k]: int(x) for k, x in zip(M.KEKULE_COUNTS, K.kekule_of_rows(rows.cls, rows.order)['counts'])})
     m['hydrogens'] = HY.molecule_entry(r['status'], r['counts'], r['min_contact'], r['h_pos'], r['h_placed'], r['site_shape'])
     return m
-
-
-def _read_block(text):
-    """A small V2000 reader: ([(symbol, x, y, z)], [(a, b, type)]) with 0-based atoms."""
-    lines = text.split('\n')
-    na, nb = int(lines[3][0:3]), int(lines[3][3:6])
-    atoms = [(ln[31:34].strip(), float(ln[0:10]), float(ln[10:20]), float(ln[20:30])) for ln in lines[4:4 + na]]
-    bonds = [(int(ln[0:3]) - 1, int(ln[3:6]) - 1, int(ln[6:9])) for ln in lines[4 + na:4 + na + nb]]
-    assert lines[4 + na + nb].startswith('M  ') and lines[3].endswith('V2000')
-    return atoms, bonds
 
 
 def test_mol_block_is_unchanged_without_hydrogens_and_all_atom_with_them(tmp_path):
@@ -251,7 +239,7 @@ def test_mol_block_is_unchanged_without_hydrogens_and_all_atom_with_them(tmp_pat
 
 # ---- the binding and the argument errors -------------------------------------------------------------------------------------------------------
 def test_binding_exports_the_entry_point_and_the_header_documents_it():
-    header = open(os.path.join(ROOT, 'include', 'phoregen_hip.h')).read()
+    header = header_text()
     assert 'pg_mol_hydrogens' in hip.EXPORTS and hip.ABI_VERSION == 11
     res, args = hip._PROTOS['pg_mol_hydrogens']
     proto = re.search(r'int pg_mol_hydrogens\((.*?)\);', header, re.S).group(1)

@@ -13,6 +13,7 @@ import torch
 
 import kekule_reference as K
 import mol_reference as R
+from mol_support import arg_count, build_host_check, header_macro, header_text, mol_dict as _mol
 from phoregen_amd import hip
 from phoregen_amd import molecule as M
 
@@ -93,13 +94,6 @@ def test_formula_and_weight():
     assert M.formula_of([7, 6, 6, 6, 6, 6, 6], [0, 1, 1, 1, 1, 1, 3], 1) == ('C6H8N+', pytest.approx(94.137))
     assert M.formula_of([8, 16, 8, 8, 8], [1, 0, 0, 0, 1])[0] == 'H2O4S' and M.formula_of([17, 6, 35], [0, 2, 0])[0] == 'CH2BrCl'
     assert M.formula_of([7, 7], [0, 0], 2)[0] == 'N22+' and M.formula_of([], [])[0] == ''
-
-
-def _mol(elements, bonds, types):
-    n = len(elements)
-    return {'element': list(elements), 'atom_pos': torch.arange(3 * n, dtype=torch.float32).reshape(n, 3) * 0.5 - 1.0,
-            'bond_index': torch.tensor(bonds, dtype=torch.long).reshape(-1, 2).T, 'bond_type': torch.tensor(types, dtype=torch.long),
-            'status': 0, 'valid': True}
 
 
 def _documented_block(mol, name, types=None, charge=None):
@@ -209,7 +203,7 @@ def test_matching_core_on_the_host_under_sanitizers(family, tmp_path):
     """The text the kernel compiles (csrc/kekule_core.h), built as a stand-alone host program with ASan + UBSan, on the named
     molecules, the blossom cases, the random family (both options) and two thousand further random graphs."""
     graphs, rows, want = family
-    exe = K.build_host_check(tmp_path)
+    exe = build_host_check('kekule_host_check', tmp_path)
     cases = [(*K.rows_of(c, b), allow) for c, b, allow, *_ in K.NAMED.values()] + [(*K.rows_of(c, b), True) for c, b in K.BLOSSOM.values()]
     cases += [(cls, order, True) for cls, order in rows] + [(cls, order, False) for cls, order in rows]
     rng = np.random.default_rng(77)
@@ -240,15 +234,15 @@ def test_kekulize_needs_the_device():
 
 def test_binding_declares_the_kekule_kernel():
     lib = hip.load_library()
-    header = open(os.path.join(ROOT, 'include', 'phoregen_hip.h')).read()
+    header = header_text()
     assert re.search(r'\bint pg_mol_kekule\s*\(', header)
     assert 'pg_mol_kekule' in hip.EXPORTS and hasattr(lib, 'pg_mol_kekule')
-    assert len(hip._PROTOS['pg_mol_kekule'][1]) == 20 == re.sub(r'/\*.*?\*/', '', header.split('int pg_mol_kekule(')[1].split(');')[0]).count(',') + 1
+    assert len(hip._PROTOS['pg_mol_kekule'][1]) == 20 == arg_count('pg_mol_kekule')
     assert hip.ABI_VERSION == 11 == lib.pg_abi_version()
     assert 'mol_kekule.hip' in open(os.path.join(ROOT, 'phoregen_amd', 'csrc', 'Makefile')).read()
     for bit, name in M.KEKULE_NAMES.items():
-        assert re.search(r'#define PG_KEKULE_%s %d\b' % (name, bit), header), name
-    assert re.search(r'#define PG_KEKULE_N_COUNTS %d\b' % len(M.KEKULE_COUNTS), header)
+        assert header_macro('PG_KEKULE_' + name) == str(bit), name
+    assert header_macro('PG_KEKULE_N_COUNTS') == str(len(M.KEKULE_COUNTS))
     # argument errors are refused before any launch, without a GPU: oversize, negative sizes, null tables
     tab = hip.C.cast((hip.C.c_uint8 * 44)(), hip.C.c_void_p)
 

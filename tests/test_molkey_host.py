@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import molkey_reference as K
+from mol_support import header_text
 from phoregen_amd import hip
 from phoregen_amd import molecule as M
 
@@ -213,7 +214,7 @@ def test_molecule_keys_needs_the_device():
 
 def test_binding_declares_the_key():
     lib = hip.load_library()
-    header = open(os.path.join(ROOT, 'include', 'phoregen_hip.h')).read()
+    header = header_text()
     assert re.search(r'\bint pg_mol_key\s*\(', header)
     assert 'pg_mol_key' in hip.EXPORTS and hasattr(lib, 'pg_mol_key')
     assert len(hip._PROTOS['pg_mol_key'][1]) == 12 == header.split('int pg_mol_key(')[1].split(');')[0].count(',') + 1

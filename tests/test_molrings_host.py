@@ -11,6 +11,7 @@ import torch
 
 import mol_reference as R
 import ring_reference as G
+from mol_support import arg_count, header_macro, header_text
 from phoregen_amd import hip
 from phoregen_amd import molecule as M
 
@@ -130,15 +131,15 @@ def test_rings_needs_the_device():
 
 def test_binding_declares_the_ring_screen():
     lib = hip.load_library()
-    header = open(os.path.join(ROOT, 'include', 'phoregen_hip.h')).read()
+    header = header_text()
     assert re.search(r'\bint pg_mol_rings\s*\(', header)
     assert 'pg_mol_rings' in hip.EXPORTS and hasattr(lib, 'pg_mol_rings')
-    assert len(hip._PROTOS['pg_mol_rings'][1]) == 16 == header.split('int pg_mol_rings(')[1].split(');')[0].count(',') + 1
+    assert len(hip._PROTOS['pg_mol_rings'][1]) == 16 == arg_count('pg_mol_rings')
     assert hip.ABI_VERSION == 11 == lib.pg_abi_version()
     assert 'mol_rings.hip' in open(os.path.join(ROOT, 'phoregen_amd', 'csrc', 'Makefile')).read()
     for bit, name in M.RING_NAMES.items():
-        assert re.search(r'#define PG_RING_%s %d\b' % (name, bit), header), name
-    assert re.search(r'#define PG_RING_N_COUNTS %d\b' % len(M.RING_COUNTS), header)
+        assert header_macro('PG_RING_' + name) == str(bit), name
+    assert header_macro('PG_RING_N_COUNTS') == str(len(M.RING_COUNTS))
     # argument errors are refused before any launch, without a GPU: oversize, negative sizes, no limits
     lim = (hip.C.c_int * 4)(3, 128, 128, 8128)
     args = lambda B, n_lig, n_bond, max_n, F=1, limits=lim: (None, None, None, None, B, F, n_lig, n_bond, max_n, limits, None, None, None,   # noqa: E731

@@ -15,6 +15,7 @@ import torch
 import kekule_reference as K
 import mol_reference as R
 import smiles_reference as S
+from mol_support import arg_count, build_host_check, header_macro, header_text, mol_dict as _mol
 from phoregen_amd import hip
 from phoregen_amd import molecule as M
 
@@ -25,7 +26,7 @@ needs_gxx = pytest.mark.skipif(shutil.which('g++') is None, reason='no g++ to co
 
 @pytest.fixture(scope='module')
 def exe(tmp_path_factory):
-    return S.build_host_check(tmp_path_factory.mktemp('smiles_host'))
+    return build_host_check('smiles_host_check', tmp_path_factory.mktemp('smiles_host'))
 
 
 def test_tables_and_constants():
@@ -152,13 +153,6 @@ def test_capacity_boundary(exe, tmp_path):
         assert got['counts'].tolist() == exact['counts'].tolist() and got['counts'][CI('length')] == len(text)
 
 
-def _mol(elements, bonds, types):
-    n = len(elements)
-    return {'element': list(elements), 'atom_pos': torch.arange(3 * n, dtype=torch.float32).reshape(n, 3) * 0.5 - 1.0,
-            'bond_index': torch.tensor(bonds, dtype=torch.long).reshape(-1, 2).T, 'bond_type': torch.tensor(types, dtype=torch.long),
-            'status': 0, 'valid': True}
-
-
 def test_sdf_item_and_formula(tmp_path):
     w = S.smiles_of_rows(*S.kekule_rows(*S.EXAMPLES['tetramethylammonium'][:2]))
     mol = _mol([7, 6, 6, 6, 6], [(0, 1), (0, 2), (0, 3), (0, 4)], [1] * 4)
@@ -187,15 +181,15 @@ def test_smiles_needs_the_device():
 
 def test_binding_declares_the_smiles_kernel():
     lib = hip.load_library()
-    header = open(os.path.join(ROOT, 'include', 'phoregen_hip.h')).read()
+    header = header_text()
     assert re.search(r'\bint pg_mol_smiles\s*\(', header)
     assert 'pg_mol_smiles' in hip.EXPORTS and hasattr(lib, 'pg_mol_smiles')
-    assert len(hip._PROTOS['pg_mol_smiles'][1]) == 20 == re.sub(r'/\*.*?\*/', '', header.split('int pg_mol_smiles(')[1].split(');')[0]).count(',') + 1
+    assert len(hip._PROTOS['pg_mol_smiles'][1]) == 20 == arg_count('pg_mol_smiles')
     makefile = open(os.path.join(ROOT, 'phoregen_amd', 'csrc', 'Makefile')).read()
     assert 'mol_smiles.hip' in makefile and re.search(r'mol_smiles\.o:.*smiles_core\.h', makefile) and re.search(r'mol_smiles\.o.*: mol_common\.h', makefile)
     for bit, name in M.SMILES_NAMES.items():
-        assert re.search(r'#define PG_SMILES_%s %d\b' % (name, bit), header), name
-    assert re.search(r'#define PG_SMILES_N_COUNTS %d\b' % len(M.SMILES_COUNTS), header)
+        assert header_macro('PG_SMILES_' + name) == str(bit), name
+    assert header_macro('PG_SMILES_N_COUNTS') == str(len(M.SMILES_COUNTS))
     # argument errors are refused before any launch, without a GPU: oversize, negative sizes, no capacity, a null table, null arrays
     tab = hip.C.cast((hip.C.c_uint8 * 44)(), hip.C.c_void_p)
 

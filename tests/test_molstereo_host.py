@@ -13,6 +13,7 @@ import pytest
 import torch
 
 import mol_reference as R
+import mol_support as MS
 import smiles_reference as S
 import stereo_reference as T
 from phoregen_amd import hip
@@ -24,7 +25,7 @@ needs_gxx = pytest.mark.skipif(shutil.which('g++') is None, reason='no g++ to co
 
 @pytest.fixture(scope='module')
 def exe(tmp_path_factory):
-    return T.build_host_check(tmp_path_factory.mktemp('stereo_host'))
+    return MS.build_host_check('stereo_host_check', tmp_path_factory.mktemp('stereo_host'))
 
 
 @pytest.fixture(scope='module')
@@ -34,8 +35,8 @@ def family():
 
 
 def _restated(rows, limits=None):
-    st = T.stereo_of_rows(rows[0], rows[1], rows[2], rows[3], rows[5], rows[6], rows[7], rows[8], rows[9], limits)
-    return st, T.smiles_of_rows(rows[0], rows[2], rows[3], rows[4], rows[5], st['atom_parity'], st['bond_stereo'])
+    st = T.restate(rows, limits)
+    return st, T.smiles_of_rows(*rows.smiles_inputs(), st['atom_parity'], st['bond_stereo'])
 
 
 def test_constants_and_limits():
@@ -80,14 +81,14 @@ def test_example_by_hand(name):
     classes, bonds, pos, text = T.EXAMPLES[name]
     rows = T.all_rows(classes, bonds, pos)
     st, tx = _restated(rows)
-    _, _, at = T.graph_of_rows(rows[0], rows[1])
+    _, _, at = T.graph_of_rows(rows.cls, rows.order)
     assert tx['text'] == text and tx['ok'] and st['ok']
-    n_centres, n_read, n_extra = T.check_text_against_geometry(text, tx['atom_rank'], rows[9], st, at, where=name)
+    n_centres, n_read, n_extra = T.check_text_against_geometry(text, tx['atom_rank'], rows.pos, st, at, where=name)
     assert (n_centres, n_read, n_extra) == (text.count('[') if '@' in text else 0, st['counts'][6], 0)
     assert tx['stereo_counts'].tolist() == [n_centres, text.count('@@'), text.count('/') + text.count('\\'), n_read]
     # without its stereo the text is the plain writer's, and reads back to the molecule
-    plain = S.smiles_of_rows(rows[0], rows[2], rows[3], rows[4], rows[5], capacity=12 * 8)
-    zero = T.smiles_of_rows(rows[0], rows[2], rows[3], rows[4], rows[5], np.zeros_like(st['atom_parity']), np.zeros_like(st['bond_stereo']))
+    plain = S.smiles_of_rows(*rows.smiles_inputs(), capacity=12 * 8)
+    zero = T.smiles_of_rows(*rows.smiles_inputs(), np.zeros_like(st['atom_parity']), np.zeros_like(st['bond_stereo']))
     S.same_answer(zero, plain, where=name)
     if '@' not in text:
         assert T.plain_text(text) == plain['text']
@@ -100,7 +101,7 @@ def test_example_by_hand(name):
 
 def test_example_details_by_hand():
     by = {name: _restated(T.all_rows(c, b, p))[0] for name, (c, b, p, _) in T.EXAMPLES.items()}
-    key = {name: T.all_rows(c, b, p)[8] for name, (c, b, p, _) in T.EXAMPLES.items()}
+    key = {name: T.all_rows(c, b, p).key for name, (c, b, p, _) in T.EXAMPLES.items()}
     for name in ('ring double bond', 'allene'):                        # nothing stereogenic: the key is the identity key
         assert not by[name]['counts'][[1, 5]].any() and by[name]['stereo_key'] == key[name] and by[name]['status'] == 0
     assert by['ring double bond']['counts'].tolist() == [0] * 8 and by['allene']['counts'].tolist() == [0] * 8
@@ -119,7 +120,7 @@ def test_example_details_by_hand():
     c, b, p, _ = T.EXAMPLES['CHFClBr skeleton']
     flat = [[0, 0, 0], [1, 0, 0], [-0.5, 0.9, 0], [-0.5, -0.9, 0.01]]
     r = T.stereo_of(c, b, flat)
-    assert r['atom_parity'].tolist() == [2, 0, 0, 0] == r['atom_label'].tolist() and r['status'] == 0 and r['stereo_key'] == T.all_rows(c, b, flat)[8]
+    assert r['atom_parity'].tolist() == [2, 0, 0, 0] == r['atom_label'].tolist() and r['status'] == 0 and r['stereo_key'] == T.all_rows(c, b, flat).key
     assert T.stereo_of(c, b, flat, M.StereoLimits(max_undefined=0))['status'] == M.STEREO_UNDEFINED
     assert T.stereo_of(c, b, flat, M.StereoLimits(vol_min=0.01))['atom_parity'][0] in (1, -1)
     # a neighbour that lies on the centre has no direction: undefined
@@ -187,11 +188,11 @@ def test_cores_on_the_host_under_sanitizers(exe, tmp_path, family):
         T.same_text(tx, want_tx, where=k)
         assert tx['status'] & M.SMILES_STEREO_DROPPED == 0
         if tx['ok']:
-            _, _, at = T.graph_of_rows(r[0], r[1])
-            a, b, _ = T.check_text_against_geometry(tx['text'], tx['atom_rank'], r[9], want_st, at, where=k)
+            _, _, at = T.graph_of_rows(r.cls, r.order)
+            a, b, _ = T.check_text_against_geometry(tx['text'], tx['atom_rank'], r.pos, want_st, at, where=k)
             centres, doubles = centres + a, doubles + b
-            S.same_answer(T.smiles_of_rows(r[0], r[2], r[3], r[4], r[5], 0 * st['atom_parity'], 0 * st['bond_stereo'], capacity=12 * 128),
-                          S.smiles_of_rows(r[0], r[2], r[3], r[4], r[5], capacity=12 * 128), where=k)
+            S.same_answer(T.smiles_of_rows(*r.smiles_inputs(), 0 * st['atom_parity'], 0 * st['bond_stereo'], capacity=12 * 128),
+                          S.smiles_of_rows(*r.smiles_inputs(), capacity=12 * 128), where=k)
     assert centres >= 200 and doubles >= 100
 
 
@@ -201,7 +202,7 @@ def test_stereo_handed_in_contradiction_and_zero(exe, tmp_path):
     trans ones do not; values on atoms and pairs that cannot carry them are not read; all zeros give the plain text."""
     classes, bonds = [T.C_] * 6, {(0, 1): 2, (1, 2): 1, (2, 3): 2, (3, 4): 1, (4, 5): 2, (0, 5): 1}
     rows = T.all_rows(classes, bonds, np.arange(18).reshape(6, 3) * 0.3)
-    h = len(rows[1])
+    h = len(rows.order)
     at = {p: R.pair_row(*p, 6) for p in bonds}
     zero_a, zero_b = np.zeros(6, dtype=np.int8), np.zeros(h, dtype=np.int8)
     cis, trans, wrong = zero_b.copy(), zero_b.copy(), np.ones(h, dtype=np.int8)
@@ -210,9 +211,9 @@ def test_stereo_handed_in_contradiction_and_zero(exe, tmp_path):
             cis[at[p]], trans[at[p]], wrong[at[p]] = 1, -1, 0
     cases = {0: (zero_a, cis), 1: (zero_a, trans), 2: (zero_a + 1, wrong), 3: (zero_a, zero_b), 4: (zero_a + 2, zero_b + 2)}
     got = T.run_host_check(exe, [rows] * 5, tmp_path, stereo_in=cases)
-    plain = S.smiles_of_rows(rows[0], rows[2], rows[3], rows[4], rows[5], capacity=12 * 8)
+    plain = S.smiles_of_rows(*rows.smiles_inputs(), capacity=12 * 8)
     for k, (_, tx) in enumerate(got):
-        T.same_text(tx, T.smiles_of_rows(rows[0], rows[2], rows[3], rows[4], rows[5], *cases[k]), where=k)
+        T.same_text(tx, T.smiles_of_rows(*rows.smiles_inputs(), *cases[k]), where=k)
         if k != 1:
             assert tx['text'] == plain['text'] == 'C1=CC=CC=C1' and tx['stereo_counts'].tolist() == [0] * 4
             assert tx['status'] == (M.SMILES_STEREO_DROPPED if k == 0 else 0) and np.array_equal(tx['counts'], plain['counts'])
@@ -258,24 +259,20 @@ def test_stereo_needs_the_device():
         M.smiles(res)
 
 
-def _arg_count(header, name):
-    return re.sub(r'/\*.*?\*/', '', header.split('int %s(' % name)[1].split(');')[0]).count(',') + 1
-
-
 def test_binding_declares_the_stereo_kernels():
     lib = hip.load_library()
-    header = open(os.path.join(ROOT, 'include', 'phoregen_hip.h')).read()
+    header = MS.header_text()
     assert lib.pg_abi_version() == 11 == hip.ABI_VERSION
     for name, n_args in (('pg_mol_stereo', 29), ('pg_mol_smiles_stereo', 23), ('pg_mol_smiles', 20)):
         assert re.search(r'\bint %s\s*\(' % name, header) and name in hip.EXPORTS and hasattr(lib, name)
-        assert len(hip._PROTOS[name][1]) == n_args == _arg_count(header, name), name
+        assert len(hip._PROTOS[name][1]) == n_args == MS.arg_count(name), name
     makefile = open(os.path.join(ROOT, 'phoregen_amd', 'csrc', 'Makefile')).read()
     assert 'mol_stereo.hip' in makefile and re.search(r'mol_stereo\.o:.*stereo_core\.h', makefile) and re.search(r'mol_stereo\.o.*: mol_common\.h', makefile)
     for bit, name in M.STEREO_NAMES.items():
-        assert re.search(r'#define PG_STEREO_%s %d\b' % (name, bit), header), name
-    assert re.search(r'#define PG_STEREO_N_COUNTS %d\b' % len(M.STEREO_COUNTS), header)
-    assert re.search(r'#define PG_SMILES_N_STEREO_COUNTS %d\b' % len(M.SMILES_STEREO_COUNTS), header)
-    assert re.search(r'#define PG_SMILES_STEREO_DROPPED %d\b' % M.SMILES_STEREO_DROPPED, header)
+        assert MS.header_macro('PG_STEREO_' + name) == str(bit), name
+    assert MS.header_macro('PG_STEREO_N_COUNTS') == str(len(M.STEREO_COUNTS))
+    assert MS.header_macro('PG_SMILES_N_STEREO_COUNTS') == str(len(M.SMILES_STEREO_COUNTS))
+    assert MS.header_macro('PG_SMILES_STEREO_DROPPED') == str(M.SMILES_STEREO_DROPPED)
     for word in ('STEREO_KEY_A', 'STEREO_KEY_B', 'STEREO_KEY_C', 'STEREO_KEY_D'):
         assert '0x%016X' % getattr(M, word) in header, word
     tab = hip.C.cast((hip.C.c_uint8 * 64)(), hip.C.c_void_p)

@@ -7,19 +7,18 @@ import json
 import os
 import re
 import shutil
-import subprocess
 
 import numpy as np
 import pytest
 
 import molkey_reference as Q
 import sub_reference as R
+from mol_support import C_, N_, build_host_check, cycle, header_text, run_program
 from phoregen_amd import hip
 from phoregen_amd import substructure as S
 from phoregen_amd.utils.sample_utils import ATOM_TYPES
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-C_, N_, O_ = 1, 2, 3
 
 
 @pytest.fixture(scope='module')
@@ -113,7 +112,7 @@ def test_property_constraints_on_the_named_bases():
 def test_a_graph_without_a_kekule_structure():
     """Five aromatic carbons in a ring have no Kekulé structure: a pattern that reads hydrogens or charge has no embedding and says
     why, any other pattern is searched as always."""
-    five = R.target_of_classes([C_] * 5, Q._ring(5, order=4))
+    five = R.target_of_classes([C_] * 5, cycle(5, 4))
     assert five['kekule_failed']
     for name in ('CH2', 'cation', 'OH', 'neutral-chain-C'):
         assert _row(five, name) == (0, 0, [], ('NO_KEKULE',))
@@ -176,9 +175,7 @@ def test_match_order_is_breadth_first_from_atom_0():
 
 
 def test_table_round_trip_and_header_macros(tmp_path):
-    with open(os.path.join(ROOT, 'include', 'phoregen_hip.h')) as fh:
-        header = fh.read()
-    macros = {k: int(v) for k, v in re.findall(r'#define (PG_SUB_\w+) (\d+)', header)}
+    macros = {k: int(v) for k, v in re.findall(r'#define (PG_SUB_\w+) (\d+)', header_text())}
     mine = {k: getattr(hip, k) for k in dir(hip) if k.startswith('PG_SUB_')}
     mine.update(PG_SUB_MATCHED=S.SUB_MATCHED, PG_SUB_NO_KEKULE=S.SUB_NO_KEKULE, PG_SUB_TRUNCATED=S.SUB_TRUNCATED,
                 PG_SUB_OUT_OF_BOUNDS=S.SUB_OUT_OF_BOUNDS)
@@ -213,7 +210,7 @@ def _assembled(classes, bonds):
 
 
 def test_find_matches_equals_the_restatement():
-    graphs = [(c, b) for _, c, b in Q.named_bases()] + [([C_] * 5, Q._ring(5, order=4)), ([N_, C_, C_, C_, C_], {(0, i): 1 for i in (1, 2, 3, 4)})]
+    graphs = [(c, b) for _, c, b in Q.named_bases()] + [([C_] * 5, cycle(5, 4)), ([N_, C_, C_, C_, C_], {(0, i): 1 for i in (1, 2, 3, 4)})]
     rng = np.random.default_rng(Q.CORPUS_SEED)
     graphs += [Q._random_base(rng) for _ in range(6)]
     for classes, bonds in graphs:
@@ -254,9 +251,7 @@ def test_library_exports_the_entry_point_and_keeps_its_abi():
 # ---- the core under the host sanitizers ------------------------------------------------------------------------------------------------
 @pytest.mark.skipif(shutil.which('g++') is None, reason='no g++ to compile the host check with')
 def test_core_under_the_host_sanitizers_equals_the_restatement(corpus, corpus_results, tmp_path):
-    exe = os.path.join(str(tmp_path), 'mol_sub_host_check')
-    subprocess.run(['g++', '-std=c++17', '-O1', '-g', '-fsanitize=address,undefined', '-fno-sanitize-recover=all',
-                    os.path.join(ROOT, 'tools', 'mol_sub_host_check.cpp'), '-o', exe], check=True)
+    exe = build_host_check('mol_sub_host_check', tmp_path)
     patterns = R.PATTERNS + R.PROPERTY_PATTERNS
     rows = dict(zip((p['name'] for p in patterns), S.pattern_table([S.Pattern.from_dict(p) for p in patterns]).tolist()))
     cases, wants = [], []
@@ -268,7 +263,7 @@ def test_core_under_the_host_sanitizers_equals_the_restatement(corpus, corpus_re
                 cases.append((t, rows[p['name']], 100))
                 wants.append((t, p, dict(r, truncated=max(r['steps'].values()) > 100)))
     extra = [R.target_of_classes(c, b) for _, c, b in Q.named_bases()]
-    extra += [R.target_of_classes([C_] * 5, Q._ring(5, order=4)), R.target_of_classes([N_, C_, C_, C_, C_], {(0, i): 1 for i in (1, 2, 3, 4)}),
+    extra += [R.target_of_classes([C_] * 5, cycle(5, 4)), R.target_of_classes([N_, C_, C_, C_, C_], {(0, i): 1 for i in (1, 2, 3, 4)}),
               R.target_of_classes([], {}), R.target_of_classes([11, 11], {})]
     for t in extra:
         for p in patterns:
@@ -291,7 +286,7 @@ def test_core_under_the_host_sanitizers_equals_the_restatement(corpus, corpus_re
     cases.append((extra[0], no_parent, 10))
     path = os.path.join(str(tmp_path), 'sub_cases.txt')
     R.write_host_cases(path, cases)
-    got = R.read_host_answers(subprocess.run([exe, path], check=True, capture_output=True, text=True).stdout)
+    got = R.read_host_answers('\n'.join(run_program(exe, path)))
     assert len(got) == len(cases) == len(wants) + len(malformed)
     for (code, row), (t, p, want) in zip(got, wants):
         assert code == 0
