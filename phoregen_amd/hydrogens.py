@@ -174,3 +174,15 @@ def sdf_item(hy):
     mc = hy['min_contact']
     return ('> <PHOREGEN_HYDROGENS>\nstatus 0x%02x\n' % int(hy['status']) + ''.join('%s %d\n' % (k, hy[k]) for k in HYD_COUNTS)
             + 'min_contact %s\n\n' % ('%.4f' % mc if np.isfinite(mc) else 'inf'))
+
+
+# What `molecule.assemble`, `write_sdf` and `sample_valid` know about this analysis.  An all-atom block needs the Kekulé form: `also`.
+ANALYSIS = M._Analysis(
+    'hydrogens', 'hydrogens', Hydrogens, also=('kekule',),
+    parts=lambda x: [('h_status', x.status[0], np.int32), ('h_counts', x.counts[0], np.int32), ('h_min', x.min_contact[0], np.float32),
+                     ('h_pos', x.h_pos[0], np.float32), ('h_placed', x.h_placed[0], np.uint8), ('h_shape', x.site_shape[0], np.uint8)],
+    entry=lambda x, v, at, mol: {'hydrogens': molecule_entry(at.row(v['h_status']), at.row(v['h_counts']), at.row(v['h_min']),
+                                                             at.atoms(v['h_pos']), at.atoms(v['h_placed']), at.atoms(v['h_shape']))},
+    sdf=lambda m: sdf_item(m['hydrogens']), read=lambda value: None if value is False else M._true_or('hydrogens', HydrogenOptions)(value),
+    compute=lambda d, opt: hydrogens(d.res, screen=d.screen, kekule=d.of('kekule'), options=opt),
+    verdict=lambda m: m['hydrogens']['hydrogens_ok'])

@@ -66,8 +66,11 @@ neighbours, and a count of the contacts the hydrogens make.  `assemble(hydrogens
 all-atom block) and `write_sdf` carry it.  Ideal local geometry only: no force field, no rotor search; lengths and thresholds are
 design choices, not checked against RDKit / OpenBabel."""
 import ctypes
+from collections import namedtuple
 from dataclasses import astuple, dataclass, replace
 from functools import cached_property, lru_cache
+from importlib import import_module
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -235,6 +238,7 @@ FEAT_NAMES = {FEAT_NO_KEKULE: 'NO_KEKULE', FEAT_UNMATCHED: 'UNMATCHED', FEAT_HAS
 FEATURE_COUNTS = (('typed_points', 'matched', 'unmatched', 'untyped_points') + tuple('atoms_' + t for t in FEATURE_TYPES)
                   + tuple('points_' + t for t in FEATURE_TYPES) + tuple('matched_' + t for t in FEATURE_TYPES))
 POINT_UNTYPED, POINT_IGNORED = -1, -2   # point kinds beside 0..6: a feature that is not typed; an exclusion sphere
+_TYPES_OF_BYTE = [tuple(t for k, t in enumerate(FEATURE_TYPES) if b >> k & 1) for b in range(256)]    # an `atom_fp` byte -> its type names
 
 # The SMILES writer (DESIGN.md 2.9 "SMILES"): status bits, the names of the count columns in the kernel's order, and the notation's
 # own table: the OpenSMILES normal valences of the elements that may be written without brackets, per element in ATOM_TYPES order (an
@@ -1216,16 +1220,235 @@ _features = features
 _smiles = smiles
 _stereo = stereo
 _fingerprints = fingerprints
-_PAIRS = {}
 
 
+@lru_cache(maxsize=None)
 def _pairs(n):
-    """The pairs a < b of n atoms in row-major order: the first half of a graph's bond rows (plan.make_edge_data)."""
-    p = _PAIRS.get(n)
-    if p is None:
-        a, b = np.triu_indices(n, 1)
-        p = _PAIRS[n] = (a.astype(np.int64), b.astype(np.int64))
-    return p
+    """The pairs a < b of n atoms in row-major order: the first half of a graph's bond rows (plan.make_edge_data).  Kept per n."""
+    a, b = np.triu_indices(n, 1)
+    return a.astype(np.int64), b.astype(np.int64)
+
+
+# ---- carriers: what `assemble`, `write_sdf` and `sample_valid` know about each analysis ------------------------------------------------
+@dataclass(frozen=True)
+class _Analysis:
+    """One analysis of the decoded molecules as the three carrying functions see it.  A further analysis is one more record in
+    _ANALYSES, its keyword in the signatures of `assemble` and `sample_valid`, and a paragraph in their docstrings."""
+    keyword: str                 # its keyword of `assemble` and `sample_valid`
+    key: str                     # the key a molecule that carries it has (the first one, if it adds several)
+    holder: type                 # what `assemble` is handed: a dataclass of device tensors with a `screen`
+    parts: object                # holder -> [(name, final-frame tensor, numpy dtype)]: its parts of the blob; names are the views' keys
+    entry: object                # (holder, views, _MolView, the molecule so far) -> the entries it adds to the molecule's dict
+    sdf: object                  # molecule -> the text of its data item of `write_sdf`
+    read: object                 # `sample_valid`'s argument -> what `compute` takes (True: the defaults), None: not asked for; ValueError
+    compute: object              # (_Draw, what `read` gave) -> the holder of a draw
+    verdict: object = None       # molecule -> bool, what `sample_valid` filters on; None: nothing
+    frames: str = 'status'       # a tensor of the holder with the frames as its first dimension
+    also: tuple = ()             # keywords of the analyses `sample_valid` carries, and filters on, along with it
+
+
+def _analyses(want):
+    """The records of the entries of _ANALYSES that `want` accepts (it sees `keyword` and `key`), in the list's order.  An entry that
+    is no record stands for the ANALYSIS of phoregen_amd.<keyword>, which is loaded here: only for a caller who asks for it."""
+    return [a if isinstance(a, _Analysis) else import_module('.' + a.keyword, __package__).ANALYSIS for a in _ANALYSES if want(a)]
+
+
+def _handed(args):
+    """[(record, value)] of the analyses whose keyword has a value in `args`, in the list's order."""
+    return [(rec, args[rec.keyword]) for rec in _analyses(lambda a: args.get(a.keyword) is not None)]
+
+
+class _MolView(namedtuple('_MolView', 'g n0 n keep h0 h nz cmp_g')):
+    """Where graph g lies in the host views of `assemble` -- its atom rows n0 .. n0 + n and which were kept (keep, bool [n]), its pair
+    rows h0 .. h0 + h and which, counted from h0, are bonds (nz), its atoms' indices among the kept ones (cmp_g, int64 [n], -1 =
+    dropped) -- and the slicings its entries are made of."""
+
+    def atoms(self, a):                                                # the rows of the kept atoms of a per-atom view
+        return a[self.n0:self.n0 + self.n][self.keep]
+
+    def bonds(self, a):                                                # the entries of the bonds of a per-pair view, in 'bond_type's order
+        return a[self.h0:self.h0 + self.h][self.nz]
+
+    def row(self, a):                                                  # the graph's row of a per-graph view
+        return a[self.g]
+
+    def points(self, a, off):                                          # the graph's points off[g] .. off[g + 1] of a per-point view
+        return a[int(off[self.g]):int(off[self.g + 1])]
+
+
+def _status_entry(ok_key, mask, names, status, counts):
+    """How an analysis's dict begins: 'status', its verdict (no bit of `mask`) and the counts by name."""
+    return dict({'status': int(status), ok_key: (int(status) & mask) == 0}, **{k: int(x) for k, x in zip(names, counts)})
+
+
+def _true_or(keyword, cls=None):
+    """The reader of a `sample_valid` argument that is True (the defaults) or a `cls`; without a `cls`, True and nothing else."""
+    def read(value):
+        opt = cls() if cls and value is True else value
+        if not (isinstance(opt, cls) if cls else opt is True):
+            raise ValueError(f'phoregen_amd.molecule.sample_valid: {keyword}= must be True{f" or a {cls.__name__}" if cls else ""}, not {value!r}')
+        return opt
+    return read
+
+
+def _geom_entry(x, v, at, mol):
+    return {'geom': dict(_status_entry('geom_ok', GEOM_FAIL_MASK, (), at.row(v['g_status']), ()),
+                         **{k: float(a) for k, a in zip(GEOM_METRICS, at.row(v['g_metrics']))},
+                         **{k: int(a) for k, a in zip(GEOM_COUNTS, at.row(v['g_counts']))},
+                         point_dist=at.points(v['g_dist'], v['g_off']).copy(), point_atom=at.points(v['g_atom'], v['g_off']).copy())}
+
+
+def _rings_entry(x, v, at, mol):
+    sys_g = at.atoms(v['r_sys']).astype(np.int64)                      # local index of the system's first atom -> its compact index
+    return {'rings': dict(_status_entry('rings_ok', RING_FAIL_MASK, RING_COUNTS, at.row(v['r_status']), at.row(v['r_counts'])),
+                          bond_ring_size=at.bonds(v['r_size']).copy(), atom_ring=at.atoms(v['r_atom']).copy(),
+                          ring_sys=np.where(sys_g >= 0, at.cmp_g[np.maximum(sys_g, 0)], -1).astype(np.int16))}
+
+
+def _kekule_entry(x, v, at, mol):
+    k_h, k_q = at.atoms(v['k_h']).copy(), at.atoms(v['k_q']).copy()
+    formula, weight = formula_of(mol['element'], k_h, int(k_q.astype(np.int64).sum()))
+    return {'kekule': dict(_status_entry('kekule_ok', KEKULE_FAIL_MASK, _KEKULE_KEYS.values(), at.row(v['k_status']), at.row(v['k_counts'])),
+                           bond_type=torch.from_numpy(at.bonds(v['k_order']).astype(np.int64)), hcount=k_h, charge=k_q,
+                           formula=formula, mol_weight=weight)}
+
+
+def _features_entry(x, v, at, mol):
+    fp, (lo, hi) = at.atoms(v['f_fp']).copy(), at.row(v['f_range'])
+    ft = dict(_status_entry('features_ok', FEAT_FAIL_MASK, FEATURE_COUNTS, at.row(v['f_status']), at.row(v['f_counts'])), atom_fp=fp,
+              atom_types=[_TYPES_OF_BYTE[b] for b in fp.tolist()],
+              point_kind=v['f_kind'][int(lo):int(hi)].copy(),
+              point_dist=at.points(v['f_dist'], v['f_off']).copy(), point_atom=at.points(v['f_atom'], v['f_off']).copy())
+    # (the kernel's own comparison: fp32 distance < fp32 cutoff; a non-finite point has distance +inf)
+    ft['point_matched'] = ft['point_dist'] < np.float32(x.limits.feat_cut)
+    return {'features': ft}
+
+
+def _features_item(ft):
+    """The PHOREGEN_FEATURES data item of a molecule's 'features' dict (`assemble`)."""
+    lines = ['> <PHOREGEN_FEATURES>', 'status 0x%02x' % int(ft['status'])] + ['%s %d' % (k, ft[k]) for k in FEATURE_COUNTS]
+    kinds = np.asarray(ft['point_kind']).reshape(-1).tolist()
+    dist, atom = np.asarray(ft['point_dist']).reshape(-1).tolist(), np.asarray(ft['point_atom']).reshape(-1).tolist()
+    for k, d, a, hit in zip(kinds, dist, atom, np.asarray(ft['point_matched']).reshape(-1).tolist()):
+        if 0 <= k < len(FEATURE_TYPES):
+            lines.append('%s %s %s' % (FEATURE_TYPES[k], str(a + 1) if hit else '-', '%.4f' % d if np.isfinite(d) else 'inf'))
+    return '\n'.join(lines) + '\n\n'
+
+
+def _read_features(value):
+    if value is not True and not (isinstance(value, tuple) and len(value) == 3 and isinstance(value[2], FeatureLimits)):
+        raise ValueError(f'phoregen_amd.molecule.sample_valid: features= must be True or (point_pos, point_kind, FeatureLimits), not {value!r}')
+    return value
+
+
+def _smiles_entry(x, v, at, mol):
+    sm = _status_entry('smiles_ok', SMILES_FAIL_MASK, (), at.row(v['s_status']), ())
+    sm['text'] = at.row(v['s_text'])[:int(at.row(v['s_length']))].tobytes().decode('ascii') if sm['smiles_ok'] else ''
+    sm.update({k: int(a) for k, a in zip(SMILES_COUNTS, at.row(v['s_counts']))}, atom_rank=at.atoms(v['s_rank']).copy())
+    if x.stereo_counts is not None:
+        sm.update({k: int(a) for k, a in zip(SMILES_STEREO_COUNTS, at.row(v['s_stereo']))})
+    return {'smiles': sm}
+
+
+def _stereo_item(m):
+    """The PHOREGEN_STEREO data item of a molecule that carries 'stereo' (`assemble`)."""
+    st, sign = m['stereo'], {1: '+', -1: '-', STEREO_UNDEFINED_VALUE: '?'}
+    lines = ['> <PHOREGEN_STEREO>', 'status 0x%02x' % int(st['status']), 'stereo_key %016x' % (int(st['stereo_key']) & _M64)]
+    lines += ['%s %d' % (k, st[k]) for k in STEREO_COUNTS]
+    for i, (p, l) in enumerate(zip(np.asarray(st['atom_parity']).tolist(), np.asarray(st['atom_label']).tolist())):
+        if p:
+            lines.append('centre %d %s %s' % (i + 1, sign[p], sign[l]))
+    bi = np.asarray(m['bond_index']).reshape(2, -1)
+    for (a, b), p, l in zip(bi.T.tolist(), np.asarray(st['bond_stereo']).tolist(), np.asarray(st['bond_label']).tolist()):
+        if p:
+            lines.append('bond %d %d %s %s' % (a + 1, b + 1, sign[p], sign[l]))
+    return '\n'.join(lines) + '\n\n'
+
+
+def _fingerprint_item(m):
+    """The PHOREGEN_FINGERPRINT data item of a molecule that carries 'fingerprint' (`assemble`)."""
+    words = [int(w) & _M64 for w in np.asarray(m['fingerprint']).reshape(-1).tolist()]
+    if len(words) != FP_WORDS:
+        raise ValueError(f"write_sdf: 'fingerprint' has {len(words)} words, not {FP_WORDS}")
+    return '> <PHOREGEN_FINGERPRINT>\n%s\nradius %d\n\n' % (''.join('%016x' % w for w in words), int(m.get('fp_radius', FP_RADIUS)))
+
+
+# The analyses in the order their keys stand in a molecule's dict, which is also the order of their data items in an SDF record
+_ANALYSES = [
+    _Analysis('geometry', 'geom', Geometry,
+              parts=lambda x: [('g_status', x.status[0], np.int32), ('g_metrics', x.metrics[0], np.float32), ('g_counts', x.counts[0], np.int32),
+                               ('g_dist', x.point_dist[0], np.float32), ('g_off', x.point_off, np.int32), ('g_atom', x.point_atom[0], np.int16)],
+              entry=_geom_entry, read=lambda value: value, verdict=lambda m: m['geom']['geom_ok'],
+              sdf=lambda m: '> <PHOREGEN_GEOM>\nstatus 0x%02x\n' % int(m['geom']['status'])
+              + ''.join('%s %.4f\n' % (k, m['geom'][k]) for k in GEOM_METRICS[:7]) + '\n',
+              compute=lambda d, opt: (geometry_for(d.data, d.res, screen=d.screen, ex_col=getattr(d.model, 'ex_col', 12)) if opt is True
+                                      else _geometry(d.res, opt[0], opt[1], screen=d.screen, limits=opt[2]))),
+    _Analysis('rings', 'rings', Rings,
+              parts=lambda x: [('r_status', x.status[0], np.int32), ('r_counts', x.counts[0], np.int32), ('r_sys', x.ring_sys[0], np.int16),
+                               ('r_atom', x.atom_ring[0], np.uint8), ('r_size', x.ring_size[0], np.uint8)],
+              entry=_rings_entry, read=_true_or('rings', RingLimits), verdict=lambda m: m['rings']['rings_ok'],
+              sdf=lambda m: '> <PHOREGEN_RINGS>\nstatus 0x%02x\n' % int(m['rings']['status'])
+              + ''.join('%s %d\n' % (k, m['rings'][k]) for k in RING_COUNTS) + '\n',
+              compute=lambda d, opt: _rings(d.res, screen=d.screen, limits=opt)),
+    _Analysis('kekule', 'kekule', Kekule,
+              parts=lambda x: [('k_status', x.status[0], np.int32), ('k_counts', x.counts[0], np.int32), ('k_order', x.kekule_order[0], np.int8),
+                               ('k_h', x.hcount[0], np.uint8), ('k_q', x.charge[0], np.int8)],
+              entry=_kekule_entry, read=_true_or('kekule', KekuleOptions), verdict=lambda m: m['kekule']['kekule_ok'],
+              sdf=lambda m: '> <PHOREGEN_KEKULE>\nstatus 0x%02x\nformula %s\nmol_weight %.3f\n'
+              % (int(m['kekule']['status']), m['kekule']['formula'], m['kekule']['mol_weight'])
+              + ''.join('%s %d\n' % (k, m['kekule'][_KEKULE_KEYS[k]]) for k in KEKULE_COUNTS) + '\n',
+              compute=lambda d, opt: _kekulize(d.res, screen=d.screen, options=opt)),
+    _Analysis('features', 'features', Features,
+              parts=lambda x: [('f_status', x.status[0], np.int32), ('f_counts', x.counts[0], np.int32), ('f_dist', x.point_dist[0], np.float32),
+                               ('f_off', x.point_off, np.int32), ('f_range', x.point_range, np.int32), ('f_atom', x.point_atom[0], np.int16),
+                               ('f_fp', x.atom_fp[0], np.uint8), ('f_kind', x.point_kind, np.int8)],
+              entry=_features_entry, sdf=lambda m: _features_item(m['features']), read=_read_features, verdict=lambda m: m['features']['features_ok'],
+              compute=lambda d, opt: (features_for(d.data, d.res, screen=d.screen, kekule=d.of('kekule'), rings=d.of('rings')) if opt is True
+                                      else _features(d.res, opt[0], opt[1], screen=d.screen, kekule=d.of('kekule'), rings=d.of('rings'), limits=opt[2]))),
+    _Analysis('smiles', 'smiles', Smiles,
+              parts=lambda x: [('s_status', x.status[0], np.int32), ('s_counts', x.counts[0], np.int32), ('s_length', x.length[0], np.int32),
+                               ('s_rank', x.atom_rank[0], np.int16), ('s_text', x.text[0], np.uint8)]
+              + ([] if x.stereo_counts is None else [('s_stereo', x.stereo_counts[0], np.int32)]),
+              entry=_smiles_entry, read=_true_or('smiles'),
+              sdf=lambda m: '> <PHOREGEN_SMILES>\n%s\n\n' % m['smiles']['text'] if m['smiles'].get('smiles_ok') else '',
+              compute=lambda d, opt: _smiles(d.res, screen=d.screen, kekule=d.of('kekule'), stereo=d.of('stereo') if 'stereo' in d.options else None),
+              verdict=lambda m: m['smiles']['smiles_ok']),
+    _Analysis('stereo', 'stereo', Stereo,
+              parts=lambda x: [('t_key', x.stereo_key[0], np.uint64), ('t_status', x.status[0], np.int32), ('t_counts', x.counts[0], np.int32),
+                               ('t_parity', x.atom_parity[0], np.int8), ('t_alabel', x.atom_label[0], np.int8),
+                               ('t_bond', x.bond_stereo[0], np.int8), ('t_blabel', x.bond_label[0], np.int8)],
+              entry=lambda x, v, at, mol: {'stereo': dict(
+                  _status_entry('stereo_ok', STEREO_FAIL_MASK, STEREO_COUNTS, at.row(v['t_status']), at.row(v['t_counts'])),
+                  atom_parity=at.atoms(v['t_parity']).copy(), atom_label=at.atoms(v['t_alabel']).copy(),
+                  bond_stereo=at.bonds(v['t_bond']).copy(), bond_label=at.bonds(v['t_blabel']).copy(), stereo_key=int(at.row(v['t_key'])))},
+              sdf=_stereo_item, read=_true_or('stereo', StereoLimits),
+              compute=lambda d, opt: _stereo(d.res, screen=d.screen, kekule=d.of('kekule'), rings=d.of('rings'), keys=d.keys, limits=opt),
+              verdict=lambda m: m['stereo']['stereo_ok']),
+    _Analysis('fingerprints', 'fingerprint', Fingerprints, frames='fp',
+              parts=lambda x: [('p_fp', x.fp[0], np.uint64), ('p_bits', x.bits[0], np.int32)],
+              entry=lambda x, v, at, mol: {'fingerprint': at.row(v['p_fp']).copy(), 'fp_bits': int(at.row(v['p_bits'])), 'fp_radius': x.radius},
+              sdf=_fingerprint_item, read=lambda value: None if value is False else _check_radius('sample_valid', FP_RADIUS if value is True else value),
+              compute=lambda d, opt: _fingerprints(d.screen, opt)),
+    # (their records live in modules of their own, which import this one)
+    SimpleNamespace(keyword='substructure', key='substructure'), SimpleNamespace(keyword='hydrogens', key='hydrogens'),
+]
+
+
+def _blob_parts(pos_t, sc, mk, agree, handed):
+    """The parts of the one blob of `assemble` as (name, final-frame tensor, numpy dtype): the screen's and the coordinates, the keys'
+    (mk, None: without), the screen's agreement counts (agree) and those of every (record, holder) handed in -- the widest elements
+    first, by a stable sort, so that every part stays aligned in the blob wherever its line stands.  A view has its tensor's shape."""
+    parts = [('status', sc.status[0], np.int32), ('counts', sc.counts[0], np.int32), ('pos', pos_t, np.float32),
+             ('compact', sc.compact[0], np.int16), ('cls', sc.cls[0], np.int8), ('valence2', sc.valence2[0], np.uint8),
+             ('order', sc.order[0], np.int8)]
+    if mk is not None:
+        parts += [('key', mk.key[0], np.uint64), ('colour', mk.colour[0], np.uint64)]
+    if agree:
+        parts += [('agree', sc.agree[0], np.int32)]
+    for rec, x in handed:
+        parts += rec.parts(x)
+    assert len({name for name, _, _ in parts}) == len(parts) and all(t.element_size() == np.dtype(dt).itemsize for _, t, dt in parts)
+    return sorted(parts, key=lambda part: -np.dtype(part[2]).itemsize)
 
 
 @torch.no_grad()
@@ -1278,126 +1501,31 @@ def assemble(results, keys=False, geometry=None, rings=None, kekule=None, featur
     bits), 'hydrogens_ok' (no bit of HYD_FAIL_MASK), the eight HYD_COUNTS by name, 'min_contact', 'h_pos' (fp32 [n_h, 3], the placed
     hydrogens in (parent, slot) order), 'h_parent' (per hydrogen an index into this dict's atoms) and 'site_shape' (per kept atom) --
     in the same copy; its screen is reused, and it must have been computed from the screen of the others."""
-    geom, pos_t, fps, sub, hyd = geometry, results['pred'][1], fingerprints, substructure, hydrogens
-    sc_in = screen
-    if sc_in is not None and (not isinstance(sc_in, Screen) or sc_in.status.size(0) != 1 or sc_in.cls.size(1) != pos_t.size(-2)
-                              or sc_in.cls.device != pos_t.device):
+    handed, pos_t = _handed(locals()), results['pred'][1]              # (locals: this signature's keywords by name)
+    # 1. the one screen: screen= if given, else the first holder's, else a new one; every holder must be of it
+    if screen is not None and (not isinstance(screen, Screen) or screen.status.size(0) != 1 or screen.cls.size(1) != pos_t.size(-2)
+                               or screen.cls.device != pos_t.device):
         raise ValueError('phoregen_amd.molecule.assemble: screen= must be a Screen of the final frame of this result')
-    if sub is not None:
-        from . import substructure as _sub
-        if (not isinstance(sub, _sub.Substructure) or sub.status.size(0) != 1 or sub.screen.cls.size(1) != pos_t.size(-2)
-                or sub.status.device != pos_t.device):
-            raise ValueError('phoregen_amd.molecule.assemble: substructure= must be a Substructure of the final frame of this result')
-    if hyd is not None:
-        from . import hydrogens as _hyd
-        if (not isinstance(hyd, _hyd.Hydrogens) or hyd.status.size(0) != 1 or hyd.screen.cls.size(1) != pos_t.size(-2)
-                or hyd.status.device != pos_t.device):
-            raise ValueError('phoregen_amd.molecule.assemble: hydrogens= must be a Hydrogens of the final frame of this result')
-    if fps is not None and (not isinstance(fps, Fingerprints) or fps.screen is None or fps.fp.size(0) != 1
-                            or fps.screen.cls.size(1) != pos_t.size(-2) or fps.fp.device != pos_t.device):
-        raise ValueError('phoregen_amd.molecule.assemble: fingerprints= must be a Fingerprints of the final frame of this result')
-    given = [(what, x) for what, x in (('geometry', geom), ('rings', rings), ('kekule', kekule), ('features', features), ('smiles', smiles),
-                                       ('stereo', stereo)) if x is not None]
-    for what, x in given:
-        if x.status.size(0) != 1 or x.screen.cls.size(1) != pos_t.size(-2) or x.status.device != pos_t.device:
-            raise ValueError(f'phoregen_amd.molecule.assemble: {what}= must be a {what.capitalize()} of the final frame of this result')
-    for (what_a, xa), (what_b, xb) in zip(given, given[1:]):
-        if not _same_screen(xa.screen, xb.screen):
-            raise ValueError(f'phoregen_amd.molecule.assemble: {what_a}= and {what_b}= were computed from screens of different results')
-    if fps is not None and given and not _same_screen(given[-1][1].screen, fps.screen):
-        raise ValueError(f'phoregen_amd.molecule.assemble: {given[-1][0]}= and fingerprints= were computed from screens of different results')
-    if sub is not None and (given or fps is not None) and not _same_screen(given[-1][1].screen if given else fps.screen, sub.screen):
-        raise ValueError('phoregen_amd.molecule.assemble: substructure= and the others were computed from screens of different results')
-    others = [(what, x.screen) for what, x in given] + [(what, x.screen) for what, x in (('fingerprints', fps), ('substructure', sub))
-                                                        if x is not None]
-    if hyd is not None:
-        if others and not _same_screen(others[-1][1], hyd.screen):
-            raise ValueError(f'phoregen_amd.molecule.assemble: {others[-1][0]}= and hydrogens= were computed from screens of different results')
-        others.append(('hydrogens', hyd.screen))
-    for what, x_sc in others if sc_in is not None else ():
-        if not _same_screen(sc_in, x_sc):
-            raise ValueError(f'phoregen_amd.molecule.assemble: screen= and {what}= were computed from screens of different results or '
-                             f'bond sources ({sc_in.bonds!r}, {x_sc.bonds!r})')
-    sc = sc_in if sc_in is not None else others[0][1] if others else _screen(results, 'final')
-    # the parts of the one blob, widest elements first so that every part stays aligned in it
-    parts = []
-    if keys:
-        mk = molecule_keys(sc)
-        parts += [('key', mk.key[0], np.uint64), ('colour', mk.colour[0], np.uint64)]
-    if stereo is not None:
-        parts += [('t_key', stereo.stereo_key[0], np.uint64)]
-    if fps is not None:
-        parts += [('p_fp', fps.fp[0], np.uint64)]
-    if sub is not None:
-        parts += [('u_mask', sub.atom_mask[0], np.int64), ('u_emb', sub.embeddings[0], np.int32), ('u_anchors', sub.anchors[0], np.int32),
-                  ('u_status', sub.status[0], np.int32)]
-    if rings is not None:
-        parts += [('r_status', rings.status[0], np.int32), ('r_counts', rings.counts[0], np.int32)]
-    if kekule is not None:
-        parts += [('k_status', kekule.status[0], np.int32), ('k_counts', kekule.counts[0], np.int32)]
-    if smiles is not None:
-        parts += [('s_status', smiles.status[0], np.int32), ('s_counts', smiles.counts[0], np.int32), ('s_length', smiles.length[0], np.int32)]
-    if stereo is not None:
-        parts += [('t_status', stereo.status[0], np.int32), ('t_counts', stereo.counts[0], np.int32)]
-    if smiles is not None and smiles.stereo_counts is not None:
-        parts += [('s_stereo', smiles.stereo_counts[0], np.int32)]
-    if geom is not None:
-        parts += [('g_status', geom.status[0], np.int32), ('g_metrics', geom.metrics[0], np.float32), ('g_counts', geom.counts[0], np.int32),
-                  ('g_dist', geom.point_dist[0], np.float32), ('g_off', geom.point_off, np.int32)]
-    if features is not None:
-        parts += [('f_status', features.status[0], np.int32), ('f_counts', features.counts[0], np.int32),
-                  ('f_dist', features.point_dist[0], np.float32), ('f_off', features.point_off, np.int32),
-                  ('f_range', features.point_range, np.int32)]
-    if fps is not None:
-        parts += [('p_bits', fps.bits[0], np.int32)]
-    if sc_in is not None and sc.agree is not None:
-        parts += [('agree', sc.agree[0], np.int32)]
-    if hyd is not None:
-        parts += [('h_status', hyd.status[0], np.int32), ('h_counts', hyd.counts[0], np.int32), ('h_min', hyd.min_contact[0], np.float32),
-                  ('h_pos', hyd.h_pos[0], np.float32)]
-    parts += [('status', sc.status[0], np.int32), ('counts', sc.counts[0], np.int32), ('pos', pos_t, np.float32),
-              ('compact', sc.compact[0], np.int16)]
-    if sub is not None:
-        parts += [('u_first', sub.first[0], np.int16)]
-    if geom is not None:
-        parts += [('g_atom', geom.point_atom[0], np.int16)]
-    if rings is not None:
-        parts += [('r_sys', rings.ring_sys[0], np.int16)]
-    if features is not None:
-        parts += [('f_atom', features.point_atom[0], np.int16)]
-    if smiles is not None:
-        parts += [('s_rank', smiles.atom_rank[0], np.int16)]
-    parts += [('cls', sc.cls[0], np.int8), ('valence2', sc.valence2[0], np.uint8), ('order', sc.order[0], np.int8)]
-    if rings is not None:
-        parts += [('r_atom', rings.atom_ring[0], np.uint8), ('r_size', rings.ring_size[0], np.uint8)]
-    if kekule is not None:
-        parts += [('k_order', kekule.kekule_order[0], np.int8), ('k_h', kekule.hcount[0], np.uint8), ('k_q', kekule.charge[0], np.int8)]
-    if features is not None:
-        parts += [('f_fp', features.atom_fp[0], np.uint8), ('f_kind', features.point_kind, np.int8)]
-    if smiles is not None:
-        parts += [('s_text', smiles.text[0], np.uint8)]
-    if stereo is not None:
-        parts += [('t_parity', stereo.atom_parity[0], np.int8), ('t_alabel', stereo.atom_label[0], np.int8),
-                  ('t_bond', stereo.bond_stereo[0], np.int8), ('t_blabel', stereo.bond_label[0], np.int8)]
-    if hyd is not None:
-        parts += [('h_placed', hyd.h_placed[0], np.uint8), ('h_shape', hyd.site_shape[0], np.uint8)]
-    sizes = [t.numel() * t.element_size() for _, t, _ in parts]
+    for rec, x in handed:
+        t = getattr(x, rec.frames) if isinstance(x, rec.holder) and x.screen is not None else None
+        if t is None or t.size(0) != 1 or x.screen.cls.size(1) != pos_t.size(-2) or t.device != pos_t.device:
+            raise ValueError(f'phoregen_amd.molecule.assemble: {rec.keyword}= must be a {rec.holder.__name__} of the final frame of this result')
+    for rec, x in handed[1:]:
+        if not _same_screen(handed[0][1].screen, x.screen):
+            raise ValueError(f'phoregen_amd.molecule.assemble: {handed[0][0].keyword}= and {rec.keyword}= were computed from screens of '
+                             'different results')
+    for rec, x in handed if screen is not None else ():
+        if not _same_screen(screen, x.screen):
+            raise ValueError(f'phoregen_amd.molecule.assemble: screen= and {rec.keyword}= were computed from screens of different results or '
+                             f'bond sources ({screen.bonds!r}, {x.screen.bonds!r})')
+    sc = screen if screen is not None else handed[0][1].screen if handed else _screen(results, 'final')
+    # 2. - 4. the parts of what was handed in, widest first, in ONE copy; the views by name
+    parts = _blob_parts(pos_t, sc, molecule_keys(sc) if keys else None, screen is not None and sc.agree is not None, handed)
     blob = torch.cat([t.reshape(-1).view(torch.uint8) for _, t, _ in parts]).cpu().numpy()
-    cut = np.cumsum([0] + sizes)
-    v = {name: blob[cut[i]:cut[i + 1]].view(dt) for i, (name, _, dt) in enumerate(parts)}
-    status, cls, valence2, order, compact = v['status'], v['cls'], v['valence2'], v['order'], v['compact']
-    counts, pos = v['counts'].reshape(-1, 4), v['pos'].reshape(-1, 3)
-    if geom is not None:
-        g_status, g_dist, g_off, g_atom = v['g_status'], v['g_dist'], v['g_off'], v['g_atom']
-        g_metrics, g_counts = v['g_metrics'].reshape(-1, 8), v['g_counts'].reshape(-1, 6)
-    if rings is not None:
-        r_counts = v['r_counts'].reshape(-1, len(RING_COUNTS))
-    if kekule is not None:
-        k_counts = v['k_counts'].reshape(-1, len(KEKULE_COUNTS))
-    if features is not None:
-        f_counts, f_range = v['f_counts'].reshape(-1, len(FEATURE_COUNTS)), v['f_range'].reshape(-1, 2)
-    if smiles is not None:
-        s_counts, s_text = v['s_counts'].reshape(-1, len(SMILES_COUNTS)), v['s_text'].reshape(-1, smiles.capacity)
+    cut = np.cumsum([0] + [t.numel() * t.element_size() for _, t, _ in parts])
+    v = {name: blob[cut[i]:cut[i + 1]].view(dt).reshape(tuple(t.shape)) for i, (name, t, dt) in enumerate(parts)}
+    # 5. the split by offsets: the base dict, then what each holder adds
+    status, cls, valence2, order, compact, counts, pos = (v[k] for k in ('status', 'cls', 'valence2', 'order', 'compact', 'counts', 'pos'))
     mols, n0, h0 = [], 0, 0
     for g, n in enumerate(sc.num_atoms):
         h = n * (n - 1) // 2
@@ -1405,76 +1533,22 @@ def assemble(results, keys=False, geometry=None, rings=None, kekule=None, featur
         o = order[h0:h0 + h]
         nz = np.nonzero(o)[0]
         a, b = _pairs(n)
-        cmp_g = compact[n0:n0 + n].astype(np.int64)
-        mols.append({'element': [ATOM_TYPES[c] for c in cls[n0:n0 + n][keep].tolist()],
-                     'atom_pos': torch.from_numpy(pos[n0:n0 + n][keep]),
-                     'bond_index': torch.from_numpy(np.stack([cmp_g[a[nz]], cmp_g[b[nz]]])),
-                     'bond_type': torch.from_numpy(o[nz].astype(np.int64)),
-                     'status': int(status[g]), 'valid': (int(status[g]) & FAIL_MASK) == 0, 'n_components': int(counts[g, 2]),
-                     'valence': valence2[n0:n0 + n][keep].astype(np.float64) / 2.0})
-        if sc_in is not None:
-            mols[-1]['bonds'] = sc.bonds
+        at = _MolView(g, n0, n, keep, h0, h, nz, compact[n0:n0 + n].astype(np.int64))
+        mol = {'element': [ATOM_TYPES[c] for c in at.atoms(cls).tolist()],
+               'atom_pos': torch.from_numpy(at.atoms(pos)),
+               'bond_index': torch.from_numpy(np.stack([at.cmp_g[a[nz]], at.cmp_g[b[nz]]])),
+               'bond_type': torch.from_numpy(o[nz].astype(np.int64)),
+               'status': int(status[g]), 'valid': (int(status[g]) & FAIL_MASK) == 0, 'n_components': int(counts[g, 2]),
+               'valence': at.atoms(valence2).astype(np.float64) / 2.0}
+        if screen is not None:
+            mol['bonds'] = sc.bonds
             if sc.agree is not None:
-                mols[-1]['bond_agreement'] = {k: int(x) for k, x in zip(BOND_AGREE_COUNTS, v['agree'].reshape(-1, len(BOND_AGREE_COUNTS))[g])}
+                mol['bond_agreement'] = {k: int(x) for k, x in zip(BOND_AGREE_COUNTS, at.row(v['agree']))}
         if keys:
-            mols[-1]['key'], mols[-1]['atom_colour'] = int(v['key'][g]), v['colour'][n0:n0 + n][keep].copy()
-        if geom is not None:
-            q0, q1 = int(g_off[g]), int(g_off[g + 1])
-            mols[-1]['geom'] = dict({'status': int(g_status[g]), 'geom_ok': (int(g_status[g]) & GEOM_FAIL_MASK) == 0},
-                                    **{k: float(x) for k, x in zip(GEOM_METRICS, g_metrics[g])},
-                                    **{k: int(x) for k, x in zip(GEOM_COUNTS, g_counts[g])},
-                                    point_dist=g_dist[q0:q1].copy(), point_atom=g_atom[q0:q1].copy())
-        if rings is not None:
-            sys_g = v['r_sys'][n0:n0 + n][keep].astype(np.int64)         # local index of the system's first atom -> its compact index
-            mols[-1]['rings'] = dict({'status': int(v['r_status'][g]), 'rings_ok': (int(v['r_status'][g]) & RING_FAIL_MASK) == 0},
-                                     **{k: int(x) for k, x in zip(RING_COUNTS, r_counts[g])},
-                                     bond_ring_size=v['r_size'][h0:h0 + h][nz].copy(), atom_ring=v['r_atom'][n0:n0 + n][keep].copy(),
-                                     ring_sys=np.where(sys_g >= 0, cmp_g[np.maximum(sys_g, 0)], -1).astype(np.int16))
-        if kekule is not None:
-            k_h, k_q = v['k_h'][n0:n0 + n][keep].copy(), v['k_q'][n0:n0 + n][keep].copy()
-            formula, weight = formula_of(mols[-1]['element'], k_h, int(k_q.astype(np.int64).sum()))
-            mols[-1]['kekule'] = dict({'status': int(v['k_status'][g]), 'kekule_ok': (int(v['k_status'][g]) & KEKULE_FAIL_MASK) == 0},
-                                      **{_KEKULE_KEYS[k]: int(x) for k, x in zip(KEKULE_COUNTS, k_counts[g])},
-                                      bond_type=torch.from_numpy(v['k_order'][h0:h0 + h][nz].astype(np.int64)), hcount=k_h, charge=k_q,
-                                      formula=formula, mol_weight=weight)
-        if features is not None:
-            q0, q1 = int(v['f_off'][g]), int(v['f_off'][g + 1])
-            fp = v['f_fp'][n0:n0 + n][keep].copy()
-            mols[-1]['features'] = dict({'status': int(v['f_status'][g]), 'features_ok': (int(v['f_status'][g]) & FEAT_FAIL_MASK) == 0},
-                                        **{k: int(x) for k, x in zip(FEATURE_COUNTS, f_counts[g])}, atom_fp=fp,
-                                        atom_types=[tuple(t for k, t in enumerate(FEATURE_TYPES) if b >> k & 1) for b in fp.tolist()],
-                                        point_kind=v['f_kind'][int(f_range[g, 0]):int(f_range[g, 1])].copy(),
-                                        point_dist=v['f_dist'][q0:q1].copy(), point_atom=v['f_atom'][q0:q1].copy())
-            # (the kernel's own comparison: fp32 distance < fp32 cutoff; a non-finite point has distance +inf)
-            mols[-1]['features']['point_matched'] = mols[-1]['features']['point_dist'] < np.float32(features.limits.feat_cut)
-        if smiles is not None:
-            s_ok = (int(v['s_status'][g]) & SMILES_FAIL_MASK) == 0
-            mols[-1]['smiles'] = dict({'status': int(v['s_status'][g]), 'smiles_ok': s_ok,
-                                       'text': s_text[g, :int(v['s_length'][g])].tobytes().decode('ascii') if s_ok else ''},
-                                      **{k: int(x) for k, x in zip(SMILES_COUNTS, s_counts[g])},
-                                      atom_rank=v['s_rank'][n0:n0 + n][keep].copy())
-            if smiles.stereo_counts is not None:
-                mols[-1]['smiles'].update({k: int(x) for k, x in zip(SMILES_STEREO_COUNTS, v['s_stereo'].reshape(-1, 4)[g])})
-        if stereo is not None:
-            t_st = int(v['t_status'][g])
-            mols[-1]['stereo'] = dict({'status': t_st, 'stereo_ok': (t_st & STEREO_FAIL_MASK) == 0},
-                                      **{k: int(x) for k, x in zip(STEREO_COUNTS, v['t_counts'].reshape(-1, len(STEREO_COUNTS))[g])},
-                                      atom_parity=v['t_parity'][n0:n0 + n][keep].copy(), atom_label=v['t_alabel'][n0:n0 + n][keep].copy(),
-                                      bond_stereo=v['t_bond'][h0:h0 + h][nz].copy(), bond_label=v['t_blabel'][h0:h0 + h][nz].copy(),
-                                      stereo_key=int(v['t_key'][g]))
-        if fps is not None:
-            mols[-1]['fingerprint'] = v['p_fp'].reshape(-1, FP_WORDS)[g].copy()
-            mols[-1]['fp_bits'], mols[-1]['fp_radius'] = int(v['p_bits'][g]), fps.radius
-        if sub is not None:
-            n_pat = len(sub.patterns)
-            mols[-1]['substructure'] = _sub.molecule_entries(sub.patterns, v['u_emb'].reshape(-1, n_pat)[g], v['u_anchors'].reshape(-1, n_pat)[g],
-                                                             v['u_mask'].reshape(-1, n_pat, 2)[g], v['u_first'].reshape(-1, n_pat, _sub.MAX_ATOMS)[g],
-                                                             v['u_status'].reshape(-1, n_pat)[g])
-            mols[-1]['substructure_ok'] = _sub.entries_ok(mols[-1]['substructure'])
-        if hyd is not None:
-            mols[-1]['hydrogens'] = _hyd.molecule_entry(v['h_status'][g], v['h_counts'].reshape(-1, len(_hyd.HYD_COUNTS))[g], v['h_min'][g],
-                                                        v['h_pos'].reshape(-1, _hyd.MAX_PER_ATOM, 3)[n0:n0 + n][keep],
-                                                        v['h_placed'][n0:n0 + n][keep], v['h_shape'][n0:n0 + n][keep])
+            mol['key'], mol['atom_colour'] = int(at.row(v['key'])), at.atoms(v['colour']).copy()
+        for rec, x in handed:
+            mol.update(rec.entry(x, v, at, mol))
+        mols.append(mol)
         n0, h0 = n0 + n, h0 + h
     return mols
 
@@ -1529,74 +1603,10 @@ def mol_block(mol, name=''):
     return '\n'.join(lines) + '\n'
 
 
-def _features_item(ft):
-    """The PHOREGEN_FEATURES data item of a molecule's 'features' dict (`assemble`)."""
-    lines = ['> <PHOREGEN_FEATURES>', 'status 0x%02x' % int(ft['status'])] + ['%s %d' % (k, ft[k]) for k in FEATURE_COUNTS]
-    kinds = np.asarray(ft['point_kind']).reshape(-1).tolist()
-    dist, atom = np.asarray(ft['point_dist']).reshape(-1).tolist(), np.asarray(ft['point_atom']).reshape(-1).tolist()
-    for k, d, a, hit in zip(kinds, dist, atom, np.asarray(ft['point_matched']).reshape(-1).tolist()):
-        if 0 <= k < len(FEATURE_TYPES):
-            lines.append('%s %s %s' % (FEATURE_TYPES[k], str(a + 1) if hit else '-', '%.4f' % d if np.isfinite(d) else 'inf'))
-    return '\n'.join(lines) + '\n\n'
-
-
-def _stereo_item(m):
-    """The PHOREGEN_STEREO data item of a molecule that carries 'stereo' (`assemble`)."""
-    st, sign = m['stereo'], {1: '+', -1: '-', STEREO_UNDEFINED_VALUE: '?'}
-    lines = ['> <PHOREGEN_STEREO>', 'status 0x%02x' % int(st['status']), 'stereo_key %016x' % (int(st['stereo_key']) & _M64)]
-    lines += ['%s %d' % (k, st[k]) for k in STEREO_COUNTS]
-    for i, (p, l) in enumerate(zip(np.asarray(st['atom_parity']).tolist(), np.asarray(st['atom_label']).tolist())):
-        if p:
-            lines.append('centre %d %s %s' % (i + 1, sign[p], sign[l]))
-    bi = np.asarray(m['bond_index']).reshape(2, -1)
-    for (a, b), p, l in zip(bi.T.tolist(), np.asarray(st['bond_stereo']).tolist(), np.asarray(st['bond_label']).tolist()):
-        if p:
-            lines.append('bond %d %d %s %s' % (a + 1, b + 1, sign[p], sign[l]))
-    return '\n'.join(lines) + '\n\n'
-
-
-def _fingerprint_item(m):
-    """The PHOREGEN_FINGERPRINT data item of a molecule that carries 'fingerprint' (`assemble`)."""
-    words = [int(w) & _M64 for w in np.asarray(m['fingerprint']).reshape(-1).tolist()]
-    if len(words) != FP_WORDS:
-        raise ValueError(f"write_sdf: 'fingerprint' has {len(words)} words, not {FP_WORDS}")
-    return '> <PHOREGEN_FINGERPRINT>\n%s\nradius %d\n\n' % (''.join('%016x' % w for w in words), int(m.get('fp_radius', FP_RADIUS)))
-
-
-def _substructure_item(m):
-    from .substructure import sdf_item
-    return sdf_item(m['substructure'])
-
-
-def _hydrogens_item(m):
-    from .hydrogens import sdf_item
-    return sdf_item(m['hydrogens'])
-
-
-# The data items of `write_sdf`, in the order they are written: (the key a molecule must carry, molecule -> the item's text)
 def _bonds_item(m):
     """The PHOREGEN_BONDS data item of a molecule that carries 'bonds' (`assemble(screen=)`)."""
     ag = m.get('bond_agreement')
     return '> <PHOREGEN_BONDS>\nmode %s\n' % m['bonds'] + ('' if ag is None else ''.join('%s %d\n' % (k, ag[k]) for k in BOND_AGREE_COUNTS)) + '\n'
-
-
-_SDF_ITEMS = [
-    ('bonds', _bonds_item),
-    ('key', lambda m: '> <PHOREGEN_KEY>\n%016x\n\n' % (int(m['key']) & _M64)),
-    ('geom', lambda m: '> <PHOREGEN_GEOM>\nstatus 0x%02x\n' % int(m['geom']['status'])
-     + ''.join('%s %.4f\n' % (k, m['geom'][k]) for k in GEOM_METRICS[:7]) + '\n'),
-    ('rings', lambda m: '> <PHOREGEN_RINGS>\nstatus 0x%02x\n' % int(m['rings']['status'])
-     + ''.join('%s %d\n' % (k, m['rings'][k]) for k in RING_COUNTS) + '\n'),
-    ('kekule', lambda m: '> <PHOREGEN_KEKULE>\nstatus 0x%02x\nformula %s\nmol_weight %.3f\n'
-     % (int(m['kekule']['status']), m['kekule']['formula'], m['kekule']['mol_weight'])
-     + ''.join('%s %d\n' % (k, m['kekule'][_KEKULE_KEYS[k]]) for k in KEKULE_COUNTS) + '\n'),
-    ('features', lambda m: _features_item(m['features'])),
-    ('smiles', lambda m: '> <PHOREGEN_SMILES>\n%s\n\n' % m['smiles']['text'] if m['smiles'].get('smiles_ok') else ''),
-    ('stereo', _stereo_item),
-    ('fingerprint', _fingerprint_item),
-    ('substructure', _substructure_item),
-    ('hydrogens', _hydrogens_item),
-]
 
 
 def write_sdf(path, mols, names=None):
@@ -1630,7 +1640,8 @@ def write_sdf(path, mols, names=None):
     with open(path, 'w') as fh:
         for m, nm in zip(mols, names):
             fh.write(mol_block(m, nm))
-            fh.write(''.join(item(m) for key, item in _SDF_ITEMS if key in m))
+            fh.write((_bonds_item(m) if 'bonds' in m else '') + ('> <PHOREGEN_KEY>\n%016x\n\n' % (int(m['key']) & _M64) if 'key' in m else ''))
+            fh.write(''.join(rec.sdf(m) for rec in _analyses(lambda a: a.key in m)))
             fh.write('$$$$\n')
 
 
@@ -1777,12 +1788,20 @@ def duplicate_groups(keys):
 
 # ---- the top-up loop of sample_all.py:79-84,172 ------------------------------------------------------------------------------
 class _Draw:
-    """What the analyses of one draw share: its screen, rings, Kekulé form and keys, each computed on first demand and at most once,
-    the rings and the Kekulé form with the user's limits / options if given, else with the defaults."""
+    """One draw of `sample_valid`, and the one place where its analyses are computed: its screen, its keys and the holder of every
+    analysis (`of`), each on first demand and at most once.  An analysis is computed (its record's `compute`, which takes what it
+    needs from the draw again) with what the user gave for its keyword -- `options`, {keyword: what the record's `read` made of the
+    argument} -- else with the defaults."""
 
-    def __init__(self, res, ring_limits, kek_options, add_edge='predicted', margins=None, agreement=False):
-        self.res, self.ring_limits, self.kek_options = res, ring_limits or RingLimits(), kek_options or KekuleOptions()
+    def __init__(self, res, data, model, options, add_edge='predicted', margins=None, agreement=False):
+        self.res, self.data, self.model, self.options, self._held = res, data, model, options, {}
         self.add_edge, self.margins, self.agreement = add_edge, margins or BondMargins(), agreement
+
+    def of(self, keyword):
+        if keyword not in self._held:
+            rec, = _analyses(lambda a: a.keyword == keyword)
+            self._held[keyword] = rec.compute(self, self.options[keyword] if keyword in self.options else rec.read(True))
+        return self._held[keyword]
 
     @cached_property
     def screen(self):
@@ -1795,16 +1814,13 @@ class _Draw:
         return _screen(self.res, 'final', bonds=self.add_edge, margins=self.margins)
 
     @cached_property
-    def rings(self):
-        return _rings(self.res, screen=self.screen, limits=self.ring_limits)
-
-    @cached_property
-    def kekule(self):
-        return _kekulize(self.res, screen=self.screen, options=self.kek_options)
-
-    @cached_property
     def keys(self):
         return molecule_keys(self.screen)
+
+
+def _identity(m):
+    """`sample_valid(unique=True)`: (the key a molecule is looked up by, `same_molecule`'s stereo=), by whether it carries 'stereo'."""
+    return (m['stereo']['stereo_key'], True) if 'stereo' in m else (m['key'], False)
 
 
 def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, device='cuda', unique=False, geometry=None,
@@ -1851,39 +1867,14 @@ def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, d
     goes to 'failed'.  The molecules then carry 'hydrogens' and, since an all-atom block needs it, the Kekulé form of the draw as
     'kekule' (computed with kekule= if given, else with the default options), so `write_sdf` writes all-atom blocks.
     All of these share one screen per draw."""
+    args = locals()                                                    # (this signature's keywords by name, for the records' readers)
     if add_edge not in BOND_MODES:
         raise ValueError(f'phoregen_amd.molecule.sample_valid: add_edge must be one of {BOND_MODES}, not {add_edge!r}')
     if bond_margins is not None and not isinstance(bond_margins, BondMargins):
         raise ValueError(f'phoregen_amd.molecule.sample_valid: bond_margins= must be a BondMargins, not {bond_margins!r}')
-    sub_patterns = sub_steps = None
-    if substructure is not None:
-        from . import substructure as _sub
-        sub_patterns, sub_steps = substructure if isinstance(substructure, tuple) else (substructure, _sub.DEFAULT_STEPS)
-        sub_patterns, sub_steps = _sub._checked(sub_patterns), _sub._check_steps('sample_valid', sub_steps)
-    fp_radius = None
-    if fingerprints is not None and fingerprints is not False:
-        fp_radius = _check_radius('sample_valid', FP_RADIUS if fingerprints is True else fingerprints)
-    ring_limits = RingLimits() if rings is True else rings
-    if ring_limits is not None and not isinstance(ring_limits, RingLimits):
-        raise ValueError(f'phoregen_amd.molecule.sample_valid: rings= must be True or a RingLimits, not {rings!r}')
-    kek_options = KekuleOptions() if kekule is True else kekule
-    if kek_options is not None and not isinstance(kek_options, KekuleOptions):
-        raise ValueError(f'phoregen_amd.molecule.sample_valid: kekule= must be True or a KekuleOptions, not {kekule!r}')
-    if features is not None and features is not True:
-        if not (isinstance(features, tuple) and len(features) == 3 and isinstance(features[2], FeatureLimits)):
-            raise ValueError(f'phoregen_amd.molecule.sample_valid: features= must be True or (point_pos, point_kind, FeatureLimits), not '
-                             f'{features!r}')
-    if smiles is not None and smiles is not True:
-        raise ValueError(f'phoregen_amd.molecule.sample_valid: smiles= must be True, not {smiles!r}')
-    stereo_limits = StereoLimits() if stereo is True else stereo
-    if stereo_limits is not None and not isinstance(stereo_limits, StereoLimits):
-        raise ValueError(f'phoregen_amd.molecule.sample_valid: stereo= must be True or a StereoLimits, not {stereo!r}')
-    hyd_options = None
-    if hydrogens is not None and hydrogens is not False:
-        from . import hydrogens as _hyd
-        hyd_options = _hyd.HydrogenOptions() if hydrogens is True else hydrogens
-        if not isinstance(hyd_options, _hyd.HydrogenOptions):
-            raise ValueError(f'phoregen_amd.molecule.sample_valid: hydrogens= must be True or a HydrogenOptions, not {hydrogens!r}')
+    options = {rec.keyword: opt for rec, value in _handed(args) if (opt := rec.read(value)) is not None}      # (a reader's None: not asked for)
+    carry = set(options).union(*(rec.also for rec in _analyses(lambda a: a.keyword in options)))
+    carried = _analyses(lambda a: a.keyword in carry)                            # carried, and filtered on where there is a verdict
     finished, failed, duplicates, n_calls = [], [], [], 0
     by_key = {}                                                        # key -> finished molecules that have it
     while len(finished) < num_samples:
@@ -1892,38 +1883,16 @@ def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, d
         n = min(batch_size, num_samples - len(finished))
         res = model.sample(data, n, device, return_traj=False, **sample_kwargs)
         n_calls += 1
-        draw = _Draw(res, ring_limits, kek_options, add_edge, bond_margins, bool(bond_agreement))
-        geo = (None if geometry is None else geometry_for(data, res, screen=draw.screen, ex_col=getattr(model, 'ex_col', 12)) if geometry is True
-               else _geometry(res, geometry[0], geometry[1], screen=draw.screen, limits=geometry[2]))
-        ring = draw.rings if ring_limits is not None else None
-        kek = draw.kekule if kek_options is not None or hyd_options is not None else None
-        hyds = None if hyd_options is None else _hyd.hydrogens(res, screen=draw.screen, kekule=draw.kekule, options=hyd_options)
-        feat = (None if features is None else features_for(data, res, screen=draw.screen, kekule=draw.kekule, rings=draw.rings) if features is True
-                else _features(res, features[0], features[1], screen=draw.screen, kekule=draw.kekule, rings=draw.rings, limits=features[2]))
-        ster = None if stereo_limits is None else _stereo(res, screen=draw.screen, kekule=draw.kekule, rings=draw.rings, keys=draw.keys,
-                                                          limits=stereo_limits)
-        smi = None if smiles is None else _smiles(res, screen=draw.screen, kekule=draw.kekule, stereo=ster)
-        fps = None if fp_radius is None else _fingerprints(draw.screen, fp_radius)
-        subs = None if sub_patterns is None else _sub.substructure(res, sub_patterns, screen=draw.screen, rings=draw.rings, kekule=draw.kekule,
-                                                                   max_steps=sub_steps)
-        mols = assemble(res, keys=unique, **{k: v for k, v in (('geometry', geo), ('rings', ring), ('kekule', kek), ('features', feat),
-                                                               ('smiles', smi), ('stereo', ster), ('fingerprints', fps),
-                                                               ('substructure', subs), ('hydrogens', hyds),
-                                                               ('screen', draw.screen if add_edge != 'predicted' or bond_agreement else None))
-                                          if v is not None})
-        for m in mols:
-            if (not m['valid'] or (geometry is not None and not m['geom']['geom_ok'])
-                    or (ring_limits is not None and not m['rings']['rings_ok'])
-                    or (kek is not None and not m['kekule']['kekule_ok'])
-                    or (features is not None and not m['features']['features_ok'])
-                    or (smiles is not None and not m['smiles']['smiles_ok'])
-                    or (ster is not None and not m['stereo']['stereo_ok'])
-                    or (subs is not None and not m['substructure_ok'])
-                    or (hyds is not None and not m['hydrogens']['hydrogens_ok'])):
+        draw = _Draw(res, data, model, options, add_edge, bond_margins, bool(bond_agreement))
+        held = {rec.keyword: draw.of(rec.keyword) for rec in carried}
+        if add_edge != 'predicted' or bond_agreement:
+            held['screen'] = draw.screen
+        for m in assemble(res, keys=unique, **held):
+            if not m['valid'] or not all(rec.verdict(m) for rec in carried if rec.verdict is not None):
                 failed.append(m)
                 continue
-            key = m['stereo']['stereo_key'] if unique and ster is not None else m['key'] if unique else None
-            if unique and any(same_molecule(m, other, ster is not None) for other in by_key.setdefault(key, [])):
+            key, labels = _identity(m) if unique else (None, False)
+            if unique and any(same_molecule(m, other, labels) for other in by_key.setdefault(key, [])):
                 duplicates.append(m)
             else:
                 finished.append(m)

@@ -558,11 +558,6 @@ def molecule_entries(patterns, embeddings, anchors, atom_mask, first, status):
     return out
 
 
-def entries_ok(entries):
-    """A molecule passes iff none of its patterns is SUB_OUT_OF_BOUNDS (`Substructure.ok`)."""
-    return all(not e['status'] & SUB_OUT_OF_BOUNDS for e in entries.values())
-
-
 def sdf_item(entries):
     """The PHOREGEN_SUBSTRUCTURE data item: one line per pattern -- name, embeddings, anchors, status as hex, the atoms in an
     embedding and the first embedding as comma-separated 1-based atom numbers ('-' if empty)."""
@@ -572,6 +567,26 @@ def sdf_item(entries):
     lines += ['%s %d %d 0x%02x %s %s' % (name, e['embeddings'], e['anchors'], e['status'], numbers(e['atoms']), numbers(e['first']))
               for name, e in entries.items()]
     return '\n'.join(lines) + '\n\n'
+
+
+def _molecule_entry(x, v, at, mol):
+    """What a molecule carries: 'substructure', and 'substructure_ok' iff none of its patterns is SUB_OUT_OF_BOUNDS (`Substructure.ok`)."""
+    entries = molecule_entries(x.patterns, *(at.row(v[name]) for name in ('u_emb', 'u_anchors', 'u_mask', 'u_first', 'u_status')))
+    return {'substructure': entries, 'substructure_ok': all(not e['status'] & SUB_OUT_OF_BOUNDS for e in entries.values())}
+
+
+def _read(value):
+    """`sample_valid(substructure=)`: a list of patterns, or (patterns, max_steps)."""
+    patterns, steps = value if isinstance(value, tuple) else (value, DEFAULT_STEPS)
+    return _checked(patterns), _check_steps('sample_valid', steps)
+
+
+ANALYSIS = M._Analysis(
+    'substructure', 'substructure', Substructure, entry=_molecule_entry, sdf=lambda m: sdf_item(m['substructure']), read=_read,
+    parts=lambda x: [('u_mask', x.atom_mask[0], np.int64), ('u_emb', x.embeddings[0], np.int32), ('u_anchors', x.anchors[0], np.int32),
+                     ('u_status', x.status[0], np.int32), ('u_first', x.first[0], np.int16)],
+    compute=lambda d, opt: substructure(d.res, opt[0], screen=d.screen, rings=d.of('rings'), kekule=d.of('kekule'), max_steps=opt[1]),
+    verdict=lambda m: m['substructure_ok'])
 
 
 def parse_sdf_item(text):
