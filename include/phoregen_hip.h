@@ -276,6 +276,69 @@ typedef struct {
 } PgSegAttn;
 int pg_seg_attn(const PgTopo* t, const PgSegAttn* p, void* stream);
 
+/* ---- which kernel serves a pg_seg_attn / pg_seg_attn_bwd call --------------------------------
+ * The limits of the kernel forms, by name (phoregen_amd/hip.py mirrors them; the kernel files take them from here).  A row tile
+ * is 16 rows of a segment; "tiles" below is ceil(rows / 16) of the largest segment a launch may meet. */
+#define PG_SEG_ROW_TILE 16
+#define PG_SEG_KNN_MAX_K 32             /* knn modes: the node kernels (csrc/node_attn.hip) hold 2 row tiles, knn_k up to 32          */
+#define PG_SEG_NODE_MIN_TILES 3         /* bond modes: the node kernels are built for 3, 4 and 5 row tiles of PgTopo.max_nlig ...     */
+#define PG_SEG_NODE_MAX_TILES 5         /* ... ligands of up to 80 atoms                                                              */
+#define PG_SEG_POS_TILED_MIN_TILES 2    /* PgSegAttn.pos_tiled: built for 2, 3 and 4 row tiles ...                                    */
+#define PG_SEG_POS_TILED_MAX_TILES 4    /* ... ligands of up to 64 atoms                                                              */
+#define PG_SEG_TRI_STAGED_ROWS 80       /* staged triplet kernel (csrc/triplet2.hip): rows of P a workgroup stages, max_nlig - 1 <= 80 */
+#define PG_SEG_TRI_STAGED_ATOMS 96      /* ... and ligand atoms whose coordinates it stages                                           */
+#define PG_SEG_TRI_STAGED_LD 256        /* ... ld_csrc of its one [n_bond, 256] = [P_k | P_v] tensor, Csrc_v == Csrc_k + 128           */
+#define PG_SEG_TRI_MIN_TILES 3          /* ... built for 3, 4 and 5 row tiles of the n - 2 rows a segment visits                      */
+#define PG_SEG_TRI_MAX_TILES 5
+#define PG_SEG_TRI_WAVES 12             /* ... on 12 waves per workgroup ...                                                          */
+#define PG_SEG_TRI_WAVES_DEBUG 8        /* ... or 8 (sampling form, pg_debug_force_generic_seg bit 2)                                 */
+#define PG_SEG_BWD_TRI_MAX_ATOMS 64     /* triplet adjoint: 4 waves per workgroup, the two-pass and the channel-split form up to 64
+                                           atoms of PgTopo.max_nlig; above, the one-wave form on 2 waves                              */
+#define PG_SEG_BWD_TRI_FORM2_ATOMS 32   /* PgSegAttnGrad.tri_form 2: ligands up to 32 atoms on the 8-wave launch                      */
+#define PG_SEG_BWD_LDS_BYTES 163840     /* the adjoint's LDS budget; for the triplet's one-wave form that is                          */
+#define PG_SEG_BWD_TRI_BASE_FLOATS 7680 /* ... weight tables and accumulators of a workgroup ...                                      */
+#define PG_SEG_BWD_TRI_WAVE_FLOATS 3072 /* ... + per wave ...                                                                         */
+#define PG_SEG_BWD_TRI_ROW_FLOATS 259   /* ... + per atom of max_nlig rounded up to a row tile: refused (PG_ERR_ARG) when it is more  */
+#define PG_SEG_PHORE_RECORD_ROWS 256    /* training path: pharmacophore graphs up to this size ask the forward for its per-row record */
+
+/* kernel families (PgSegForm.family) and the file that holds the kernel */
+enum {
+  PG_FORM_NONE = 0,               /* nothing is launched: no segments                                                               */
+  PG_FORM_GENERIC = 1,            /* one-pass, one wave per segment, any shape             seg_attn.hip    seg_attn_kernel<mode>     */
+  PG_FORM_NODE_TWO_PASS = 2,      /* node modes, U given                                   node_attn.hip   node_attn_kernel<.., false> */
+  PG_FORM_NODE_FUSED = 3,         /* node modes, query fold (and value unfold) in-kernel   node_attn.hip   node_attn_kernel<.., true> */
+  PG_FORM_POS_TILED = 4,          /* fused position modes, a node's row tiles over waves   node_attn.hip   node_attn_pos_tiled_kernel */
+  PG_FORM_TRI_STAGED = 5,         /* triplet, sampling: out = resid + update               triplet2.hip    triplet2_kernel<.., false> */
+  PG_FORM_TRI_STAGED_TRAIN = 6,   /* triplet, training: S, swn (and the record)            triplet2.hip    triplet2_kernel<.., true> */
+  PG_FORM_BWD_ONE_WAVE = 7,       /* adjoint, one wave per row tile, both MLP paths        seg_attn_bwd.hip seg_attn_bwd_kernel<.., 0> */
+  PG_FORM_BWD_TWO_PASS = 8,       /* adjoint as a value pass, then a key pass              seg_attn_bwd.hip seg_attn_bwd_kernel<.., 1 / 2> */
+  PG_FORM_BWD_CHANNEL_SPLIT = 9   /* triplet adjoint, a tile's channels over the waves     triplet_bwd2.hip triplet_bwd2_kernel       */
+};
+/* composite cases (PgSegForm.compose, a bit set) */
+#define PG_FORM_TWO_LISTS 1      /* forward: the two target lists are served one after the other, each in the form described        */
+#define PG_FORM_FOLD_UNFOLD 2    /* forward: a fused request served as pg_attn_fold_query + the form described (+ pg_attn_unfold_value
+                                    in the node-update modes)                                                                       */
+#define PG_FORM_SECOND_LAUNCH 4  /* adjoint, tri_form 2: the 8-wave launch (tiles, threads), then the 4-wave launch (tiles2, threads2)
+                                    for the ligands of more than PG_SEG_BWD_TRI_FORM2_ATOMS atoms                                   */
+/* What a call runs.  Two calls with equal PgSegForm run the same code: (mode, family, tiles, threads, record_floats) name the template
+ * instantiation, compose / tiles2 / threads2 the launches around or after it. */
+typedef struct {
+  int mode;            /* PG_SEG_*                                                                                                  */
+  int family;          /* PG_FORM_*                                                                                                 */
+  int tiles;           /* row tiles the kernel is instantiated for; 0: the family is not instantiated per tile count                */
+  int threads;         /* threads per workgroup (64 per wave); PG_FORM_BWD_TWO_PASS: of the value pass                              */
+  int compose;         /* PG_FORM_TWO_LISTS | PG_FORM_FOLD_UNFOLD | PG_FORM_SECOND_LAUNCH                                           */
+  int tiles2;          /* second launch of the same family (PG_FORM_SECOND_LAUNCH; the key pass of PG_FORM_BWD_TWO_PASS) ...        */
+  int threads2;        /* ... 0: there is none                                                                                      */
+  int record_floats;   /* forward: floats per row the launch leaves at PgSegAttn.alpha (16: softmax weights, 32: logits | value
+                          scalars, 0: no record); adjoint: floats per row of the record it reads from PgSegAttnGrad.alpha           */
+  int rowbuf_waves;    /* adjoint: waves per workgroup PgSegAttnGrad.rowbuf must be sized for; 0: the form has no row buffer        */
+} PgSegForm;
+/* Host arithmetic only (no GPU needed, nothing is dereferenced): the form pg_seg_attn / pg_seg_attn_bwd would run for these
+ * arguments, or PG_ERR_ARG with the message of the entry point for everything it refuses by its argument and LDS checks.
+ * Honours pg_debug_force_generic_seg. */
+int pg_seg_attn_form(const PgTopo* t, const PgSegAttn* p, PgSegForm* out);
+
 /* U[s][c][h] = sum_d q[s,8h+d] * W2k[8h+d,c]  in lane-fixed layout (key second layer folded into the query) */
 int pg_attn_fold_query(const float* q /*[n,128] pre-scaled*/, int ldq, const float* W2k_l, int n,
                        const int* ids, float* U, void* stream);
@@ -430,8 +493,11 @@ typedef struct {
                                               rowbuf unused; same gradients up to summation order): 1 = 4 waves x 32 channels, 2 = ligands of up to
                                               32 atoms on 8 waves x 16 channels and the larger ones in a second launch of the 4-wave form */
 } PgSegAttnGrad;
-int pg_seg_attn_bwd_waves(int mode);
+int pg_seg_attn_bwd_waves(int mode);      /* the largest PgSegForm.rowbuf_waves of any form of the mode */
 int pg_seg_attn_bwd(const PgTopo* t, const PgSegAttn* p, const PgSegAttnGrad* g, void* stream);
+/* The form pg_seg_attn_bwd would run (see pg_seg_attn_form).  The form is inferred from what the caller filled in: alpha + S + swn
+ * (the forward's record) select the one-pass kernels, dlogit + gfeat_v on top the two-pass form, tri_form the channel-split one. */
+int pg_seg_attn_bwd_form(const PgTopo* t, const PgSegAttn* p, const PgSegAttnGrad* g, PgSegForm* out);
 
 /* gW2_l (+=) in the lane-fixed layout of W2k_l / W2v_l:  gW2[8h+d, c] += sum_s X[s, 8h+d] * T[s][c][h]
  * (adjoint of pg_attn_fold_query w.r.t. the weights with X = q, T = dU; of pg_attn_unfold_value with X = dout, T = S) */

@@ -488,25 +488,24 @@ static int launch_na(const PgTopo* t, const PgSegAttn* p, hipStream_t st) {
   return check_launch("pg_seg_attn(node)");
 }
 
+// PG_FORM_NODE_TWO_PASS / PG_FORM_NODE_FUSED for the form's row tiles
 template <bool FUSED>
-static int launch_node_attn_t(const PgTopo* t, const PgSegAttn* p, hipStream_t st) {
+static int launch_node_attn_t(const PgSegForm& f, const PgTopo* t, const PgSegAttn* p, hipStream_t st) {
   constexpr int TH = FUSED ? 768 : 256;
-  const bool knn = p->mode == PG_SEG_KNN_NODE || p->mode == PG_SEG_KNN_POS;
-  const bool pos = p->mode == PG_SEG_KNN_POS || p->mode == PG_SEG_BOND_POS;
-  if (knn) {
-    if (p->knn_k > 32) return -1;
+  const bool pos = f.mode == PG_SEG_KNN_POS || f.mode == PG_SEG_BOND_POS;
+  if (f.mode == PG_SEG_KNN_NODE || f.mode == PG_SEG_KNN_POS)
     return pos ? launch_na<true, true, 2, TH, FUSED>(t, p, st) : launch_na<true, false, 2, TH, FUSED>(t, p, st);
+  if (pos) switch (f.tiles) {
+    case 3: return launch_na<false, true, 3, TH, FUSED>(t, p, st);
+    case 4: return launch_na<false, true, 4, TH, FUSED>(t, p, st);
+    case 5: return launch_na<false, true, 5, TH, FUSED>(t, p, st);
+  } else switch (f.tiles) {
+    case 3: return launch_na<false, false, 3, TH, FUSED>(t, p, st);
+    case 4: return launch_na<false, false, 4, TH, FUSED>(t, p, st);
+    case 5: return launch_na<false, false, 5, TH, FUSED>(t, p, st);
   }
-  const int tiles = (t->max_nlig + 15) / 16;
-  if (tiles > 5) return -1;
-  if (pos) {
-    if (tiles <= 3) return launch_na<false, true, 3, TH, FUSED>(t, p, st);
-    if (tiles == 4) return launch_na<false, true, 4, TH, FUSED>(t, p, st);
-    return launch_na<false, true, 5, TH, FUSED>(t, p, st);
-  }
-  if (tiles <= 3) return launch_na<false, false, 3, TH, FUSED>(t, p, st);
-  if (tiles == 4) return launch_na<false, false, 4, TH, FUSED>(t, p, st);
-  return launch_na<false, false, 5, TH, FUSED>(t, p, st);
+  set_error("pg_seg_attn: no node kernel instance for %d row tiles", f.tiles);
+  return PG_ERR_ARG;
 }
 
 // ------------------------------------------------------------------------------------------------------------------------------
@@ -805,36 +804,19 @@ static int launch_pos_tiled(const PgTopo* t, const PgSegAttn* p, hipStream_t st)
   return check_launch("pg_seg_attn(node pos, tiled)");
 }
 
-// the tiled form serves the fused sampler calls of the position modes (no second target list, no training outputs); -1 otherwise
-static int launch_pos_tiled_any(const PgTopo* t, const PgSegAttn* p, hipStream_t st) {
-  if (p->alpha || p->n_seg2 > 0) return -1;
-  if (p->mode == PG_SEG_KNN_POS) return p->knn_k <= 32 ? launch_pos_tiled<true, 2>(t, p, st) : -1;
-  const int tiles = (t->max_nlig + 15) / 16;
-  if (tiles <= 2) return launch_pos_tiled<false, 2>(t, p, st);
-  if (tiles == 3) return launch_pos_tiled<false, 3>(t, p, st);
-  if (tiles == 4) return launch_pos_tiled<false, 4>(t, p, st);
-  return -1;
-}
-
-// returns -1 when the shape is outside what the two-pass kernels hold in registers (caller falls back to seg_attn.hip).
-// Fused form: q and W2k_l given (and, for the node-update modes, W2v_l, b2v, out) -- see node_attn_fused_request()
-bool node_attn_fused_request(const PgSegAttn* p) {
-  const bool pos = p->mode == PG_SEG_KNN_POS || p->mode == PG_SEG_BOND_POS;
-  return p->mode <= PG_SEG_BOND_POS && p->q && p->W2k_l && (pos || (p->W2v_l && p->b2v && p->out));
-}
-
-int launch_node_attn(const PgTopo* t, const PgSegAttn* p, hipStream_t st) {
-  // the weight tables go to LDS in 16-byte pieces
-  if ((((size_t)p->Wf_k | (size_t)p->Wf_v | (size_t)p->Wf_k2 | (size_t)p->Wf_v2 | (size_t)p->W2xv_l) & 15) != 0) {
-    set_error("pg_seg_attn: Wf_k / Wf_v / W2xv_l must be 16-byte aligned");
+// the node-mode forms of pg_seg_attn_form: PG_FORM_POS_TILED, PG_FORM_NODE_FUSED, PG_FORM_NODE_TWO_PASS
+int launch_node_attn(const PgSegForm& f, const PgTopo* t, const PgSegAttn* p, hipStream_t st) {
+  if (f.family == PG_FORM_POS_TILED) {
+    if (f.mode == PG_SEG_KNN_POS) return launch_pos_tiled<true, 2>(t, p, st);
+    switch (f.tiles) {
+      case 2: return launch_pos_tiled<false, 2>(t, p, st);
+      case 3: return launch_pos_tiled<false, 3>(t, p, st);
+      case 4: return launch_pos_tiled<false, 4>(t, p, st);
+    }
+    set_error("pg_seg_attn: no tiled position instance for %d row tiles", f.tiles);
     return PG_ERR_ARG;
   }
-  if (!node_attn_fused_request(p)) return launch_node_attn_t<false>(t, p, st);
-  if (p->pos_tiled && (p->mode == PG_SEG_KNN_POS || p->mode == PG_SEG_BOND_POS)) {
-    const int rc = launch_pos_tiled_any(t, p, st);
-    if (rc != -1) return rc;
-  }
-  return launch_node_attn_t<true>(t, p, st);
+  return f.family == PG_FORM_NODE_TWO_PASS ? launch_node_attn_t<false>(f, t, p, st) : launch_node_attn_t<true>(f, t, p, st);
 }
 
 }  // namespace pg

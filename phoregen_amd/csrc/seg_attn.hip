@@ -17,9 +17,8 @@
 
 namespace pg {
 
-int launch_triplet_staged(const PgTopo* t, const PgSegAttn* p, hipStream_t st);   // triplet2.hip (-1: not applicable)
-int launch_node_attn(const PgTopo* t, const PgSegAttn* p, hipStream_t st);   // node_attn.hip (-1: shape not covered)
-bool node_attn_fused_request(const PgSegAttn* p);                            // node_attn.hip
+int launch_triplet_staged(const PgSegForm& f, const PgTopo* t, const PgSegAttn* p, hipStream_t st);   // triplet2.hip
+int launch_node_attn(const PgSegForm& f, const PgTopo* t, const PgSegAttn* p, hipStream_t st);        // node_attn.hip
 
 // Folded LayerNorm + ReLU like ln_relu_kpath (wave_prims.h) on a
 // V-path tile: hid[tau][r] = hidden[row = 4g + r][c = 16 tau + m]; returns 1/sigma per row r
@@ -576,65 +575,48 @@ static int launch_seg(const PgTopo* t, const PgSegAttn* p, hipStream_t st) {
 
 using namespace pg;
 
-static int g_force_generic = 0;
-namespace pg { extern int g_t2_waves; }
-extern "C" int pg_debug_force_generic_seg(int on) {
-  const int old = g_force_generic;
-  g_force_generic = on;
-  pg::g_t2_waves = (on & 4) ? 8 : 12;
-  return old;
-}
-
-extern "C" int pg_seg_attn(const PgTopo* t, const PgSegAttn* p, void* stream) {
-  if (!t || !p) { set_error("pg_seg_attn: null argument"); return PG_ERR_ARG; }
-  if (p->n_seg == 0 && p->n_seg2 <= 0) return PG_OK;
-  hipStream_t st = (hipStream_t)stream;
-  if (p->n_seg2 > 0) {
-    // two target lists in one call (fused knn form): one launch when the two-pass kernel takes it, else list after list
-    if ((p->mode != PG_SEG_KNN_NODE && p->mode != PG_SEG_KNN_POS) || !p->seg_ids || !p->seg_ids2 || !p->Wf_k2 || !p->Wf_v2) {
-      set_error("pg_seg_attn: a second target list needs a knn mode, seg_ids, seg_ids2 and Wf_k2 / Wf_v2");
-      return PG_ERR_ARG;
-    }
-    if (p->n_seg > 0 && node_attn_fused_request(p) && !(g_force_generic & 1)) {
-      const int rc = launch_node_attn(t, p, st);
-      if (rc >= 0) return rc;
-    }
+// launches what pg_seg_attn_form resolved; the two composite forms come back here once per part
+static int launch_form(PgSegForm f, const PgTopo* t, const PgSegAttn* p, hipStream_t st) {
+  if (f.compose & PG_FORM_TWO_LISTS) {
     PgSegAttn a = *p, b = *p;
     a.n_seg2 = 0; a.seg_ids2 = nullptr;
     b.n_seg2 = 0; b.seg_ids2 = nullptr; b.seg_ids = p->seg_ids2; b.n_seg = p->n_seg2; b.Wf_k = p->Wf_k2; b.Wf_v = p->Wf_v2;
-    if (int rc = pg_seg_attn(t, &a, stream)) return rc;
-    return pg_seg_attn(t, &b, stream);
+    f.compose &= ~PG_FORM_TWO_LISTS;
+    if (a.n_seg > 0)
+      if (int rc = launch_form(f, t, &a, st)) return rc;
+    return launch_form(f, t, &b, st);
   }
-  if (p->mode <= PG_SEG_BOND_POS && !(g_force_generic & 1)) {   // two-pass kernels; pg_debug_force_generic_seg keeps the one-pass kernel testable
-    const int rc = launch_node_attn(t, p, st);
-    if (rc >= 0) return rc;
-  }
-  if (node_attn_fused_request(p)) {
-    // the fused form was asked for but the one-pass kernel runs (shape outside the two-pass kernels, or forced): fold, attend
-    // and unfold as separate launches through the caller's U / S / swn scratch
-    const bool pos = p->mode == PG_SEG_KNN_POS || p->mode == PG_SEG_BOND_POS;
-    if (!p->U || !p->seg_ids || (!pos && (!p->S || !p->swn))) { set_error("pg_seg_attn: the fused node form needs U (and S, swn) scratch and seg_ids for the one-pass kernel"); return PG_ERR_ARG; }
-    if (int rc = pg_attn_fold_query(p->q, 128, p->W2k_l, p->n_seg, p->seg_ids, const_cast<float*>(p->U), stream)) return rc;
+  if (f.compose & PG_FORM_FOLD_UNFOLD) {     // through the caller's U / S / swn scratch
+    if (int rc = pg_attn_fold_query(p->q, 128, p->W2k_l, p->n_seg, p->seg_ids, const_cast<float*>(p->U), st)) return rc;
     PgSegAttn u = *p;
     u.q = nullptr; u.W2k_l = nullptr;
-    if (int rc = pg_seg_attn(t, &u, stream)) return rc;
-    return pos ? PG_OK : pg_attn_unfold_value(p->S, p->swn, p->W2v_l, p->b2v, p->n_seg, p->seg_ids, p->out, 128, stream);
+    f.compose &= ~PG_FORM_FOLD_UNFOLD;
+    if (int rc = launch_form(f, t, &u, st)) return rc;
+    const bool pos = p->mode == PG_SEG_KNN_POS || p->mode == PG_SEG_BOND_POS;
+    return pos ? PG_OK : pg_attn_unfold_value(p->S, p->swn, p->W2v_l, p->b2v, p->n_seg, p->seg_ids, p->out, 128, st);
   }
-  switch (p->mode) {
-    case PG_SEG_KNN_NODE: return launch_seg<PG_SEG_KNN_NODE>(t, p, st);
-    case PG_SEG_KNN_POS: return launch_seg<PG_SEG_KNN_POS>(t, p, st);
-    case PG_SEG_BOND_NODE: return launch_seg<PG_SEG_BOND_NODE>(t, p, st);
-    case PG_SEG_BOND_POS: return launch_seg<PG_SEG_BOND_POS>(t, p, st);
-    case PG_SEG_TRIPLET: {
-      // source-atom rows staged in LDS (sampling and training forms, target-major bond order); without the plan's queue, or for
-      // ligands of more than 81 atoms, the generic form
-      const int rc = launch_triplet_staged(t, p, st);
-      return rc >= 0 ? rc : launch_seg<PG_SEG_TRIPLET>(t, p, st);
-    }
-    case PG_SEG_PHORE: return launch_seg<PG_SEG_PHORE>(t, p, st);
+  switch (f.family) {
+    case PG_FORM_NONE: return PG_OK;
+    case PG_FORM_NODE_TWO_PASS: case PG_FORM_NODE_FUSED: case PG_FORM_POS_TILED: return launch_node_attn(f, t, p, st);
+    case PG_FORM_TRI_STAGED: case PG_FORM_TRI_STAGED_TRAIN: return launch_triplet_staged(f, t, p, st);
+    case PG_FORM_GENERIC:
+      switch (f.mode) {
+        case PG_SEG_KNN_NODE: return launch_seg<PG_SEG_KNN_NODE>(t, p, st);
+        case PG_SEG_KNN_POS: return launch_seg<PG_SEG_KNN_POS>(t, p, st);
+        case PG_SEG_BOND_NODE: return launch_seg<PG_SEG_BOND_NODE>(t, p, st);
+        case PG_SEG_BOND_POS: return launch_seg<PG_SEG_BOND_POS>(t, p, st);
+        case PG_SEG_TRIPLET: return launch_seg<PG_SEG_TRIPLET>(t, p, st);
+        case PG_SEG_PHORE: return launch_seg<PG_SEG_PHORE>(t, p, st);
+      }
   }
-  set_error("pg_seg_attn: unknown mode %d", p->mode);
+  set_error("pg_seg_attn: form %d of mode %d has no launch", f.family, f.mode);
   return PG_ERR_ARG;
+}
+
+extern "C" int pg_seg_attn(const PgTopo* t, const PgSegAttn* p, void* stream) {
+  PgSegForm f;
+  if (int rc = pg_seg_attn_form(t, p, &f)) return rc;
+  return launch_form(f, t, p, (hipStream_t)stream);
 }
 
 extern "C" int pg_attn_fold_query(const float* q, int ldq, const float* W2k_l, int n, const int* ids, float* U, void* stream) {

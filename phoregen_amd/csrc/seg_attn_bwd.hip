@@ -138,7 +138,7 @@ struct BwdLds {
 
 // SPLIT (one-pass forms of the feature modes only): the key path and the value path of a segment as two launches, so that a wave
 // holds ONE path's operands, accumulators and tiles -- half the registers and, for the triplet rows, half the LDS.  That allows 8 waves
-// per workgroup = two per SIMD at 256 registers each, or 4 waves that no longer spill at 512 (launch_bwd_split picks per mode and
+// per workgroup = two per SIMD at 256 registers each, or 4 waves that no longer spill at 512 (pg_seg_attn_bwd_form picks per mode and
 // pass).  SPLIT = 1, the value pass, runs first: it needs nothing of the key path and leaves
 // d logit [segment][row][16] (PgSegAttnGrad.dlogit) and its d feat rows (PgSegAttnGrad.gfeat_v) for SPLIT = 2, the key pass,
 // which adds the two d feat parts and runs the geometry adjoint once.  SPLIT = 0: both paths in one wave (every other form).
@@ -1033,12 +1033,7 @@ __global__ __launch_bounds__(64 * NW) void seg_attn_bwd_kernel(PgTopo t, PgSegAt
 template <int MODE, int NW, bool OP = false, int SPLIT = 0>
 static int launch_bwd(const PgTopo* t, const PgSegAttn* p, const PgSegAttnGrad* gr, hipStream_t st) {
   using T = ModeTraits<MODE>;
-  constexpr int NSTEP = T::NSTEP, F = 4 * NSTEP, NFT = (F + 15) / 16, NF = NFT > 0 ? NFT : 1, FS = 16 * NF + 1;
-  constexpr int PW = 128 * 17 + 2 * 16 * FS + 64 + 32 + 256;
-  constexpr int NPATH = SPLIT ? 1 : 2, ACCW = SPLIT ? 128 : 256;
-  const size_t lds = ((size_t)NPATH * NSTEP * 512 + 256 + (T::TRI ? (size_t)((t->max_nlig + 15) & ~15) * (ACCW + 3) : 0) +
-                      (NFT == 1 ? NPATH * 128 * 17 : 0) + (size_t)NW * PW) * sizeof(float);
-  if (lds > 160 * 1024) { set_error("pg_seg_attn_bwd: %zu B of LDS needed (ligand of %d atoms is too large)", lds, t->max_nlig); return PG_ERR_ARG; }
+  const size_t lds = bwd_lds_floats<MODE>(NW, SPLIT, t->max_nlig) * sizeof(float);      // (pg_seg_attn_bwd_form has refused what does not fit)
   if (int rc = reserve_lds(reinterpret_cast<const void*>(seg_attn_bwd_kernel<MODE, NW, OP, SPLIT>), lds, "pg_seg_attn_bwd")) return rc;
   int blocks = T::TRI ? t->n_lig : (p->n_seg + NW - 1) / NW;
   if (blocks > gr->grid) blocks = gr->grid;
@@ -1047,18 +1042,15 @@ static int launch_bwd(const PgTopo* t, const PgSegAttn* p, const PgSegAttnGrad* 
   return check_launch("pg_seg_attn_bwd");
 }
 
-// The one-pass adjoint as a value pass and a key pass.  Workgroup size per pass, measured (profiles/r04_adjoint_codegen_fences.txt):
-// a wave that holds ONE path fits 512 registers without spilling (336 ... 446; both paths in a wave: 22 / 431 spilled), and that is
-// worth more than a second wave per SIMD at 256 registers (45 ... 307 spilled) -- except for the triplet value pass, the lightest of
-// the four, which runs best as 8 waves.
+// PG_FORM_BWD_TWO_PASS: the one-pass adjoint as a value pass and a key pass (the workgroup sizes: pg_seg_attn_bwd_form)
 template <int MODE, bool OP = true>
-static int launch_bwd_split(const PgTopo* t, const PgSegAttn* p, const PgSegAttnGrad* gr, hipStream_t st) {
+static int launch_two_pass(const PgTopo* t, const PgSegAttn* p, const PgSegAttnGrad* gr, hipStream_t st) {
   constexpr int NW_V = MODE == PG_SEG_TRIPLET ? 8 : 4;
   if (int rc = launch_bwd<MODE, NW_V, OP, 1>(t, p, gr, st)) return rc;
   return launch_bwd<MODE, 4, OP, 2>(t, p, gr, st);
 }
 
-int triplet_bwd2_launch(const PgTopo* t, const PgSegAttn* p, const PgSegAttnGrad* gr, hipStream_t st);   // triplet_bwd2.hip
+int triplet_bwd2_launch(const PgSegForm& f, const PgTopo* t, const PgSegAttn* p, const PgSegAttnGrad* gr, hipStream_t st);   // triplet_bwd2.hip
 
 }  // namespace pg
 
@@ -1072,52 +1064,29 @@ extern "C" int pg_debug_bwd_prof(unsigned long long* out, int reset) {
 }
 #endif
 
-// waves per workgroup the row buffer must be sized for (PgSegAttnGrad.rowbuf: grid x waves x rows x 48 floats): the LARGEST workgroup of any
-// form this mode can be launched in -- the generic / one-wave forms use 4 waves, the triplet's value pass of the two-pass form 8 (the
-// one-pass kernels do not touch the buffer today; sizing it for them anyway keeps a later change from writing past it)
-extern "C" int pg_seg_attn_bwd_waves(int mode) { return mode == PG_SEG_TRIPLET ? 8 : 4; }
-
 extern "C" int pg_seg_attn_bwd(const PgTopo* t, const PgSegAttn* p, const PgSegAttnGrad* gr, void* stream) {
-  if (!t || !p || !gr) { set_error("pg_seg_attn_bwd: null argument"); return PG_ERR_ARG; }
-  if (p->n_seg == 0) return PG_OK;
-  if (!p->U || !p->Cdst_k || !p->Cdst_v || gr->grid < 1) {
-    set_error("pg_seg_attn_bwd: U, Cdst_k/v and a grid are required");
-    return PG_ERR_ARG;
-  }
-  // the row buffer: every form but the triplet's channel-split one (its rows live in LDS) -- a launch that needs it and has none is refused
-  const bool tri_split = p->mode == PG_SEG_TRIPLET && gr->tri_form && t->max_nlig <= 64 && p->Cdst_v == p->Cdst_k + 128;
-  if (!gr->rowbuf && !tri_split) {
-    set_error("pg_seg_attn_bwd: mode %d in this form needs PgSegAttnGrad.rowbuf (grid x pg_seg_attn_bwd_waves x rows x 48 floats)", p->mode);
-    return PG_ERR_ARG;
-  }
+  PgSegForm f;
+  if (int rc = pg_seg_attn_bwd_form(t, p, gr, &f)) return rc;
   hipStream_t st = (hipStream_t)stream;
-  switch (p->mode) {
+  if (f.family == PG_FORM_NONE) return PG_OK;
+  if (f.family == PG_FORM_BWD_CHANNEL_SPLIT) return triplet_bwd2_launch(f, t, p, gr, st);
+  const bool two_pass = f.family == PG_FORM_BWD_TWO_PASS, op = f.record_floats != 0;     // op: with the forward's softmax weights, S and swn
+  switch (f.mode) {
     case PG_SEG_KNN_NODE:
-      if (gr->alpha && gr->S && gr->swn && gr->dlogit && gr->gfeat_v) return launch_bwd_split<PG_SEG_KNN_NODE>(t, p, gr, st);
-      return (gr->alpha && gr->S && gr->swn) ? launch_bwd<PG_SEG_KNN_NODE, 4, true>(t, p, gr, st)
-                                             : launch_bwd<PG_SEG_KNN_NODE, 4>(t, p, gr, st);
+      if (two_pass) return launch_two_pass<PG_SEG_KNN_NODE>(t, p, gr, st);
+      return op ? launch_bwd<PG_SEG_KNN_NODE, 4, true>(t, p, gr, st) : launch_bwd<PG_SEG_KNN_NODE, 4>(t, p, gr, st);
     case PG_SEG_KNN_POS:
       // (two passes need the forward's logits / value scalars: each pass redoes the softmax adjoint from them)
-      if (gr->alpha && gr->dlogit && gr->gfeat_v) return launch_bwd_split<PG_SEG_KNN_POS, false>(t, p, gr, st);
-      return launch_bwd<PG_SEG_KNN_POS, 4>(t, p, gr, st);
-    case PG_SEG_BOND_NODE:
-      return (gr->alpha && gr->S && gr->swn) ? launch_bwd<PG_SEG_BOND_NODE, 4, true>(t, p, gr, st)
-                                             : launch_bwd<PG_SEG_BOND_NODE, 4>(t, p, gr, st);
+      return two_pass ? launch_two_pass<PG_SEG_KNN_POS, false>(t, p, gr, st) : launch_bwd<PG_SEG_KNN_POS, 4>(t, p, gr, st);
+    case PG_SEG_BOND_NODE: return op ? launch_bwd<PG_SEG_BOND_NODE, 4, true>(t, p, gr, st) : launch_bwd<PG_SEG_BOND_NODE, 4>(t, p, gr, st);
     case PG_SEG_BOND_POS: return launch_bwd<PG_SEG_BOND_POS, 4>(t, p, gr, st);
-    case PG_SEG_TRIPLET: {
-      // the per-source-atom rows (max_nlig x 259 floats) share the LDS with the per-wave tiles: 4 waves up to 64 atoms,
-      // 2 waves up to the reference's maximum of 78 (and beyond, to 96)
-      const bool op = gr->alpha && gr->S && gr->swn;
-      if (tri_split) return triplet_bwd2_launch(t, p, gr, st);   // (Cdst k | v: one 1 KB row)
-      if (op && gr->dlogit && gr->gfeat_v && t->max_nlig <= 64) return launch_bwd_split<PG_SEG_TRIPLET>(t, p, gr, st);
-      if (t->max_nlig <= 64) return op ? launch_bwd<PG_SEG_TRIPLET, 4, true>(t, p, gr, st) : launch_bwd<PG_SEG_TRIPLET, 4>(t, p, gr, st);
+    case PG_SEG_TRIPLET:
+      if (two_pass) return launch_two_pass<PG_SEG_TRIPLET>(t, p, gr, st);
+      if (f.threads == 256) return op ? launch_bwd<PG_SEG_TRIPLET, 4, true>(t, p, gr, st) : launch_bwd<PG_SEG_TRIPLET, 4>(t, p, gr, st);
       return op ? launch_bwd<PG_SEG_TRIPLET, 2, true>(t, p, gr, st) : launch_bwd<PG_SEG_TRIPLET, 2>(t, p, gr, st);
-    }
-    case PG_SEG_PHORE:
-      // (the pharmacophore encoder, training: with the forward's softmax weights one pass; as a value pass + a key pass it measured
-      //  slower -- 136.6 against 136.2 ms per training step -- and is not built in)
-      return (gr->alpha && gr->S && gr->swn) ? launch_bwd<PG_SEG_PHORE, 4, true>(t, p, gr, st) : launch_bwd<PG_SEG_PHORE, 4>(t, p, gr, st);
+    // (the pharmacophore encoder as a value pass + a key pass measured slower -- 136.6 against 136.2 ms per training step -- and is not built)
+    case PG_SEG_PHORE: return op ? launch_bwd<PG_SEG_PHORE, 4, true>(t, p, gr, st) : launch_bwd<PG_SEG_PHORE, 4>(t, p, gr, st);
   }
-  set_error("pg_seg_attn_bwd: unknown mode %d", p->mode);
+  set_error("pg_seg_attn_bwd: form %d of mode %d has no launch", f.family, f.mode);
   return PG_ERR_ARG;
 }

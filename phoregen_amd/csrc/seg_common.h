@@ -13,6 +13,18 @@ template <> struct ModeTraits<PG_SEG_BOND_POS>  { static constexpr int NSTEP = 0
 template <> struct ModeTraits<PG_SEG_TRIPLET>   { static constexpr int NSTEP = 3;  static constexpr bool POS = false, KNN = false, BOND = false, TRI = true,  PH = false; };
 template <> struct ModeTraits<PG_SEG_PHORE>     { static constexpr int NSTEP = 1;  static constexpr bool POS = false, KNN = false, BOND = false, TRI = false, PH = true;  };
 
+// LDS floats of seg_attn_bwd_kernel<MODE, nw waves, ., split> (seg_attn_bwd.hip lays them out; the launch reserves them and the form
+// resolver, seg_form.hip, refuses a ligand whose rows do not fit)
+template <int MODE>
+constexpr size_t bwd_lds_floats(int nw, int split, int max_nlig) {
+  using T = ModeTraits<MODE>;
+  constexpr int NSTEP = T::NSTEP, F = 4 * NSTEP, NFT = (F + 15) / 16, NF = NFT > 0 ? NFT : 1, FS = 16 * NF + 1;
+  constexpr int PW = 128 * 17 + 2 * 16 * FS + 64 + 32 + 256;
+  const int NPATH = split ? 1 : 2, ACCW = split ? 128 : 256;
+  return (size_t)NPATH * NSTEP * 512 + 256 + (T::TRI ? (size_t)((max_nlig + 15) & ~15) * (ACCW + 3) : 0) +
+         (NFT == 1 ? NPATH * 128 * 17 : 0) + (size_t)nw * PW;
+}
+
 struct RowInfo {
   bool valid;
   int csrc;  // row of Csrc_{k,v}

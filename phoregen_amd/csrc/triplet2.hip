@@ -42,8 +42,8 @@ typedef float t2_f2 __attribute__((ext_vector_type(2)));
 #endif
 
 constexpr int T2_ROW = 260;          // floats per staged row: P_k[128] | P_v[128] | 4 (bank spread of the b128 key-layout reads)
-constexpr int T2_ROWS = 80;          // staged rows per workgroup
-constexpr int T2_XS = 96;            // ligand atoms whose coordinates are staged
+constexpr int T2_ROWS = PG_SEG_TRI_STAGED_ROWS;    // staged rows per workgroup (80)
+constexpr int T2_XS = PG_SEG_TRI_STAGED_ATOMS;     // ligand atoms whose coordinates are staged (96)
 
 constexpr size_t t2_lds_floats() { return 16384 + 2 * 1536 + 3 * 128 + 3 * T2_XS + 4 + (size_t)T2_ROWS * T2_ROW; }
 
@@ -427,37 +427,23 @@ static int launch_t2(const PgTopo* t, const PgSegAttn* p, hipStream_t st) {
   return check_launch("pg_seg_attn(triplet, staged)");
 }
 
-int g_t2_waves = 12;  // waves per workgroup: 12 (3 per SIMD, no look-ahead prefetch; measured 1.98 ms) or 8 (with it, 2.07 ms);
-                      // pg_debug_force_generic_seg bit 2 selects 8
-
-// usable when the caller provides the source-atom groups (PgSegAttn.tri_iters) and P is one [n_bond, 256] = [P_k | P_v] tensor,
-// for the sampling form (out = resid + update) and for the training form (S, swn and optionally alpha out; q and W2k_l given);
-// returns -1 otherwise
-int launch_triplet_staged(const PgTopo* t, const PgSegAttn* p, hipStream_t st) {
-  if (!p->tri_iters || !p->tri_counter || p->n_tri_iters <= 0) return -1;
-  const bool train = p->S != nullptr;
-#ifdef PG_T2_PROF
-  if (train || !p->out || !p->resid) return -1;
-#else
-  if (train ? (!p->swn || !p->q || !p->W2k_l || (p->alpha && p->alpha_rows < t->max_nlig)) : (p->alpha || !p->out || !p->resid)) return -1;
-#endif
-  if (p->Csrc_v != p->Csrc_k + 128 || p->ld_csrc != 256 || ((size_t)p->Csrc_k & 15) || !p->Cdst_k || !p->Cdst_v) return -1;
-  if (t->max_nlig - 1 > T2_ROWS || t->max_nlig > T2_XS) return -1;
-  const int maxn = (p->tri_max_nlig > 0 && p->tri_max_nlig < t->max_nlig) ? p->tri_max_nlig : t->max_nlig;     // largest ligand among this queue's entries
-  const int tiles = (maxn - 2 + 15) / 16;          // rows a segment visits: every atom but its source and its target
-  if (train) {
-    if (tiles <= 3) return launch_t2<768, 3, true>(t, p, st);
-    if (tiles == 4) return launch_t2<768, 4, true>(t, p, st);
-    return launch_t2<768, 5, true>(t, p, st);
+// PG_FORM_TRI_STAGED / PG_FORM_TRI_STAGED_TRAIN (pg_seg_attn_form chose it).  Waves per workgroup: 12 (3 per SIMD, no look-ahead prefetch;
+// measured 1.98 ms) or, sampling form under pg_debug_force_generic_seg bit 2, 8 (with it, 2.07 ms)
+int launch_triplet_staged(const PgSegForm& f, const PgTopo* t, const PgSegAttn* p, hipStream_t st) {
+  const int variant = f.family == PG_FORM_TRI_STAGED_TRAIN ? 2 : f.threads == 512 ? 1 : 0;     // 2 training; sampling on 12 waves 0, on 8 waves 1
+  switch (f.tiles * 10 + variant) {
+    case 32: return launch_t2<768, 3, true>(t, p, st);
+    case 42: return launch_t2<768, 4, true>(t, p, st);
+    case 52: return launch_t2<768, 5, true>(t, p, st);
+    case 30: return launch_t2<768, 3>(t, p, st);
+    case 40: return launch_t2<768, 4>(t, p, st);
+    case 50: return launch_t2<768, 5>(t, p, st);
+    case 31: return launch_t2<512, 3>(t, p, st);
+    case 41: return launch_t2<512, 4>(t, p, st);
+    case 51: return launch_t2<512, 5>(t, p, st);
   }
-  if (g_t2_waves == 12) {
-    if (tiles <= 3) return launch_t2<768, 3>(t, p, st);
-    if (tiles == 4) return launch_t2<768, 4>(t, p, st);
-    return launch_t2<768, 5>(t, p, st);
-  }
-  if (tiles <= 3) return launch_t2<512, 3>(t, p, st);
-  if (tiles == 4) return launch_t2<512, 4>(t, p, st);
-  return launch_t2<512, 5>(t, p, st);
+  set_error("pg_seg_attn: no staged triplet instance for %d row tiles", f.tiles);
+  return PG_ERR_ARG;
 }
 
 }  // namespace pg

@@ -629,22 +629,23 @@ static int launch_tb2(const PgTopo* t, const PgSegAttn* p, const PgSegAttnGrad* 
   return check_launch("pg_seg_attn_bwd (channel split)");
 }
 
-// entry used by pg_seg_attn_bwd (seg_attn_bwd.hip) for PG_SEG_TRIPLET when PgSegAttnGrad.tri_form asks for it; ligands of up to 64 atoms.
-// tri_form 1: 4 waves x 32 channels (up to 512 registers, one wave per SIMD).  tri_form 2: ligands of up to 32 atoms on 8 waves x 16 channels
-// (two waves per SIMD at 256 registers, no spills: the fastest form), the larger ones of the batch in a second launch of the 4-wave form --
-// every launch walks the same atom list and skips the ligands outside its range of row tiles.  (The 8-wave instances for 3 / 4 row tiles
-// need more than 256 registers; they are not built into the dispatch.)
-int triplet_bwd2_launch(const PgTopo* t, const PgSegAttn* p, const PgSegAttnGrad* gr, hipStream_t st) {
-  const int nt = (t->max_nlig + 15) / 16;
-  int lo = 1;
-  if (gr->tri_form == 2) {
+// PG_FORM_BWD_CHANNEL_SPLIT (pg_seg_attn_bwd_form chose it): the 8-wave launch of tri_form 2 first, then the 4-wave instance for the
+// form's row tiles -- every launch walks the same atom list and skips the ligands outside its range of row tiles
+int triplet_bwd2_launch(const PgSegForm& f, const PgTopo* t, const PgSegAttn* p, const PgSegAttnGrad* gr, hipStream_t st) {
+  int lo = 1, nt = f.tiles;
+  if (f.threads == 512) {
     if (int rc = launch_tb2<8, 2>(t, p, gr, 1, st)) return rc;
-    if (nt <= 2) return PG_OK;
-    lo = 3;
+    if (!(f.compose & PG_FORM_SECOND_LAUNCH)) return PG_OK;
+    lo = f.tiles + 1;
+    nt = f.tiles2;
   }
-  if (nt <= 2) return launch_tb2<4, 2>(t, p, gr, lo, st);
-  if (nt == 3) return launch_tb2<4, 3>(t, p, gr, lo, st);
-  return launch_tb2<4, 4>(t, p, gr, lo, st);
+  switch (nt) {
+    case 2: return launch_tb2<4, 2>(t, p, gr, lo, st);
+    case 3: return launch_tb2<4, 3>(t, p, gr, lo, st);
+    case 4: return launch_tb2<4, 4>(t, p, gr, lo, st);
+  }
+  set_error("pg_seg_attn_bwd: no channel-split instance for %d row tiles", nt);
+  return PG_ERR_ARG;
 }
 
 }  // namespace pg

@@ -268,6 +268,7 @@ class Engine:
             setattr(s, key, val.data_ptr() if torch.is_tensor(val) else val)
             self._keep.append(val)
         self._keep += [s, seg_ids, a]
+        s.form_name = hip.form_name(hip.seg_form(self.plan.topo_ref, s))      # what the library runs for it, asked once, kept beside the launch
         self._call(prog, self.lib.pg_seg_attn, self.plan.topo_ref, C.byref(s))
 
     def _query_gemm(self, prog, a, Y, col0, h_dst_lists, buf):
@@ -320,7 +321,7 @@ class Engine:
                     kw.update(pos_tiled=1)
             else:
                 kw.update(S=wS, swn=wsw)
-            if fused:      # (U / S / swn stay attached as scratch for the one-pass fallback inside pg_seg_attn)
+            if fused:      # (U / S / swn stay attached: PG_FORM_FOLD_UNFOLD, the form of shapes outside the node kernels, goes through them)
                 kw.update(q=wq, W2k_l=a.W2k_l)
                 if not pos:
                     assert out.stride(0) == 128
@@ -839,7 +840,7 @@ class Engine:
             what = fn.__name__
             if what in ('pg_gemm', 'pg_seg_attn'):
                 s = args[-1]._obj
-                what += f'[{s.M}x{s.N}x{s.K1}+{s.K2}]' if what == 'pg_gemm' else f'[mode {s.mode}, {s.n_seg}+{s.n_seg2}]'
+                what += f'[{s.M}x{s.N}x{s.K1}+{s.K2}]' if what == 'pg_gemm' else f'[{s.form_name}, {s.n_seg}+{s.n_seg2}]'
             self.trace.append((what, lane, a, b))
             if rc:
                 hip.check(rc, fn.__name__)

@@ -63,6 +63,15 @@ class PgSegAttnGrad(C.Structure):
                 ('dlogit', c_fp), ('gfeat_v', c_fp), ('tri_form', C.c_int)]
 
 
+class PgSegForm(C.Structure):
+    """What a pg_seg_attn / pg_seg_attn_bwd call runs (pg_seg_attn_form / pg_seg_attn_bwd_form)."""
+    _fields_ = [('mode', C.c_int), ('family', C.c_int), ('tiles', C.c_int), ('threads', C.c_int), ('compose', C.c_int),
+                ('tiles2', C.c_int), ('threads2', C.c_int), ('record_floats', C.c_int), ('rowbuf_waves', C.c_int)]
+
+    def key(self):
+        return tuple(getattr(self, f) for f, _ in self._fields_)
+
+
 PG_PROGRAM_LANES, PG_LAUNCH_MAX_ARGS = 4, 12
 
 
@@ -78,6 +87,25 @@ PROGRAM_OPS = {'pg_gemm': 2, 'pg_seg_attn': 3, 'pg_embed_ctx': 4, 'pg_embed_bond
 
 SEG_KNN_NODE, SEG_KNN_POS, SEG_BOND_NODE, SEG_BOND_POS, SEG_TRIPLET, SEG_PHORE = range(6)
 ACT_NONE, ACT_SSP, ACT_RELU = 0, 1, 2
+
+# kernel families and composite cases of a PgSegForm, and the limits of the forms, as the PG_FORM_* / PG_SEG_* macros of the header
+(FORM_NONE, FORM_GENERIC, FORM_NODE_TWO_PASS, FORM_NODE_FUSED, FORM_POS_TILED, FORM_TRI_STAGED, FORM_TRI_STAGED_TRAIN,
+ FORM_BWD_ONE_WAVE, FORM_BWD_TWO_PASS, FORM_BWD_CHANNEL_SPLIT) = range(10)
+FORM_NAMES = ('none', 'generic', 'node_two_pass', 'node_fused', 'pos_tiled', 'tri_staged', 'tri_staged_train',
+              'bwd_one_wave', 'bwd_two_pass', 'bwd_channel_split')
+PG_FORM_TWO_LISTS, PG_FORM_FOLD_UNFOLD, PG_FORM_SECOND_LAUNCH = 1, 2, 4
+PG_SEG_ROW_TILE, PG_SEG_KNN_MAX_K = 16, 32
+PG_SEG_NODE_MIN_TILES, PG_SEG_NODE_MAX_TILES, PG_SEG_POS_TILED_MIN_TILES, PG_SEG_POS_TILED_MAX_TILES = 3, 5, 2, 4
+PG_SEG_TRI_STAGED_ROWS, PG_SEG_TRI_STAGED_ATOMS, PG_SEG_TRI_STAGED_LD = 80, 96, 256
+PG_SEG_TRI_MIN_TILES, PG_SEG_TRI_MAX_TILES, PG_SEG_TRI_WAVES, PG_SEG_TRI_WAVES_DEBUG = 3, 5, 12, 8
+PG_SEG_BWD_TRI_MAX_ATOMS, PG_SEG_BWD_TRI_FORM2_ATOMS = 64, 32
+PG_SEG_BWD_LDS_BYTES, PG_SEG_BWD_TRI_BASE_FLOATS, PG_SEG_BWD_TRI_WAVE_FLOATS, PG_SEG_BWD_TRI_ROW_FLOATS = 163840, 7680, 3072, 259
+PG_SEG_PHORE_RECORD_ROWS = 256
+SEG_LIMITS = ('PG_SEG_ROW_TILE', 'PG_SEG_KNN_MAX_K', 'PG_SEG_NODE_MIN_TILES', 'PG_SEG_NODE_MAX_TILES', 'PG_SEG_POS_TILED_MIN_TILES',
+              'PG_SEG_POS_TILED_MAX_TILES', 'PG_SEG_TRI_STAGED_ROWS', 'PG_SEG_TRI_STAGED_ATOMS', 'PG_SEG_TRI_STAGED_LD',
+              'PG_SEG_TRI_MIN_TILES', 'PG_SEG_TRI_MAX_TILES', 'PG_SEG_TRI_WAVES', 'PG_SEG_TRI_WAVES_DEBUG', 'PG_SEG_BWD_TRI_MAX_ATOMS',
+              'PG_SEG_BWD_TRI_FORM2_ATOMS', 'PG_SEG_BWD_LDS_BYTES', 'PG_SEG_BWD_TRI_BASE_FLOATS', 'PG_SEG_BWD_TRI_WAVE_FLOATS',
+              'PG_SEG_BWD_TRI_ROW_FLOATS', 'PG_SEG_PHORE_RECORD_ROWS', 'PG_FORM_TWO_LISTS', 'PG_FORM_FOLD_UNFOLD', 'PG_FORM_SECOND_LAUNCH')
 
 ABI_VERSION = 11
 PG_MOL_MAX_ATOMS = 128          # include/phoregen_hip.h (the library refuses a larger graph before it launches anything)
@@ -119,6 +147,7 @@ _PROTOS = {
     'pg_knn_group_by_kind': (C.c_int, [C.POINTER(PgTopo), C.c_int, c_ip, c_ip, c_fp, C.c_void_p]),
     'pg_bond_smear': (C.c_int, [C.POINTER(PgTopo), c_fp, c_fp, C.c_void_p]),
     'pg_seg_attn': (C.c_int, [C.POINTER(PgTopo), C.POINTER(PgSegAttn), C.c_void_p]),
+    'pg_seg_attn_form': (C.c_int, [C.POINTER(PgTopo), C.POINTER(PgSegAttn), C.POINTER(PgSegForm)]),
     'pg_attn_fold_query': (C.c_int, [c_fp, C.c_int, c_fp, C.c_int, c_ip, c_fp, C.c_void_p]),
     'pg_attn_unfold_value': (C.c_int, [c_fp, c_fp, c_fp, c_fp, C.c_int, c_ip, c_fp, C.c_int, C.c_void_p]),
     'pg_apply_dx': (C.c_int, [C.POINTER(PgTopo), c_fp, c_fp, c_fp, c_fp, C.c_void_p]),
@@ -152,6 +181,7 @@ _PROTOS = {
                                  C.c_void_p]),
     'pg_seg_attn_bwd_waves': (C.c_int, [C.c_int]),
     'pg_seg_attn_bwd': (C.c_int, [C.POINTER(PgTopo), C.POINTER(PgSegAttn), C.POINTER(PgSegAttnGrad), C.c_void_p]),
+    'pg_seg_attn_bwd_form': (C.c_int, [C.POINTER(PgTopo), C.POINTER(PgSegAttn), C.POINTER(PgSegAttnGrad), C.POINTER(PgSegForm)]),
     'pg_attn_fold_wgrad': (C.c_int, [c_fp, C.c_int, c_fp, C.c_int, c_ip, c_fp, C.c_void_p]),
     'pg_guidance_grad': (C.c_int, [C.POINTER(PgTopo), c_fp, c_fp, c_ip, c_ip, C.c_int, C.c_float, C.c_float,
                                    C.c_int, c_fp, C.c_int, c_fp, c_fp, c_fp, C.c_void_p]),
@@ -301,6 +331,35 @@ class Program:
                 self.h = None
         except Exception:
             pass
+
+
+def form_name(f):
+    """A PgSegForm as text: family, row tiles, threads of every launch, composite parts, record width --
+    e.g. 'node_fused/t2/768', 'fold+generic/256+unfold', '2x node_two_pass/t2/256/rec16', 'bwd_channel_split/t2/512+t3/256'."""
+    one = lambda tiles, threads: (f't{tiles}/' if tiles else '') + str(threads)
+    name = FORM_NAMES[f.family]
+    if f.family != FORM_NONE:
+        name += '/' + one(f.tiles, f.threads)
+    if f.threads2:
+        name += '+' + one(f.tiles2, f.threads2)
+    if f.record_floats:
+        name += f'/rec{f.record_floats}'
+    if f.compose & PG_FORM_FOLD_UNFOLD:
+        name = 'fold+' + name + ('' if f.mode in (SEG_KNN_POS, SEG_BOND_POS) else '+unfold')
+    if f.compose & PG_FORM_TWO_LISTS:
+        name = '2x ' + name
+    return name
+
+
+def seg_form(topo_ref, s, grad=None):
+    """The PgSegForm the library resolves for a PgSegAttn (forward) or a PgSegAttn + PgSegAttnGrad (adjoint); raises on PG_ERR_ARG.
+    Host arithmetic: no GPU is touched."""
+    f, l = PgSegForm(), load_library()
+    if grad is None:
+        check(l.pg_seg_attn_form(topo_ref, C.byref(s), C.byref(f)), 'pg_seg_attn_form')
+    else:
+        check(l.pg_seg_attn_bwd_form(topo_ref, C.byref(s), C.byref(grad), C.byref(f)), 'pg_seg_attn_bwd_form')
+    return f
 
 
 def check(rc, what=''):

@@ -113,12 +113,13 @@ class BatchPlan:
         self.tri_chunks = i32(torch.searchsorted(csum, targets).clamp(max=self.n_bond))
         self.tri_chunks[0], self.tri_chunks[-1] = 0, self.n_bond
         # source-atom groups of the LDS-staged triplet kernel (csrc/triplet2.hip): consecutive source atoms of one ligand whose
-        # P blocks ((n-1) rows each) fit the 80 staged rows; pulled from a queue, most expensive first
-        rows_cap, waves = 80, 12
+        # P blocks ((n-1) rows each) fit the staged rows; pulled from a queue, most expensive first.  The kernel's limits are the header's
+        rows_cap, atoms_cap, waves = hip.PG_SEG_TRI_STAGED_ROWS, hip.PG_SEG_TRI_STAGED_ATOMS, hip.PG_SEG_TRI_WAVES
+        tile = hip.PG_SEG_ROW_TILE
         groups = []
         for gi in range(B):
             n = int(nlig[gi])
-            if n < 2 or n - 1 > rows_cap or n > 96:
+            if n < 2 or n - 1 > rows_cap or n > atoms_cap:
                 continue
             A = max(1, min(rows_cap // (n - 1), n))
             for j0 in range(0, n, A):
@@ -131,7 +132,7 @@ class BatchPlan:
         def queue(grps):
             its = []
             for gi, n, j0, a in grps:
-                tiles = (n - 2 + 15) // 16              # rows of a segment: every atom but its source and its target
+                tiles = (n - 2 + tile - 1) // tile      # rows of a segment: every atom but its source and its target
                 n_seg = a * (n - 1)
                 rounds = (n_seg + waves - 1) // waves
                 parts = max(1, min(want_parts, rounds // 2))
@@ -161,16 +162,17 @@ class BatchPlan:
                 halves += [(c / 2, lig0, w1, boff, s0 | (mid << 16)), (c / 2, lig0, w1, boff, mid | (s1 << 16))]
             its = head + sorted(halves, key=lambda r: -r[0])
             return torch.tensor([[r[1], r[2], r[3], r[4]] for r in its], dtype=torch.int32).reshape(-1, 4).to(device), len(its)
-        usable = bool(B and int(nlig.max()) - 1 <= rows_cap and int(nlig.max()) <= 96)
+        usable = bool(B and int(nlig.max()) - 1 <= rows_cap and int(nlig.max()) <= atoms_cap)
         self.tri_iters, n_its = queue(groups)
         self.n_tri_iters = n_its if usable else 0
         # the same entries as two queues, by the row tiles of the ligand: the kernel is instantiated for the largest ligand a queue holds,
         # and the instance for 4 (5) tiles costs every segment ~4 % (8 %) -- a few 51+-atom ligands in a batch of smaller ones get their own
         # launch (engine: options.tri_split) and the rest run on the 3-tile instance
-        small = [g_ for g_ in groups if g_[1] - 2 <= 48]
+        small_rows = hip.PG_SEG_TRI_MIN_TILES * tile         # (a segment visits n - 2 rows)
+        small = [g_ for g_ in groups if g_[1] - 2 <= small_rows]
         self.tri_split = None
         if usable and small and len(small) < len(groups):
-            big = [g_ for g_ in groups if g_[1] - 2 > 48]
+            big = [g_ for g_ in groups if g_[1] - 2 > small_rows]
             it_s, n_s = queue(small)
             it_b, n_b = queue(big)
             self.tri_split = dict(small=(it_s, n_s, max(g_[1] for g_ in small), torch.zeros(2, dtype=torch.int32, device=device)),

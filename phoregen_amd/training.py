@@ -11,6 +11,7 @@ itself) is composed from elementwise tensor ops here; the kNN searches stay in t
 No CPU fallback: every entry point raises without the library / a GPU.
 """
 import ctypes as C
+from types import SimpleNamespace
 
 import torch
 import torch.nn.functional as F
@@ -366,34 +367,24 @@ class SegCoreFn(torch.autograd.Function):
         else:
             s.S, s.swn = out[0].data_ptr(), out[1].data_ptr()
         tf = cfg.get('tri_fwd')
-        alpha = None
-        onepass = options.get('tri_onepass')
-        ph_onepass = cfg['mode'] == hip.SEG_PHORE and onepass and options.get('ph_onepass') and 0 < cfg['max_rows'] <= 256
-        if ph_onepass or cfg['mode'] in (hip.SEG_KNN_NODE, hip.SEG_BOND_NODE, hip.SEG_KNN_POS, hip.SEG_BOND_POS) and onepass and \
-                (cfg['k'] <= 32 if cfg['mode'] in (hip.SEG_KNN_NODE, hip.SEG_KNN_POS) else cfg['max_rows'] <= 80):
-            # the two-pass node kernels run (csrc/node_attn.hip): they hand alpha x gate to a one-pass adjoint (node update), or
-            # the logits and value scalars of every row to the adjoint's softmax step (position update: 32 floats per row); the
-            # pharmacophore encoder's generic kernel leaves its softmax weights the same way
-            arows = (cfg['max_rows'] + 15) // 16 * 16
-            alpha = torch.empty(n_rows * arows * (32 if pos else 16), dtype=torch.float32, device=dev)
-            s.alpha, s.alpha_rows = alpha.data_ptr(), arows
-            ctx.alpha_rows = arows
         if tf is not None:
             for k in ('q', 'W2k_l', 'W2v_l', 'b2v', 'Wg2_k', 'Wg2_v', 'G', 'seg_ids', 'seg_chunks'):
                 setattr(s, k, tf[k].data_ptr())
             if tf.get('n_tri_iters'):
                 # source-atom groups of the plan: the LDS-staged kernel (csrc/triplet2.hip, training form) takes the launch
                 s.tri_iters, s.n_tri_iters, s.tri_counter = tf['tri_iters'].data_ptr(), tf['n_tri_iters'], tf['tri_counter'].data_ptr()
-            # ligands of up to 80 atoms: the triplet kernel can hand the softmax weights to the one-wave-per-tile adjoint (the channel-split
-            # adjoint, options.tri_bwd_form, recomputes them and reads nothing of the forward back)
-            if cfg['max_rows'] <= 80 and onepass and not (options.get('tri_bwd_form') and cfg['max_rows'] <= 64):
-                arows = (cfg['max_rows'] + 15) // 16 * 16
-                alpha = torch.empty(cfg['n_seg'] * arows * 16, dtype=torch.float32, device=dev)
-                s.alpha, s.alpha_rows = alpha.data_ptr(), arows
-                ctx.alpha_rows = arows
-        ctx.has_alpha = alpha is not None
-        if alpha is not None:
+        plan = ctx.plan = _seg_plan(cfg, pos)
+        alpha = None
+        if plan.record_floats:
+            alpha = torch.empty(plan.record_segments * plan.record_rows * plan.record_floats, dtype=torch.float32, device=dev)
+            s.alpha, s.alpha_rows = alpha.data_ptr(), plan.record_rows
             ctx.save_for_backward(alpha, *(() if pos else out))      # (the adjoint reads S / swn of the node modes; dx of a position mode is not needed)
+        form = hip.seg_form(cfg['topo'], s)
+        if form.record_floats != plan.record_floats:
+            raise RuntimeError(f"SegCoreFn: mode {cfg['mode']} runs as {hip.form_name(form)}, which leaves {form.record_floats} floats per row "
+                               f"where the adjoint was planned to read {plan.record_floats}")
+        if form_log is not None:
+            form_log.append(('forward', cfg['mode'], hip.form_name(form)))
         hip.check(lib.pg_seg_attn(cfg['topo'], C.byref(s), _st()), 'pg_seg_attn')
         ctx.cfg, ctx.tensors, ctx.pos = cfg, tensors, pos
         return out if not pos else out[0]
@@ -454,45 +445,41 @@ class SegCoreFn(torch.autograd.Function):
         g.gWf_k, g.gWf_v, g.gbk, g.gbv = hip.ptr(gWf_k), hip.ptr(gWf_v), gbk.data_ptr(), gbv.data_ptr()
         g.gW2xv_l, g.gb2xv = hip.ptr(gW2), hip.ptr(gb2)
         g.gx, g.gnrm, g.gew = hip.ptr(gx), hip.ptr(gnrm), hip.ptr(gew)
-        waves = lib.pg_seg_attn_bwd_waves(cfg['mode'])
-        # one persistent workgroup per CU (the adjoints hold a CU's LDS / registers alone): every workgroup stages its weight tables and
-        # flushes its weight-gradient accumulators (hundreds of atomics per wave) ONCE, and no partial last round of workgroups is
-        # left -- training step 179.5 ms with 1 024 workgroups, 171-173 with 512, 168 with 256 (320: 205, 8 192: 206)
-        grid = max(1, min((cfg['n_seg'] + 3) // 4, options.get('bwd_grid')))          # (the forms' smallest workgroup has 4 waves)
-        rows = (cfg['max_rows'] + 15) // 16 * 16
-        if cfg['mode'] == hip.SEG_TRIPLET and options.get('tri_bwd_form') and cfg['max_rows'] <= 64:
-            # the channel-split form (csrc/triplet_bwd2.hip) keeps its rows in LDS: no row buffer (the library rejects a launch that would need one)
-            g.tri_form = int(options.get('tri_bwd_form'))
-            grid = max(1, min(cfg['n_seg'], options.get('tri_bwd_grid')))
-            g.rowbuf, g.rowbuf_rows, g.grid = None, rows, grid
-        else:
-            rowbuf = torch.empty(grid * waves * rows * 48, dtype=torch.float32, device=dev)
-            g.rowbuf, g.rowbuf_rows, g.grid = rowbuf.data_ptr(), rows, grid
-            keep.append(rowbuf)
-        if cfg['mode'] == hip.SEG_TRIPLET and cfg.get('plan') is not None and options.get('bwd_atom_sort'):
-            ao = cfg['plan'].bwd_atom_order(grid)          # cost-sorted source atoms, dealt out in a snake (levels the persistent workgroups)
+        plan = ctx.plan
+        g.tri_form, g.rowbuf_rows, g.grid = plan.tri_form, plan.record_rows, plan.grid
+        if plan.atom_sort:
+            ao = cfg['plan'].bwd_atom_order(plan.grid)     # cost-sorted source atoms, dealt out in a snake (levels the persistent workgroups)
             g.atom_order = ao.data_ptr()
             keep.append(ao)
-        if getattr(ctx, 'has_alpha', False):
+        if plan.record_floats:
             a_ = ctx.saved_tensors[0]
-            g.alpha, g.alpha_rows = a_.data_ptr(), ctx.alpha_rows
+            g.alpha, g.alpha_rows = a_.data_ptr(), plan.record_rows
             keep.append(a_)
             if not pos:
                 S_, sw_ = ctx.saved_tensors[1:3]
                 g.S, g.swn = S_.data_ptr(), sw_.data_ptr()
                 keep += [S_, sw_]
-            # (the pharmacophore encoder's adjoint stays one pass: as a value pass + a key pass it measured 0.4 ms per step slower)
-            split_modes = {'knn': (hip.SEG_KNN_NODE, hip.SEG_KNN_POS), 'all': (hip.SEG_TRIPLET, hip.SEG_KNN_NODE, hip.SEG_KNN_POS)}
-            # (the library takes the triplet's two-pass form for ligands of up to 64 atoms only: no scratch for a launch that will not use it)
-            if cfg['mode'] in split_modes.get(options.get('bwd_split'), ()) and (cfg['mode'] != hip.SEG_TRIPLET or cfg['max_rows'] <= 64):
+            if plan.two_pass:
                 # scratch of the two-pass form (value pass, then key pass): d logit (position update: one value per row) and the value
                 # pass's d feat rows, indexed like the forward's per-row record
-                n_rows_rec = a_.numel() // (32 if pos else 16)
-                dl_ = torch.empty(n_rows_rec * 16, dtype=torch.float32, device=dev)
-                gf_ = torch.empty(n_rows_rec * (16 if cfg['mode'] == hip.SEG_TRIPLET else 48), dtype=torch.float32, device=dev)
+                n_rec = plan.record_segments * plan.record_rows
+                dl_ = torch.empty(n_rec * 16, dtype=torch.float32, device=dev)
+                gf_ = torch.empty(n_rec * plan.gfeat_floats, dtype=torch.float32, device=dev)
                 g.dlogit, g.gfeat_v = dl_.data_ptr(), gf_.data_ptr()
                 keep += [dl_, gf_]
         s = SegCoreFn._struct(cfg, t)
+        g.rowbuf = g.gU                 # (a stand-in while the form is asked for: the resolver tests it for NULL only)
+        form = hip.seg_form(cfg['topo'], s, g)
+        if form.family != plan.bwd_family:
+            raise RuntimeError(f"SegCoreFn: the adjoint of mode {cfg['mode']} was planned as {hip.FORM_NAMES[plan.bwd_family]}, "
+                               f"the library runs {hip.form_name(form)}")
+        g.rowbuf = None
+        if form.rowbuf_waves:
+            rowbuf = torch.empty(plan.grid * form.rowbuf_waves * plan.record_rows * 48, dtype=torch.float32, device=dev)
+            g.rowbuf = rowbuf.data_ptr()
+            keep.append(rowbuf)
+        if form_log is not None:
+            form_log.append(('adjoint', cfg['mode'], hip.form_name(form)))
         if bwd_timers is not None:       # measurement (tools/bench_train.py): HIP events around the adjoint launch, on its stream
             ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             ev[0].record()
@@ -504,7 +491,41 @@ class SegCoreFn(torch.autograd.Function):
         return (None, gYdst, gYsrc, gU, gx, gnrm, gew, gWf_k, gWf_v, gbk, gbv, gW2, gb2)
 
 
+def _seg_plan(cfg, pos):
+    """The one decision per SegCoreFn.apply, from `cfg` and `options`: the per-row record the forward leaves (floats per row, rows per
+    segment, segments), whether S / swn and the two-pass scratch go with it, the adjoint's tri_form, grid and the kernel family it is planned
+    to run in.  `forward` stores it on ctx and `backward` reads it -- no second look at `options` -- and each holds the library's own answer
+    (pg_seg_attn_form / pg_seg_attn_bwd_form) against it.  The limits are the header's (hip.PG_SEG_*)."""
+    mode, max_rows, n_seg = cfg['mode'], cfg['max_rows'], cfg['n_seg']
+    tri, onepass = mode == hip.SEG_TRIPLET, options.get('tri_onepass')
+    # the channel-split adjoint (csrc/triplet_bwd2.hip) recomputes the softmax weights and reads nothing of the forward back
+    tri_form = int(options.get('tri_bwd_form')) if tri and max_rows <= hip.PG_SEG_BWD_TRI_MAX_ATOMS else 0
+    if mode in (hip.SEG_KNN_NODE, hip.SEG_KNN_POS):
+        record = onepass and cfg['k'] <= hip.PG_SEG_KNN_MAX_K
+    elif mode in (hip.SEG_BOND_NODE, hip.SEG_BOND_POS):
+        record = onepass and max_rows <= hip.PG_SEG_NODE_MAX_TILES * hip.PG_SEG_ROW_TILE
+    elif mode == hip.SEG_PHORE:        # the generic kernel leaves the encoder's softmax weights the same way
+        record = onepass and options.get('ph_onepass') and 0 < max_rows <= hip.PG_SEG_PHORE_RECORD_ROWS
+    else:                              # the staged kernel's training form (it holds one atom more)
+        record = cfg.get('tri_fwd') is not None and onepass and max_rows <= hip.PG_SEG_TRI_STAGED_ROWS and not tri_form
+    # the node kernels hand alpha x gate to a one-pass adjoint (node update), or the logits and value scalars of every row to the
+    # adjoint's softmax step (position update: 32 floats per row)
+    split_modes = {'knn': (hip.SEG_KNN_NODE, hip.SEG_KNN_POS), 'all': (hip.SEG_TRIPLET, hip.SEG_KNN_NODE, hip.SEG_KNN_POS)}
+    # (the pharmacophore encoder's adjoint stays one pass: as a value pass + a key pass it measured 0.4 ms per step slower)
+    two_pass = bool(record) and mode in split_modes.get(options.get('bwd_split'), ()) and (not tri or max_rows <= hip.PG_SEG_BWD_TRI_MAX_ATOMS)
+    # one persistent workgroup per CU (the adjoints hold a CU's LDS / registers alone): every workgroup stages its weight tables and
+    # flushes its weight-gradient accumulators (hundreds of atomics per wave) ONCE, and no partial last round of workgroups is
+    # left -- training step 179.5 ms with 1 024 workgroups, 171-173 with 512, 168 with 256 (320: 205, 8 192: 206)
+    grid = min(n_seg, options.get('tri_bwd_grid')) if tri_form else min((n_seg + 3) // 4, options.get('bwd_grid'))   # (the forms' smallest workgroup has 4 waves)
+    return SimpleNamespace(
+        record_floats=(32 if pos else 16) if record else 0, record_rows=(max_rows + 15) // 16 * 16,
+        record_segments=n_seg if tri else cfg['n_out_rows'], two_pass=two_pass, gfeat_floats=16 if tri else 48,
+        tri_form=tri_form, grid=max(1, grid), atom_sort=bool(tri and cfg.get('plan') is not None and options.get('bwd_atom_sort')),
+        bwd_family=hip.FORM_BWD_CHANNEL_SPLIT if tri_form else hip.FORM_BWD_TWO_PASS if two_pass else hip.FORM_BWD_ONE_WAVE)
+
+
 bwd_timers = None       # dict mode -> [(start, end) events] when a benchmark wants the adjoint launches timed
+form_log = None         # a list when a test wants every forward and adjoint launch of SegCoreFn as (direction, mode, form name)
 lib_timers = None       # list of (start, end) events around every LIBRARY GEMM of the step (the input gradients, `_dgrad`): the one place
                         # where the training path leaves the in-tree kernels -- benchmarks report it as `library_ms`
 

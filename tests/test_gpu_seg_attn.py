@@ -92,10 +92,15 @@ def _ptr(t):
     return None if t is None else t.data_ptr()
 
 
-def _call(topo_ref, p, force=0):
+def _call(topo_ref, p, force=0, runs=None):
+    """runs: (family, row tiles, threads, composite parts, floats per row of the record) the case's label promises; the library's own
+    answer (pg_seg_attn_form) is held against it before the launch."""
     hip, lib, s = _lib()
     old = lib.pg_debug_force_generic_seg(force)
     try:
+        if runs is not None:
+            f = hip.seg_form(topo_ref, p)
+            assert (hip.FORM_NAMES[f.family], f.tiles, f.threads, f.compose, f.record_floats) == runs, (hip.form_name(f), runs)
         rc = lib.pg_seg_attn(topo_ref, C.byref(p), s)
     finally:
         lib.pg_debug_force_generic_seg(old)
@@ -156,16 +161,29 @@ def _node_args(d, mode, lists, n_ctx, form, accumulate=0, alpha=False, pos_tiled
     return p, o
 
 
-def _node_form(case, plan, d, mode, lists, refs, form, force=0, **kw):
-    """One launch of one form over one or two target lists, every output against the lists' references."""
+def _node_form(case, plan, d, mode, lists, refs, form, force=0, tiles=0, tiled=0, **kw):
+    """One launch of one form over one or two target lists, every output against the lists' references.  tiles: the row-tile instance
+    of the node kernels that holds the case (0: none does, or force: the generic kernel); tiled: the tiled position form's, where
+    pos_tiled is asked for and the form holds the case.  The label says what runs, and the library is asked whether it does."""
+    from phoregen_amd import hip
     pos = mode in (sr.KNN_POS, sr.BOND_POS)
     n_ctx = plan.n_ctx
     U = torch.cat([r.U for r in refs]) if form == 'plain' else None
     p, o = _node_args(d, mode, lists, n_ctx, form, U=U, **kw)
-    rc, msg = _call(plan.topo_ref, p, force)
+    generic = bool(force & 1) or not tiles
+    record = 0 if not kw.get('alpha') or (generic and mode != sr.PHORE) else 32 if pos else 16
+    if generic:
+        runs = ('generic', 0, 256, (hip.PG_FORM_FOLD_UNFOLD if form == 'fused' else 0) | (hip.PG_FORM_TWO_LISTS if len(lists) == 2 else 0), record)
+    elif tiled:
+        runs = ('pos_tiled', tiled, 768, 0, 0)
+    elif form == 'fused':
+        runs = ('node_fused', tiles, 768, 0, record)
+    else:
+        runs = ('node_two_pass', tiles, 256, hip.PG_FORM_TWO_LISTS if len(lists) == 2 else 0, record)
+    rc, msg = _call(plan.topo_ref, p, force, runs)
     assert rc == OK, (rc, msg)
     name = f'{("knn", "knn", "bond", "bond", "triplet", "phore")[mode]} {("node", "pos")[pos]} {form}' + \
-        (' generic' if force & 1 else '') + (' tiled' if kw.get('pos_tiled') else '') + (' 2 lists' if len(lists) == 2 else '') + \
+        (' generic' if generic and mode != sr.PHORE else '') + (' tiled' if tiled and not generic else '') + (' 2 lists' if len(lists) == 2 else '') + \
         (' record' if kw.get('alpha') else '')
     ids = torch.cat([l[0] for l in lists]).long().to(DEV)
     ref = NS(**{k: torch.cat([getattr(r, k) for r in refs]) for k in vars(refs[0]) if torch.is_tensor(getattr(refs[0], k))
@@ -223,11 +241,11 @@ def test_knn_modes_against_float64(idx):
         pos = mode == sr.KNN_POS
         lists = [(c.ids, c.Wf[0])]
         refs = _node_refs(c, t, d, mode, lists)
-        run = functools.partial(_node_form, c.name, plan, d, mode, lists, refs)
+        run = functools.partial(_node_form, c.name, plan, d, mode, lists, refs, tiles=2 if two_pass else 0)
         run('plain', **(dict(accumulate=1) if pos else {}))
         run('fused')
         if pos:
-            run('fused', pos_tiled=1, accumulate=1)
+            run('fused', pos_tiled=1, accumulate=1, tiled=2 if two_pass else 0)
         if c.name != 'rounds2':
             run('plain', force=1)
             run('fused', force=1, **(dict(accumulate=1) if pos else {}))
@@ -238,7 +256,7 @@ def test_knn_modes_against_float64(idx):
             for split, (a, b) in c.splits.items():
                 lists2 = [(a, c.Wf[0]), (b, c.Wf[1])]
                 refs2 = _node_refs(c, t, d, mode, lists2)
-                _node_form(f'{c.name} {split}', plan, d, mode, lists2, refs2, 'fused')
+                _node_form(f'{c.name} {split}', plan, d, mode, lists2, refs2, 'fused', tiles=2 if two_pass else 0)
                 _node_form(f'{c.name} {split}', plan, d, mode, lists2, refs2, 'fused', force=1)
 
 
@@ -254,11 +272,11 @@ def test_bond_modes_against_float64(name):
         pos = mode == sr.BOND_POS
         lists = [(c.ids, (None, None))]
         refs = _node_refs(c, t, d, mode, lists)
-        run = functools.partial(_node_form, c.name, plan, d, mode, lists, refs)
+        run = functools.partial(_node_form, c.name, plan, d, mode, lists, refs, tiles=dict(t2=3, t3=3, t4=4, t5=5, generic=0)[name])
         run('plain')
         run('fused', **(dict(accumulate=1) if pos else {}))
         if pos:
-            run('fused', pos_tiled=1)
+            run('fused', pos_tiled=1, tiled=dict(t2=2, t3=3, t4=4, t5=0, generic=0)[name])
         if name in ('t2', 't4', 'generic'):
             run('plain', force=1, **(dict(accumulate=1) if pos else {}))
             run('fused', force=1)
@@ -321,8 +339,9 @@ def _tri_args(plan, d, queue=None, train=False, alpha=False, seg_ids=None, tri_g
     return p, o
 
 
-def _tri_launch(plan, p, o, force=0):
-    rc, msg = _call(plan.topo_ref, p, force)
+def _tri_launch(plan, p, o, runs, force=0):
+    """runs: (family, row tiles, threads) the launch's label promises."""
+    rc, msg = _call(plan.topo_ref, p, force, runs + (0, 16 if o.alpha is not None and runs[0] != 'generic' else 0))
     assert rc == OK, (rc, msg)
     if o.counter is not None:
         assert not bool(o.counter.any()), 'tri_counter is not zero after the launch'
@@ -366,27 +385,28 @@ def test_staged_triplet_against_float64(name):
     every = torch.arange(plan.n_bond)
     assert plan.n_tri_iters > 0
     queue = (plan.tri_iters, plan.n_tri_iters, 0, plan.tri_counter)
+    tiles = dict(t3=3, t4=4, t5=5)[name]
     for grid in (0, 3):
         p, o = _tri_args(plan, d, queue, tri_grid=grid)
-        _tri_launch(plan, p, o)
+        _tri_launch(plan, p, o, ('tri_staged', tiles, 768))
         _tri_check(f'triplet staged grid={grid}', name, o, ref, every)
     p, o = _tri_args(plan, d, queue)
-    _tri_launch(plan, p, o, force=4)
+    _tri_launch(plan, p, o, ('tri_staged', tiles, 512), force=4)
     _tri_check('triplet staged 8 waves', name, o, ref, every)
     p, o = _tri_args(plan, d, queue, train=True, alpha=True)
-    _tri_launch(plan, p, o)
+    _tri_launch(plan, p, o, ('tri_staged_train', tiles, 768))
     _tri_check('triplet staged S-form', name, o, ref, every)
     assert plan.tri_split is not None or name == 't3'
     if plan.tri_split is not None:
         small_n = plan.tri_split['small'][2]
         is_small = (ref.n_of <= small_n).cpu()
         p, o = _tri_args(plan, d, plan.tri_split['small'])
-        _tri_launch(plan, p, o)
+        _tri_launch(plan, p, o, ('tri_staged', 3, 768))                                   # (the point of the split: the 3-tile instance)
         _tri_check('triplet staged split small', name, o, ref, every[is_small])       # the other queue's segments are still NaN
         p.tri_iters, p.n_tri_iters, p.tri_max_nlig, p.tri_counter = plan.tri_split['big'][0].data_ptr(), plan.tri_split['big'][1], \
             plan.tri_split['big'][2], plan.tri_split['big'][3].data_ptr()
         o.counter = plan.tri_split['big'][3]
-        _tri_launch(plan, p, o)
+        _tri_launch(plan, p, o, ('tri_staged', tiles, 768))
         _tri_check('triplet staged split both', name, o, ref, every)
 
 
@@ -399,10 +419,10 @@ def test_generic_triplet_against_float64(name):
     g = torch.Generator().manual_seed(5)
     ids = torch.randperm(plan.n_bond, generator=g)[:plan.n_bond - 5]
     p, o = _tri_args(plan, d, None, seg_ids=ids, given_cdst=False)
-    _tri_launch(plan, p, o)
+    _tri_launch(plan, p, o, ('generic', 0, 256))
     _tri_check('triplet generic', name, o, ref, ids)
     p, o = _tri_args(plan, d, None, train=True, seg_ids=ids)
-    _tri_launch(plan, p, o)
+    _tri_launch(plan, p, o, ('generic', 0, 256))
     _tri_check('triplet generic S-form', name, o, ref, ids)
 
 

@@ -268,6 +268,33 @@ def test_gradients_on_small_and_ragged_graphs(model, tri_grid):
         assert err < GRAD_TOL, (k, err)
 
 
+def _form_log(training, step):
+    """The (direction, mode, form name) of every segment-attention launch that `step` makes."""
+    training.form_log = log = []
+    try:
+        step()
+    finally:
+        training.form_log = None
+    return log
+
+
+def _modes_a_switch_names(switch):
+    """The segment-attention modes whose kernel form a training switch changes against the defaults (tri_onepass, bwd_split='all',
+    tri_bwd_form=2, ph_onepass) on a batch whose ligands all have at most 64 atoms."""
+    modes = set()
+    if switch.get('tri_onepass') is False:            # no per-row record: the node modes and the pharmacophore encoder (the triplet's
+        modes |= {0, 1, 2, 3, 5}                      # channel-split adjoint reads none anyway)
+    if switch.get('tri_bwd_form', 2) != 2:
+        modes |= {4}
+    if switch.get('ph_onepass') is False:
+        modes |= {5}
+    # bwd_split='knn' differs from 'all' in the triplet adjoint alone, and only where tri_bwd_form leaves that to csrc/seg_attn_bwd.hip
+    # with the forward's record: under the default tri_bwd_form it selects nothing
+    if switch.get('bwd_split') == 'knn' and switch.get('tri_bwd_form', 2) == 0 and switch.get('tri_onepass', True):
+        modes |= {4}
+    return modes
+
+
 def test_two_pass_adjoints_equal_the_one_wave_form(model):
     """The triplet / knn-node adjoints as a value pass + a key pass (8-wave workgroups, PgSegAttnGrad.dlogit / gfeat_v) against the
     form with both MLP paths in one wave: the same sums in the same order per segment -- only the weight-gradient atomics and the
@@ -283,13 +310,20 @@ def test_two_pass_adjoints_equal_the_one_wave_form(model):
                  u_node=torch.rand(N, 12, generator=gen), u_edge=torch.rand(E, 6, generator=gen))
     keys = ('ligand_x', 'ligand_pos', 'ligand_batch', 'ligand_ptr', 'f_edge_index', 'f_edge_attr', 'f_edge_batch',
             'phore_x', 'phore_pos', 'phore_norm', 'phore_batch')
-    grads = {}
+    from phoregen_amd import hip, training
+    grads, logs = {}, {}
     for split in (False, True):
         with options.override(bwd_split='all' if split else 'none', tri_bwd_form=0):      # (the one-wave-per-tile triplet adjoint: its two forms)
             model.zero_grad()
-            loss, _ = model.compute_loss(TrainBatch(*[b[k] for k in keys]), draws=draws)
-            loss.backward()
+            logs[split] = _form_log(training, lambda: model.compute_loss(TrainBatch(*[b[k] for k in keys]), draws=draws)[0].backward())
         grads[split] = {k: p.grad.detach().clone() for k, p in model.named_parameters() if p.grad is not None}
+    # the two runs are the two forms: both MLP paths in one 4-wave workgroup / a value pass (the triplet's on 8 waves) and a key pass
+    for mode, one, two in ((hip.SEG_KNN_NODE, 'bwd_one_wave/256/rec16', 'bwd_two_pass/256+256/rec16'),
+                           (hip.SEG_KNN_POS, 'bwd_one_wave/256', 'bwd_two_pass/256+256/rec32'),
+                           (hip.SEG_TRIPLET, 'bwd_one_wave/256/rec16', 'bwd_two_pass/512+256/rec16')):
+        for split, name in ((False, one), (True, two)):
+            ran = {n for d, m, n in logs[split] if d == 'adjoint' and m == mode}
+            assert ran == {name}, (mode, split, ran)
     assert grads[True].keys() == grads[False].keys()
     gmax = max(float(v.norm()) for v in grads[False].values())
     for k, r in grads[False].items():
@@ -321,14 +355,23 @@ def test_every_training_switch_gives_the_default_paths_gradients(model, switch):
                  u_node=torch.rand(N, 12, generator=gen), u_edge=torch.rand(E, 6, generator=gen))
     keys = ('ligand_x', 'ligand_pos', 'ligand_batch', 'ligand_ptr', 'f_edge_index', 'f_edge_attr', 'f_edge_batch',
             'phore_x', 'phore_pos', 'phore_norm', 'phore_batch')
-    out = {}
+    from phoregen_amd import training
+    out, logs = {}, {}
+
+    def step():
+        step.loss, _ = model.compute_loss(TrainBatch(*[b[k] for k in keys]), draws=draws)
+        step.loss.backward()
     for name, kw in (('default', {}), ('variant', switch)):
         with options.override(**kw):
             model._plan = None
             model.zero_grad()
-            loss, _ = model.compute_loss(TrainBatch(*[b[k] for k in keys]), draws=draws)
-            loss.backward()
-        out[name] = (float(loss), {k: p.grad.detach().clone() for k, p in model.named_parameters() if p.grad is not None})
+            logs[name] = _form_log(training, step)
+        out[name] = (float(step.loss), {k: p.grad.detach().clone() for k, p in model.named_parameters() if p.grad is not None})
+    # the switch selected what it names, and nothing else: the launches of exactly those modes run in another form
+    by_mode = lambda log, mode: [(d, n) for d, m, n in log if m == mode]
+    assert {m for m in range(6) if by_mode(logs['variant'], m) != by_mode(logs['default'], m)} == _modes_a_switch_names(switch), \
+        (switch, sorted(set(logs['default']) ^ set(logs['variant'])))
+    assert all(by_mode(logs['default'], m) for m in range(6))
     assert abs(out['variant'][0] - out['default'][0]) <= 1e-6 * abs(out['default'][0]), (out['variant'][0], out['default'][0])
     ref, var = out['default'][1], out['variant'][1]
     assert ref.keys() == var.keys()
@@ -362,9 +405,17 @@ def test_gradients_with_a_maximum_size_ligand(model):
     loss_ref.backward()
     keys = ('ligand_x', 'ligand_pos', 'ligand_batch', 'ligand_ptr', 'f_edge_index', 'f_edge_attr', 'f_edge_batch',
             'phore_x', 'phore_pos', 'phore_norm', 'phore_batch')
+    from phoregen_amd import hip, training
     model.zero_grad()
-    loss, _ = model.compute_loss(TrainBatch(*[b[k] for k in keys]), draws=draws)
-    loss.backward()
+
+    def step():
+        step.loss, _ = model.compute_loss(TrainBatch(*[b[k] for k in keys]), draws=draws)
+        step.loss.backward()
+    log = _form_log(training, step)
+    loss = step.loss
+    # 78 atoms: the staged forward's 5-tile instance with its record, and the one-wave triplet adjoint on 2 waves that reads it
+    tri = {(d, n) for d, m, n in log if m == hip.SEG_TRIPLET}
+    assert tri == {('forward', 'tri_staged_train/t5/768/rec16'), ('adjoint', 'bwd_one_wave/128/rec16')}, tri
     assert abs(loss.item() - loss_ref.item()) <= 1e-4 * abs(loss_ref.item())
     params = dict(model.named_parameters())
     for k in probe:

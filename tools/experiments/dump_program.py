@@ -25,5 +25,5 @@ for name, prog in zip(('prog_step', 'prog_ahead'), progs):
                 g = args[0]._obj
                 extra = f'M={g.M} N={g.N} K1={g.K1} K2={g.K2} add1={"y" if g.add1 else "n"} ln={"y" if g.ln_gamma else "n"}'
             elif fn.__name__ == 'pg_seg_attn':
-                extra = f'mode={args[1]._obj.mode}'
+                extra = f'mode={args[1]._obj.mode} form={args[1]._obj.form_name}'
             print(f'{i:4d} lane {lane} {fn.__name__:28s} {extra}')
