@@ -955,6 +955,40 @@ int pg_mol_hydrogens(const float* pos, int64_t pos_fs, const int8_t* cls, const 
                      uint8_t* site_shape /*[F][n_lig]*/, float* min_contact /*[F][B]*/, int* counts /*[F][B][PG_HYD_N_COUNTS]*/,
                      int* status /*[F][B]*/, void* stream);
 
+/* Murcko scaffold of the molecules the screen decoded, written as the arrays of a screen of its own, one wave per (frame, graph).
+ * Reads the screen's outputs cls [F][n_lig] and order [F][n_bond / 2] (frames dense) with the same offsets, as pg_mol_rings does: an
+ * atom is kept if its class is 0..10, a pair row a < b is a bond if its order is 1..4 and both ends are kept.
+ * Definition: DESIGN.md 2.9 "Scaffolds".  Core: what is left after every atom with at most one remaining neighbour has been removed,
+ * again and again.  A bond of the core is a ring bond if a ring passes through it (pg_mol_rings' search), else a linker bond; an atom of the core with a
+ * ring bond is a ring atom, any other a linker atom.  With PG_SCAF_EXOCYCLIC an atom outside the core that has a bond of order exactly
+ * 2 to an atom of the core is kept as well (nothing else of it).  With PG_SCAF_GENERIC every scaffold atom gets carbon's class and
+ * every scaffold bond order 1, after the selection.
+ *   part [F][n_lig]: PG_SCAF_PART_* of the atom
+ *   counts [F][B][PG_SCAF_N_COUNTS]: 0 scaffold atoms, 1 scaffold bonds, 2 ring atoms, 3 linker atoms, 4 exocyclic atoms, 5 side-chain
+ *     atoms, 6 ring systems = components of the ring atoms under ring bonds, 7 linker bonds
+ *   s_cls, s_compact, s_valence2, s_comp [F][n_lig], s_order [F][n_bond / 2], s_counts [F][B][4], s_status [F][B]: the scaffold as
+ *     pg_mol_screen would write it had it decoded the scaffold alone: class (or carbon's) of a scaffold atom, else -1; index among the
+ *     graph's scaffold atoms, else -1; twice the valence over scaffold bonds (aromatic 3), saturating at 255; smallest local index of
+ *     the atom's scaffold component, else -1; order (or 1) of a bond between two scaffold atoms, else 0; scaffold atoms, bonds,
+ *     components, atoms of the largest component; PG_MOL_NO_ATOMS (no scaffold atom) and PG_MOL_DISCONNECTED only: no valence rule.
+ * The outputs must not overlap the inputs.  Integer work only: results are exact and a graph's rows do not depend on its batch or on
+ * the numbering of its atoms (part, s_cls, s_valence2 move with the atoms).  max_n above PG_MOL_MAX_ATOMS, a negative size or flags
+ * outside 0..3: error before anything is launched, outputs untouched.  Every element of every output is written (nothing needs
+ * zeroing). */
+#define PG_SCAF_EXOCYCLIC 1          /* flags: keep atoms double-bonded to the core                            */
+#define PG_SCAF_GENERIC 2            /* flags: carbon's class and order 1 throughout the scaffold              */
+#define PG_SCAF_PART_NONE 0          /* a dropped atom                                                         */
+#define PG_SCAF_PART_SIDE_CHAIN 1
+#define PG_SCAF_PART_LINKER 2
+#define PG_SCAF_PART_RING 3
+#define PG_SCAF_PART_EXOCYCLIC 4
+#define PG_SCAF_CARBON 1             /* carbon's atom class                                                    */
+#define PG_SCAF_N_COUNTS 8
+int pg_mol_scaffold(const int8_t* cls, const int8_t* order, const int* g_lig_off /*[B+1]*/, const int* g_bond_off /*[B+1]*/, int B, int F,
+                    int n_lig, int n_bond, int max_n, int flags, uint8_t* part /*[F][n_lig]*/, int* counts /*[F][B][PG_SCAF_N_COUNTS]*/,
+                    int* s_status /*[F][B]*/, int* s_counts /*[F][B][4]*/, int8_t* s_cls, int16_t* s_compact, uint8_t* s_valence2,
+                    int16_t* s_comp, int8_t* s_order /*[F][n_bond / 2]*/, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,8 +1,8 @@
 // Ring perception of the molecules the screen decoded: smallest ring through every bond and atom, ring systems, and the counts users
 // filter on (pg_mol_rings, include/phoregen_hip.h; phoregen_amd/molecule.py; definition: DESIGN.md 2.9 "Rings").  Reads the screen's
 // outputs (cls, order), not the scores.  One wave per (frame, graph) (mol_common.h); the divergent loops below (bond rows, the search
-// of a bond's ring) hold no barrier or vote.  Integer work only, no floating point anywhere, so every output is exact.
-#include "mol_common.h"
+// of a bond's ring, ring_search.h) hold no barrier or vote.  Integer work only, no floating point anywhere, so every output is exact.
+#include "ring_search.h"
 #include "wave_prims.h"
 
 namespace pg {
@@ -13,50 +13,6 @@ static_assert(kRingMax <= 255, "a ring size fits one byte");
 struct RingLimits {
   int ring_min, ring_max, system_max, rotatable_max;
 };
-
-// Atoms of the smallest ring through the bond (a, b), 0 if the bond is a bridge: breadth-first from a over the masks with b struck
-// from a's own row (a is never expanded again, so the bond itself is never walked); the frontier at step d holds the atoms d bonds
-// from a, and the first of them that has b as a neighbour closes a ring of d + 2 atoms.  (The walk over the frontier's bits is written
-// out: it returns from inside.)
-__device__ __forceinline__ int ring_through(const MolAdjRow* adj, int a, int b) {
-  const int bw = b >> 6;
-  const unsigned long long bbit = 1ull << (b & 63);
-  unsigned long long seen[kRingCh], front[kRingCh];
-  const MolAdjRow ra = adj[a];
-  bool more = false;
-#pragma unroll
-  for (int w = 0; w < kRingCh; ++w) {
-    front[w] = ra.w[w] & ~(w == bw ? bbit : 0ull);
-    seen[w] = front[w] | (w == (a >> 6) ? 1ull << (a & 63) : 0ull);
-    more |= front[w] != 0ull;
-  }
-  for (int d = 1; more; ++d) {                                    // (d <= n - 2: every step adds an atom to `seen`)
-    unsigned long long next[kRingCh];
-#pragma unroll
-    for (int w = 0; w < kRingCh; ++w) next[w] = 0ull;
-#pragma unroll
-    for (int w = 0; w < kRingCh; ++w) {
-      unsigned long long m = front[w];
-      while (m) {
-        const int j = w * 64 + __builtin_ctzll(m);
-        m &= m - 1ull;
-        const MolAdjRow rj = adj[j];
-#pragma unroll
-        for (int v = 0; v < kRingCh; ++v) next[v] |= rj.w[v];
-        if ((bw ? next[kRingCh - 1] : next[0]) & bbit) return d + 2;
-      }
-    }
-    more = false;
-#pragma unroll
-    for (int w = 0; w < kRingCh; ++w) {
-      next[w] &= ~seen[w];
-      seen[w] |= next[w];
-      front[w] = next[w];
-      more |= next[w] != 0ull;
-    }
-  }
-  return 0;
-}
 
 __global__ __launch_bounds__(64) void mol_rings_kernel(const int8_t* __restrict__ cls_i, const int8_t* __restrict__ order_i,
                                                        const int* __restrict__ g_lig_off, const int* __restrict__ g_bond_off, int B,

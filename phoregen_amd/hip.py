@@ -116,6 +116,9 @@ PG_SUB_ATOM_BYTES, PG_SUB_ATOM_ELEMENTS, PG_SUB_ATOM_DEGREE, PG_SUB_ATOM_HCOUNT,
 PG_SUB_ANY, PG_SUB_YES, PG_SUB_NO = 0, 1, 2
 # the hydrogen placement (pg_mol_hydrogens): slots per atom, count columns and the degeneracy threshold, as the PG_HYD_* macros
 PG_HYD_MAX_PER_ATOM, PG_HYD_N_COUNTS, PG_HYD_DEG_EPS = 4, 8, 1e-3
+# the scaffold (pg_mol_scaffold): the flag bits, the values of `part`, carbon's class and the count columns, as the PG_SCAF_* macros
+PG_SCAF_EXOCYCLIC, PG_SCAF_GENERIC, PG_SCAF_CARBON, PG_SCAF_N_COUNTS = 1, 2, 1, 8
+PG_SCAF_PART_NONE, PG_SCAF_PART_SIDE_CHAIN, PG_SCAF_PART_LINKER, PG_SCAF_PART_RING, PG_SCAF_PART_EXOCYCLIC = range(5)
 _lib = None
 
 _PROTOS = {
@@ -212,6 +215,7 @@ _PROTOS = {
     'pg_mol_sub': (C.c_int, [c_ip] * 10 + [C.c_int] * 5 + [c_ip, c_ip, C.c_int, C.c_int] + [c_ip] * 5 + [C.c_void_p]),
     'pg_mol_hydrogens': (C.c_int, [c_fp, C.c_int64] + [c_ip] * 8 + [C.c_int] * 5 + [c_fp, C.c_float, C.c_int, c_fp, c_ip, c_ip, c_fp, c_ip, c_ip,
                                    C.c_void_p]),
+    'pg_mol_scaffold': (C.c_int, [c_ip] * 4 + [C.c_int] * 6 + [c_ip] * 9 + [C.c_void_p]),
 }
 
 EXPORTS = tuple(_PROTOS)

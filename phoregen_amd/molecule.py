@@ -64,7 +64,12 @@ Hydrogens: `phoregen_amd.hydrogens` gives every hydrogen `kekulize` counted its 
 "Hydrogens"): the shape of each site by an integer rule over the Kekulé orders, the directions from the unit vectors to its heavy
 neighbours, and a count of the contacts the hydrogens make.  `assemble(hydrogens=)`, `sample_valid(hydrogens=)`, `mol_block` (an
 all-atom block) and `write_sdf` carry it.  Ideal local geometry only: no force field, no rotor search; lengths and thresholds are
-design choices, not checked against RDKit / OpenBabel."""
+design choices, not checked against RDKit / OpenBabel.
+
+Scaffolds: `phoregen_amd.scaffold` writes the Murcko scaffold of every decoded molecule as a `Screen` of its own
+(csrc/mol_scaffold.hip; DESIGN.md 2.9 "Scaffolds"), so that `molecule_keys`, `fingerprints`, `kekulize`, `smiles` and
+`assemble(screen=)` work on scaffolds unchanged, and groups molecules by scaffold.  It is a module of its own: `assemble`,
+`sample_valid` and `write_sdf` do not carry it."""
 import ctypes
 from collections import namedtuple
 from dataclasses import astuple, dataclass, replace

@@ -53,7 +53,14 @@ PHOREGEN_BONDS.  --hydrogens (implies --valid_only and the Kekulé form) also gi
 (phoregen_amd.hydrogens: ideal local geometry, no force field) and finishes a molecule only if it has a Kekulé structure, finite
 coordinates and no more contacts than allowed; with --sdf the blocks are then all-atom blocks and carry the counts as the data item
 PHOREGEN_HYDROGENS; --hydrogen_options '{"clash_min": 1.2, "max_contacts": 0}' replaces single options of
-phoregen_amd.hydrogens.HydrogenOptions.  --num_steps shortens the reverse process (default: the model's).  Without them
+phoregen_amd.hydrogens.HydrogenOptions.  --scaffolds (implies --valid_only) takes the finished molecules back to the device
+(phoregen_amd.scaffold.batch_of) and writes the Murcko scaffold of each (phoregen_amd.scaffold.scaffolds: ring systems and linkers, with
+the atoms double-bonded to them; --scaffold_plain leaves those out) and its generic framework (every atom carbon, every bond single):
+<outdir>/{name}_scaffolds.txt holds one line 'index scaffold_key framework_key group scaffold_atoms ring_systems smiles' per finished
+molecule -- the keys as 16 hex digits, group = the index of the first molecule with the same scaffold (confirmed exactly), the
+scaffold's Kekulé-form SMILES or '-' without one -- and <outdir>/{name}_scaffold_summary.txt the lines 'molecules', 'distinct_scaffolds',
+'distinct_frameworks', 'without_scaffold' and 'largest_group'.  --max_per_scaffold K (implies --scaffolds) writes
+<outdir>/{name}_scaffold_picks.txt: the indices of the first K molecules of every scaffold, ascending.  --num_steps shortens the reverse process (default: the model's).  Without them
 nothing changes.
 """
 import argparse
@@ -71,12 +78,40 @@ from phoregen_amd.config import default_model_config, load_config  # noqa: E402
 from phoregen_amd.data import PHORETYPES1, parse_phore_file  # noqa: E402
 from phoregen_amd.fragment import load_fragment_json  # noqa: E402
 from phoregen_amd.models.diffusion import PhoreDiff  # noqa: E402
+from phoregen_amd import scaffold as scaffold_mod  # noqa: E402
 from phoregen_amd import similarity  # noqa: E402
 from phoregen_amd import substructure as substruct  # noqa: E402
 from phoregen_amd.hydrogens import HydrogenOptions  # noqa: E402
-from phoregen_amd.molecule import BOND_AGREE_COUNTS, FP_MAX_RADIUS, FP_RADIUS, FP_WORDS, FeatureLimits, GeomLimits, KekuleOptions, RingLimits, StereoLimits, STATUS_NONFINITE, assemble, point_kinds_of, sample_valid, write_sdf  # noqa: E402
+from phoregen_amd.molecule import BOND_AGREE_COUNTS, FP_MAX_RADIUS, FP_RADIUS, FP_WORDS, FeatureLimits, GeomLimits, KekuleOptions, RingLimits, StereoLimits, STATUS_NONFINITE, assemble, molecule_keys, point_kinds_of, sample_valid, screen, smiles, write_sdf  # noqa: E402
 from phoregen_amd.utils.sample_utils import decode_batch  # noqa: E402
 from phoregen_amd.weights import init_deterministic_  # noqa: E402
+
+
+def write_scaffold_files(outdir, name, done, exocyclic, max_per_scaffold):
+    """<name>_scaffolds.txt, <name>_scaffold_summary.txt and, with max_per_scaffold, <name>_scaffold_picks.txt for the finished
+    molecules: batch_of -> screen -> scaffolds as given and generic, keys of both, SMILES of the scaffold screen."""
+    n = len(done)
+    lines, group, sizes = [], torch.zeros(0, dtype=torch.long), torch.zeros(0, dtype=torch.long)
+    if n:
+        res = scaffold_mod.batch_of(done, 'cuda')
+        sc = screen(res)
+        sf = scaffold_mod.scaffolds(sc, scaffold_mod.ScaffoldOptions(exocyclic=exocyclic))
+        fw = scaffold_mod.scaffolds(sc, scaffold_mod.ScaffoldOptions(exocyclic=exocyclic, generic=True))
+        key, fkey = scaffold_mod.scaffold_keys(sf).key[0], molecule_keys(fw.screen).key[0]
+        text = smiles(res, screen=sf.screen)
+        group, sizes = scaffold_mod.scaffold_groups(key, assemble(res, screen=sf.screen))
+        counts, ok = sf.counts[0].tolist(), text.ok[0].tolist()
+        for i, (k, f, g, c, t) in enumerate(zip(key.tolist(), fkey.tolist(), group.tolist(), counts, text.strings())):
+            lines.append('%d %016x %016x %d %d %d %s\n' % (i, k & (1 << 64) - 1, f & (1 << 64) - 1, g, c[0], c[6], t if ok[i] and t else '-'))
+    with open(os.path.join(outdir, name + '_scaffolds.txt'), 'w') as fh:
+        fh.writelines(lines)
+    with open(os.path.join(outdir, name + '_scaffold_summary.txt'), 'w') as fh:
+        fh.write('molecules: %d\ndistinct_scaffolds: %d\ndistinct_frameworks: %d\nwithout_scaffold: %d\nlargest_group: %d\n'
+                 % (n, len(set(group.tolist())), len({ln.split()[2] for ln in lines}), sum(int(ln.split()[4]) == 0 for ln in lines),
+                    int(sizes.max()) if n else 0))
+    if max_per_scaffold is not None:
+        with open(os.path.join(outdir, name + '_scaffold_picks.txt'), 'w') as fh:
+            fh.writelines('%d\n' % i for i in scaffold_mod.pick_per_scaffold(group, max_per_scaffold).tolist())
 
 
 def main():
@@ -145,6 +180,13 @@ def main():
                     help='implies --valid_only: places the hydrogens of the Kekulé form in 3D; .sdf blocks are written as all-atom blocks')
     ap.add_argument('--hydrogen_options', type=json.loads, default=None,
                     help='JSON object replacing single options of HydrogenOptions (with --hydrogens): xh_length, clash_min, max_contacts')
+    ap.add_argument('--scaffolds', action='store_true',
+                    help='implies --valid_only: writes <outdir>/<name>_scaffolds.txt (per finished molecule its Murcko scaffold key, framework '
+                         'key, group, sizes and scaffold SMILES) and <name>_scaffold_summary.txt')
+    ap.add_argument('--scaffold_plain', action='store_true',
+                    help='with --scaffolds: the plain Bemis-Murcko framework, without the atoms double-bonded to a ring or a linker')
+    ap.add_argument('--max_per_scaffold', type=int, default=None, metavar='K',
+                    help='implies --scaffolds: writes <outdir>/<name>_scaffold_picks.txt, the first K finished molecules of every scaffold')
     ap.add_argument('--num_steps', type=int, default=None, help='reverse steps of the sampler (default: the model\'s)')
     ap.add_argument('--sdf', action='store_true', help='write one .sdf per molecule under <outdir>/sdf_results/')
     args = ap.parse_args()
@@ -175,6 +217,11 @@ def main():
         reference = np.load(args.reference_fps)
         if reference.dtype != np.uint64 or reference.ndim != 2 or reference.shape[1] != FP_WORDS:
             ap.error(f'--reference_fps must hold uint64 [m, {FP_WORDS}], not {reference.dtype} {reference.shape}')
+    args.scaffolds = args.scaffolds or args.max_per_scaffold is not None
+    if args.scaffold_plain and not args.scaffolds:
+        ap.error('--scaffold_plain needs --scaffolds')
+    if args.max_per_scaffold is not None and args.max_per_scaffold < 0:
+        ap.error('--max_per_scaffold must not be negative')
     if args.substructure_steps is not None and args.substructure is None:
         ap.error('--substructure_steps needs --substructure')
     patterns = None
@@ -183,7 +230,7 @@ def main():
         if not 1 <= steps <= substruct.MAX_STEPS:
             ap.error('--substructure_steps must be 1 .. 2**30')
         patterns = (substruct.load_patterns_json(args.substructure), steps)
-    args.valid_only = args.valid_only or args.add_edge != 'predicted' or args.bond_agreement or patterns is not None or args.fingerprints or args.unique or args.geometry or args.rings or args.kekule or args.features or args.smiles or args.stereo or args.hydrogens
+    args.valid_only = args.valid_only or args.scaffolds or args.add_edge != 'predicted' or args.bond_agreement or patterns is not None or args.fingerprints or args.unique or args.geometry or args.rings or args.kekule or args.features or args.smiles or args.stereo or args.hydrogens
     stereo_limits = StereoLimits(**(args.stereo_limits or {})) if args.stereo else None
     hydrogen_options = HydrogenOptions(**(args.hydrogen_options or {})) if args.hydrogens else None
     feature_limits = FeatureLimits(**(args.feature_limits or {})) if args.features else None
@@ -265,6 +312,8 @@ def main():
                     ref = similarity.nearest(fps, torch.from_numpy(reference.view(np.int64)).to('cuda').contiguous())
                     with open(os.path.join(args.outdir, data.name + '_nearest.txt'), 'w') as fh:
                         fh.writelines('%.6f %d\n' % (s, j) for s, j in zip(ref.sim.tolist(), ref.index.tolist()))
+            if args.scaffolds:
+                write_scaffold_files(args.outdir, data.name, done, not args.scaffold_plain, args.max_per_scaffold)
         while len(done) < args.num_samples and not args.valid_only:
             n = min(args.batch_size, args.num_samples - len(done))
             res = model.sample(data, n, 'cuda', return_traj=False, **kw)
