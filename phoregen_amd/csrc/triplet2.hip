@@ -18,6 +18,7 @@
 // spare feature column.
 // Lane l = (g = l>>4, m = l&15); 16x16x4 maps as in seg_attn.hip.
 #include "wave_prims.h"
+#include "triplet2_rows.h"
 #include "../../include/phoregen_hip.h"
 
 namespace pg {
@@ -123,6 +124,13 @@ __global__ __launch_bounds__(THREADS) void triplet2_kernel(PgTopo t, PgSegAttn p
     // and masked, is skipped in the row index instead -- ligands of 34 / 50 atoms need a row tile less, 2.7 % of the headline batch's tiles)
     const int nr = nm1 - 1;
     const int n_tiles = (nr + 15) >> 4;
+    // The segment's LAST tile (1 ... 16 rows) is the tail tile.  It lives in slot MAXT - 1 of the per-tile registers whatever the
+    // ligand's size, and its rows are transposed in the 4 x 4 grid of the MFMA layout (triplet2_rows.h): its valid rows fill whole
+    // k-steps of pass B's aggregate product, and the k-steps behind them are skipped.  The slots in front hold the full tiles, whose
+    // code has no row mask at all.  Sums run over the full tiles in order, then the tail: a segment's result depends on its
+    // ligand's size alone, not on MAXT.
+    const int tail_tile = n_tiles - 1;
+    const int tail_slices = t2_tail_slices(t2_tail_rows(nr, n_tiles));
 
     // per-segment global inputs (the Q row of Cdst, the query, the residual row) are fetched ONE SEGMENT AHEAD: their HBM
     // round trip overlaps the previous segment's arithmetic instead of opening every segment with a wait
@@ -177,8 +185,8 @@ __global__ __launch_bounds__(THREADS) void triplet2_kernel(PgTopo t, PgSegAttn p
       f4 lg[MAXT];
 
       // angle at i between j and k (uni_denoiser.py:131-135) for row m of tile g (+4 for a fifth tile): one atan2 per lane and
-      // segment instead of one per tile, the tiles then fetch theta of (tile, m) from lane 16 tile + m.  Rows past the ligand
-      // take the first row's angle (finite; such rows are masked by selects on the logits).
+      // segment instead of one per tile, the tiles then fetch theta of (tile, row) from lane 16 tile + row (the tail tile's row of
+      // tile row m: t2_tile_row).  Rows past the ligand take the first row's angle (finite; such rows are masked by selects on the logits).
       float th_own[(MAXT + 3) / 4];
 #pragma unroll
       for (int rep = 0; rep < (MAXT + 3) / 4; ++rep) {
@@ -210,14 +218,20 @@ __global__ __launch_bounds__(THREADS) void triplet2_kernel(PgTopo t, PgSegAttn p
             }
         }
 #pragma unroll
-        for (int tile = 0; tile < MAXT; ++tile) {
-          lg[tile] = (f4){NEG_BIG, NEG_BIG, NEG_BIG, NEG_BIG};
-          feat[tile][0] = feat[tile][1] = feat[tile][2] = 0.f;
-          if (tile < n_tiles) {
-            const int kp = tile * 16 + m;                                  // row = k-th atom that is neither j nor i
-            const int kq = kp < nr ? kp : 0;                               // rows past the ligand read the first row (finite, masked below)
+        for (int slot = 0; slot < MAXT; ++slot) {
+          const bool tail = slot == MAXT - 1;                              // (a constant of every unrolled copy)
+          const int tile = tail ? tail_tile : slot;
+          lg[slot] = (f4){NEG_BIG, NEG_BIG, NEG_BIG, NEG_BIG};
+          feat[slot][0] = feat[slot][1] = feat[slot][2] = 0.f;
+          if (tail ? tail_tile >= 0 : slot < tail_tile) {
+            const int mr = t2_tile_row(tail, m);
+            const int kp = tile * 16 + mr;                                 // row = k-th atom that is neither j nor i
+            const int kq = !tail || kp < nr ? kp : 0;                      // rows past the ligand read the first row (finite, masked below)
             const int kc = kq + (kq >= ip ? 1 : 0);
-            const float theta = from_lane(th_own[tile >> 2], 16 * (tile & 3) + m);
+            float th_src = th_own[0];
+#pragma unroll
+            for (int rep = 1; rep < (MAXT + 3) / 4; ++rep) th_src = (tile >> 2) == rep ? th_own[rep] : th_src;      // (scalar condition)
+            const float theta = from_lane(th_src, 16 * (tile & 3) + mr);
             // angular features of row kp for f = 4 step + g  (common.py:85); f = 11 carries the per-segment constant Q
             // the four lanes of a row share the work: lane g evaluates sin / cos of theta, theta/2, theta/3 (one range reduction
             // each; g = 3 idles), three ds_bpermutes hand round what the others need, the multiples come from
@@ -227,9 +241,9 @@ __global__ __launch_bounds__(THREADS) void triplet2_kernel(PgTopo t, PgSegAttn p
             const float s1 = from_lane(sg, m), c1 = from_lane(cg, m);
             const float sx = from_lane(sg, m + (g == 0 ? 16 : 32));      // g = 0: sin(theta/2), g = 1: sin(theta/3)
             // f = 4 st + g: [theta, sin t, sin 2t, sin 3t | sin t/2, sin t/3, cos t, cos 2t | cos 3t, cos t/2, cos t/3, 1 (Q)]
-            feat[tile][0] = g == 0 ? theta : (g == 1 ? s1 : (g == 2 ? 2.0f * s1 * c1 : s1 * fmaf(-4.0f * s1, s1, 3.0f)));
-            feat[tile][1] = g < 2 ? sx : (g == 2 ? c1 : fmaf(-2.0f * s1, s1, 1.0f));
-            feat[tile][2] = g == 0 ? c1 * fmaf(4.0f * c1, c1, -3.0f) : (g == 3 ? 1.0f : cg);
+            feat[slot][0] = g == 0 ? theta : (g == 1 ? s1 : (g == 2 ? 2.0f * s1 * c1 : s1 * fmaf(-4.0f * s1, s1, 3.0f)));
+            feat[slot][1] = g < 2 ? sx : (g == 2 ? c1 : fmaf(-2.0f * s1, s1, 1.0f));
+            feat[slot][2] = g == 0 ? c1 * fmaf(4.0f * c1, c1, -3.0f) : (g == 3 ? 1.0f : cg);
             // hidden^T[c, row] = P_k[row][c] + Q_k[c] + Wf_k . feat   (past-the-end rows are computed like any other: their logits are
             // replaced below, so no per-element selects are needed)
             f4 hid[8];
@@ -242,12 +256,12 @@ __global__ __launch_bounds__(THREADS) void triplet2_kernel(PgTopo t, PgSegAttn p
                 const f4 wa = *reinterpret_cast<const f4*>(wf_k + ((st * 2) * 64 + lane) * 4);
                 const f4 wb = *reinterpret_cast<const f4*>(wf_k + ((st * 2 + 1) * 64 + lane) * 4);
 #pragma unroll
-                for (int tq = 0; tq < 4; ++tq) hid[tq] = mfma16(wa[tq], feat[tile][st], hid[tq]);
+                for (int tq = 0; tq < 4; ++tq) hid[tq] = mfma16(wa[tq], feat[slot][st], hid[tq]);
 #pragma unroll
-                for (int tq = 0; tq < 4; ++tq) hid[4 + tq] = mfma16(wb[tq], feat[tile][st], hid[4 + tq]);
+                for (int tq = 0; tq < 4; ++tq) hid[4 + tq] = mfma16(wb[tq], feat[slot][st], hid[4 + tq]);
               }
 #pragma unroll
-            for (int tq = 0; tq < 8; ++tq) hid[tq] = mfma16(wk2[tq], feat[tile][2], hid[tq]);
+            for (int tq = 0; tq < 8; ++tq) hid[tq] = mfma16(wk2[tq], feat[slot][2], hid[tq]);
             // folded LayerNorm + ReLU (packing._kv_mlp): z = ReLU(hidden + b' * sigma); 1/sigma multiplies the 16 logits
             float q2 = 0.f;
 #pragma unroll
@@ -273,8 +287,8 @@ __global__ __launch_bounds__(THREADS) void triplet2_kernel(PgTopo t, PgSegAttn p
             for (int r = 0; r < 4; ++r) acc[r] *= __shfl(rs, 4 * g + r);     // rstd of row 4g+r lives in lane m = 4g+r
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-              const int kr = tile * 16 + 4 * g + r;
-              lg[tile][r] = kr < nr ? acc[r] : NEG_BIG;
+              const int kr = tile * 16 + t2_elem_row(tail, g, r);          // every row of a full tile exists
+              lg[slot][r] = !tail || kr < nr ? acc[r] : NEG_BIG;
             }
           }
         }
@@ -284,18 +298,18 @@ __global__ __launch_bounds__(THREADS) void triplet2_kernel(PgTopo t, PgSegAttn p
       // =============================== softmax over all rows, per head m ===============================
       float mx = NEG_BIG;
 #pragma unroll
-      for (int tile = 0; tile < MAXT; ++tile)
+      for (int slot = 0; slot < MAXT; ++slot)
 #pragma unroll
-        for (int r = 0; r < 4; ++r) mx = fmaxf(mx, lg[tile][r]);
+        for (int r = 0; r < 4; ++r) mx = fmaxf(mx, lg[slot][r]);
       mx = fmaxf(mx, __shfl_xor(mx, 16));
       mx = fmaxf(mx, __shfl_xor(mx, 32));
       float l = 0.f;
 #pragma unroll
-      for (int tile = 0; tile < MAXT; ++tile)
+      for (int slot = 0; slot < MAXT; ++slot)
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-          const float e = lg[tile][r] > 0.5f * NEG_BIG ? __builtin_amdgcn_exp2f(lg[tile][r] - mx) : 0.f;
-          lg[tile][r] = e;
+          const float e = lg[slot][r] > 0.5f * NEG_BIG ? __builtin_amdgcn_exp2f(lg[slot][r] - mx) : 0.f;
+          lg[slot][r] = e;
           l += e;
         }
       l += __shfl_xor(l, 16);
@@ -306,13 +320,18 @@ __global__ __launch_bounds__(THREADS) void triplet2_kernel(PgTopo t, PgSegAttn p
         if (p.alpha) {
           float* const ap = p.alpha + (size_t)seg * p.alpha_rows * 16 + m;
 #pragma unroll
-          for (int tile = 0; tile < MAXT; ++tile)
+          for (int slot = 0; slot < MAXT; ++slot) {
+            const bool tail = slot == MAXT - 1;
+            const int tile = tail ? tail_tile : slot;
+            if (tail ? tail_tile >= 0 : slot < tail_tile) {
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const int kr = tile * 16 + 4 * g + r;                 // row among the atoms that are neither j nor i -> its atom
-              const int kc = kr + (kr >= ip ? 1 : 0);
-              if (kr < nr) ap[(kc + (kc >= j ? 1 : 0)) * 16] = lg[tile][r] * inv;
+              for (int r = 0; r < 4; ++r) {
+                const int kr = tile * 16 + t2_elem_row(tail, g, r);   // row among the atoms that are neither j nor i -> its atom
+                const int kc = kr + (kr >= ip ? 1 : 0);
+                if (!tail || kr < nr) ap[(kc + (kc >= j ? 1 : 0)) * 16] = lg[slot][r] * inv;
+              }
             }
+          }
           if (g == 0) { ap[j * 16] = 0.f; ap[i * 16] = 0.f; }      // the rows this kernel never visits: the source atom and the target
         }
       }
@@ -322,16 +341,26 @@ __global__ __launch_bounds__(THREADS) void triplet2_kernel(PgTopo t, PgSegAttn p
 #pragma unroll
       for (int tq = 0; tq < 8; ++tq) sT[tq] = (f4){0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-      for (int tile = 0; tile < MAXT; ++tile) {
-        if (tile < n_tiles) {
+      for (int slot = 0; slot < MAXT; ++slot) {
+        const bool tail = slot == MAXT - 1;
+        const int tile = tail ? tail_tile : slot;
+        if (tail ? tail_tile >= 0 : slot < tail_tile) {
+          // element r of every lane is k-step r of the aggregate product.  Full tile: all four hold rows.  Tail tile: the first
+          // tail_slices do (rows 4 r ... 4 r + 3 of the tile), the others hold no row -- their reads, LayerNorm, activation and
+          // MFMAs are skipped on a scalar condition, and their elements of hv stay what the feature products leave in them
           f4 hv[8];
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
-            const int kr = tile * 16 + 4 * g + r;
-            const int kq = kr < nr ? kr : 0;
-            const float* pv = prow + (kq + (kq >= ip ? 1 : 0)) * T2_ROW + 128 + m;     // past-the-end rows carry alpha = 0 below
+            if (!tail || r < tail_slices) {
+              const int kr = tile * 16 + t2_elem_row(tail, g, r);
+              const int kq = !tail || kr < nr ? kr : 0;
+              const float* pv = prow + (kq + (kq >= ip ? 1 : 0)) * T2_ROW + 128 + m;     // past-the-end rows carry alpha = 0 below
 #pragma unroll
-            for (int tq = 0; tq < 8; ++tq) hv[tq][r] = pv[16 * tq];
+              for (int tq = 0; tq < 8; ++tq) hv[tq][r] = pv[16 * tq];
+            } else {
+#pragma unroll
+              for (int tq = 0; tq < 8; ++tq) hv[tq][r] = 0.f;
+            }
           }
 #pragma unroll
           for (int st = 0; st < 2; ++st)
@@ -339,34 +368,55 @@ __global__ __launch_bounds__(THREADS) void triplet2_kernel(PgTopo t, PgSegAttn p
               const f4 wa = *reinterpret_cast<const f4*>(wf_v + ((st * 2) * 64 + lane) * 4);
               const f4 wb = *reinterpret_cast<const f4*>(wf_v + ((st * 2 + 1) * 64 + lane) * 4);
 #pragma unroll
-              for (int tq = 0; tq < 4; ++tq) hv[tq] = mfma16(feat[tile][st], wa[tq], hv[tq]);
+              for (int tq = 0; tq < 4; ++tq) hv[tq] = mfma16(feat[slot][st], wa[tq], hv[tq]);
 #pragma unroll
-              for (int tq = 0; tq < 4; ++tq) hv[4 + tq] = mfma16(feat[tile][st], wb[tq], hv[4 + tq]);
+              for (int tq = 0; tq < 4; ++tq) hv[4 + tq] = mfma16(feat[slot][st], wb[tq], hv[4 + tq]);
             }
 #pragma unroll
-          for (int tq = 0; tq < 8; ++tq) hv[tq] = mfma16(feat[tile][2], wv2[tq], hv[tq]);
+          for (int tq = 0; tq < 8; ++tq) hv[tq] = mfma16(feat[slot][2], wv2[tq], hv[tq]);
           // folded LayerNorm + ReLU per row r over c = (tau in-lane, m across the DPP row)
-          f4 q2 = {0.f, 0.f, 0.f, 0.f};
+          if (!tail) {
+            f4 q2 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-          for (int tq = 0; tq < 8; ++tq) q2 += hv[tq] * hv[tq];
-          f4 sg, aw;
+            for (int tq = 0; tq < 8; ++tq) q2 += hv[tq] * hv[tq];
+            f4 sg, aw;
 #pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const float var = row16_total(q2[r]) * (1.f / 128.f) + 1e-5f;
-            const float rsq = __builtin_amdgcn_rsqf(var);
-            sg[r] = var * rsq;
-            aw[r] = lg[tile][r] * rsq;                                      // alpha * rstd of the row
+            for (int r = 0; r < 4; ++r) {
+              const float var = row16_total(q2[r]) * (1.f / 128.f) + 1e-5f;
+              const float rsq = __builtin_amdgcn_rsqf(var);
+              sg[r] = var * rsq;
+              aw[r] = lg[slot][r] * rsq;                                      // alpha * rstd of the row
+            }
+#pragma unroll
+            for (int tq = 0; tq < 8; ++tq) {
+              const float bt = bv[m * 8 + tq];
+#pragma unroll
+              for (int r = 0; r < 4; ++r) hv[tq][r] = T2_DEGRADE(fmaxf(fmaf(bt, sg[r], hv[tq][r]), 0.f));
+            }
+#pragma unroll
+            for (int r = 0; r < 4; ++r)            // r outer: 8 independent accumulator chains
+#pragma unroll
+              for (int tq = 0; tq < 8; ++tq) sT[tq] = mfma16(hv[tq][r], aw[r], sT[tq]);
+          } else {
+            // the same arithmetic per row (a row's statistics do not depend on where it sits), one k-step at a time
+            float bt[8];
+#pragma unroll
+            for (int tq = 0; tq < 8; ++tq) bt[tq] = bv[m * 8 + tq];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+              if (r < tail_slices) {
+                float q2 = 0.f;
+#pragma unroll
+                for (int tq = 0; tq < 8; ++tq) q2 = fmaf(hv[tq][r], hv[tq][r], q2);
+                const float var = row16_total(q2) * (1.f / 128.f) + 1e-5f;
+                const float rsq = __builtin_amdgcn_rsqf(var);
+                const float sg = var * rsq;
+                const float aw = lg[slot][r] * rsq;
+#pragma unroll
+                for (int tq = 0; tq < 8; ++tq) sT[tq] = mfma16(T2_DEGRADE(fmaxf(fmaf(bt[tq], sg, hv[tq][r]), 0.f)), aw, sT[tq]);
+              }
+            }
           }
-#pragma unroll
-          for (int tq = 0; tq < 8; ++tq) {
-            const float bt = bv[m * 8 + tq];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) hv[tq][r] = T2_DEGRADE(fmaxf(fmaf(bt, sg[r], hv[tq][r]), 0.f));
-          }
-#pragma unroll
-          for (int r = 0; r < 4; ++r)            // r outer: 8 independent accumulator chains
-#pragma unroll
-            for (int tq = 0; tq < 8; ++tq) sT[tq] = mfma16(hv[tq][r], aw[r], sT[tq]);
         }
       }
 
