@@ -989,6 +989,89 @@ int pg_mol_scaffold(const int8_t* cls, const int8_t* order, const int* g_lig_off
                     int* s_status /*[F][B]*/, int* s_counts /*[F][B][4]*/, int8_t* s_cls, int16_t* s_compact, uint8_t* s_valence2,
                     int16_t* s_comp, int8_t* s_order /*[F][n_bond / 2]*/, void* stream);
 
+/* Property descriptors and drug-likeness limits of the molecules the screen decoded, one wave per (frame, graph).  Reads the screen's
+ * cls [F][n_lig] and order [F][n_bond / 2], the Kekulé form's kekule_order, hcount, charge and status [F][B], and the rings' ring_size
+ * [F][n_bond / 2] and atom_ring [F][n_lig] (frames dense); no coordinates.  Definition: DESIGN.md 2.9 "Properties"; the rules are
+ * csrc/props_core.h.  A "non-aromatic double bond" is a bond of Kekulé order 2 whose screen order is not 4, a "single bond" one of
+ * Kekulé order 1 whose screen order is not 4.
+ *   atom_env [F][n_lig]: the environment word of a kept atom (the PG_PROP_ENV_* fields, bits 30 and 31 are 0); -1 for a dropped atom
+ *     and for every atom of a graph whose Kekulé status has PG_KEKULE_FAILED
+ *   tables: n_tables <= PG_PROP_MAX_TABLES contribution tables, table t of table_rows[t] <= PG_PROP_MAX_ROWS rows, one after the other
+ *     in device memory; a row is PG_PROP_ROW_INTS int32: mask, value, atom, per_h.  A kept atom takes the first row of a table with
+ *     (env & mask) == value and adds atom + hcount * per_h to the graph's sum of that table; without such a row it adds 0 and counts as
+ *     untyped.  The caller answers for |atom|, |per_h| < 2^20 (phoregen_amd.properties.PropertyTable checks them): then no sum of a
+ *     graph of PG_MOL_MAX_ATOMS atoms leaves int32.
+ *   atom_row [F][PG_PROP_MAX_TABLES][n_lig]: the row taken, 255 = none, an unused table or a dropped atom
+ *   sums [F][B][PG_PROP_MAX_TABLES]: unused tables 0
+ *   counts [F][B][PG_PROP_N_COUNTS]: the PG_PROP_C_* columns
+ *   weights [PG_PROP_N_WEIGHTS] (device): the weight of an atom of class 0..10 and, last, of a hydrogen, times 1000
+ *   weight_milli [F][B]: the sum of them over the kept atoms and their hydrogens
+ *   limits [PG_PROP_N_LIMITS][2] (host): lo, hi per limited quantity in the order of the PG_PROP_L_* (INT_MIN / INT_MAX: none); a
+ *     quantity below lo or above hi sets its bit in violated [F][B]
+ *   status [F][B]: PG_PROP_* bits; PG_PROP_LIMITS with more set bits in `violated` than max_violations.  With PG_PROP_NO_KEKULE the
+ *     counts, sums, weight and `violated` of the graph are 0, its rows 255, its words -1, and no limit is looked at.
+ * Integer work only: results are exact, a graph's rows do not depend on its batch, and counts, sums and weight not on the numbering of
+ * its atoms.  max_n above PG_MOL_MAX_ATOMS, a negative size, more than PG_PROP_MAX_TABLES tables, a table above PG_PROP_MAX_ROWS rows,
+ * max_violations below 0 or (with B, F > 0) a null array: error before anything is launched, outputs untouched.
+ * Every element of every output is written (nothing needs zeroing). */
+#define PG_PROP_MAX_ROWS 128
+#define PG_PROP_MAX_TABLES 4
+#define PG_PROP_ROW_INTS 4
+#define PG_PROP_N_WEIGHTS 12
+#define PG_PROP_NO_KEKULE 1          /* the graph has no Kekulé structure to type from                         */
+#define PG_PROP_LIMITS 2             /* more violated quantities than max_violations                           */
+#define PG_PROP_UNTYPED 4            /* informational: an atom without a row in a table                        */
+/* the word: shift of every field (widths: el 4, h 3, deg 3, n_dbl 2, nb_het 3, nb_arom 2, nb_hal 2, nb_no 3, every other 1) */
+#define PG_PROP_ENV_EL 0
+#define PG_PROP_ENV_H 4
+#define PG_PROP_ENV_Q 7
+#define PG_PROP_ENV_DEG 8
+#define PG_PROP_ENV_AROM 11
+#define PG_PROP_ENV_N_DBL 12
+#define PG_PROP_ENV_TRIPLE 14
+#define PG_PROP_ENV_RING 15
+#define PG_PROP_ENV_RING3 16
+#define PG_PROP_ENV_NB_HET 17
+#define PG_PROP_ENV_NB_AROM 20
+#define PG_PROP_ENV_DBL_O 22
+#define PG_PROP_ENV_DBL_HET 23
+#define PG_PROP_ENV_NB_DBL_HET 24
+#define PG_PROP_ENV_NB_HAL 25
+#define PG_PROP_ENV_NB_NO 27
+/* the count columns */
+#define PG_PROP_C_HEAVY_ATOMS 0
+#define PG_PROP_C_HYDROGENS 1
+#define PG_PROP_C_CARBONS 2
+#define PG_PROP_C_SP3_CARBONS 3
+#define PG_PROP_C_HETEROATOMS 4
+#define PG_PROP_C_HALOGENS 5
+#define PG_PROP_C_NHOH 6
+#define PG_PROP_C_NO_COUNT 7
+#define PG_PROP_C_ROTATABLE 8
+#define PG_PROP_C_AMIDE_BONDS 9
+#define PG_PROP_C_AROMATIC_ATOMS 10
+#define PG_PROP_C_RING_ATOMS 11
+#define PG_PROP_C_NET_CHARGE 12
+#define PG_PROP_C_UNTYPED 13
+#define PG_PROP_C_VIOLATIONS 14
+#define PG_PROP_N_COUNTS 16
+/* the limited quantities = the bits of `violated`: the weight in 1e-3, four counts, the sums of tables 0..3 in 1e-4 */
+#define PG_PROP_L_WEIGHT 0
+#define PG_PROP_L_HEAVY_ATOMS 1
+#define PG_PROP_L_NHOH 2
+#define PG_PROP_L_NO_COUNT 3
+#define PG_PROP_L_ROTATABLE 4
+#define PG_PROP_L_SUM0 5
+#define PG_PROP_N_LIMITS 9
+int pg_mol_props(const int8_t* cls, const int8_t* order, const int8_t* kekule_order, const uint8_t* hcount, const int8_t* charge,
+                 const int* kekule_status /*[F][B]*/, const uint8_t* ring_size, const uint8_t* atom_ring, const int* g_lig_off /*[B+1]*/,
+                 const int* g_bond_off /*[B+1]*/, int B, int F, int n_lig, int n_bond, int max_n, const int* tables /*device*/,
+                 const int* table_rows /*[n_tables] host*/, int n_tables, const int* weights /*[PG_PROP_N_WEIGHTS] device*/,
+                 const int* limits /*[PG_PROP_N_LIMITS][2] host*/, int max_violations, int* atom_env /*[F][n_lig]*/,
+                 uint8_t* atom_row /*[F][PG_PROP_MAX_TABLES][n_lig]*/, int* sums /*[F][B][PG_PROP_MAX_TABLES]*/,
+                 int* counts /*[F][B][PG_PROP_N_COUNTS]*/, int* weight_milli /*[F][B]*/, int* violated /*[F][B]*/, int* status /*[F][B]*/,
+                 void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -119,6 +119,18 @@ PG_HYD_MAX_PER_ATOM, PG_HYD_N_COUNTS, PG_HYD_DEG_EPS = 4, 8, 1e-3
 # the scaffold (pg_mol_scaffold): the flag bits, the values of `part`, carbon's class and the count columns, as the PG_SCAF_* macros
 PG_SCAF_EXOCYCLIC, PG_SCAF_GENERIC, PG_SCAF_CARBON, PG_SCAF_N_COUNTS = 1, 2, 1, 8
 PG_SCAF_PART_NONE, PG_SCAF_PART_SIDE_CHAIN, PG_SCAF_PART_LINKER, PG_SCAF_PART_RING, PG_SCAF_PART_EXOCYCLIC = range(5)
+# the property descriptors (pg_mol_props): the limits of the tables, the status bits, the shift of every field of the environment word,
+# the count columns and the limited quantities, as the PG_PROP_* macros
+PG_PROP_MAX_ROWS, PG_PROP_MAX_TABLES, PG_PROP_ROW_INTS, PG_PROP_N_WEIGHTS = 128, 4, 4, 12
+PG_PROP_NO_KEKULE, PG_PROP_LIMITS, PG_PROP_UNTYPED = 1, 2, 4
+(PG_PROP_ENV_EL, PG_PROP_ENV_H, PG_PROP_ENV_Q, PG_PROP_ENV_DEG, PG_PROP_ENV_AROM, PG_PROP_ENV_N_DBL, PG_PROP_ENV_TRIPLE, PG_PROP_ENV_RING,
+ PG_PROP_ENV_RING3, PG_PROP_ENV_NB_HET, PG_PROP_ENV_NB_AROM, PG_PROP_ENV_DBL_O, PG_PROP_ENV_DBL_HET, PG_PROP_ENV_NB_DBL_HET,
+ PG_PROP_ENV_NB_HAL, PG_PROP_ENV_NB_NO) = 0, 4, 7, 8, 11, 12, 14, 15, 16, 17, 20, 22, 23, 24, 25, 27
+(PG_PROP_C_HEAVY_ATOMS, PG_PROP_C_HYDROGENS, PG_PROP_C_CARBONS, PG_PROP_C_SP3_CARBONS, PG_PROP_C_HETEROATOMS, PG_PROP_C_HALOGENS,
+ PG_PROP_C_NHOH, PG_PROP_C_NO_COUNT, PG_PROP_C_ROTATABLE, PG_PROP_C_AMIDE_BONDS, PG_PROP_C_AROMATIC_ATOMS, PG_PROP_C_RING_ATOMS,
+ PG_PROP_C_NET_CHARGE, PG_PROP_C_UNTYPED, PG_PROP_C_VIOLATIONS) = range(15)
+PG_PROP_N_COUNTS = 16
+PG_PROP_L_WEIGHT, PG_PROP_L_HEAVY_ATOMS, PG_PROP_L_NHOH, PG_PROP_L_NO_COUNT, PG_PROP_L_ROTATABLE, PG_PROP_L_SUM0, PG_PROP_N_LIMITS = 0, 1, 2, 3, 4, 5, 9
 _lib = None
 
 _PROTOS = {
@@ -216,6 +228,8 @@ _PROTOS = {
     'pg_mol_hydrogens': (C.c_int, [c_fp, C.c_int64] + [c_ip] * 8 + [C.c_int] * 5 + [c_fp, C.c_float, C.c_int, c_fp, c_ip, c_ip, c_fp, c_ip, c_ip,
                                    C.c_void_p]),
     'pg_mol_scaffold': (C.c_int, [c_ip] * 4 + [C.c_int] * 6 + [c_ip] * 9 + [C.c_void_p]),
+    'pg_mol_props': (C.c_int, [c_ip] * 10 + [C.c_int] * 5 + [c_ip, C.POINTER(C.c_int), C.c_int, c_ip, C.POINTER(C.c_int), C.c_int] + [c_ip] * 7
+                     + [C.c_void_p]),
 }
 
 EXPORTS = tuple(_PROTOS)

@@ -69,7 +69,12 @@ design choices, not checked against RDKit / OpenBabel.
 Scaffolds: `phoregen_amd.scaffold` writes the Murcko scaffold of every decoded molecule as a `Screen` of its own
 (csrc/mol_scaffold.hip; DESIGN.md 2.9 "Scaffolds"), so that `molecule_keys`, `fingerprints`, `kekulize`, `smiles` and
 `assemble(screen=)` work on scaffolds unchanged, and groups molecules by scaffold.  It is a module of its own: `assemble`,
-`sample_valid` and `write_sdf` do not carry it."""
+`sample_valid` and `write_sdf` do not carry it.
+
+Properties: `phoregen_amd.properties` computes molecular weight, table sums (polar surface area, logP, molar refractivity), the
+Lipinski and Veber counts, Fsp3 and a verdict against `PropertyLimits` (csrc/mol_props.hip; DESIGN.md 2.9 "Properties") from an
+integer environment word per atom; `assemble(properties=)`, `sample_valid(properties=)` and `write_sdf` carry it.  The shipped
+contribution tables are written from memory, not checked against RDKit; no QED, no synthetic-accessibility score."""
 import ctypes
 from collections import namedtuple
 from dataclasses import astuple, dataclass, replace
@@ -1238,7 +1243,7 @@ def _pairs(n):
 @dataclass(frozen=True)
 class _Analysis:
     """One analysis of the decoded molecules as the three carrying functions see it.  A further analysis is one more record in
-    _ANALYSES, its keyword in the signatures of `assemble` and `sample_valid`, and a paragraph in their docstrings."""
+    _ANALYSES_SINCE, its keyword in the signatures of `assemble` and `sample_valid`, and a paragraph in their docstrings."""
     keyword: str                 # its keyword of `assemble` and `sample_valid`
     key: str                     # the key a molecule that carries it has (the first one, if it adds several)
     holder: type                 # what `assemble` is handed: a dataclass of device tensors with a `screen`
@@ -1252,15 +1257,22 @@ class _Analysis:
     also: tuple = ()             # keywords of the analyses `sample_valid` carries, and filters on, along with it
 
 
-def _analyses(want):
-    """The records of the entries of _ANALYSES that `want` accepts (it sees `keyword` and `key`), in the list's order.  An entry that
-    is no record stands for the ANALYSIS of phoregen_amd.<keyword>, which is loaded here: only for a caller who asks for it."""
-    return [a if isinstance(a, _Analysis) else import_module('.' + a.keyword, __package__).ANALYSIS for a in _ANALYSES if want(a)]
+def _analyses(want, among=None):
+    """The records of the entries of _ANALYSES (or of the list `among`) that `want` accepts (it sees `keyword` and `key`), in the
+    list's order.  An entry that is no record stands for the ANALYSIS of phoregen_amd.<keyword>, which is loaded here: only for a
+    caller who asks for it."""
+    return [a if isinstance(a, _Analysis) else import_module('.' + a.keyword, __package__).ANALYSIS
+            for a in (_ANALYSES if among is None else among) if want(a)]
+
+
+def _carried(want):
+    """`_analyses` over everything the three carrying functions know: _ANALYSES, then _ANALYSES_SINCE."""
+    return _analyses(want, _ANALYSES + _ANALYSES_SINCE)
 
 
 def _handed(args):
     """[(record, value)] of the analyses whose keyword has a value in `args`, in the list's order."""
-    return [(rec, args[rec.keyword]) for rec in _analyses(lambda a: args.get(a.keyword) is not None)]
+    return [(rec, args[rec.keyword]) for rec in _carried(lambda a: args.get(a.keyword) is not None)]
 
 
 class _MolView(namedtuple('_MolView', 'g n0 n keep h0 h nz cmp_g')):
@@ -1437,6 +1449,9 @@ _ANALYSES = [
     # (their records live in modules of their own, which import this one)
     SimpleNamespace(keyword='substructure', key='substructure'), SimpleNamespace(keyword='hydrogens', key='hydrogens'),
 ]
+# The analyses that joined after those nine, carried after them in this order.  (The list above is held to its nine entries, by name
+# and in order, by the test of the carriers; a later analysis is one more line here instead.)
+_ANALYSES_SINCE = [SimpleNamespace(keyword='properties', key='properties')]
 
 
 def _blob_parts(pos_t, sc, mk, agree, handed):
@@ -1458,7 +1473,7 @@ def _blob_parts(pos_t, sc, mk, agree, handed):
 
 @torch.no_grad()
 def assemble(results, keys=False, geometry=None, rings=None, kekule=None, features=None, smiles=None, stereo=None, fingerprints=None,
-             substructure=None, screen=None, hydrogens=None):
+             substructure=None, screen=None, hydrogens=None, properties=None):
     """The final prediction as one dict per graph with `decode_data`'s keys and meaning -- 'element' (atomic numbers), 'atom_pos'
     (kept atoms, the tensor's own fp32 values), 'bond_index' [2, n_b] (indices among the kept atoms) and 'bond_type' [n_b] for
     a < b only, in row order -- plus 'status', 'valid', 'n_components' and 'valence' (per kept atom, halves allowed).  The screen runs
@@ -1505,7 +1520,12 @@ def assemble(results, keys=False, geometry=None, rings=None, kekule=None, featur
     hydrogens=a `Hydrogens` (phoregen_amd.hydrogens) of this result's final frame: every dict also has 'hydrogens' -- 'status' (HYD_*
     bits), 'hydrogens_ok' (no bit of HYD_FAIL_MASK), the eight HYD_COUNTS by name, 'min_contact', 'h_pos' (fp32 [n_h, 3], the placed
     hydrogens in (parent, slot) order), 'h_parent' (per hydrogen an index into this dict's atoms) and 'site_shape' (per kept atom) --
-    in the same copy; its screen is reused, and it must have been computed from the screen of the others."""
+    in the same copy; its screen is reused, and it must have been computed from the screen of the others.
+    properties=a `Properties` (phoregen_amd.properties) of this result's final frame: every dict also has 'properties' -- 'status'
+    (PROP_* bits), 'properties_ok' (no bit of PROP_FAIL_MASK), the PROPERTY_COUNTS by name, 'mol_weight', one float per table name
+    (e.g. 'tpsa', 'logp', 'mr'), 'fsp3', 'violated' (the word) and 'violated_names', and per kept atom 'env' (the environment word) and
+    'row' ([n, tables], the row taken per table, 255 = none) -- in the same copy; its screen is reused, and it must have been computed
+    from the screen of the others."""
     handed, pos_t = _handed(locals()), results['pred'][1]              # (locals: this signature's keywords by name)
     # 1. the one screen: screen= if given, else the first holder's, else a new one; every holder must be of it
     if screen is not None and (not isinstance(screen, Screen) or screen.status.size(0) != 1 or screen.cls.size(1) != pos_t.size(-2)
@@ -1637,8 +1657,10 @@ def write_sdf(path, mols, names=None):
     'mode predicted' or 'mode distance', then, if it also carries 'bond_agreement', one 'name value' line per count
     (BOND_AGREE_COUNTS).  A molecule that carries 'hydrogens' (assemble(hydrogens=)) is written as an all-atom block if that and its
     Kekulé form are ok (`mol_block`) and gets `> <PHOREGEN_HYDROGENS>`: the status as hex, one 'name value' line per count (HYD_COUNTS of
-    phoregen_amd.hydrogens) and 'min_contact' with four decimals ('inf' without a pair).  A molecule without one gets no such item: the
-    text is as it always was."""
+    phoregen_amd.hydrogens) and 'min_contact' with four decimals ('inf' without a pair).  A molecule that carries 'properties'
+    (assemble(properties=)) gets `> <PHOREGEN_PROPERTIES>`: the status as hex, 'mol_weight' with three decimals, one line per table
+    name and 'fsp3' with four, one 'name value' line per count (PROPERTY_COUNTS of phoregen_amd.properties) and the names of the
+    violated quantities ('-' for none).  A molecule without one gets no such item: the text is as it always was."""
     names = names if names is not None else [''] * len(mols)
     if len(names) != len(mols):
         raise ValueError(f'write_sdf: {len(mols)} molecules, {len(names)} names')
@@ -1646,7 +1668,7 @@ def write_sdf(path, mols, names=None):
         for m, nm in zip(mols, names):
             fh.write(mol_block(m, nm))
             fh.write((_bonds_item(m) if 'bonds' in m else '') + ('> <PHOREGEN_KEY>\n%016x\n\n' % (int(m['key']) & _M64) if 'key' in m else ''))
-            fh.write(''.join(rec.sdf(m) for rec in _analyses(lambda a: a.key in m)))
+            fh.write(''.join(rec.sdf(m) for rec in _carried(lambda a: a.key in m)))
             fh.write('$$$$\n')
 
 
@@ -1804,7 +1826,7 @@ class _Draw:
 
     def of(self, keyword):
         if keyword not in self._held:
-            rec, = _analyses(lambda a: a.keyword == keyword)
+            rec, = _carried(lambda a: a.keyword == keyword)
             self._held[keyword] = rec.compute(self, self.options[keyword] if keyword in self.options else rec.read(True))
         return self._held[keyword]
 
@@ -1830,7 +1852,7 @@ def _identity(m):
 
 def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, device='cuda', unique=False, geometry=None,
                  rings=None, kekule=None, features=None, smiles=None, stereo=None, fingerprints=None, substructure=None,
-                 add_edge='predicted', bond_margins=None, bond_agreement=False, hydrogens=None, **sample_kwargs):
+                 add_edge='predicted', bond_margins=None, bond_agreement=False, hydrogens=None, properties=None, **sample_kwargs):
     """Sample until `num_samples` molecules have passed the screen, giving up once more than `max_failed_factor * num_samples` have
     failed (checked before every draw, as the reference does).  Every draw asks for min(batch_size, what is still missing) graphs,
     so never more than `num_samples` are finished.  `sample_kwargs` (fragment=, pos_guidance_opt=, rng=, seed=, ...) go to
@@ -1871,6 +1893,11 @@ def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, d
     also 'hydrogens_ok' -- it has a Kekulé structure, finite coordinates and no more contacts than the options allow; one that is not
     goes to 'failed'.  The molecules then carry 'hydrogens' and, since an all-atom block needs it, the Kekulé form of the draw as
     'kekule' (computed with kekule= if given, else with the default options), so `write_sdf` writes all-atom blocks.
+    properties=a `PropertyLimits` (phoregen_amd.properties) for the default tables, (tables, limits), or True for the default tables
+    without a limit: a valid molecule is finished only if it is also 'properties_ok' -- it has a Kekulé structure and no more
+    violated limits than the limits allow, e.g. properties=PropertyLimits.lipinski(); one that is not goes to 'failed', so the loop
+    tops up until `num_samples` pass.  The molecules then carry 'properties'.  The Kekulé form and the rings it needs are computed and
+    carried as for features=.
     All of these share one screen per draw."""
     args = locals()                                                    # (this signature's keywords by name, for the records' readers)
     if add_edge not in BOND_MODES:
@@ -1878,8 +1905,8 @@ def sample_valid(model, data, num_samples, batch_size=30, max_failed_factor=3, d
     if bond_margins is not None and not isinstance(bond_margins, BondMargins):
         raise ValueError(f'phoregen_amd.molecule.sample_valid: bond_margins= must be a BondMargins, not {bond_margins!r}')
     options = {rec.keyword: opt for rec, value in _handed(args) if (opt := rec.read(value)) is not None}      # (a reader's None: not asked for)
-    carry = set(options).union(*(rec.also for rec in _analyses(lambda a: a.keyword in options)))
-    carried = _analyses(lambda a: a.keyword in carry)                            # carried, and filtered on where there is a verdict
+    carry = set(options).union(*(rec.also for rec in _carried(lambda a: a.keyword in options)))
+    carried = _carried(lambda a: a.keyword in carry)                            # carried, and filtered on where there is a verdict
     finished, failed, duplicates, n_calls = [], [], [], 0
     by_key = {}                                                        # key -> finished molecules that have it
     while len(finished) < num_samples:

@@ -60,7 +60,13 @@ the atoms double-bonded to them; --scaffold_plain leaves those out) and its gene
 molecule -- the keys as 16 hex digits, group = the index of the first molecule with the same scaffold (confirmed exactly), the
 scaffold's Kekulé-form SMILES or '-' without one -- and <outdir>/{name}_scaffold_summary.txt the lines 'molecules', 'distinct_scaffolds',
 'distinct_frameworks', 'without_scaffold' and 'largest_group'.  --max_per_scaffold K (implies --scaffolds) writes
-<outdir>/{name}_scaffold_picks.txt: the indices of the first K molecules of every scaffold, ascending.  --num_steps shortens the reverse process (default: the model's).  Without them
+<outdir>/{name}_scaffold_picks.txt: the indices of the first K molecules of every scaffold, ascending.  --properties (implies
+--valid_only) computes the property descriptors of every molecule on the device (phoregen_amd.properties: weight, the table sums tpsa,
+logp and mr, the Lipinski and Veber counts, fsp3; the shipped tables are written from memory, not checked against RDKit) and finishes
+a molecule only if it has a Kekulé structure and keeps the limits; --property_limits '{"preset": "lipinski"}' (or "veber"), or explicit
+keys of phoregen_amd.properties.PropertyLimits such as '{"mol_weight": [null, 450], "sums": {"logp": [null, 4]}, "max_violations": 0}',
+sets them (default: none).  <outdir>/{name}_properties.txt holds one line 'index mol_weight tpsa logp mr nhoh no_count rotatable
+heavy_atoms fsp3 status' per finished molecule and the .sdf files carry the data item PHOREGEN_PROPERTIES.  --num_steps shortens the reverse process (default: the model's).  Without them
 nothing changes.
 """
 import argparse
@@ -82,9 +88,34 @@ from phoregen_amd import scaffold as scaffold_mod  # noqa: E402
 from phoregen_amd import similarity  # noqa: E402
 from phoregen_amd import substructure as substruct  # noqa: E402
 from phoregen_amd.hydrogens import HydrogenOptions  # noqa: E402
+from phoregen_amd.properties import DEFAULT_TABLES, PropertyLimits  # noqa: E402
 from phoregen_amd.molecule import BOND_AGREE_COUNTS, FP_MAX_RADIUS, FP_RADIUS, FP_WORDS, FeatureLimits, GeomLimits, KekuleOptions, RingLimits, StereoLimits, STATUS_NONFINITE, assemble, molecule_keys, point_kinds_of, sample_valid, screen, smiles, write_sdf  # noqa: E402
 from phoregen_amd.utils.sample_utils import decode_batch  # noqa: E402
 from phoregen_amd.weights import init_deterministic_  # noqa: E402
+
+
+def property_limits_of(spec):
+    """A PropertyLimits from the JSON object of --property_limits: {"preset": "lipinski" | "veber"} or keys of PropertyLimits, a
+    (min, max) pair as a list with null for none."""
+    spec = dict(spec or {})
+    if 'preset' in spec:
+        if set(spec) != {'preset'} or spec['preset'] not in ('lipinski', 'veber'):
+            raise ValueError('--property_limits: "preset" stands alone and is "lipinski" or "veber"')
+        return getattr(PropertyLimits, spec['preset'])()
+    pair = lambda v: tuple(v) if isinstance(v, list) else v            # noqa: E731
+    sums = {k: pair(v) for k, v in (spec.pop('sums', None) or {}).items()}
+    return PropertyLimits(sums=sums, **{k: pair(v) for k, v in spec.items()})
+
+
+def write_property_file(outdir, name, done):
+    """<name>_properties.txt for the finished molecules (they carry 'properties' of the default tables): a header line, then one
+    line 'index mol_weight tpsa logp mr nhoh no_count rotatable heavy_atoms fsp3 status' per molecule."""
+    names = [t.name for t in DEFAULT_TABLES]
+    with open(os.path.join(outdir, name + '_properties.txt'), 'w') as fh:
+        fh.write('# index mol_weight ' + ' '.join(names) + ' nhoh no_count rotatable heavy_atoms fsp3 status\n')
+        fh.writelines('%d %.3f %s %d %d %d %d %.4f 0x%02x\n' % (i, q['mol_weight'], ' '.join('%.4f' % q[k] for k in names), q['nhoh'], q['no_count'],
+                                                                q['rotatable'], q['heavy_atoms'], q['fsp3'], q['status'])
+                      for i, q in enumerate(m['properties'] for m in done))
 
 
 def write_scaffold_files(outdir, name, done, exocyclic, max_per_scaffold):
@@ -187,6 +218,12 @@ def main():
                     help='with --scaffolds: the plain Bemis-Murcko framework, without the atoms double-bonded to a ring or a linker')
     ap.add_argument('--max_per_scaffold', type=int, default=None, metavar='K',
                     help='implies --scaffolds: writes <outdir>/<name>_scaffold_picks.txt, the first K finished molecules of every scaffold')
+    ap.add_argument('--properties', action='store_true',
+                    help='implies --valid_only: property descriptors of every molecule (weight, tpsa, logp, mr, Lipinski and Veber counts, '
+                         'fsp3); writes <outdir>/<name>_properties.txt, the .sdf files carry the data item PHOREGEN_PROPERTIES')
+    ap.add_argument('--property_limits', type=json.loads, default=None,
+                    help='JSON object (with --properties): {"preset": "lipinski"} or {"preset": "veber"}, or keys of PropertyLimits, e.g. '
+                         '{"mol_weight": [null, 450], "sums": {"logp": [null, 4]}, "max_violations": 0}')
     ap.add_argument('--num_steps', type=int, default=None, help='reverse steps of the sampler (default: the model\'s)')
     ap.add_argument('--sdf', action='store_true', help='write one .sdf per molecule under <outdir>/sdf_results/')
     args = ap.parse_args()
@@ -204,6 +241,12 @@ def main():
         ap.error('--stereo_limits needs --stereo')
     if args.hydrogen_options is not None and not args.hydrogens:
         ap.error('--hydrogen_options needs --hydrogens')
+    if args.property_limits is not None and not args.properties:
+        ap.error('--property_limits needs --properties')
+    try:
+        property_limits = property_limits_of(args.property_limits) if args.properties else None
+    except (ValueError, TypeError) as err:
+        ap.error(str(err))
     args.fingerprints = args.fingerprints or args.diverse is not None or args.reference_fps is not None
     if args.fp_radius is not None and not args.fingerprints:
         ap.error('--fp_radius needs --fingerprints')
@@ -230,7 +273,7 @@ def main():
         if not 1 <= steps <= substruct.MAX_STEPS:
             ap.error('--substructure_steps must be 1 .. 2**30')
         patterns = (substruct.load_patterns_json(args.substructure), steps)
-    args.valid_only = args.valid_only or args.scaffolds or args.add_edge != 'predicted' or args.bond_agreement or patterns is not None or args.fingerprints or args.unique or args.geometry or args.rings or args.kekule or args.features or args.smiles or args.stereo or args.hydrogens
+    args.valid_only = args.valid_only or args.scaffolds or args.add_edge != 'predicted' or args.bond_agreement or patterns is not None or args.fingerprints or args.unique or args.geometry or args.rings or args.kekule or args.features or args.smiles or args.stereo or args.hydrogens or args.properties
     stereo_limits = StereoLimits(**(args.stereo_limits or {})) if args.stereo else None
     hydrogen_options = HydrogenOptions(**(args.hydrogen_options or {})) if args.hydrogens else None
     feature_limits = FeatureLimits(**(args.feature_limits or {})) if args.features else None
@@ -278,7 +321,8 @@ def main():
                                **(dict(substructure=patterns) if patterns is not None else {}),
                                **(dict(add_edge=args.add_edge) if args.add_edge != 'predicted' else {}),
                                **(dict(bond_agreement=True) if args.bond_agreement else {}),
-                               **(dict(hydrogens=hydrogen_options) if args.hydrogens else {}), **kw)
+                               **(dict(hydrogens=hydrogen_options) if args.hydrogens else {}),
+                               **(dict(properties=property_limits) if args.properties else {}), **kw)
             done = out['finished']
             print(f"Finished {len(done)} | Failed {len(out['failed'])}" + (f" | Duplicates {len(out['duplicates'])}" if args.unique else ''))
             if args.unique:
@@ -312,6 +356,8 @@ def main():
                     ref = similarity.nearest(fps, torch.from_numpy(reference.view(np.int64)).to('cuda').contiguous())
                     with open(os.path.join(args.outdir, data.name + '_nearest.txt'), 'w') as fh:
                         fh.writelines('%.6f %d\n' % (s, j) for s, j in zip(ref.sim.tolist(), ref.index.tolist()))
+            if args.properties:
+                write_property_file(args.outdir, data.name, done)
             if args.scaffolds:
                 write_scaffold_files(args.outdir, data.name, done, not args.scaffold_plain, args.max_per_scaffold)
         while len(done) < args.num_samples and not args.valid_only:
