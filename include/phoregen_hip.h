@@ -838,6 +838,66 @@ int pg_fp_nearest(const uint64_t* a, int na, const uint64_t* b, int nb, int same
 int pg_fp_maxmin(const uint64_t* fp, int n, int k, int first, int32_t* picked /*[k]*/, float* pick_sim /*[k]*/, float* work /*[n]*/,
                  uint64_t* slots /*[k]*/, void* stream);
 
+/* Gaussian shape and feature ("colour") overlap of molecules where they lie, with no alignment.  Definition: DESIGN.md 2.9 "Shape".
+ * A kept atom of class e is the Gaussian p exp(-alpha_e |r - x|^2), p = 2 sqrt(2).  For molecules A, B:
+ *   V(A, B) = sum over kept atoms i of A, j of B of p^2 (pi / (a_i + a_j))^(3/2) exp(-(a_i a_j / (a_i + a_j)) d_ij^2)
+ *   C(A, B) = sum over i, j of popcount(fp_i & fp_j) p^2 (pi / (2 a_c))^(3/2) exp(-(a_c / 2) d_ij^2), fp = the atoms' feature bytes
+ *   ST = V(A, B) / (V(A, A) + V(B, B) - V(A, B)), CT the same over C; either is 0 where its denominator is not positive
+ *   score = (1 - w) ST + w CT, each product and the sum rounded to fp32
+ * fp32 arithmetic, first-order terms only, no hydrogens.  alpha: PG_SHAPE_N_ALPHA floats in HOST memory, the alpha of the 11 atom
+ * classes, then the colour alpha a_c, in the units of the coordinates^-2; every entry point refuses an entry that is not positive and
+ * finite.  A pair's values depend on the two molecules alone (one summation order per pair: csrc/shape_sim.hip), not on where they
+ * sit in their sets, on the other rows, on the tiling or the split, or on which entry point computes them; V(A, B) and V(B, A) may
+ * differ in the last bits.
+ *
+ * A set of n molecules is four arrays: atoms [n_atoms][4] fp32, 16-byte aligned (x, y, z, and as bits class | feature byte << 8, or
+ * -1 for a dropped atom), mol [n][2] int32 (first atom row, atoms; at most PG_MOL_MAX_ATOMS; a row whose span leaves the atom rows
+ * reads as empty), and the self overlaps self_shape [n], self_colour [n] = V(A, A), C(A, A).
+ *
+ * pg_shape_pack builds the set of F * B molecules in (frame, graph) order from a screen's cls [F][n_lig] and g_lig_off, the
+ * coordinates pos (frame f at pos + f * pos_fs floats, rows of 3), the optional feature bytes atom_fp [F][n_lig] (null: all 0) and the
+ * optional select [F * B] (uint8, null: all selected), one wave per molecule, no host read.  The kept atoms (class 0..10) of a graph
+ * are compacted, in their order, to the front of the graph's span of atom rows, the rest of the span is written as dropped:
+ * atoms [F * n_lig][4], mol [F * B][2], status [F * B] = PG_SHAPE_EMPTY (no kept atom) | PG_SHAPE_NONFINITE (a kept atom with a
+ * non-finite coordinate) | PG_SHAPE_UNSELECTED.  A molecule with any bit has no atoms: an empty row.  Every element of the three
+ * outputs is written.  max_n = the largest graph.
+ * Errors, before anything is launched and with the outputs untouched: a negative size, max_n above PG_MOL_MAX_ATOMS, a null array
+ * that is needed, a bad alpha. */
+#define PG_SHAPE_N_ALPHA 12
+#define PG_SHAPE_EMPTY 1
+#define PG_SHAPE_NONFINITE 2
+#define PG_SHAPE_UNSELECTED 4
+#define PG_SHAPE_TILE_A 16           /* rows of set a per workgroup, one pair of molecules per wave at a time ... */
+#define PG_SHAPE_TILE_B 16           /* ... and molecules of one LDS tile of set b; a run of b is whole tiles     */
+int pg_shape_pack(const int8_t* cls, const int* g_lig_off /*[B+1]*/, const float* pos, int64_t pos_fs, const uint8_t* atom_fp,
+                  const uint8_t* select, int B, int F, int n_lig, int max_n, const float* alpha /*host [12]*/,
+                  float* atoms /*[F*n_lig*4]*/, int* mol /*[F*B*2]*/, int* status /*[F*B]*/, void* stream);
+
+/* self_shape [n] = V(A, A) and, where self_colour is not null, self_colour [n] = C(A, A) of every row of a set (the terms i = j
+ * included); one wave per row.  Errors as above. */
+int pg_shape_self(const float* atoms, int n_atoms, const int* mol, int n, const float* alpha /*host [12]*/, float* self_shape /*[n]*/,
+                  float* self_colour /*[n] or null*/, void* stream);
+
+/* shape_out [na][nb] = ST(a_i, b_j) and, where colour_out is not null, colour_out [na][nb] = CT(a_i, b_j) (the self_colour arrays are
+ * then read).  na * nb above 2^31 - 1 is an error.  Errors as above. */
+int pg_shape_similarity(const float* a_atoms, int a_n_atoms, const int* a_mol, const float* a_self_shape, const float* a_self_colour,
+                        int na, const float* b_atoms, int b_n_atoms, const int* b_mol, const float* b_self_shape,
+                        const float* b_self_colour, int nb, const float* alpha /*host [12]*/, float* shape_out /*[na*nb]*/,
+                        float* colour_out /*[na*nb] or null*/, void* stream);
+
+/* For every row i of a against the rows j of b (no [na][nb] matrix in memory), with the score above (has_colour = 0: CT = 0 and the
+ * self_colour arrays are not read):
+ *   sim [na]: the largest score; index [na]: the lowest j that attains it; sum [na]: the fp64 sum over j of the fp32 scores, j
+ *   ascending within a run, the runs in their order.
+ * same != 0: a and b must be one set (one mol pointer, one size) and j = i is left out.  An empty row of b scores 0 and is still a
+ * candidate.  A row without a candidate (nb = 0, or same with one row) gets sim -1, index -1, sum 0.  sim and index do not depend on
+ * how b is cut into runs; where a has few rows and b many, the runs are combined by a second launch in run order, their parts in
+ * stream-ordered memory: no host synchronisation.  w outside [0, 1] or not a number is an error; errors as above. */
+int pg_shape_nearest(const float* a_atoms, int a_n_atoms, const int* a_mol, const float* a_self_shape, const float* a_self_colour,
+                     int na, const float* b_atoms, int b_n_atoms, const int* b_mol, const float* b_self_shape,
+                     const float* b_self_colour, int nb, int same, int has_colour, float w, const float* alpha /*host [12]*/,
+                     float* sim /*[na]*/, int32_t* index /*[na]*/, double* sum /*[na]*/, void* stream);
+
 /* Substructure search: for every (frame, graph) the screen decoded and every pattern of a table, the embeddings of the pattern in the
  * molecule, one wave per (frame, graph, pattern).  Definition: DESIGN.md 2.9 "Substructure".
  * Target: the kept atoms (class 0..10) in the screen's compact numbering (compact [F][n_lig]) and the pair rows a < b with order 1..4

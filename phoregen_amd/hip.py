@@ -130,6 +130,8 @@ PG_PROP_NO_KEKULE, PG_PROP_LIMITS, PG_PROP_UNTYPED = 1, 2, 4
  PG_PROP_C_NHOH, PG_PROP_C_NO_COUNT, PG_PROP_C_ROTATABLE, PG_PROP_C_AMIDE_BONDS, PG_PROP_C_AROMATIC_ATOMS, PG_PROP_C_RING_ATOMS,
  PG_PROP_C_NET_CHARGE, PG_PROP_C_UNTYPED, PG_PROP_C_VIOLATIONS) = range(15)
 PG_PROP_N_COUNTS = 16
+# the shape overlap (pg_shape_*): the length of the alpha table, the status bits and the tiles, as the PG_SHAPE_* macros
+PG_SHAPE_N_ALPHA, PG_SHAPE_EMPTY, PG_SHAPE_NONFINITE, PG_SHAPE_UNSELECTED, PG_SHAPE_TILE_A, PG_SHAPE_TILE_B = 12, 1, 2, 4, 16, 16
 PG_PROP_L_WEIGHT, PG_PROP_L_HEAVY_ATOMS, PG_PROP_L_NHOH, PG_PROP_L_NO_COUNT, PG_PROP_L_ROTATABLE, PG_PROP_L_SUM0, PG_PROP_N_LIMITS = 0, 1, 2, 3, 4, 5, 9
 _lib = None
 
@@ -230,6 +232,12 @@ _PROTOS = {
     'pg_mol_scaffold': (C.c_int, [c_ip] * 4 + [C.c_int] * 6 + [c_ip] * 9 + [C.c_void_p]),
     'pg_mol_props': (C.c_int, [c_ip] * 10 + [C.c_int] * 5 + [c_ip, C.POINTER(C.c_int), C.c_int, c_ip, C.POINTER(C.c_int), C.c_int] + [c_ip] * 7
                      + [C.c_void_p]),
+    'pg_shape_pack': (C.c_int, [c_ip, c_ip, c_fp, C.c_int64, c_ip, c_ip, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), c_fp, c_ip,
+                                c_ip, C.c_void_p]),
+    'pg_shape_self': (C.c_int, [c_fp, C.c_int, c_ip, C.c_int, C.POINTER(C.c_float), c_fp, c_fp, C.c_void_p]),
+    'pg_shape_similarity': (C.c_int, [c_fp, C.c_int, c_ip, c_fp, c_fp, C.c_int] * 2 + [C.POINTER(C.c_float), c_fp, c_fp, C.c_void_p]),
+    'pg_shape_nearest': (C.c_int, [c_fp, C.c_int, c_ip, c_fp, c_fp, C.c_int] * 2 + [C.c_int, C.c_int, C.c_float, C.POINTER(C.c_float), c_fp, c_ip,
+                                   c_fp, C.c_void_p]),
 }
 
 EXPORTS = tuple(_PROTOS)

@@ -74,7 +74,13 @@ Scaffolds: `phoregen_amd.scaffold` writes the Murcko scaffold of every decoded m
 Properties: `phoregen_amd.properties` computes molecular weight, table sums (polar surface area, logP, molar refractivity), the
 Lipinski and Veber counts, Fsp3 and a verdict against `PropertyLimits` (csrc/mol_props.hip; DESIGN.md 2.9 "Properties") from an
 integer environment word per atom; `assemble(properties=)`, `sample_valid(properties=)` and `write_sdf` carry it.  The shipped
-contribution tables are written from memory, not checked against RDKit; no QED, no synthetic-accessibility score."""
+contribution tables are written from memory, not checked against RDKit; no QED, no synthetic-accessibility score.
+
+Shape: `phoregen_amd.shape` compares molecules in space, where they lie in the pharmacophore's frame: Gaussian-volume shape overlap
+and, with `Features.atom_fp`, feature ("colour") overlap, their Tanimoto values as an all-pairs matrix or a nearest-neighbour search,
+and the 3D diversity of a run (csrc/shape_sim.hip; DESIGN.md 2.9 "Shape").  No alignment search, first order only, no hydrogens; the
+radii are written from memory and the values are not ROCS's or RDKit's.  Like scaffolds it is a module of its own: `assemble`,
+`sample_valid` and `write_sdf` do not carry it."""
 import ctypes
 from collections import namedtuple
 from dataclasses import astuple, dataclass, replace

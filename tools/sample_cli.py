@@ -66,7 +66,15 @@ logp and mr, the Lipinski and Veber counts, fsp3; the shipped tables are written
 a molecule only if it has a Kekulé structure and keeps the limits; --property_limits '{"preset": "lipinski"}' (or "veber"), or explicit
 keys of phoregen_amd.properties.PropertyLimits such as '{"mol_weight": [null, 450], "sums": {"logp": [null, 4]}, "max_violations": 0}',
 sets them (default: none).  <outdir>/{name}_properties.txt holds one line 'index mol_weight tpsa logp mr nhoh no_count rotatable
-heavy_atoms fsp3 status' per finished molecule and the .sdf files carry the data item PHOREGEN_PROPERTIES.  --num_steps shortens the reverse process (default: the model's).  Without them
+heavy_atoms fsp3 status' per finished molecule and the .sdf files carry the data item PHOREGEN_PROPERTIES.  --shape (implies
+--valid_only) compares the finished molecules in space, where they lie in the pharmacophore's frame (phoregen_amd.shape: Gaussian-volume
+overlap with no alignment; the radii are design choices, the values are not ROCS's): <outdir>/{name}_shape.txt holds one line 'index
+volume nearest_sim nearest_index' per finished molecule -- volume = the molecule's self overlap in cubic Angstrom, the nearest other
+finished molecule by shape Tanimoto -- and <outdir>/{name}_shape_summary.txt the lines 'molecules', 'internal_shape_diversity' and
+'mean_nearest_shape_similarity'.  --shape_colour (needs --shape, implies --features) gives the set the atoms' feature types as colour and
+scores by (1 - W) shape + W colour Tanimoto, W = --shape_colour_weight (default 0.5).  --shape_reference FILE.sdf (implies --shape)
+reads the first mol block of the file, e.g. the ligand the pharmacophore was derived from, which must lie in the .phore file's frame:
+every line gets the column 'reference_shape_sim' (shape only) and the summary the line 'mean_reference_shape_similarity'.  --num_steps shortens the reverse process (default: the model's).  Without them
 nothing changes.
 """
 import argparse
@@ -85,6 +93,7 @@ from phoregen_amd.data import PHORETYPES1, parse_phore_file  # noqa: E402
 from phoregen_amd.fragment import load_fragment_json  # noqa: E402
 from phoregen_amd.models.diffusion import PhoreDiff  # noqa: E402
 from phoregen_amd import scaffold as scaffold_mod  # noqa: E402
+from phoregen_amd import shape as shape_mod  # noqa: E402
 from phoregen_amd import similarity  # noqa: E402
 from phoregen_amd import substructure as substruct  # noqa: E402
 from phoregen_amd.hydrogens import HydrogenOptions  # noqa: E402
@@ -143,6 +152,40 @@ def write_scaffold_files(outdir, name, done, exocyclic, max_per_scaffold):
     if max_per_scaffold is not None:
         with open(os.path.join(outdir, name + '_scaffold_picks.txt'), 'w') as fh:
             fh.writelines('%d\n' % i for i in scaffold_mod.pick_per_scaffold(group, max_per_scaffold).tolist())
+
+
+def first_mol_block_of(text):
+    """The first mol block of the text of an .sdf file: everything up to and including its 'M  END' line."""
+    end = text.find('M  END')
+    if end < 0:
+        raise ValueError('no mol block (no "M  END" line)')
+    return text[:end + len('M  END')] + '\n'
+
+
+def write_shape_files(outdir, name, done, colour, weight, reference):
+    """<name>_shape.txt and <name>_shape_summary.txt for the finished molecules: from_molecules -> nearest / internal_diversity, and
+    with `reference` (a mol block) the shape Tanimoto to it.  colour: the molecules carry 'features' and the score is the combined one."""
+    n, w = len(done), weight if colour else 0.0
+    lines, diversity, mean_near, mean_ref = [], float('nan'), float('nan'), float('nan')
+    if n:
+        mols = done if colour else [{'element': m['element'], 'atom_pos': m['atom_pos']} for m in done]
+        st = shape_mod.from_molecules(mols, 'cuda')
+        near = shape_mod.nearest(st, colour_weight=w)
+        cols = [st.self_shape.tolist(), near.sim.tolist(), near.index.tolist()]
+        if reference is not None:
+            ref = shape_mod.nearest(st, shape_mod.from_mol_block(reference, 'cuda'))
+            cols.append(ref.sim.tolist())
+            mean_ref = ref.sim.double().mean().item()
+        diversity = shape_mod.internal_diversity(st, colour_weight=w)
+        mean_near = near.sim.double().mean().item() if n >= 2 else float('nan')
+        lines = ['%d %.3f %.6f %d' % (i, *row[:3]) + (' %.6f' % row[3] if reference is not None else '') + '\n' for i, row in enumerate(zip(*cols))]
+    with open(os.path.join(outdir, name + '_shape.txt'), 'w') as fh:
+        fh.write('# index volume nearest_sim nearest_index' + (' reference_shape_sim' if reference is not None else '') + '\n')
+        fh.writelines(lines)
+    with open(os.path.join(outdir, name + '_shape_summary.txt'), 'w') as fh:
+        fh.write('molecules: %d\ninternal_shape_diversity: %.6f\nmean_nearest_shape_similarity: %.6f\n' % (n, diversity, mean_near))
+        if reference is not None:
+            fh.write('mean_reference_shape_similarity: %.6f\n' % mean_ref)
 
 
 def main():
@@ -224,6 +267,15 @@ def main():
     ap.add_argument('--property_limits', type=json.loads, default=None,
                     help='JSON object (with --properties): {"preset": "lipinski"} or {"preset": "veber"}, or keys of PropertyLimits, e.g. '
                          '{"mol_weight": [null, 450], "sums": {"logp": [null, 4]}, "max_violations": 0}')
+    ap.add_argument('--shape', action='store_true',
+                    help='implies --valid_only: writes <outdir>/<name>_shape.txt (per finished molecule its volume and its nearest other '
+                         'molecule by 3D shape Tanimoto, compared where they lie) and <name>_shape_summary.txt')
+    ap.add_argument('--shape_colour', action='store_true',
+                    help='with --shape, implies --features: the atoms\' feature types as colour, the score is (1 - W) shape + W colour Tanimoto')
+    ap.add_argument('--shape_colour_weight', type=float, default=None, metavar='W', help='with --shape_colour: W in [0, 1] (default 0.5)')
+    ap.add_argument('--shape_reference', type=str, default=None, metavar='FILE.sdf',
+                    help='implies --shape: the first mol block of the file, in the frame of the .phore file; adds the column '
+                         'reference_shape_sim and the summary line mean_reference_shape_similarity')
     ap.add_argument('--num_steps', type=int, default=None, help='reverse steps of the sampler (default: the model\'s)')
     ap.add_argument('--sdf', action='store_true', help='write one .sdf per molecule under <outdir>/sdf_results/')
     args = ap.parse_args()
@@ -243,6 +295,22 @@ def main():
         ap.error('--hydrogen_options needs --hydrogens')
     if args.property_limits is not None and not args.properties:
         ap.error('--property_limits needs --properties')
+    args.shape = args.shape or args.shape_reference is not None
+    if args.shape_colour and not args.shape:
+        ap.error('--shape_colour needs --shape')
+    if args.shape_colour_weight is not None and not args.shape_colour:
+        ap.error('--shape_colour_weight needs --shape_colour')
+    shape_weight = 0.5 if args.shape_colour_weight is None else args.shape_colour_weight
+    if not 0.0 <= shape_weight <= 1.0:
+        ap.error('--shape_colour_weight must lie in [0, 1]')
+    args.features = args.features or args.shape_colour
+    shape_reference = None
+    if args.shape_reference is not None:
+        try:
+            shape_reference = first_mol_block_of(open(args.shape_reference).read())
+            shape_mod.read_mol_block(shape_reference)
+        except (OSError, ValueError) as err:
+            ap.error(f'--shape_reference: {err}')
     try:
         property_limits = property_limits_of(args.property_limits) if args.properties else None
     except (ValueError, TypeError) as err:
@@ -273,7 +341,7 @@ def main():
         if not 1 <= steps <= substruct.MAX_STEPS:
             ap.error('--substructure_steps must be 1 .. 2**30')
         patterns = (substruct.load_patterns_json(args.substructure), steps)
-    args.valid_only = args.valid_only or args.scaffolds or args.add_edge != 'predicted' or args.bond_agreement or patterns is not None or args.fingerprints or args.unique or args.geometry or args.rings or args.kekule or args.features or args.smiles or args.stereo or args.hydrogens or args.properties
+    args.valid_only = args.valid_only or args.shape or args.scaffolds or args.add_edge != 'predicted' or args.bond_agreement or patterns is not None or args.fingerprints or args.unique or args.geometry or args.rings or args.kekule or args.features or args.smiles or args.stereo or args.hydrogens or args.properties
     stereo_limits = StereoLimits(**(args.stereo_limits or {})) if args.stereo else None
     hydrogen_options = HydrogenOptions(**(args.hydrogen_options or {})) if args.hydrogens else None
     feature_limits = FeatureLimits(**(args.feature_limits or {})) if args.features else None
@@ -358,6 +426,8 @@ def main():
                         fh.writelines('%.6f %d\n' % (s, j) for s, j in zip(ref.sim.tolist(), ref.index.tolist()))
             if args.properties:
                 write_property_file(args.outdir, data.name, done)
+            if args.shape:
+                write_shape_files(args.outdir, data.name, done, args.shape_colour, shape_weight, shape_reference)
             if args.scaffolds:
                 write_scaffold_files(args.outdir, data.name, done, not args.scaffold_plain, args.max_per_scaffold)
         while len(done) < args.num_samples and not args.valid_only:
