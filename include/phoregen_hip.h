@@ -898,6 +898,43 @@ int pg_shape_nearest(const float* a_atoms, int a_n_atoms, const int* a_mol, cons
                      const float* b_self_colour, int nb, int same, int has_colour, float w, const float* alpha /*host [12]*/,
                      float* sim /*[na]*/, int32_t* index /*[na]*/, double* sum /*[na]*/, void* stream);
 
+/* Rigid overlay of molecule pairs: the best of up to five local ascents of the score above over the rigid poses of B, A fixed.
+ * Definition: DESIGN.md 2.9 "Shape alignment".  A pose is (R, p): B's atom y lies at R (y - c_B) + p, c_B = B's centroid.
+ *   frame of a row (pg_shape_frames, frames [n][PG_SHAPE_FRAME_FLOATS]): centroid 3 (the unweighted mean of the kept atoms), axes 9
+ *     (axis k at 3 + 3 k: the eigenvectors of the covariance, divided by n, by cyclic Jacobi in double, eigenvalues descending, the
+ *     largest-magnitude component of axes 1 and 2 positive, axis 3 = axis 1 x axis 2), rho = max(radius of gyration, 0.5), the three
+ *     eigenvalues; computed in double in packed order and rounded once to fp32.  An empty row: origin, identity, rho 0.5, zeros.
+ *   starts: 0 in place (R = I, p = c_B; B is read as stored until the first accepted step), 1..4 inertial (R = E_A D_k E_B^T,
+ *     p = c_A, D_k = diag(1,1,1), (1,-1,-1), (-1,1,-1), (-1,-1,1)); `starts` is a mask of the bits 0..4
+ *     (PG_SHAPE_ALIGN_IN_PLACE, PG_SHAPE_ALIGN_INERTIAL).
+ *   objective f = score(ST, CT, w) over V(A, B'), C(A, B') and the stored self overlaps; has_colour = 0 or w = 0: CT = C = 0 and the
+ *     colour terms are skipped.  Gradient: force F = sum_ij 2 k_ij g_ij (x_i - y'_j), torque tau about p, each objective weighted by
+ *     its chain-rule factor ((1 - w) (aa + bb) / (aa + bb - V)^2, w (caa + cbb) / (caa + cbb - C)^2, 0 for a denominator <= 0).
+ *   step rule: d = g6 / |g6|, g6 = (F, tau / rho_B); trial p + s d[0:3], exp([s d[3:6] / rho_B]x) R (a unit quaternion, renormalised);
+ *     f_trial > f: accept, s *= 1.5; else s *= 0.5; stop at |g6| = 0, s < min_step or after max_steps evaluations (the first counts).
+ *   winner: the start with the largest final f, ties to the lowest start.
+ * Outputs per pair: values [n_pairs][5] = V, C, ST, CT, score at the winning pose; transform [n_pairs][12] = R row-major, then
+ * t = p - R c_B (y' = R y + t on B's stored coordinates); start [n_pairs]; steps [n_pairs] = the evaluations the winner used.  A
+ * pair with an empty row: zeros, R = I, t = 0, start -1, steps 0.  A pair's outputs depend on the two rows and the arguments alone
+ * (one summation order per evaluation: csrc/shape_align.hip).  pairs [n_pairs][2] int32 on the device names (row of a, row of b);
+ * pairs = null: the grid a x b in row-major order, n_pairs = na * nb.  One workgroup per pair, one wave per start.
+ * Errors, before anything is launched and with the outputs untouched: null arrays, negative sizes, a listed pair outside its set
+ * (the list is read back once for this -- the one host read; the grid needs none), max_steps outside 1 .. PG_SHAPE_ALIGN_MAX_STEPS,
+ * a step that is not positive and finite or min_step > first_step, an empty or unknown starts mask, w outside [0, 1] or not a
+ * number, a bad alpha.  n_pairs = 0 is nothing to do. */
+#define PG_SHAPE_FRAME_FLOATS 16
+#define PG_SHAPE_ALIGN_N_STARTS 5
+#define PG_SHAPE_ALIGN_IN_PLACE 0x01
+#define PG_SHAPE_ALIGN_INERTIAL 0x1e
+#define PG_SHAPE_ALIGN_MAX_STEPS 1024
+int pg_shape_frames(const float* atoms, int n_atoms, const int* mol, int n, float* frames /*[n][16]*/, void* stream);
+int pg_shape_align(const float* a_atoms, int a_n_atoms, const int* a_mol, const float* a_self_shape, const float* a_self_colour,
+                   const float* a_frames, int na, const float* b_atoms, int b_n_atoms, const int* b_mol, const float* b_self_shape,
+                   const float* b_self_colour, const float* b_frames, int nb, const int32_t* pairs /*[n_pairs][2] or null*/, int n_pairs,
+                   int has_colour, float w, const float* alpha /*host [12]*/, int max_steps, float first_step, float min_step, int starts,
+                   float* values /*[n_pairs][5]*/, float* transform /*[n_pairs][12]*/, int32_t* start /*[n_pairs]*/,
+                   int32_t* steps /*[n_pairs]*/, void* stream);
+
 /* Substructure search: for every (frame, graph) the screen decoded and every pattern of a table, the embeddings of the pattern in the
  * molecule, one wave per (frame, graph, pattern).  Definition: DESIGN.md 2.9 "Substructure".
  * Target: the kept atoms (class 0..10) in the screen's compact numbering (compact [F][n_lig]) and the pair rows a < b with order 1..4

@@ -132,6 +132,8 @@ PG_PROP_NO_KEKULE, PG_PROP_LIMITS, PG_PROP_UNTYPED = 1, 2, 4
 PG_PROP_N_COUNTS = 16
 # the shape overlap (pg_shape_*): the length of the alpha table, the status bits and the tiles, as the PG_SHAPE_* macros
 PG_SHAPE_N_ALPHA, PG_SHAPE_EMPTY, PG_SHAPE_NONFINITE, PG_SHAPE_UNSELECTED, PG_SHAPE_TILE_A, PG_SHAPE_TILE_B = 12, 1, 2, 4, 16, 16
+# the overlay (pg_shape_frames, pg_shape_align): the floats of a frame, the starts and the bits of their mask, the largest max_steps
+PG_SHAPE_FRAME_FLOATS, PG_SHAPE_ALIGN_N_STARTS, PG_SHAPE_ALIGN_IN_PLACE, PG_SHAPE_ALIGN_INERTIAL, PG_SHAPE_ALIGN_MAX_STEPS = 16, 5, 0x01, 0x1e, 1024
 PG_PROP_L_WEIGHT, PG_PROP_L_HEAVY_ATOMS, PG_PROP_L_NHOH, PG_PROP_L_NO_COUNT, PG_PROP_L_ROTATABLE, PG_PROP_L_SUM0, PG_PROP_N_LIMITS = 0, 1, 2, 3, 4, 5, 9
 _lib = None
 
@@ -238,6 +240,9 @@ _PROTOS = {
     'pg_shape_similarity': (C.c_int, [c_fp, C.c_int, c_ip, c_fp, c_fp, C.c_int] * 2 + [C.POINTER(C.c_float), c_fp, c_fp, C.c_void_p]),
     'pg_shape_nearest': (C.c_int, [c_fp, C.c_int, c_ip, c_fp, c_fp, C.c_int] * 2 + [C.c_int, C.c_int, C.c_float, C.POINTER(C.c_float), c_fp, c_ip,
                                    c_fp, C.c_void_p]),
+    'pg_shape_frames': (C.c_int, [c_fp, C.c_int, c_ip, C.c_int, c_fp, C.c_void_p]),
+    'pg_shape_align': (C.c_int, [c_fp, C.c_int, c_ip, c_fp, c_fp, c_fp, C.c_int] * 2 + [c_ip, C.c_int, C.c_int, C.c_float, C.POINTER(C.c_float),
+                                 C.c_int, C.c_float, C.c_float, C.c_int, c_fp, c_fp, c_ip, c_ip, C.c_void_p]),
 }
 
 EXPORTS = tuple(_PROTOS)

@@ -20,8 +20,11 @@ V2000 block such as the reference ligand; `concat` joins sets.  `similarity` is 
 of every row with the row sums (no matrix in memory), `internal_diversity` one minus the mean score of the distinct pairs.
 
 The radii are Bondi's and Mantina's values written from memory, and the colour radius is a design choice, not a calibration: the
-values are not ROCS's or RDKit's.  Out of scope: alignment or overlay optimisation, higher-order volume corrections, hydrogens,
-colour for a mol-block reference, MaxMin picks by shape, a shape filter inside `sample_valid`."""
+values are not ROCS's or RDKit's.  Molecules that do not share a frame -- two runs against different pharmacophores, a reference
+ligand in its crystal frame -- are overlaid first: `align` searches the best rigid pose of one molecule on the other (csrc/shape_align.hip;
+DESIGN.md 2.9 "Shape alignment"), `frames` gives the principal frames it starts from, `transformed` applies a result.  Out of scope:
+higher-order volume corrections, hydrogens, colour for a mol-block reference, MaxMin picks by shape, a shape filter inside
+`sample_valid`."""
 import ctypes as C
 import math
 from dataclasses import dataclass, field
@@ -365,3 +368,135 @@ def internal_diversity(a, colour_weight=0.0):
     near = nearest(a, colour_weight=colour_weight)
     total, m = torch.stack([torch.where(live, near.sum, torch.zeros_like(near.sum)).sum(), live.sum().double()]).tolist()
     return _diversity(total, int(m))
+
+
+# ---- rigid overlay (csrc/shape_align.hip; DESIGN.md 2.9 "Shape alignment") -------------------------------------------------------------
+START_NAMES = ('in_place', 'inertial', 'both')
+_START_MASK = {'in_place': hip.PG_SHAPE_ALIGN_IN_PLACE, 'inertial': hip.PG_SHAPE_ALIGN_INERTIAL,
+               'both': hip.PG_SHAPE_ALIGN_IN_PLACE | hip.PG_SHAPE_ALIGN_INERTIAL}
+
+
+@dataclass(frozen=True)
+class AlignOptions:
+    """The step rule of `align`: at most max_steps evaluations per start (1 .. 1024, the first counts), steps from first_step down to
+    min_step (Angstrom of the six-vector (translation, rho * rotation)), and the starts: 'in_place' (start 0), 'inertial' (starts
+    1 .. 4, the four proper sign choices of the principal axes) or 'both'."""
+    max_steps: int = 128
+    first_step: float = 0.5
+    min_step: float = 1e-4
+    starts: str = 'both'
+
+    def mask(self):
+        if self.starts not in _START_MASK:
+            raise ValueError(f'phoregen_amd.shape.AlignOptions: starts must be one of {START_NAMES}, not {self.starts!r}')
+        return _START_MASK[self.starts]
+
+
+@dataclass
+class ShapeAlignment:
+    """Device tensors of one `align` call, one row per pair."""
+    pairs: torch.Tensor            # int32 [n, 2] row of a, row of b
+    shape_overlap: torch.Tensor    # fp32  [n] V(A, B') at the winning pose
+    colour_overlap: torch.Tensor   # fp32  [n] C(A, B'); 0 without colour or with colour_weight 0
+    shape: torch.Tensor            # fp32  [n] ST
+    colour: torch.Tensor           # fp32  [n] CT
+    score: torch.Tensor            # fp32  [n] (1 - w) ST + w CT
+    rotation: torch.Tensor         # fp32  [n, 3, 3] R ...
+    translation: torch.Tensor      # fp32  [n, 3]    ... and t: y' = R y + t on b's stored coordinates
+    start: torch.Tensor            # int32 [n] the winning start, 0 in place, 1 .. 4 inertial; -1 for a pair with an empty row
+    steps: torch.Tensor            # int32 [n] the evaluations the winning start used
+
+
+def _launch_frames(lib, s, out):
+    """pg_shape_frames on the current stream."""
+    hip.check(lib.pg_shape_frames(s.atoms.data_ptr(), s.atoms.size(0), s.mol.data_ptr(), s.n, out.data_ptr(), hip.stream_ptr()), 'pg_shape_frames')
+
+
+def _align_args(s, frames_):
+    return (s.atoms.data_ptr(), s.atoms.size(0), s.mol.data_ptr(), s.self_shape.data_ptr(), s.self_colour.data_ptr(), frames_.data_ptr(), s.n)
+
+
+def _launch_align(lib, a, fa, b, fb, pairs, n_pairs, has_colour, w, alpha, max_steps, first_step, min_step, mask, values, transform, start, steps):
+    """pg_shape_align on the current stream; pairs may be None (the grid a x b).  Bad options, a bad weight or alpha and a listed pair
+    outside its set are the library's errors: nothing is launched and the outputs are not written."""
+    hip.check(lib.pg_shape_align(*_align_args(a, fa), *_align_args(b, fb), hip.ptr(pairs), n_pairs, int(has_colour), w, alpha, max_steps,
+                                 first_step, min_step, mask, values.data_ptr(), transform.data_ptr(), start.data_ptr(), steps.data_ptr(),
+                                 hip.stream_ptr()), 'pg_shape_align')
+
+
+@torch.no_grad()
+def frames(s):
+    """The frame of every row of a set, fp32 [n, 16] on the device (pg_shape_frames): centroid 3, principal axes 9 (axis k at
+    3 + 3 k, eigenvalues descending, right-handed), rho = max(radius of gyration, 0.5), the three eigenvalues of the covariance.
+    Computed in double, rounded once.  An empty row: the origin, the identity, rho 0.5."""
+    _check_set('frames', s, 's')
+    dev = s.atoms.device
+    with torch.cuda.device(dev):
+        out = torch.empty(s.n, hip.PG_SHAPE_FRAME_FLOATS, dtype=torch.float32, device=dev)
+        _launch_frames(hip.lib(), s, out)
+    return out
+
+
+@torch.no_grad()
+def align(a, b=None, pairs=None, colour_weight=0.0, options=AlignOptions()):
+    """The best rigid overlay of b's row onto a's row for every pair (pg_shape_frames, pg_shape_align): a stays, b moves; from each
+    enabled start a fixed-rule gradient ascent of the score (1 - colour_weight) ST + colour_weight CT, the best final score winning, ties
+    to the lowest start.  pairs: int32 [n, 2] on the device (row of a, row of b; read back once to be checked), default the grid
+    a x b in row-major order, built on the device with no host read.  b=None: a against itself.  With colour_weight 0 or a set without
+    colour, CT and the colour overlap are 0.  A pair's values are bit-identical wherever it stands in the list.  The scores are this
+    module's, not ROCS's or RDKit's."""
+    w = _check_weight('align', colour_weight)
+    _pair('align', a, b)
+    b = a if b is None else b
+    if not isinstance(options, AlignOptions):
+        raise ValueError(f'phoregen_amd.shape.align: options must be an AlignOptions, not {options!r}')
+    mask = options.mask()
+    dev = a.atoms.device
+    if pairs is not None:
+        if not torch.is_tensor(pairs) or pairs.dtype != torch.int32 or pairs.dim() != 2 or pairs.size(1) != 2 or pairs.device != dev:
+            raise ValueError(f'phoregen_amd.shape.align: pairs must be an int32 tensor [n, 2] on {dev}')
+        pairs = pairs.contiguous()
+        n = pairs.size(0)
+    else:
+        n = a.n * b.n
+    if n > 0x7fffffff:
+        raise ValueError(f'phoregen_amd.shape.align: {n} pairs exceed 2**31 - 1; cut the sets')
+    with torch.cuda.device(dev):
+        lib = hip.lib()
+        fa = frames(a)
+        fb = fa if b is a else frames(b)
+        values = torch.empty(n, 5, dtype=torch.float32, device=dev)
+        transform = torch.empty(n, 12, dtype=torch.float32, device=dev)
+        start = torch.empty(n, dtype=torch.int32, device=dev)
+        steps = torch.empty(n, dtype=torch.int32, device=dev)
+        _launch_align(lib, a, fa, b, fb, pairs, n, a.has_colour and b.has_colour, w, _alpha_arg(a.options), int(options.max_steps),
+                      float(options.first_step), float(options.min_step), mask, values, transform, start, steps)
+        if pairs is None:
+            pairs = torch.cartesian_prod(torch.arange(a.n, dtype=torch.int32, device=dev),
+                                         torch.arange(b.n, dtype=torch.int32, device=dev)).reshape(-1, 2)
+    return ShapeAlignment(pairs=pairs, shape_overlap=values[:, 0], colour_overlap=values[:, 1], shape=values[:, 2], colour=values[:, 3],
+                          score=values[:, 4], rotation=transform[:, :9].reshape(n, 3, 3), translation=transform[:, 9:], start=start, steps=steps)
+
+
+@torch.no_grad()
+def transformed(s, rows, rotation, translation):
+    """The rows `rows` of a set moved by the given transforms, as a set of their own in that order: row k's atoms at R_k y + t_k (torch
+    on the device, fp32), the feature words kept, the self overlaps copied -- a rigid move does not change them.  rotation [n, 3, 3],
+    translation [n, 3], e.g. `ShapeAlignment.rotation` / `.translation` with rows = pairs[:, 1]."""
+    _check_set('transformed', s, 's')
+    dev = s.atoms.device
+    rows = torch.as_tensor(rows, dtype=torch.long, device=dev).reshape(-1)
+    n = rows.numel()
+    if (not torch.is_tensor(rotation) or not torch.is_tensor(translation) or tuple(rotation.shape) != (n, 3, 3) or tuple(translation.shape) != (n, 3)
+            or rotation.dtype != torch.float32 or translation.dtype != torch.float32 or rotation.device != dev or translation.device != dev):
+        raise ValueError(f'phoregen_amd.shape.transformed: rotation must be fp32 [{n}, 3, 3] and translation fp32 [{n}, 3] on {dev}')
+    mol = s.mol[rows]
+    count = mol[:, 1].long()
+    first = torch.cumsum(count, 0) - count
+    owner = torch.repeat_interleave(torch.arange(n, device=dev), count)
+    src = mol[:, 0].long()[owner] + (torch.arange(owner.numel(), device=dev) - first[owner])
+    atoms = s.atoms[src].clone()
+    atoms[:, :3] = torch.einsum('nij,nj->ni', rotation[owner], atoms[:, :3]) + translation[owner]
+    return ShapeSet(atoms=atoms, mol=torch.stack([first, count], 1).to(torch.int32).contiguous(), status=s.status[rows].contiguous(),
+                    self_shape=s.self_shape[rows].contiguous(), self_colour=s.self_colour[rows].contiguous(), has_colour=s.has_colour,
+                    options=s.options)

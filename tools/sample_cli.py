@@ -74,7 +74,12 @@ finished molecule by shape Tanimoto -- and <outdir>/{name}_shape_summary.txt the
 'mean_nearest_shape_similarity'.  --shape_colour (needs --shape, implies --features) gives the set the atoms' feature types as colour and
 scores by (1 - W) shape + W colour Tanimoto, W = --shape_colour_weight (default 0.5).  --shape_reference FILE.sdf (implies --shape)
 reads the first mol block of the file, e.g. the ligand the pharmacophore was derived from, which must lie in the .phore file's frame:
-every line gets the column 'reference_shape_sim' (shape only) and the summary the line 'mean_reference_shape_similarity'.  --num_steps shortens the reverse process (default: the model's).  Without them
+every line gets the column 'reference_shape_sim' (shape only) and the summary the line 'mean_reference_shape_similarity'.
+--shape_align (needs --shape --shape_reference) searches the best rigid overlay of the reference onto every finished molecule
+(phoregen_amd.shape.align: five local ascents of the score; neither the definition nor the values are ROCS's or RDKit's), so the
+reference may lie in any frame: every line gets 'aligned_shape_sim aligned_start' (the winning start, 0 in place, 1 .. 4 inertial) and
+with --shape_colour 'aligned_colour_sim aligned_score', the summary 'mean_aligned_reference_shape_similarity'; --shape_align_sdf
+(implies --shape_align) writes every finished molecule overlaid onto the reference under <outdir>/sdf_aligned/.  --num_steps shortens the reverse process (default: the model's).  Without them
 nothing changes.
 """
 import argparse
@@ -162,30 +167,56 @@ def first_mol_block_of(text):
     return text[:end + len('M  END')] + '\n'
 
 
-def write_shape_files(outdir, name, done, colour, weight, reference):
+def write_shape_files(outdir, name, done, colour, weight, reference, align=False):
     """<name>_shape.txt and <name>_shape_summary.txt for the finished molecules: from_molecules -> nearest / internal_diversity, and
-    with `reference` (a mol block) the shape Tanimoto to it.  colour: the molecules carry 'features' and the score is the combined one."""
+    with `reference` (a mol block) the shape Tanimoto to it.  colour: the molecules carry 'features' and the score is the combined one.
+    align (needs `reference`): the best rigid overlay of the reference onto every molecule (`shape.align`) adds the columns
+    'aligned_shape_sim aligned_start' -- with colour also 'aligned_colour_sim aligned_score'; the reference carries no colour, so its
+    colour Tanimoto is 0 -- and the summary line 'mean_aligned_reference_shape_similarity'.  Returns the `ShapeAlignment` (None
+    without align or without molecules): its transform moves the reference onto molecule i."""
     n, w = len(done), weight if colour else 0.0
-    lines, diversity, mean_near, mean_ref = [], float('nan'), float('nan'), float('nan')
+    lines, diversity, mean_near, mean_ref, mean_aligned, overlay = [], float('nan'), float('nan'), float('nan'), float('nan'), None
     if n:
         mols = done if colour else [{'element': m['element'], 'atom_pos': m['atom_pos']} for m in done]
         st = shape_mod.from_molecules(mols, 'cuda')
         near = shape_mod.nearest(st, colour_weight=w)
         cols = [st.self_shape.tolist(), near.sim.tolist(), near.index.tolist()]
         if reference is not None:
-            ref = shape_mod.nearest(st, shape_mod.from_mol_block(reference, 'cuda'))
+            ref_set = shape_mod.from_mol_block(reference, 'cuda')
+            ref = shape_mod.nearest(st, ref_set)
             cols.append(ref.sim.tolist())
             mean_ref = ref.sim.double().mean().item()
         diversity = shape_mod.internal_diversity(st, colour_weight=w)
         mean_near = near.sim.double().mean().item() if n >= 2 else float('nan')
-        lines = ['%d %.3f %.6f %d' % (i, *row[:3]) + (' %.6f' % row[3] if reference is not None else '') + '\n' for i, row in enumerate(zip(*cols))]
+        lines = ['%d %.3f %.6f %d' % (i, *row[:3]) + (' %.6f' % row[3] if reference is not None else '') for i, row in enumerate(zip(*cols))]
+        if align:
+            overlay = shape_mod.align(st, ref_set, colour_weight=w)
+            mean_aligned = overlay.shape.double().mean().item()
+            extra = zip(overlay.shape.tolist(), overlay.start.tolist(), overlay.colour.tolist(), overlay.score.tolist())
+            lines = [ln + ' %.6f %d' % (s, k) + (' %.6f %.6f' % (c, f) if colour else '') for ln, (s, k, c, f) in zip(lines, extra)]
+        lines = [ln + '\n' for ln in lines]
     with open(os.path.join(outdir, name + '_shape.txt'), 'w') as fh:
-        fh.write('# index volume nearest_sim nearest_index' + (' reference_shape_sim' if reference is not None else '') + '\n')
+        fh.write('# index volume nearest_sim nearest_index' + (' reference_shape_sim' if reference is not None else '')
+                 + (' aligned_shape_sim aligned_start' + (' aligned_colour_sim aligned_score' if colour else '') if align else '') + '\n')
         fh.writelines(lines)
     with open(os.path.join(outdir, name + '_shape_summary.txt'), 'w') as fh:
         fh.write('molecules: %d\ninternal_shape_diversity: %.6f\nmean_nearest_shape_similarity: %.6f\n' % (n, diversity, mean_near))
         if reference is not None:
             fh.write('mean_reference_shape_similarity: %.6f\n' % mean_ref)
+        if align:
+            fh.write('mean_aligned_reference_shape_similarity: %.6f\n' % mean_aligned)
+    return overlay
+
+
+def overlaid_onto_reference(m, rotation, translation):
+    """The molecule moved by the inverse of (R, t), the transform that puts the reference onto it: x -> R^T (x - t), hydrogens
+    included.  float64 on the host."""
+    r, t = np.asarray(rotation, dtype=np.float64), np.asarray(translation, dtype=np.float64)
+    move = lambda x: torch.as_tensor((np.asarray(x, dtype=np.float64).reshape(-1, 3) - t) @ r, dtype=torch.float32)     # noqa: E731
+    out = dict(m, atom_pos=move(m['atom_pos']))
+    if 'hydrogens' in m and 'h_pos' in m['hydrogens']:
+        out['hydrogens'] = dict(m['hydrogens'], h_pos=move(m['hydrogens']['h_pos']))
+    return out
 
 
 def main():
@@ -276,6 +307,12 @@ def main():
     ap.add_argument('--shape_reference', type=str, default=None, metavar='FILE.sdf',
                     help='implies --shape: the first mol block of the file, in the frame of the .phore file; adds the column '
                          'reference_shape_sim and the summary line mean_reference_shape_similarity')
+    ap.add_argument('--shape_align', action='store_true',
+                    help='with --shape --shape_reference: the best rigid overlay of the reference onto every finished molecule; adds the '
+                         'columns aligned_shape_sim aligned_start (with --shape_colour also aligned_colour_sim aligned_score) and the '
+                         'summary line mean_aligned_reference_shape_similarity')
+    ap.add_argument('--shape_align_sdf', action='store_true',
+                    help='with --shape_align: also writes every finished molecule overlaid onto the reference under <outdir>/sdf_aligned/')
     ap.add_argument('--num_steps', type=int, default=None, help='reverse steps of the sampler (default: the model\'s)')
     ap.add_argument('--sdf', action='store_true', help='write one .sdf per molecule under <outdir>/sdf_results/')
     args = ap.parse_args()
@@ -304,6 +341,9 @@ def main():
     if not 0.0 <= shape_weight <= 1.0:
         ap.error('--shape_colour_weight must lie in [0, 1]')
     args.features = args.features or args.shape_colour
+    args.shape_align = args.shape_align or args.shape_align_sdf
+    if args.shape_align and args.shape_reference is None:
+        ap.error('--shape_align needs --shape --shape_reference FILE')
     shape_reference = None
     if args.shape_reference is not None:
         try:
@@ -427,7 +467,17 @@ def main():
             if args.properties:
                 write_property_file(args.outdir, data.name, done)
             if args.shape:
-                write_shape_files(args.outdir, data.name, done, args.shape_colour, shape_weight, shape_reference)
+                overlay = write_shape_files(args.outdir, data.name, done, args.shape_colour, shape_weight, shape_reference, args.shape_align)
+                if args.shape_align_sdf:
+                    aligned_dir = os.path.join(args.outdir, 'sdf_aligned')
+                    os.makedirs(aligned_dir, exist_ok=True)
+                    moves = zip(overlay.rotation.tolist(), overlay.translation.tolist()) if overlay is not None else ()
+                    for i, (m, (rot, shift)) in enumerate(zip(done, moves)):
+                        n_h = len(m['hydrogens']['h_parent']) if 'hydrogens' in m else 0
+                        if m['status'] & STATUS_NONFINITE or m['bond_type'].numel() + n_h > 999:      # (the rule of sdf_results/ below)
+                            continue
+                        write_sdf(os.path.join(aligned_dir, f'{pidx}_{data.name}_{i}.sdf'), [overlaid_onto_reference(m, rot, shift)],
+                                  names=[f'{data.name}_{i}'])
             if args.scaffolds:
                 write_scaffold_files(args.outdir, data.name, done, not args.scaffold_plain, args.max_per_scaffold)
         while len(done) < args.num_samples and not args.valid_only:
