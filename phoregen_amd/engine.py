@@ -855,6 +855,11 @@ class Engine:
         return self.forward_inplace()
 
     TUNE_REPS = 6          # timing marks per candidate grid (five timed steps between them, behind one settling step)
+    TUNE_WARMUP = 3        # steps in front of the first candidate: the first steps of an engine pay one-time costs (kernel attributes, allocator)
+
+    def calibration_steps(self):
+        """How many steps `calibrate_tri_grid` runs when it times the candidates (`run_step(0)` .. `run_step(n - 1)`); 0: none is due."""
+        return 0 if self._tune is None else self.TUNE_WARMUP + len(self._tune['cands']) * self.TUNE_REPS
 
     def _set_tri_grid(self, grid):
         for i in self.tri_calls:
@@ -883,7 +888,7 @@ class Engine:
             self._set_tri_grid(self.tuned_tri_grid)
             return
         k = 0
-        for _ in range(3):                            # the first steps of an engine pay one-time costs (kernel attributes, allocator)
+        for _ in range(self.TUNE_WARMUP):
             run_step(k)
             k += 1
         marks = {}

@@ -11,6 +11,9 @@ Design differences that do not change results:
   * one step = one pre-built list of kernel launches (phoregen_amd/engine.py), transition fused in
     csrc/posterior.hip, no host synchronisation inside the loop.
 """
+import dataclasses
+import numbers
+
 import torch
 from torch import nn
 from torch.nn import functional as F
@@ -18,7 +21,7 @@ from torch.nn import functional as F
 from . import get_denoiser_net, get_phore_encoder
 from .common import GaussianSmearing, ShiftedSoftplus, TimeGaussianSmearing, get_beta_schedule
 from .transition import ContigousTransition, GeneralCategoricalTransition
-from .. import hip
+from .. import hip, posterior
 from ..engine import Engine
 from ..fragment import STREAM_EDGE, STREAM_NODE, STREAM_POS, as_fragment, fragment_atom_counts, fragment_layout
 from ..packing import ModelPack
@@ -67,17 +70,49 @@ class _LazyFloats(dict):
         return repr(dict(self.items()))
 
 
-def _posterior_cat(lib, frag_cls, frag_stream, args, stream, what):
-    """pg_posterior_categorical, or its fragment form when the batch carries a fragment (frag_cls [rows] int32, -1 = free)."""
-    if frag_cls is None:
-        hip.check(lib.pg_posterior_categorical(*args, stream), what)
-    else:
-        hip.check(lib.pg_posterior_categorical_frag(*args, frag_cls.data_ptr(), frag_stream, stream), what)
+def check_step(step, T):
+    """A reverse step is a row of the T-row transition tables (and of `SamplerState.t_table`): an integer in 0..T-1, else ValueError.
+    Host arithmetic: no GPU is touched."""
+    if isinstance(step, bool) or not isinstance(step, numbers.Integral) or not 0 <= step < T:
+        raise ValueError(f'phoregen_amd: reverse step {step!r} is not an integer in 0..{T - 1} (the sampler state was begun for {T} timesteps)')
 
 
-def _frag_pos_args(frag, pk):
-    """the trailing arguments of pg_posterior_position(_ctx)_frag"""
-    return (frag.node_cls.data_ptr(), frag.x0f.data_ptr(), pk.frag_tab[0].data_ptr(), pk.frag_tab[1].data_ptr(), STREAM_POS)
+@dataclasses.dataclass(eq=False)            # (compared and hashed by identity: the fields are tensors)
+class SamplerState:
+    """What `begin_sampling` sets up and `reverse_step` / `finish_sampling` carry (every field is set in `begin_sampling`)."""
+    eng: object                    # Engine of the batch: launch lists, workspace (`eng.ws` holds the carried one-hot types and coordinates)
+    plan: object                   # BatchPlan: topology of the batch
+    num_atoms: torch.Tensor        # [B] int64, host: atoms per graph
+    N: int                         # ligand rows of the batch
+    E: int                         # bond rows of the batch
+    B: int                         # graphs
+    T: int                         # timesteps the transition tables and `t_table` were built for: steps are 0..T-1
+    cpu: bool                      # rng='cpu': noise from torch's CPU generator in the reference's order
+    seed: int                      # Philox key of the device noise
+    return_traj: bool              # trajectories are recorded
+    n_steps: int                   # reverse steps the caller will run (frames of the trajectories - 1)
+    pipelined: bool                # `reverse_step` runs as a stage of the software pipeline (`_reverse_step_pipelined`)
+    next_step: object = None       # pipelined: the step whose features `prog_ahead` has embedded (None: nothing launched ahead)
+    t_table: object = None         # pipelined: [T, B] int64, row s = s -- the step counter the side lanes' posteriors read
+    x0_buf: object = None          # pipelined: [N,3] x0 in ligand rows, written by the Gaussian posterior
+    bond_drawn: object = None      # pipelined: event on lane 3 behind the bond draw, which the guidance on lane 0 waits for
+    centers: object = None         # [B,3] added back to coordinates
+    center_rows: object = None     # [N,3] `centers` per ligand row
+    graph_key: object = None       # [B] int32: id of each graph in the noise counters
+    guidance_batch: int = 0        # graphs the guidance energies average over
+    frag: object = None            # fragment tables on the device (fragment.fragment_layout), None: no graph carries a fragment
+    log_node: object = None        # two [N,12] buffers: log of the carried node types in [cur], the next one's in [1 - cur]
+    log_edge: object = None        # two [E,6] buffers, likewise for the bond types
+    cur: int = 0                   # which of the two log buffers holds the current state
+    node_traj: object = None       # [n_steps + 1, N, 12] or None
+    pos_traj: object = None        # [n_steps + 1, N, 3] or None (centres added from frame 1 on)
+    edge_traj: object = None       # [n_steps + 1, E, 6] or None
+    grad: object = None            # [N,3] sum of the guidance gradients of a step
+    cnt_ws: object = None          # [B] guidance scratch
+    mean_ws: object = None         # [B,3] guidance scratch
+    gtmp: object = None            # [N,3] one guidance energy's gradient
+    gc: object = None              # [B,3] target of the center_prox energy
+    x0: object = None              # [N,3] the denoiser's last predicted coordinates (model frame)
 
 
 class PhoreDiff(nn.Module):
@@ -393,8 +428,7 @@ class PhoreDiff(nn.Module):
                                  return_traj=return_traj, num_steps=num_steps, guidance_center=guidance_center,
                                  graph_ids=graph_ids, guidance_batch=guidance_batch, pipeline=pipeline and on_step is None,
                                  fragments=fragments)
-        T = self.num_timesteps
-        for i, step in enumerate(range(T)[::-1][:st.n_steps]):
+        for i, step in enumerate(range(st.T)[::-1][:st.n_steps]):
             self.reverse_step(st, i, step, pos_guidance_opt)
             if on_step is not None:
                 on_step(i, step, st.eng.ws.out_v, st.x0, st.eng.ws.out_bond)
@@ -413,7 +447,6 @@ class PhoreDiff(nn.Module):
             raise NotImplementedError("phoregen_amd: fragment-conditioned sampling runs with rng='device' only (rng='cpu' replays the "
                                       'reference, which has no fragment mode)')
         dev = self._device()
-        lib = hip.lib()
         B = int(num_atoms.numel())
         num_atoms = num_atoms.detach().cpu().long()
         batch_node = torch.repeat_interleave(torch.arange(B), num_atoms)
@@ -424,23 +457,21 @@ class PhoreDiff(nn.Module):
         h_phore, pos_phore = h_phore.to(dev), pos_phore.to(dev)
         eng.encode_phore(h_phore, pos_phore, phore_norm.to(dev), self.ex_col)
         N, E = plan.n_lig, plan.n_bond
-        st = type('SamplerState', (), {})()
-        st.eng, st.plan, st.num_atoms, st.N, st.E, st.B = eng, plan, num_atoms, N, E, B
-        st.cpu, st.seed, st.return_traj = rng == 'cpu', seed, return_traj
-        st.n_steps = self.num_timesteps if num_steps is None else num_steps
-        st.pipelined = bool(pipeline) and rng == 'device' and eng.pipelined_programs() is not None
-        st.next_step = None              # (pipelined: the step whose features `prog_ahead` has embedded)
-        # (pipelined: the posteriors of step s run on the side lanes, possibly while lane 0 has begun step s - 1: the step number they
-        #  read is a row of a table written once)
-        st.t_table = torch.arange(self.num_timesteps, dtype=torch.int64, device=dev).unsqueeze(1).expand(-1, max(B, 1)).contiguous() \
-            if st.pipelined else None
-        st.x0_buf = torch.empty(N, 3, device=dev) if st.pipelined else None
+        T = self.num_timesteps
+        st = SamplerState(eng=eng, plan=plan, num_atoms=num_atoms, N=N, E=E, B=B, T=T, cpu=rng == 'cpu', seed=seed, return_traj=return_traj,
+                          n_steps=T if num_steps is None else num_steps,
+                          pipelined=bool(pipeline) and rng == 'device' and eng.pipelined_programs() is not None)
+        if st.pipelined:
+            # the posteriors of step s run on the side lanes, possibly while lane 0 has begun step s - 1: the step number they read is a
+            # row of a table written once
+            st.t_table = torch.arange(T, dtype=torch.int64, device=dev).unsqueeze(1).expand(-1, max(B, 1)).contiguous()
+            st.x0_buf = torch.empty(N, 3, device=dev)
+            st.bond_drawn = torch.cuda.Event()
         st.centers = centers.to(dev).float().contiguous()                                # [B,3]
         st.center_rows = st.centers[plan.batch_node]                                     # [N,3]
         st.graph_key = (torch.arange(B) if graph_ids is None else graph_ids.detach().cpu()).to(torch.int32).to(dev)
         st.guidance_batch = int(guidance_batch) if guidance_batch else B
         # fragment-conditioned sampling: per-row tables, uploaded once (None: no graph carries a fragment -> today's kernels)
-        st.frag = None
         if fragments is not None:
             lay = fragment_layout(num_atoms, fragments, centers, edge_index)
             st.frag = lay.to(dev) if lay is not None else None
@@ -463,23 +494,20 @@ class PhoreDiff(nn.Module):
             # branch on logits = log prior; N(0,1) = the Gaussian posterior with mean 0 and sigma 1.  Counter step = T (never a
             # real step), so the initial noise is one more graph-keyed Philox stream
             s = hip.stream_ptr()
-            T = self.num_timesteps
             t0, t1 = torch.zeros(B, dtype=torch.int64, device=dev), torch.ones(B, dtype=torch.int64, device=dev)
             h_node, h_edge = torch.empty(N, 12, device=dev), torch.empty(E, 6, device=dev)
             for lp, tab, rows, K, sid, rg, row0, oh in ((lp_n, pk.node_tab, N, 12, 0, plan.lig_graph, plan.g_lig_off, h_node),
                                                         (lp_e, pk.edge_tab, E, 6, 1, plan.bond_graph, plan.g_bond_off, h_edge)):
                 logits = lp.float().to(dev).unsqueeze(0).expand(rows, K).contiguous()
                 scratch = torch.empty(rows, K, device=dev)
-                hip.check(lib.pg_posterior_categorical(
-                    logits.data_ptr(), logits.data_ptr(), rg.data_ptr(), t0.data_ptr(), tab[0].data_ptr(), tab[1].data_ptr(),
-                    rows, K, None, seed, sid, T, row0.data_ptr(), st.graph_key.data_ptr(), scratch.data_ptr(), oh.data_ptr(),
-                    None, s), 'init types')
+                posterior.categorical(logits=logits, log_vt_in=logits, row_graph=rg, time_step=t0, q_mats=tab[0], q_onestep_T=tab[1],
+                                      n_rows=rows, K=K, seed=seed, stream_id=sid, step=T, graph_row0=row0, graph_key=st.graph_key,
+                                      log_vt_out=scratch, onehot_out=oh, stream=s, what='init types')
             ones, zx = torch.ones(2, device=dev), torch.zeros(N, 3, device=dev)
             pos = torch.empty(N, 3, device=dev)
-            hip.check(lib.pg_posterior_position(
-                zx.data_ptr(), zx.data_ptr(), plan.lig_graph.data_ptr(), t1.data_ptr(), ones.data_ptr(), ones.data_ptr(),
-                ones.data_ptr(), None, None, seed, 2, T, N, plan.g_lig_off.data_ptr(), st.graph_key.data_ptr(), None,
-                pos.data_ptr(), None, s), 'init positions')
+            posterior.position(x_t=zx, x0=zx, row_graph=plan.lig_graph, time_step=t1, coef_x0=ones, coef_xt=ones, std=ones, n_rows=N,
+                               seed=seed, stream_id=2, step=T, graph_row0=plan.g_lig_off, graph_key=st.graph_key, x_prev=pos, stream=s,
+                               what='init positions')
             pos -= st.center_rows
 
         st.log_node = [torch.log(h_node.clamp(min=1e-30)), torch.empty(N, 12, device=dev)]   # common.py:398-402
@@ -487,15 +515,13 @@ class PhoreDiff(nn.Module):
         if st.frag is not None:
             # fixed rows: the forward-process draw at level T - 1 (types, carried log-state, coordinates in the model frame)
             f, ft = st.frag, pk.frag_tab
-            hip.check(lib.pg_fragment_noise(
-                self.num_timesteps - 1, seed, N, E, f.node_cls.data_ptr(), f.edge_cls.data_ptr(), f.x0f.data_ptr(),
-                plan.lig_graph.data_ptr(), plan.bond_graph.data_ptr(), plan.g_lig_off.data_ptr(), plan.g_bond_off.data_ptr(),
-                st.graph_key.data_ptr(), pk.node_tab[0].data_ptr(), pk.edge_tab[0].data_ptr(), ft[0].data_ptr(), ft[1].data_ptr(),
-                STREAM_NODE, STREAM_EDGE, STREAM_POS, h_node.data_ptr(), st.log_node[0].data_ptr(), h_edge.data_ptr(),
-                st.log_edge[0].data_ptr(), pos.data_ptr(), hip.stream_ptr()), 'fragment init')
-        st.cur = 0
+            posterior.fragment_noise(level=T - 1, seed=seed, n_lig=N, n_bond=E, node_cls=f.node_cls, edge_cls=f.edge_cls, x0f=f.x0f,
+                                     lig_graph=plan.lig_graph, bond_graph=plan.bond_graph, g_lig_off=plan.g_lig_off,
+                                     g_bond_off=plan.g_bond_off, graph_key=st.graph_key, q_node=pk.node_tab[0], q_edge=pk.edge_tab[0],
+                                     sqrt_ab=ft[0], sqrt_1mab=ft[1], node_stream_id=STREAM_NODE, edge_stream_id=STREAM_EDGE,
+                                     pos_stream_id=STREAM_POS, h_node=h_node, log_node=st.log_node[0], h_edge=h_edge,
+                                     log_edge=st.log_edge[0], x_out=pos, stream=hip.stream_ptr(), what='fragment init')
         w.in_h_node.copy_(h_node), w.in_pos.copy_(pos), w.in_h_edge.copy_(h_edge)
-        st.node_traj = st.pos_traj = st.edge_traj = None
         if return_traj:
             st.node_traj = torch.zeros(st.n_steps + 1, N, 12, device=dev)
             st.pos_traj = torch.zeros(st.n_steps + 1, N, 3, device=dev)
@@ -516,21 +542,23 @@ class PhoreDiff(nn.Module):
             sums = torch.zeros(B, 3).index_add_(0, bp, pos_phore.float().cpu() * keep)
             cnt = torch.zeros(B, 1).index_add_(0, bp, keep)
             st.gc = (sums / cnt).to(dev).contiguous()      # (0/0 = nan for a pharmacophore of exclusion spheres only, as in the reference)
-        st.x0 = None
-        if getattr(eng, '_tune', None) is not None and not st.cpu:
+        if eng._tune is not None and not st.cpu:
             self._calibrate_launch_configuration(st)
         return st
 
     def _calibrate_launch_configuration(self, st):
         """Small batches: `Engine.calibrate_tri_grid` times a few REAL sampler steps per candidate grid -- here, before the caller's loop, on the
         state just initialised, which is put back afterwards (the device noise is counter-based: nothing is consumed; no trajectory frame is
-        written).  The loop then runs a fixed launch list with no host synchronisation in it (round-5 review, item 8)."""
-        eng, w = st.eng, st.eng.ws
+        written).  The loop then runs a fixed launch list with no host synchronisation in it (round-5 review, item 8).  The calibration steps
+        are T - 1, T - 2, ...: a schedule with fewer timesteps than it would run is not calibrated and keeps the default grid."""
+        eng, w, T = st.eng, st.eng.ws, st.T
+        if T < eng.calibration_steps():
+            eng._tune = None                 # a schedule shorter than the calibration has no such steps to run: the default grid stays
+            return
         saved = [t.clone() for t in (w.in_h_node, w.in_pos, w.in_h_edge, st.log_node[0], st.log_edge[0])]
         keep = (st.node_traj, st.pos_traj, st.edge_traj, st.return_traj, st.n_steps)
         st.node_traj = st.pos_traj = st.edge_traj = None
-        st.return_traj, st.n_steps = False, self.num_timesteps
-        T = self.num_timesteps
+        st.return_traj, st.n_steps = False, T
         try:
             eng.calibrate_tri_grid(lambda k: self.reverse_step(st, k, T - 1 - k))
         finally:
@@ -546,61 +574,71 @@ class PhoreDiff(nn.Module):
     def reverse_step(self, st, i, step, pos_guidance_opt=None, draws=None):
         """One iteration of the loop at diffusion.py:432-517 on the state held in the engine workspace.
         `draws` = (u_node [N,12], u_edge [E,6], eps [N,3]) overrides the noise source (teacher-forced tests)."""
-        if getattr(st, 'pipelined', False):
+        check_step(step, st.T)
+        if st.pipelined:
             if draws is not None:
                 raise RuntimeError('phoregen_amd: reverse_step(draws=...) on a pipelined sampler state (begin_sampling(pipeline=True))')
             return self._reverse_step_pipelined(st, i, step, pos_guidance_opt)
-        lib, eng, plan = hip.lib(), st.eng, st.plan
-        pk, w, N, E = eng.pack, eng.ws, st.N, st.E
-        dev = self._device()
-        tp = lambda tr: tr[i + 1].data_ptr() if tr is not None else None
+        w, N, E, dev = st.eng.ws, st.N, st.E, self._device()
         w.in_t.fill_(step)
-        _, st.x0, _ = eng.forward_inplace()
+        _, st.x0, _ = st.eng.forward_inplace()
         s = hip.stream_ptr()
         un = ue = eps = None
         if draws is not None:
             un, ue, eps = (d.to(dev).contiguous() for d in draws)
         elif st.cpu:                                                 # Appendix B item 5: rand, rand, then randn
             un, ue = torch.rand(N, 12).to(dev), torch.rand(E, 6).to(dev)
-        cur = st.cur
-        frag = getattr(st, 'frag', None)
-        _posterior_cat(lib, frag and frag.node_cls, STREAM_NODE, (
-            w.out_v.data_ptr(), st.log_node[cur].data_ptr(), plan.lig_graph.data_ptr(), w.in_t.data_ptr(),
-            pk.node_tab[0].data_ptr(), pk.node_tab[1].data_ptr(), N, 12, hip.ptr(un), st.seed, 0, step,
-            plan.g_lig_off.data_ptr(), st.graph_key.data_ptr(),
-            st.log_node[1 - cur].data_ptr(), w.in_h_node.data_ptr(), tp(st.node_traj)), s, 'posterior(node)')
-        _posterior_cat(lib, frag and frag.edge_cls, STREAM_EDGE, (
-            w.out_bond.data_ptr(), st.log_edge[cur].data_ptr(), plan.bond_graph.data_ptr(), w.in_t.data_ptr(),
-            pk.edge_tab[0].data_ptr(), pk.edge_tab[1].data_ptr(), E, 6, hip.ptr(ue), st.seed, 1, step,
-            plan.g_bond_off.data_ptr(), st.graph_key.data_ptr(),
-            st.log_edge[1 - cur].data_ptr(), w.in_h_edge.data_ptr(), tp(st.edge_traj)), s, 'posterior(edge)')
-        grad = None
-        if pos_guidance_opt:                                         # diffusion.py:476-502
-            grad = st.grad
-            grad.zero_()
-            for o in pos_guidance_opt:
-                atom = o['type'] == 'atom_prox'
-                if not atom and o['type'] != 'center_prox':
-                    continue
-                hip.check(lib.pg_guidance_grad(
-                    plan.topo_ref, w.in_pos.data_ptr(), w.in_h_edge.data_ptr(), plan.lig_graph.data_ptr(),
-                    plan.g_lig_off.data_ptr(), int(atom), float(o.get('min_d', 1.2)), float(o.get('max_d', 2.8)),
-                    int(not atom), hip.ptr(st.gc), st.guidance_batch, st.cnt_ws.data_ptr(), st.mean_ws.data_ptr(),
-                    st.gtmp.data_ptr(), s),
-                    'guidance')
-                grad += st.gtmp
+        self._draw_types(st, i, step, w.in_t, s, s, un, ue)
+        grad = self._guidance_grad(st, pos_guidance_opt, s)
         if draws is None and st.cpu:
             eps = torch.randn(N, 3).to(dev)
-        args = (w.in_pos.data_ptr(), st.x0.data_ptr(), plan.lig_graph.data_ptr(), w.in_t.data_ptr(),
-                pk.pos_tab[0].data_ptr(), pk.pos_tab[1].data_ptr(), pk.pos_tab[2].data_ptr(), hip.ptr(grad), hip.ptr(eps),
-                st.seed, 2, step, N, plan.g_lig_off.data_ptr(), st.graph_key.data_ptr(),
-                st.centers.data_ptr() if st.return_traj else None,
-                w.in_pos.data_ptr(), tp(st.pos_traj))                                # in place: x_t -> x_{t-1}
-        if frag is None:
-            hip.check(lib.pg_posterior_position(*args, s), 'posterior(pos)')
-        else:
-            hip.check(lib.pg_posterior_position_frag(*args, *_frag_pos_args(frag, pk), s), 'posterior(pos)')
-        st.cur = 1 - cur
+        self._draw_positions(st, i, step, w.in_t, st.x0, grad, s, eps=eps)
+        st.cur = 1 - st.cur
+
+    # ---- the transition half of a step, one copy for the plain and the pipelined loop, which hand in what differs: `t` ([B] int64, the
+    #      step counter the kernels read), the stream of each launch, given draws, the x0 source ----
+    def _draw_types(self, st, i, step, t, s_node, s_edge, u_node=None, u_edge=None):
+        """Node and bond types of the next state from the heads' logits (transition.py:285-315)."""
+        plan, pk, w, cur, frag = st.plan, st.eng.pack, st.eng.ws, st.cur, st.frag
+        frame = lambda traj: None if traj is None else traj[i + 1]
+        posterior.categorical(logits=w.out_v, log_vt_in=st.log_node[cur], row_graph=plan.lig_graph, time_step=t, q_mats=pk.node_tab[0],
+                              q_onestep_T=pk.node_tab[1], n_rows=st.N, K=12, uniform=u_node, seed=st.seed, stream_id=0, step=step,
+                              graph_row0=plan.g_lig_off, graph_key=st.graph_key, log_vt_out=st.log_node[1 - cur], onehot_out=w.in_h_node,
+                              traj_out=frame(st.node_traj), frag_cls=frag and frag.node_cls, frag_stream_id=STREAM_NODE, stream=s_node,
+                              what='posterior(node)')
+        posterior.categorical(logits=w.out_bond, log_vt_in=st.log_edge[cur], row_graph=plan.bond_graph, time_step=t, q_mats=pk.edge_tab[0],
+                              q_onestep_T=pk.edge_tab[1], n_rows=st.E, K=6, uniform=u_edge, seed=st.seed, stream_id=1, step=step,
+                              graph_row0=plan.g_bond_off, graph_key=st.graph_key, log_vt_out=st.log_edge[1 - cur], onehot_out=w.in_h_edge,
+                              traj_out=frame(st.edge_traj), frag_cls=frag and frag.edge_cls, frag_stream_id=STREAM_EDGE, stream=s_edge,
+                              what='posterior(edge)')
+
+    def _guidance_grad(self, st, pos_guidance_opt, s):
+        """`st.grad` = the summed gradient of the guidance energies at the bond types just drawn (diffusion.py:476-502); None: no guidance."""
+        if not pos_guidance_opt:
+            return None
+        plan, w, grad = st.plan, st.eng.ws, st.grad
+        grad.zero_()
+        for o in pos_guidance_opt:
+            atom = o['type'] == 'atom_prox'
+            if not atom and o['type'] != 'center_prox':
+                continue
+            posterior.guidance_grad(topo=plan.topo_ref, x_lig=w.in_pos, h_edge_prev=w.in_h_edge, lig_graph=plan.lig_graph,
+                                    g_lig_off=plan.g_lig_off, atom_prox=atom, min_d=o.get('min_d', 1.2), max_d=o.get('max_d', 2.8),
+                                    center_prox=not atom, phore_center=st.gc, mean_over_graphs=st.guidance_batch, cnt_ws=st.cnt_ws,
+                                    mean_ws=st.mean_ws, grad=st.gtmp, stream=s)
+            grad += st.gtmp
+        return grad
+
+    def _draw_positions(self, st, i, step, t, x0, grad, s, **extra):
+        """Coordinates of the next state (transition.py:44-63), in place in the engine's `in_pos`.  `x0` in ligand rows, or the denoiser's
+        ctx-ordered buffer with `extra` = the _ctx form's lig2ctx / x_ctx_next / x0_out; `extra` = eps hands the normal draws in."""
+        plan, pk, w, frag = st.plan, st.eng.pack, st.eng.ws, st.frag
+        if frag is not None:
+            extra.update(frag_cls=frag.node_cls, x0f=frag.x0f, sqrt_ab=pk.frag_tab[0], sqrt_1mab=pk.frag_tab[1], frag_stream_id=STREAM_POS)
+        posterior.position(x_t=w.in_pos, x0=x0, row_graph=plan.lig_graph, time_step=t, coef_x0=pk.pos_tab[0], coef_xt=pk.pos_tab[1],
+                           std=pk.pos_tab[2], energy_grad=grad, seed=st.seed, stream_id=2, step=step, n_rows=st.N,
+                           graph_row0=plan.g_lig_off, graph_key=st.graph_key, center=st.centers if st.return_traj else None,
+                           x_prev=w.in_pos, traj_out=None if st.pos_traj is None else st.pos_traj[i + 1], stream=s, **extra)
 
     def _reverse_step_pipelined(self, st, i, step, pos_guidance_opt=None):
         """`reverse_step` as one stage of a software pipeline over the reverse steps (device RNG).  The order of a step's results is
@@ -611,8 +649,7 @@ class PhoreDiff(nn.Module):
         the Gaussian posterior and the next step's coordinate embedding / knn search on lanes 0 / 1.  Same kernels on the same operands
         as `reverse_step`: the trajectory is the same bit for bit (tests/test_gpu_parity.py)."""
         lib, eng, plan = hip.lib(), st.eng, st.plan
-        pk, w, N, E = eng.pack, eng.ws, st.N, st.E
-        tp = lambda tr: tr[i + 1].data_ptr() if tr is not None else None
+        pk, w = eng.pack, eng.ws
         s2, s3 = eng.lane_stream(2), eng.lane_stream(3)
         if st.next_step is None:                       # first step: nothing was launched ahead yet
             # the initial coordinates into the denoiser's buffer (from then on the Gaussian posterior writes them there itself)
@@ -626,58 +663,25 @@ class PhoreDiff(nn.Module):
             eng._run(eng.prog_ahead)
         elif st.next_step != step:
             raise RuntimeError(f'phoregen_amd: pipelined sampler state expects step {st.next_step}, got {step}')
-        tb = st.t_table.data_ptr() + step * st.t_table.stride(0) * 8        # the [B] row `step` of the table: no fill launch
+        tb = st.t_table[step]                          # the [B] row `step` of the table: no fill launch
         _, x0_ctx, _ = eng.step_forward()
-        cur = st.cur
-        frag = getattr(st, 'frag', None)
-        _posterior_cat(lib, frag and frag.node_cls, STREAM_NODE, (
-            w.out_v.data_ptr(), st.log_node[cur].data_ptr(), plan.lig_graph.data_ptr(), tb,
-            pk.node_tab[0].data_ptr(), pk.node_tab[1].data_ptr(), N, 12, None, st.seed, 0, step,
-            plan.g_lig_off.data_ptr(), st.graph_key.data_ptr(),
-            st.log_node[1 - cur].data_ptr(), w.in_h_node.data_ptr(), tp(st.node_traj)), s2.cuda_stream, 'posterior(node)')
-        _posterior_cat(lib, frag and frag.edge_cls, STREAM_EDGE, (
-            w.out_bond.data_ptr(), st.log_edge[cur].data_ptr(), plan.bond_graph.data_ptr(), tb,
-            pk.edge_tab[0].data_ptr(), pk.edge_tab[1].data_ptr(), E, 6, None, st.seed, 1, step,
-            plan.g_bond_off.data_ptr(), st.graph_key.data_ptr(),
-            st.log_edge[1 - cur].data_ptr(), w.in_h_edge.data_ptr(), tp(st.edge_traj)), s3.cuda_stream, 'posterior(edge)')
+        self._draw_types(st, i, step, tb, s2.cuda_stream, s3.cuda_stream)
         last = step == 0 or i + 1 >= st.n_steps
         if pos_guidance_opt:
             # the guidance below (lane 0, on the way to the next step's coordinates) reads the bond types just drawn: it waits for THIS point
             # of lane 3, not for what `prog_ahead` puts behind it (bond embedding, bond-node rows and attention of the next step)
-            if getattr(st, 'bond_drawn', None) is None:
-                st.bond_drawn = torch.cuda.Event()
             st.bond_drawn.record(s3)
         if not last:
             with torch.cuda.stream(s2):
                 w.in_t_next.fill_(step - 1)
             eng._run(eng.prog_ahead)
         s = hip.stream_ptr()
-        grad = None
-        if pos_guidance_opt:                                         # diffusion.py:476-502 (reads the bond types just drawn on lane 3)
+        if pos_guidance_opt:
             torch.cuda.current_stream().wait_event(st.bond_drawn)
-            grad = st.grad
-            grad.zero_()
-            for o in pos_guidance_opt:
-                atom = o['type'] == 'atom_prox'
-                if not atom and o['type'] != 'center_prox':
-                    continue
-                hip.check(lib.pg_guidance_grad(
-                    plan.topo_ref, w.in_pos.data_ptr(), w.in_h_edge.data_ptr(), plan.lig_graph.data_ptr(),
-                    plan.g_lig_off.data_ptr(), int(atom), float(o.get('min_d', 1.2)), float(o.get('max_d', 2.8)),
-                    int(not atom), hip.ptr(st.gc), st.guidance_batch, st.cnt_ws.data_ptr(), st.mean_ws.data_ptr(),
-                    st.gtmp.data_ptr(), s), 'guidance')
-                grad += st.gtmp
-        args = (w.in_pos.data_ptr(), x0_ctx.data_ptr(), plan.lig2ctx.data_ptr(), plan.lig_graph.data_ptr(), tb,
-                pk.pos_tab[0].data_ptr(), pk.pos_tab[1].data_ptr(), pk.pos_tab[2].data_ptr(), hip.ptr(grad), None,
-                st.seed, 2, step, N, plan.g_lig_off.data_ptr(), st.graph_key.data_ptr(),
-                st.centers.data_ptr() if st.return_traj else None,
-                w.in_pos.data_ptr(), tp(st.pos_traj), w.x[0].data_ptr(), st.x0_buf.data_ptr())
-        if frag is None:
-            hip.check(lib.pg_posterior_position_ctx(*args, s), 'posterior(pos)')
-        else:
-            hip.check(lib.pg_posterior_position_ctx_frag(*args, *_frag_pos_args(frag, pk), s), 'posterior(pos)')
+        grad = self._guidance_grad(st, pos_guidance_opt, s)
+        self._draw_positions(st, i, step, tb, x0_ctx, grad, s, lig2ctx=plan.lig2ctx, x_ctx_next=w.x[0], x0_out=st.x0_buf)
         st.x0 = st.x0_buf
-        st.cur = 1 - cur
+        st.cur = 1 - st.cur
         st.next_step = step - 1
         if last:
             eng.join_lanes((2, 3))
@@ -685,12 +689,12 @@ class PhoreDiff(nn.Module):
     @_on_model_device
     def finish_sampling(self, st):
         w, plan = st.eng.ws, st.plan
-        if getattr(st, 'pipelined', False):
-            st.eng.join_lanes((2, 3))              # (out_v / out_bond / the discrete trajectories are completed on the side lanes)
+        if st.pipelined:
+            st.eng.join_lanes((2, 3))             # (out_v / out_bond / the discrete trajectories are completed on the side lanes)
         res = {'pred': [w.out_v.clone(), st.x0 + st.center_rows, w.out_bond.clone()],
                'traj': [st.node_traj, st.pos_traj, st.edge_traj],
                'lig_info': [st.num_atoms.to(self._device()), plan.batch_node, plan.edge_index, plan.batch_edge]}
-        f = getattr(st, 'frag', None)
+        f = st.frag
         if f is not None:
             # fixed rows: the fragment verbatim -- its world coordinates as given, logits 0 at the fixed class and -32 elsewhere
             nf, ef = f.node_fixed, f.edge_fixed

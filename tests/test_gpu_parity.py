@@ -1071,6 +1071,35 @@ def test_online_grid_tuning_does_not_change_the_trajectory(model):
     assert len(tuned) == len(plain) and all(torch.equal(a, b) for a, b in zip(tuned, plain))
 
 
+def test_short_schedule_is_not_calibrated(model):
+    """The grid calibration runs steps T - 1, T - 2, ... on scratch state: a schedule of 4 timesteps (the short-schedule fixtures) has fewer than
+    it would run, so `begin_sampling` runs none of them -- no step outside 0..3 is ever handed to `reverse_step` -- and the engine keeps its
+    default grid."""
+    from bench import ligphore_workload
+    from phoregen_amd import engine as engine_mod
+    w = ligphore_workload(3)
+    steps, due = [], []
+    step_fn, calibrate = model.reverse_step, model._calibrate_launch_configuration
+    old_T, cache = model.num_timesteps, dict(engine_mod._TRI_GRID_CACHE)
+    try:
+        model.num_timesteps = 4
+        model._engine = None
+        engine_mod._TRI_GRID_CACHE.clear()
+        model.reverse_step = lambda st, i, step, *a, **kw: (steps.append(step), step_fn(st, i, step, *a, **kw))[1]
+        model._calibrate_launch_configuration = lambda st: (due.append(st.eng.calibration_steps()), calibrate(st))[1]
+        st = model.begin_sampling(w['h_phore'], w['pos_phore'], w['phore_norm'], w['batch_phore'], w['num_atoms'], torch.zeros(3, 3),
+                                  rng='device', seed=5, num_steps=1)
+    finally:
+        del model.reverse_step, model._calibrate_launch_configuration
+        model.num_timesteps = old_T
+        model._engine = None
+        engine_mod._TRI_GRID_CACHE.clear()
+        engine_mod._TRI_GRID_CACHE.update(cache)
+    assert st.T == 4 and due and due[0] > 4                  # a calibration was due, of more steps than the schedule has
+    assert all(0 <= s <= 3 for s in steps) and steps == []
+    assert st.eng._tune is None and st.eng.tuned_tri_grid is None
+
+
 def test_triplet_launch_split_by_row_tiles_is_bit_identical(model):
     """A batch with a few 51+-atom ligands among smaller ones runs the staged triplet kernel as two launches -- the ligands of up to 50 atoms
     on the 3-tile instance, the larger ones with their own queue (BatchPlan.tri_split, PgSegAttn.tri_max_nlig): every segment sees the same

@@ -303,3 +303,59 @@ def test_entry_points_refuse_before_any_launch():
         frag[missing] = N
         assert pos(1, frag=frag) == ERR_ARG and lib.pg_last_error().startswith(b'pg_posterior_position_frag:')
         assert pos(1, ctx=(p, p), frag=frag) == ERR_ARG and lib.pg_last_error().startswith(b'pg_posterior_position_ctx_frag:')
+
+
+# ---- the keyword wrappers of phoregen_amd/posterior.py: which entry point each call reaches (no GPU: nothing is launched) ----
+_T = torch.zeros(4, dtype=torch.int32)                  # a tensor whose (host) address nothing may dereference
+_CAT = dict(logits=None, log_vt_in=None, row_graph=None, time_step=None, q_mats=None, q_onestep_T=None, seed=1, stream_id=0, step=0,
+            graph_row0=None, graph_key=None, log_vt_out=None, onehot_out=None, stream=None)
+_POS = dict(x_t=None, x0=None, row_graph=None, time_step=None, coef_x0=None, coef_xt=None, std=None, seed=1, stream_id=2, step=0,
+            graph_row0=None, graph_key=None, x_prev=None, stream=None)
+_CTX = dict(lig2ctx=_T, x_ctx_next=_T, x0_out=_T)
+_FRAG = dict(frag_cls=_T, x0f=_T, sqrt_ab=_T, sqrt_1mab=_T, frag_stream_id=5)
+_NOISE = dict(level=3, seed=1, node_cls=None, edge_cls=None, x0f=None, lig_graph=None, bond_graph=None, g_lig_off=None, g_bond_off=None,
+              graph_key=None, q_node=None, q_edge=None, sqrt_ab=None, sqrt_1mab=None, node_stream_id=3, edge_stream_id=4, pos_stream_id=5,
+              stream=None)
+
+
+def _refused(prefix, fn, **kw):
+    with pytest.raises(RuntimeError) as e:
+        fn(**kw)
+    assert f': {prefix}: ' in str(e.value), str(e.value)
+
+
+def test_wrappers_return_on_zero_rows_for_every_entry_point():
+    from phoregen_amd import hip, posterior
+    posterior.categorical(n_rows=0, K=12, **_CAT)
+    posterior.categorical(n_rows=0, K=6, frag_cls=_T, frag_stream_id=3, **_CAT)
+    for ctx in ({}, _CTX):
+        for frag in ({}, _FRAG):
+            posterior.position(n_rows=0, **_POS, **ctx, **frag)
+    posterior.fragment_noise(n_lig=0, n_bond=0, **_NOISE)
+    posterior.guidance_grad(topo=C.byref(hip.PgTopo()), x_lig=None, h_edge_prev=None, lig_graph=None, g_lig_off=None, atom_prox=True,
+                            min_d=1.2, max_d=2.8, center_prox=False, phore_center=None, mean_over_graphs=0, cnt_ws=None, mean_ws=None,
+                            grad=None, stream=None)
+
+
+def test_wrappers_pick_the_entry_point_from_what_they_are_given():
+    """Inputs the library refuses before it launches anything; its error text names the entry point that was reached."""
+    from phoregen_amd import posterior
+    _refused('pg_posterior_categorical', posterior.categorical, n_rows=1, K=5, **_CAT)
+    _refused('pg_posterior_categorical_frag', posterior.categorical, n_rows=1, K=5, frag_cls=_T, frag_stream_id=3, **_CAT)
+    for table in ('frag_cls', 'x0f', 'sqrt_ab', 'sqrt_1mab'):
+        frag = dict(_FRAG, **{table: None})
+        _refused('pg_posterior_position_frag', posterior.position, n_rows=1, **_POS, **frag)
+        _refused('pg_posterior_position_ctx_frag', posterior.position, n_rows=1, **dict(_POS, x0=_T), **_CTX, **frag)
+    _refused('pg_posterior_position_ctx', posterior.position, n_rows=1, **_POS, **_CTX)                       # x0 missing
+    _refused('pg_posterior_position_ctx_frag', posterior.position, n_rows=1, **_POS, **_CTX, **_FRAG)
+    _refused('pg_posterior_position_ctx', posterior.position, n_rows=1, **dict(_POS, x0=_T), x_ctx_next=_T)   # lig2ctx missing
+    _refused('pg_fragment_noise', posterior.fragment_noise, n_lig=1, n_bond=0, **_NOISE)
+
+
+@pytest.mark.parametrize('T', [4, 1000])
+def test_step_check(T):
+    from phoregen_amd.models.diffusion import check_step
+    check_step(0, T), check_step(T - 1, T), check_step(np.int64(T - 1), T)
+    for bad in (-1, T, 0.5, float(T - 1), None, '0', True):
+        with pytest.raises(ValueError):
+            check_step(bad, T)

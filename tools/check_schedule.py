@@ -222,8 +222,8 @@ class Timeline:
 
 def caller_launches(tl, st, eng, buf, i, guided, tag):
     """The launches `PhoreDiff._reverse_step_pipelined` adds around the two programs (phoregen_amd/models/diffusion.py: keep in step with it):
-    node posterior on lane 2, bond posterior on lane 3, [the bond_drawn point], the step counter of the next step on lane 2, `prog_ahead`,
-    then on lane 0 the guidance (behind bond_drawn) and the Gaussian posterior."""
+    node posterior on lane 2, bond posterior on lane 3 (`_draw_types`), [the bond_drawn point], the step counter of the next step on lane 2,
+    `prog_ahead`, then on lane 0 the guidance (behind bond_drawn; `_guidance_grad`) and the Gaussian posterior (`_draw_positions`)."""
     w = eng.ws
     reg = lambda t: buf.region(t.data_ptr())
     cur = i % 2
