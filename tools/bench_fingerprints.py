@@ -9,41 +9,15 @@ and pg_mol_key on the final frame of the 128-graph headline batch and on its who
 and pg_fp_nearest at rows x rows, pg_fp_nearest at job_rows x job_rows (the config-4 job's set), pg_fp_maxmin for `picks` of job_rows.
 The torch yardstick unpacks the bits to fp16, takes the intersections with `matmul` and divides (in row blocks where the matrix would
 not fit); pairs/s are held against the popcount form's bound of DESIGN.md 2.9, which is arithmetic, not a measurement."""
-import argparse
-import os
-import statistics
-import sys
 import time
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
-from bench import ligphore_workload  # noqa: E402
-from bench_mol_key import key_kernel_ms  # noqa: E402
-from phoregen_amd import hip, molecule as M, similarity as S  # noqa: E402
-from phoregen_amd.config import default_model_config  # noqa: E402
-from phoregen_amd.models.diffusion import PhoreDiff  # noqa: E402
-from phoregen_amd.weights import init_deterministic_  # noqa: E402
+from mol_bench import event_ms, headline_run, parser      # first: puts the repository root on sys.path
+from bench_mol_key import key_kernel_ms
+from phoregen_amd import hip, molecule as M, similarity as S
 
 BOUND_PAIRS = 39e12 / 128         # lane-operations per second over the 64 v_and_b32 + 64 v_bcnt_u32_b32 of a pair
-
-
-def event_ms(fn, repeats, warmup=2):
-    """(median, min, max) of `repeats` event-timed calls after `warmup` calls."""
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(repeats):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        fn()
-        e1.record()
-        e1.synchronize()
-        ts.append(e0.elapsed_time(e1))
-    return statistics.median(ts), min(ts), max(ts)
 
 
 def fp_kernel_ms(sc, repeats, radius=M.FP_RADIUS):
@@ -51,7 +25,7 @@ def fp_kernel_ms(sc, repeats, radius=M.FP_RADIUS):
     fp = torch.empty(F, B, M.FP_WORDS, dtype=torch.int64, device=sc.cls.device)
     bits = torch.empty(F, B, dtype=torch.int32, device=sc.cls.device)
     lib = hip.lib()
-    return event_ms(lambda: M._launch_fp(lib, sc.cls, sc.order, sc.lig_off, sc.bond_off, B, F, max(sc.num_atoms), radius, fp, bits), repeats)
+    return event_ms(lambda: M._launch_fp(lib, sc.cls, sc.order, sc.lig_off, sc.bond_off, B, F, max(sc.num_atoms), radius, fp, bits), repeats, 2)
 
 
 def random_rows(n, seed):
@@ -109,16 +83,14 @@ def torch_maxmin(xa, pa, k):
     return picked
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--steps', type=int, default=1000, help='reverse steps of the sampled trajectory (frames = steps + 1)')
-    ap.add_argument('--graphs', type=int, default=128)
+def main(argv=None):
+    ap = parser()
     ap.add_argument('--rows', type=int, default=16384)
     ap.add_argument('--job_rows', type=int, default=102400)
     ap.add_argument('--picks', type=int, default=1000)
-    ap.add_argument('--out', type=str, default=None)
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     dev = 'cuda'
+    record = {}
     lines = ['# Fingerprints and similarity (`pg_mol_fp`, `pg_fp_tanimoto`, `pg_fp_nearest`, `pg_fp_maxmin`): timing', '',
              f'`python tools/bench_fingerprints.py --steps {args.steps} --rows {args.rows} --job_rows {args.job_rows} --picks {args.picks}` on '
              f'{torch.cuda.get_device_name(0)}.  HIP events around the call alone, warm, median (min .. max) of the repeats.  The bound is '
@@ -127,17 +99,14 @@ def main():
              'bits unpacked to fp16, the intersections by `matmul`, then the division.', '']
 
     # ---- (a) the fingerprint kernel beside the key kernel -------------------------------------------------------------------------
-    model = init_deterministic_(PhoreDiff(default_model_config(), 'zinc_300'), 0).eval().to(dev)
-    w = ligphore_workload(args.graphs)
-    res = model.sample_batch(w['h_phore'], w['pos_phore'], w['phore_norm'], w['batch_phore'], w['num_atoms'], torch.zeros(args.graphs, 3),
-                             rng='device', seed=1, num_steps=args.steps, return_traj=True)
-    torch.cuda.synchronize()
+    _, _, res, _, _ = headline_run(args.graphs, args.steps, warm=False)
     lines += [f'## `pg_mol_fp` beside `pg_mol_key` ({args.graphs} graphs, radius {M.FP_RADIUS})', '',
               '| frames | `pg_mol_fp` ms | `pg_mol_key` ms |', '|---|---|---|']
     for frames, reps in (('final', 50), ('traj', 7)):
         sc = M.screen(res, frames=frames)
         f, k = fp_kernel_ms(sc, reps), key_kernel_ms(sc, reps)
         lines.append(f'| {sc.status.size(0)} | {f[0]:.3f} ({f[1]:.3f} .. {f[2]:.3f}) | {k[0]:.3f} ({k[1]:.3f} .. {k[2]:.3f}) |')
+        record['fp_ms_' + frames], record['key_ms_' + frames] = f[0], k[0]
     del res, sc
     lines.append('')
 
@@ -149,19 +118,20 @@ def main():
         rate = pairs / (t[0] * 1e-3)
         lines.append(f'| {name} | {t[0]:.3f} ({t[1]:.3f} .. {t[2]:.3f}) | {rate / 1e12:.4f} | {100 * rate / BOUND_PAIRS:.1f} % | '
                      f'{t_torch[0]:.3f} ({t_torch[1]:.3f} .. {t_torch[2]:.3f}) |')
+        record[name + ' ms'], record[name + ' torch ms'] = t[0], t_torch[0]
 
     n = args.rows
     a = random_rows(n, 1)
     xa = unpack(a)
     pa = xa.float().sum(1)
     out = torch.empty(n, n, dtype=torch.float32, device=dev)
-    t = event_ms(lambda: hip.check(lib.pg_fp_tanimoto(a.data_ptr(), n, a.data_ptr(), n, out.data_ptr(), hip.stream_ptr())), 7)
-    tt = event_ms(lambda: torch_matrix(xa, xa, pa, pa), 7)
+    t = event_ms(lambda: hip.check(lib.pg_fp_tanimoto(a.data_ptr(), n, a.data_ptr(), n, out.data_ptr(), hip.stream_ptr())), 7, 2)
+    tt = event_ms(lambda: torch_matrix(xa, xa, pa, pa), 7, 2)
     worst = (out - torch_matrix(xa, xa, pa, pa)).abs().max().item()
     row(f'`pg_fp_tanimoto` {n} x {n}', t, n * n, tt)
     near = S.nearest(a)
-    t = event_ms(lambda: S.nearest(a), 7)
-    tt = event_ms(lambda: torch_nearest(xa, pa), 3)
+    t = event_ms(lambda: S.nearest(a), 7, 2)
+    tt = event_ms(lambda: torch_nearest(xa, pa), 3, 2)
     ts, ti, tsum = torch_nearest(xa, pa)
     agree = [bool((near.sim == ts).all()), bool((near.index.long() == ti).all()), (near.sum - tsum).abs().max().item()]
     row(f'`pg_fp_nearest` {n} x {n} (self)', t, n * (n - 1), tt)
@@ -184,11 +154,12 @@ def main():
               f'nearest similarity equal {agree[0]}, index equal {agree[1]}, row sums max |difference| {agree[2]:.3g}; MaxMin picks equal '
               f'{same_picks} (torch.argmin and torch.max promise no tie rule, so equality is not required of them).', '',
               'No test asserts a time.  The int8 / fp8 matrix-core form on unpacked bits has not been built or measured.', '']
-    text = '\n'.join(lines)
+    text = '\n'.join(lines)                                            # this tool's report is a whole document and prints no JSON line
     print(text)
     if args.out:
         with open(args.out, 'w') as fh:
             fh.write(text)
+    return text, record
 
 
 if __name__ == '__main__':

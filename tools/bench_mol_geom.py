@@ -6,51 +6,23 @@ in the same run; writes the table of profiles/mol_geom_timing.md.
 
 (a) final prediction of the 128-graph headline batch, (b) its whole saved trajectory in ONE launch; every graph is measured against
 its own pharmacophore of the workload.  Kernel times are HIP events around the launch alone (outputs allocated before), warm, median
-of repeats, exactly as tools/bench_mol_screen.py takes the screen's; wall times are a host clock around a call that ends in a device
-synchronise.  The reverse step the two are held against is the sampling call of this run divided by its steps.  A record, not a
-pass/fail."""
-import argparse
-import json
-import os
-import statistics
-import sys
-import time
-
+of repeats, as tools/mol_bench.py takes them; wall times are a host clock around a call that ends in a device synchronise.  The
+reverse step the two are held against is the sampling call of this run divided by its steps.  A record, not a pass/fail."""
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
-from bench import ligphore_workload  # noqa: E402
-from bench_mol_screen import kernel_ms, wall_ms  # noqa: E402
-from phoregen_amd import hip, molecule as M  # noqa: E402
-from phoregen_amd.config import default_model_config  # noqa: E402
-from phoregen_amd.models.diffusion import PhoreDiff  # noqa: E402
-from phoregen_amd.weights import init_deterministic_  # noqa: E402
+from mol_bench import fmt, headline_run, parser, relaunch_ms, report, wall_ms      # first: puts the repository root on sys.path
+from bench_mol_screen import kernel_ms
+from phoregen_amd import hip, molecule as M
 
 
 def geom_kernel_ms(geo, pos, pos_fs, ppos, pex, repeats, warmup=3):
     """Median / min / max of `repeats` event-timed pg_mol_geom launches over all frames of a Geometry's screen, after `warmup`."""
     sc = geo.screen
     F, B = sc.status.shape
-    out = {k: torch.empty_like(getattr(geo, k)) for k in ('status', 'metrics', 'counts', 'point_dist', 'point_atom')}
     lib, lim = hip.lib(), tuple(float(getattr(geo.limits, k)) for k in ('bond_min', 'bond_max', 'clash_min', 'ex_clear', 'feat_cut'))
-
-    def go():
-        M._launch_geom(lib, pos, pos_fs, sc.cls, sc.order, sc.lig_off, sc.bond_off, B, F, max(sc.num_atoms), ppos, pex, geo.point_range,
-                       geo.point_off, geo.point_dist.size(1), lim, out)
-    for _ in range(warmup):
-        go()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(repeats):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        go()
-        e1.record()
-        e1.synchronize()
-        ts.append(e0.elapsed_time(e1))
-    return statistics.median(ts), min(ts), max(ts), out
+    return relaunch_ms(geo, ('status', 'metrics', 'counts', 'point_dist', 'point_atom'),
+                       lambda out: M._launch_geom(lib, pos, pos_fs, sc.cls, sc.order, sc.lig_off, sc.bond_off, B, F, max(sc.num_atoms), ppos, pex,
+                                                  geo.point_range, geo.point_off, geo.point_dist.size(1), lim, out), repeats, warmup)
 
 
 def pair_evaluations(geo):
@@ -60,24 +32,10 @@ def pair_evaluations(geo):
     return geo.status.size(0) * sum(n * (n - 1) // 2 + n * p for n, p in zip(na, npt))
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--steps', type=int, default=1000, help='reverse steps of the sampled trajectory (frames = steps + 1)')
-    ap.add_argument('--graphs', type=int, default=128)
-    ap.add_argument('--out', type=str, default=None)
-    args = ap.parse_args()
+def main(argv=None):
+    args = parser().parse_args(argv)
     dev = 'cuda'
-    model = init_deterministic_(PhoreDiff(default_model_config(), 'zinc_300'), 0).eval().to(dev)
-    w = ligphore_workload(args.graphs)
-    sample = lambda steps, traj: model.sample_batch(w['h_phore'], w['pos_phore'], w['phore_norm'], w['batch_phore'], w['num_atoms'],   # noqa: E731
-                                                    torch.zeros(args.graphs, 3), rng='device', seed=1, num_steps=steps, return_traj=traj)
-    sample(5, False)                                                   # warm: code objects, plan, packed weights
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    res = sample(args.steps, True)
-    torch.cuda.synchronize()
-    t_sample = time.perf_counter() - t0
-    step_ms = t_sample * 1e3 / args.steps
+    model, w, res, t_sample, step_ms = headline_run(args.graphs, args.steps)
 
     ppos = w['pos_phore'].float().to(dev).contiguous()                 # (centres are zero in this workload)
     pex = (w['h_phore'][:, model.ex_col] == 1).to(torch.uint8).to(dev)
@@ -89,8 +47,6 @@ def main():
     ks = kernel_ms(node, pos, edge, 1, (0, 0, 0), sc, 50)
     geo = geometry('final', sc)
     kg = geom_kernel_ms(geo, pos, 0, ppos, pex, 50)
-    assert all(torch.equal(kg[3][k].view(torch.int32) if kg[3][k].dtype == torch.float32 else kg[3][k],
-                           getattr(geo, k).view(torch.int32) if kg[3][k].dtype == torch.float32 else getattr(geo, k)) for k in kg[3])
     w_geo = wall_ms(lambda: geometry('final', sc), 10)
     w_asm, w_asm_g = wall_ms(lambda: M.assemble(res), 10), wall_ms(lambda: M.assemble(res, geometry=geometry('final')), 10)
     n_ok, n_valid = int(geo.ok.sum()), int(sc.valid.sum())
@@ -105,7 +61,6 @@ def main():
     w_geo_t = wall_ms(lambda: geometry('traj', sct), 5)
     ev, evt = pair_evaluations(geo), pair_evaluations(geot)
 
-    fmt = lambda t: '%.3f (%.3f - %.3f)' % t[:3]   # noqa: E731
     lines = ['| case | `pg_mol_screen` kernel ms, median (min - max) | `pg_mol_geom` kernel ms | geom / screen | distances per call | `geometry()` wall ms |',
              '|---|---|---|---|---|---|',
              '| (a) final frame, %d graphs | %s | %s | %.1f x | %.3g | %s |' % (args.graphs, fmt(ks), fmt(kg), kg[0] / ks[0], ev, fmt(w_geo)),
@@ -118,13 +73,8 @@ def main():
              '',
              'Final frame, %d graphs, %d points (deterministic noise weights, so the molecules are noise): %d pass the screen, %d the geometry '
              'limits; graphs per bit: %s.' % (args.graphs, ppos.size(0), n_valid, n_ok, ', '.join('%s %d' % (k, v) for k, v in census.items()))]
-    text = '\n'.join(lines) + '\n'
-    print(text)
-    print(json.dumps({'screen_ms_final': ks[0], 'geom_ms_final': kg[0], 'screen_ms_traj': kst[0], 'geom_ms_traj': kgt[0], 'frames': F,
-                      'step_ms': step_ms, 'distances_final': ev, 'distances_traj': evt}))
-    if args.out:
-        with open(args.out, 'w') as fh:
-            fh.write(text)
+    return report(lines, {'screen_ms_final': ks[0], 'geom_ms_final': kg[0], 'screen_ms_traj': kst[0], 'geom_ms_traj': kgt[0], 'frames': F,
+                          'step_ms': step_ms, 'distances_final': ev, 'distances_traj': evt}, args.out)
 
 
 if __name__ == '__main__':

@@ -5,70 +5,28 @@ in the same run; writes the table of profiles/mol_key_timing.md.
   python tools/bench_mol_key.py [--steps 1000] [--out FILE.md]
 
 (a) final prediction of the 128-graph headline batch, (b) its whole saved trajectory in ONE launch.  Kernel times are HIP events
-around the launch alone (outputs allocated before), warm, median of repeats, exactly as tools/bench_mol_screen.py takes the
-screen's; wall times are a host clock around a call that ends in a device synchronise.  The reverse step the two are held against
-is the sampling call of this run divided by its steps."""
-import argparse
-import json
-import os
-import statistics
-import sys
-import time
-
+around the launch alone (outputs allocated before), warm, median of repeats, as tools/mol_bench.py takes them; wall times are a
+host clock around a call that ends in a device synchronise.  The reverse step the two are held against is the sampling call of
+this run divided by its steps."""
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
-from bench import ligphore_workload  # noqa: E402
-from bench_mol_screen import kernel_ms, wall_ms  # noqa: E402
-from phoregen_amd import hip, molecule as M  # noqa: E402
-from phoregen_amd.config import default_model_config  # noqa: E402
-from phoregen_amd.models.diffusion import PhoreDiff  # noqa: E402
-from phoregen_amd.weights import init_deterministic_  # noqa: E402
+from mol_bench import event_ms, fmt, headline_run, parser, report, wall_ms      # first: puts the repository root on sys.path
+from bench_mol_screen import kernel_ms
+from phoregen_amd import hip, molecule as M
 
 
 def key_kernel_ms(sc, repeats, warmup=3, colour=True):
-    """Median / min / max of `repeats` event-timed pg_mol_key launches over all frames of a Screen, after `warmup` launches."""
+    """Median / min / max of `repeats` event-timed pg_mol_key launches over all frames of a Screen, after `warmup` launches; the keys."""
     F, B = sc.status.shape
     key = torch.empty(F, B, dtype=torch.int64, device=sc.cls.device)
     col = torch.empty(F, sc.cls.size(1), dtype=torch.int64, device=sc.cls.device) if colour else None
     lib = hip.lib()
-
-    def go():
-        M._launch_key(lib, sc.cls, sc.order, sc.lig_off, sc.bond_off, B, F, max(sc.num_atoms), key, col)
-    for _ in range(warmup):
-        go()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(repeats):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        go()
-        e1.record()
-        e1.synchronize()
-        ts.append(e0.elapsed_time(e1))
-    return statistics.median(ts), min(ts), max(ts), key
+    return event_ms(lambda: M._launch_key(lib, sc.cls, sc.order, sc.lig_off, sc.bond_off, B, F, max(sc.num_atoms), key, col), repeats, warmup) + (key,)
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--steps', type=int, default=1000, help='reverse steps of the sampled trajectory (frames = steps + 1)')
-    ap.add_argument('--graphs', type=int, default=128)
-    ap.add_argument('--out', type=str, default=None)
-    args = ap.parse_args()
-    dev = 'cuda'
-    model = init_deterministic_(PhoreDiff(default_model_config(), 'zinc_300'), 0).eval().to(dev)
-    w = ligphore_workload(args.graphs)
-    sample = lambda steps, traj: model.sample_batch(w['h_phore'], w['pos_phore'], w['phore_norm'], w['batch_phore'], w['num_atoms'],   # noqa: E731
-                                                    torch.zeros(args.graphs, 3), rng='device', seed=1, num_steps=steps, return_traj=traj)
-    sample(5, False)                                                   # warm: code objects, plan, packed weights
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    res = sample(args.steps, True)
-    torch.cuda.synchronize()
-    t_sample = time.perf_counter() - t0
-    step_ms = t_sample * 1e3 / args.steps
+def main(argv=None):
+    args = parser().parse_args(argv)
+    _, _, res, t_sample, step_ms = headline_run(args.graphs, args.steps)
 
     sc = M.screen(res)
     node, pos, edge = res['pred']
@@ -89,7 +47,6 @@ def main():
     w_keys_t = wall_ms(lambda: M.molecule_keys(sct), 5)
     distinct_traj = int(M.duplicate_groups(kkt[3])[0].numel())
 
-    fmt = lambda t: '%.3f (%.3f - %.3f)' % t[:3]   # noqa: E731
     lines = ['| case | `pg_mol_screen` kernel ms, median (min - max) | `pg_mol_key` kernel ms | key / screen | `molecule_keys()` wall ms |',
              '|---|---|---|---|---|',
              '| (a) final frame, %d graphs | %s | %s | %.1f x | %s |' % (args.graphs, fmt(ks), fmt(kk), kk[0] / ks[0], fmt(w_keys)),
@@ -102,13 +59,8 @@ def main():
              '',
              'Kept atoms of the final frame: %d of %d rows.  Distinct keys: %d of %d graphs in the final frame, %d of %d (frame, graph) pairs '
              'of the trajectory (deterministic noise weights).' % (n_kept, sc.cls.numel(), distinct_final, args.graphs, distinct_traj, F * args.graphs)]
-    text = '\n'.join(lines) + '\n'
-    print(text)
-    print(json.dumps({'screen_ms_final': ks[0], 'key_ms_final': kk[0], 'key_ms_final_no_colour': kk0[0], 'screen_ms_traj': kst[0],
-                      'key_ms_traj': kkt[0], 'frames': F, 'step_ms': step_ms}))
-    if args.out:
-        with open(args.out, 'w') as fh:
-            fh.write(text)
+    return report(lines, {'screen_ms_final': ks[0], 'key_ms_final': kk[0], 'key_ms_final_no_colour': kk0[0], 'screen_ms_traj': kst[0],
+                          'key_ms_traj': kkt[0], 'frames': F, 'step_ms': step_ms}, args.out)
 
 
 if __name__ == '__main__':

@@ -9,27 +9,13 @@ chains of PG_MOL_MAX_ATOMS atoms with a hetero atom in every fourth place, all o
 typed against every row it has to pass.  The property kernel does no search: two walks over the pair rows, two passes over each
 atom's neighbours and one over the tables' rows.  A graph without a Kekulé structure leaves after staging its inputs, so the share
 of such graphs is printed with each case.  Kernel times are HIP events around the launch alone (outputs allocated before), warm,
-median of repeats, exactly as tools/bench_mol_scaffold.py takes them; wall times are a host clock around a call that ends in a device
-synchronise.  A record, not a pass/fail."""
-import argparse
-import json
-import os
-import statistics
-import sys
-import time
-
+median of repeats, as tools/mol_bench.py takes them; wall times are a host clock around a call that ends in a device synchronise.
+A record, not a pass/fail."""
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
-from bench import ligphore_workload  # noqa: E402
-from bench_mol_scaffold import scaffold_kernel_ms  # noqa: E402
-from bench_mol_screen import wall_ms  # noqa: E402
-from phoregen_amd import hip, molecule as M, properties as P, scaffold as SC  # noqa: E402
-from phoregen_amd.config import default_model_config  # noqa: E402
-from phoregen_amd.models.diffusion import PhoreDiff  # noqa: E402
-from phoregen_amd.weights import init_deterministic_  # noqa: E402
+from mol_bench import chain_result, fmt, headline_run, parser, relaunch_ms, report, wall_ms      # first: puts the repository root on sys.path
+from bench_mol_scaffold import scaffold_kernel_ms
+from phoregen_amd import hip, molecule as M, properties as P, scaffold as SC
 
 OUTPUTS = ('status', 'counts', 'atom_env', 'atom_row', 'sums', 'weight_milli', 'violated')
 
@@ -38,66 +24,18 @@ def props_kernel_ms(pr, repeats, warmup=3):
     """Median / min / max of `repeats` event-timed pg_mol_props launches over all frames of a Properties' inputs, after `warmup`."""
     sc = pr.screen
     F, B = sc.status.shape
-    out = {k: torch.empty_like(getattr(pr, k)) for k in OUTPUTS}
     packed = torch.from_numpy(P.pack_tables(pr.tables)).to(sc.cls.device)
     weights = torch.tensor(P.weight_table(), dtype=torch.int32, device=sc.cls.device)
     rows, pairs = [len(t.rows) for t in pr.tables], pr.limits.pairs(pr.tables)
     lib = hip.lib()
-
-    def go():
-        P._launch_props(lib, sc, pr.kekule, pr.rings, B, F, max(sc.num_atoms), packed, rows, weights, pairs, pr.limits.max_violations, out)
-    for _ in range(warmup):
-        go()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(repeats):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        go()
-        e1.record()
-        e1.synchronize()
-        ts.append(e0.elapsed_time(e1))
-    assert all(torch.equal(out[k], getattr(pr, k)) for k in OUTPUTS)
-    return statistics.median(ts), min(ts), max(ts)
+    return relaunch_ms(pr, OUTPUTS, lambda out: P._launch_props(lib, sc, pr.kekule, pr.rings, B, F, max(sc.num_atoms), packed, rows, weights, pairs,
+                                                                pr.limits.max_violations, out), repeats, warmup)
 
 
-def chain_result(n_graphs, n, dev):
-    """A sampler-shaped result of n_graphs chains of n atoms, single bonds, N or O in every fourth place: one-hot scores."""
-    from phoregen_amd.plan import make_edge_data
-    na = torch.full((n_graphs,), n, dtype=torch.long)
-    h = n * (n - 1) // 2
-    cls = torch.ones(n, dtype=torch.long)
-    cls[3::8], cls[7::8] = 2, 3
-    node = torch.zeros(n, 12)
-    node[torch.arange(n), cls] = 1.0
-    half = torch.zeros(h, dtype=torch.long)
-    a = torch.arange(n - 1)
-    half[a * n - a * (a + 1) // 2] = 1                                 # the pair (a, a + 1) is the first of row a
-    edge = torch.zeros(2 * h, 6)
-    edge[torch.arange(2 * h), torch.cat([half, half])] = 1.0
-    ei, eb = make_edge_data(na)
-    return {'pred': [node.repeat(n_graphs, 1).to(dev), torch.randn(n_graphs * n, 3).to(dev), edge.repeat(n_graphs, 1).to(dev)],
-            'traj': [None, None, None],
-            'lig_info': [na.to(dev), torch.repeat_interleave(torch.arange(n_graphs), na).to(dev), ei.to(dev), eb.to(dev)]}
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--steps', type=int, default=1000, help='reverse steps of the sampled trajectory (frames = steps + 1)')
-    ap.add_argument('--graphs', type=int, default=128)
-    ap.add_argument('--out', type=str, default=None)
-    args = ap.parse_args()
+def main(argv=None):
+    args = parser().parse_args(argv)
     dev = 'cuda'
-    model = init_deterministic_(PhoreDiff(default_model_config(), 'zinc_300'), 0).eval().to(dev)
-    w = ligphore_workload(args.graphs)
-    sample = lambda steps, traj: model.sample_batch(w['h_phore'], w['pos_phore'], w['phore_norm'], w['batch_phore'], w['num_atoms'],   # noqa: E731
-                                                    torch.zeros(args.graphs, 3), rng='device', seed=1, num_steps=steps, return_traj=traj)
-    sample(5, False)                                                   # warm: code objects, plan, packed weights
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    res = sample(args.steps, True)
-    torch.cuda.synchronize()
-    step_ms = (time.perf_counter() - t0) * 1e3 / args.steps
+    _, _, res, _, step_ms = headline_run(args.graphs, args.steps)
     limits = P.PropertyLimits.lipinski()
     no_kekule = lambda pr: float((pr.status & P.PROP_NO_KEKULE != 0).float().mean())   # noqa: E731
 
@@ -127,7 +65,6 @@ def main():
     ksc = scaffold_kernel_ms(SC.scaffolds(scc), 20)
     share_c = no_kekule(prc)
 
-    fmt = lambda t: '%.3f (%.3f - %.3f)' % t[:3]   # noqa: E731
     row = '| %s | %s | %s | %.2f x | %.2f | %s |'
     lines = ['| case | `pg_mol_props` kernel ms, median (min - max) | `pg_mol_scaffold` kernel ms | props / scaffold | share of graphs without a Kekulé structure | `properties()` wall ms (screen, Kekulé form and rings handed in) |',
              '|---|---|---|---|---|---|',
@@ -143,13 +80,8 @@ def main():
              'Tables: %s (%s rows), limits: Lipinski.  Final frame: %d of %d graphs pass; (c): %d of %d pass, %d untyped atoms.'
              % (', '.join(t.name for t in pr.tables), ' + '.join(str(len(t.rows)) for t in pr.tables), int(pr.ok.sum()), args.graphs,
                 int(prc.ok.sum()), args.graphs, int(prc.counts[..., hip.PG_PROP_C_UNTYPED].sum()))]
-    text = '\n'.join(lines) + '\n'
-    print(text)
-    print(json.dumps({'props_ms_final': kp[0], 'scaffold_ms_final': ks[0], 'props_ms_traj': kpt[0], 'scaffold_ms_traj': kst[0], 'frames': F,
-                      'props_ms_chains': kpc[0], 'scaffold_ms_chains': ksc[0], 'step_ms': step_ms}))
-    if args.out:
-        with open(args.out, 'w') as fh:
-            fh.write(text)
+    return report(lines, {'props_ms_final': kp[0], 'scaffold_ms_final': ks[0], 'props_ms_traj': kpt[0], 'scaffold_ms_traj': kst[0], 'frames': F,
+                          'props_ms_chains': kpc[0], 'scaffold_ms_chains': ksc[0], 'step_ms': step_ms}, args.out)
 
 
 if __name__ == '__main__':

@@ -6,85 +6,29 @@ same run; writes the table of profiles/mol_rings_timing.md.
 
 (a) final prediction of the 128-graph headline batch, (b) its whole saved trajectory in ONE launch, (c) the worst case: graphs of
 PG_MOL_MAX_ATOMS atoms with random logits, which bond about two thirds of all pairs, so every lane searches about 85 rings.  Kernel
-times are HIP events around the launch alone (outputs allocated before), warm, median of repeats, exactly as
-tools/bench_mol_screen.py takes the screen's; wall times are a host clock around a call that ends in a device synchronise.  The
-reverse step the two are held against is the sampling call of this run divided by its steps.  A record, not a pass/fail."""
-import argparse
-import json
-import os
-import statistics
-import sys
-import time
+times are HIP events around the launch alone (outputs allocated before), warm, median of repeats, as tools/mol_bench.py takes
+them; wall times are a host clock around a call that ends in a device synchronise.  The reverse step the two are held against is
+the sampling call of this run divided by its steps.  A record, not a pass/fail."""
 from dataclasses import astuple
 
-import torch
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
-from bench import ligphore_workload  # noqa: E402
-from bench_mol_screen import kernel_ms, wall_ms  # noqa: E402
-from phoregen_amd import hip, molecule as M  # noqa: E402
-from phoregen_amd.config import default_model_config  # noqa: E402
-from phoregen_amd.models.diffusion import PhoreDiff  # noqa: E402
-from phoregen_amd.plan import make_edge_data  # noqa: E402
-from phoregen_amd.weights import init_deterministic_  # noqa: E402
+from mol_bench import dense_result, fmt, headline_run, parser, relaunch_ms, report, wall_ms      # first: puts the repository root on sys.path
+from bench_mol_screen import kernel_ms
+from phoregen_amd import hip, molecule as M
 
 
 def rings_kernel_ms(rg, repeats, warmup=3):
     """Median / min / max of `repeats` event-timed pg_mol_rings launches over all frames of a Rings' screen, after `warmup`."""
     sc = rg.screen
     F, B = sc.status.shape
-    out = {k: torch.empty_like(getattr(rg, k)) for k in ('status', 'counts', 'ring_size', 'atom_ring', 'ring_sys')}
     lib, lim = hip.lib(), astuple(rg.limits)
-
-    def go():
-        M._launch_rings(lib, sc.cls, sc.order, sc.lig_off, sc.bond_off, B, F, max(sc.num_atoms), lim, out)
-    for _ in range(warmup):
-        go()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(repeats):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        go()
-        e1.record()
-        e1.synchronize()
-        ts.append(e0.elapsed_time(e1))
-    assert all(torch.equal(out[k], getattr(rg, k)) for k in out)
-    return statistics.median(ts), min(ts), max(ts)
+    return relaunch_ms(rg, ('status', 'counts', 'ring_size', 'atom_ring', 'ring_sys'),
+                       lambda out: M._launch_rings(lib, sc.cls, sc.order, sc.lig_off, sc.bond_off, B, F, max(sc.num_atoms), lim, out), repeats, warmup)
 
 
-def dense_result(graphs, n, dev, seed=0):
-    """`graphs` graphs of n atoms with random logits, in the sampler's layout."""
-    gen = torch.Generator().manual_seed(seed)
-    node, pos = torch.randn(graphs * n, 12, generator=gen), torch.randn(graphs * n, 3, generator=gen)
-    node[:, 11] -= 4.0
-    edge = torch.randn(graphs * n * (n - 1), 6, generator=gen)
-    na = torch.full((graphs,), n, dtype=torch.long)
-    ei, eb = make_edge_data(na)
-    return {'pred': [node.to(dev), pos.to(dev), edge.to(dev)], 'traj': [None, None, None],
-            'lig_info': [na.to(dev), torch.repeat_interleave(torch.arange(graphs), na).to(dev), ei.to(dev), eb.to(dev)]}
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--steps', type=int, default=1000, help='reverse steps of the sampled trajectory (frames = steps + 1)')
-    ap.add_argument('--graphs', type=int, default=128)
-    ap.add_argument('--out', type=str, default=None)
-    args = ap.parse_args()
+def main(argv=None):
+    args = parser().parse_args(argv)
     dev = 'cuda'
-    model = init_deterministic_(PhoreDiff(default_model_config(), 'zinc_300'), 0).eval().to(dev)
-    w = ligphore_workload(args.graphs)
-    sample = lambda steps, traj: model.sample_batch(w['h_phore'], w['pos_phore'], w['phore_norm'], w['batch_phore'], w['num_atoms'],   # noqa: E731
-                                                    torch.zeros(args.graphs, 3), rng='device', seed=1, num_steps=steps, return_traj=traj)
-    sample(5, False)                                                   # warm: code objects, plan, packed weights
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    res = sample(args.steps, True)
-    torch.cuda.synchronize()
-    t_sample = time.perf_counter() - t0
-    step_ms = t_sample * 1e3 / args.steps
+    _, _, res, t_sample, step_ms = headline_run(args.graphs, args.steps)
 
     sc = M.screen(res)
     node, pos, edge = res['pred']
@@ -114,7 +58,6 @@ def main():
     krd = rings_kernel_ms(rgd, 20)
     bonds_d = int(scd.counts[..., 1].sum())
 
-    fmt = lambda t: '%.3f (%.3f - %.3f)' % t[:3]   # noqa: E731
     row = '| %s | %s | %s | %.1f x | %.3g | %s |'
     lines = ['| case | `pg_mol_screen` kernel ms, median (min - max) | `pg_mol_rings` kernel ms | rings / screen | ring searches (bonds) per call | `rings()` wall ms |',
              '|---|---|---|---|---|---|',
@@ -130,13 +73,8 @@ def main():
              'Final frame, %d graphs (deterministic noise weights, so the molecules are noise): %d pass the screen, %d the default ring limits; '
              'graphs per bit: %s; totals: %s.' % (args.graphs, int(sc.valid.sum()), int(rg.ok.sum()), ', '.join('%s %d' % kv for kv in census.items()),
                                                   ', '.join('%s %d' % kv for kv in totals.items()))]
-    text = '\n'.join(lines) + '\n'
-    print(text)
-    print(json.dumps({'screen_ms_final': ks[0], 'rings_ms_final': kr[0], 'screen_ms_traj': kst[0], 'rings_ms_traj': krt[0], 'frames': F,
-                      'screen_ms_dense': ksd[0], 'rings_ms_dense': krd[0], 'step_ms': step_ms}))
-    if args.out:
-        with open(args.out, 'w') as fh:
-            fh.write(text)
+    return report(lines, {'screen_ms_final': ks[0], 'rings_ms_final': kr[0], 'screen_ms_traj': kst[0], 'rings_ms_traj': krt[0], 'frames': F,
+                          'screen_ms_dense': ksd[0], 'rings_ms_dense': krd[0], 'step_ms': step_ms}, args.out)
 
 
 if __name__ == '__main__':

@@ -7,28 +7,13 @@ the same run; writes the table of profiles/mol_scaffold_timing.md.
 (a) final prediction of the 128-graph headline batch, (b) its whole saved trajectory in ONE launch, (c) the worst case of the ring
 search: graphs of PG_MOL_MAX_ATOMS atoms with random logits, which bond about two thirds of all pairs.  Both kernels run the same
 per-bond ring search (csrc/ring_search.h); the scaffold kernel runs it on the bonds of the core only and adds the pruning rounds.
-Kernel times are HIP events around the launch alone (outputs allocated before), warm, median of repeats, exactly as
-tools/bench_mol_rings.py takes them; wall times are a host clock around a call that ends in a device synchronise.  A record, not a
-pass/fail."""
-import argparse
-import json
-import os
-import statistics
-import sys
-import time
-
+Kernel times are HIP events around the launch alone (outputs allocated before), warm, median of repeats, as tools/mol_bench.py
+takes them; wall times are a host clock around a call that ends in a device synchronise.  A record, not a pass/fail."""
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
-from bench import ligphore_workload  # noqa: E402
-from bench_mol_rings import dense_result, rings_kernel_ms  # noqa: E402
-from bench_mol_screen import wall_ms  # noqa: E402
-from phoregen_amd import hip, molecule as M, scaffold as SC  # noqa: E402
-from phoregen_amd.config import default_model_config  # noqa: E402
-from phoregen_amd.models.diffusion import PhoreDiff  # noqa: E402
-from phoregen_amd.weights import init_deterministic_  # noqa: E402
+from mol_bench import dense_result, event_ms, fmt, headline_run, parser, report, wall_ms      # first: puts the repository root on sys.path
+from bench_mol_rings import rings_kernel_ms
+from phoregen_amd import hip, molecule as M, scaffold as SC
 
 SCREEN_ARRAYS = ('status', 'counts', 'cls', 'compact', 'valence2', 'comp', 'order')
 
@@ -40,41 +25,16 @@ def scaffold_kernel_ms(sf, repeats, warmup=3):
     part, counts = torch.empty_like(sf.part), torch.empty_like(sf.counts)
     out = {k: torch.empty_like(getattr(sf.screen, k)) for k in SCREEN_ARRAYS}
     lib = hip.lib()
-
-    def go():
-        SC._launch_scaffold(lib, sc.cls, sc.order, sc.lig_off, sc.bond_off, B, F, max(sc.num_atoms), sf.options.flags, part, counts, out)
-    for _ in range(warmup):
-        go()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(repeats):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        go()
-        e1.record()
-        e1.synchronize()
-        ts.append(e0.elapsed_time(e1))
+    t = event_ms(lambda: SC._launch_scaffold(lib, sc.cls, sc.order, sc.lig_off, sc.bond_off, B, F, max(sc.num_atoms), sf.options.flags, part, counts,
+                                             out), repeats, warmup)
     assert torch.equal(part, sf.part) and torch.equal(counts, sf.counts) and all(torch.equal(out[k], getattr(sf.screen, k)) for k in out)
-    return statistics.median(ts), min(ts), max(ts)
+    return t
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--steps', type=int, default=1000, help='reverse steps of the sampled trajectory (frames = steps + 1)')
-    ap.add_argument('--graphs', type=int, default=128)
-    ap.add_argument('--out', type=str, default=None)
-    args = ap.parse_args()
+def main(argv=None):
+    args = parser().parse_args(argv)
     dev = 'cuda'
-    model = init_deterministic_(PhoreDiff(default_model_config(), 'zinc_300'), 0).eval().to(dev)
-    w = ligphore_workload(args.graphs)
-    sample = lambda steps, traj: model.sample_batch(w['h_phore'], w['pos_phore'], w['phore_norm'], w['batch_phore'], w['num_atoms'],   # noqa: E731
-                                                    torch.zeros(args.graphs, 3), rng='device', seed=1, num_steps=steps, return_traj=traj)
-    sample(5, False)                                                   # warm: code objects, plan, packed weights
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    res = sample(args.steps, True)
-    torch.cuda.synchronize()
-    step_ms = (time.perf_counter() - t0) * 1e3 / args.steps
+    _, _, res, _, step_ms = headline_run(args.graphs, args.steps)
 
     sc = M.screen(res)
     kr = rings_kernel_ms(M.rings(res, screen=sc), 50)
@@ -103,7 +63,6 @@ def main():
     kfd = scaffold_kernel_ms(sfd, 20)
     core_bonds_d = int(sfd.counts[..., 1].sum() - sfd.counts[..., 4].sum())
 
-    fmt = lambda t: '%.3f (%.3f - %.3f)' % t[:3]   # noqa: E731
     row = '| %s | %s | %s | %.2f x | %.3g | %s |'
     lines = ['| case | `pg_mol_rings` kernel ms, median (min - max) | `pg_mol_scaffold` kernel ms | scaffold / rings | ring searches (core bonds) per call | `scaffolds()` wall ms |',
              '|---|---|---|---|---|---|',
@@ -118,13 +77,8 @@ def main():
              '',
              'Final frame, %d graphs (deterministic noise weights, so the molecules are noise): %d have a scaffold, %d distinct scaffold keys; '
              'totals: %s.' % (args.graphs, int((sf.counts[0, :, 0] > 0).sum()), distinct, ', '.join('%s %d' % kv for kv in totals.items()))]
-    text = '\n'.join(lines) + '\n'
-    print(text)
-    print(json.dumps({'rings_ms_final': kr[0], 'scaffold_ms_final': kf[0], 'rings_ms_traj': krt[0], 'scaffold_ms_traj': kft[0], 'frames': F,
-                      'rings_ms_dense': krd[0], 'scaffold_ms_dense': kfd[0], 'step_ms': step_ms}))
-    if args.out:
-        with open(args.out, 'w') as fh:
-            fh.write(text)
+    return report(lines, {'rings_ms_final': kr[0], 'scaffold_ms_final': kf[0], 'rings_ms_traj': krt[0], 'scaffold_ms_traj': kft[0], 'frames': F,
+                          'rings_ms_dense': krd[0], 'scaffold_ms_dense': kfd[0], 'step_ms': step_ms}, args.out)
 
 
 if __name__ == '__main__':

@@ -10,23 +10,12 @@ tiled 32 x to 4096 graphs (the atom-count distribution of BASELINE config 4).  K
 and (c), and for (b) a frame-by-frame loop, both as one launch per frame and as `decode_batch` per frame (a few frames timed,
 scaled to all).  Next to every kernel time stands the distance bond screen's (pg_mol_screen_dist, csrc/mol_screen_dist.hip;
 `screen(bonds='distance')`, without the agreement counts) on the same tensors in the same process, and the ratio of the two medians."""
-import argparse
-import json
-import os
-import statistics
-import sys
-import time
-
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from bench import ligphore_workload  # noqa: E402
-from phoregen_amd import hip, molecule as M  # noqa: E402
-from phoregen_amd.config import default_model_config  # noqa: E402
-from phoregen_amd.models.diffusion import PhoreDiff  # noqa: E402
-from phoregen_amd.utils.sample_utils import decode_batch  # noqa: E402
-from phoregen_amd.weights import init_deterministic_  # noqa: E402
+from mol_bench import event_ms, fmt, headline_run, parser, report, wall_ms      # first: puts the repository root on sys.path
+from phoregen_amd import hip, molecule as M
+from phoregen_amd.plan import make_edge_data
+from phoregen_amd.utils.sample_utils import decode_batch
 
 
 def _buffers(F, B, N, E, dev):
@@ -51,31 +40,7 @@ def kernel_ms(node, pos, edge, F, strides, sc, repeats, warmup=3, dist=False):
                            thresholds, out, None)
         else:
             M._launch(lib, node, strides[0], edge, strides[1], pos, strides[2], sc.lig_off, sc.bond_off, B, F, N, E, max(sc.num_atoms), out)
-    for _ in range(warmup):
-        go()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(repeats):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        go()
-        e1.record()
-        e1.synchronize()
-        ts.append(e0.elapsed_time(e1))
-    return statistics.median(ts), min(ts), max(ts), out
-
-
-def wall_ms(fn, repeats, warmup=1):
-    for _ in range(warmup):
-        fn()
-    ts = []
-    for _ in range(repeats):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        ts.append((time.perf_counter() - t0) * 1e3)
-    return statistics.median(ts), min(ts), max(ts)
+    return event_ms(go, repeats, warmup) + (out,)
 
 
 def traffic_bytes(sc, F):
@@ -84,21 +49,12 @@ def traffic_bytes(sc, F):
     return F * (N * (48 + 12 + 6) + H * (24 + 1) + len(sc.num_atoms) * 20)
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--steps', type=int, default=1000, help='reverse steps of the sampled trajectory (frames = steps + 1)')
-    ap.add_argument('--graphs', type=int, default=128)
+def main(argv=None):
+    ap = parser()
     ap.add_argument('--tile', type=int, default=32, help='(c): the final prediction repeated this many times')
-    ap.add_argument('--out', type=str, default=None)
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     dev = 'cuda'
-    model = init_deterministic_(PhoreDiff(default_model_config(), 'zinc_300'), 0).eval().to(dev)
-    w = ligphore_workload(args.graphs)
-    t0 = time.perf_counter()
-    res = model.sample_batch(w['h_phore'], w['pos_phore'], w['phore_norm'], w['batch_phore'], w['num_atoms'],
-                             torch.zeros(args.graphs, 3), rng='device', seed=1, num_steps=args.steps, return_traj=True)
-    torch.cuda.synchronize()
-    t_sample = time.perf_counter() - t0
+    _, _, res, t_sample, _ = headline_run(args.graphs, args.steps, warm=False)
     rows = []
 
     # (a) final prediction
@@ -143,7 +99,6 @@ def main():
     # (c) 4096 graphs: the final prediction tiled
     big = {'pred': [t.repeat(args.tile, 1) for t in res['pred']], 'traj': [None, None, None],
            'lig_info': [res['lig_info'][0].repeat(args.tile)] + [None] * 3}
-    from phoregen_amd.plan import make_edge_data
     big['lig_info'][2] = make_edge_data(big['lig_info'][0].cpu())[0].to(dev)
     scc = M.screen(big)
     kc = kernel_ms(*big['pred'], 1, (0, 0, 0), scc, 30)
@@ -152,12 +107,12 @@ def main():
     rows.append(('(c) final frame, %d graphs' % (args.graphs * args.tile), 1, kc[:3], traffic_bytes(scc, 1),
                  wall_ms(lambda: M.screen(big), 5), wall_ms(lambda: M.assemble(big), 5), wall_ms(lambda: decode_batch(big), 5)))
 
-    fmt = lambda t: '-' if t is None else '%.3f (%.3f - %.3f)' % t   # noqa: E731
+    dash = lambda t: '-' if t is None else fmt(t)   # noqa: E731
     lines = ['| case | kernel ms, median (min - max) | GB/s of needed traffic | `screen()` wall ms | `assemble()` wall ms | `decode_batch()` wall ms '
              '| `pg_mol_screen_dist` kernel ms | dist / screen |',
              '|---|---|---|---|---|---|---|---|']
     for (name, _, k3, nbytes, ws, wa, wd), d in zip(rows, dist_ms):
-        lines.append('| %s | %s | %.0f | %s | %s | %s | %s | %.2f |' % (name, fmt(k3), nbytes / k3[0] / 1e6, fmt(ws), fmt(wa), fmt(wd), fmt(d[:3]),
+        lines.append('| %s | %s | %.0f | %s | %s | %s | %s | %.2f |' % (name, fmt(k3), nbytes / k3[0] / 1e6, fmt(ws), dash(wa), dash(wd), fmt(d),
                                                                      d[0] / k3[0]))
     lines += ['',
               'Trajectory frame by frame instead of one launch (scaled to %d frames): one launch per frame %.1f ms wall (%d frames timed: %.3f ms); '
@@ -167,13 +122,9 @@ def main():
               'Sampling the batch with its trajectory took %.1f s.  Valid graphs of the final prediction (deterministic noise weights): %d of %d; '
               'graphs with a valid frame anywhere in the trajectory: %d.' %
               (t_sample, valid_final, args.graphs, sum(v < F for v in first_valid))]
-    text = '\n'.join(lines) + '\n'
-    print(text)
-    print(json.dumps({'dist_kernel_ms': [d[0] for d in dist_ms], 'kernel_ms_final': rows[0][2][0], 'kernel_ms_traj': rows[1][2][0], 'kernel_ms_4096': rows[2][2][0], 'frames': F,
-                      'per_frame_launch_ms_scaled': pf[0] * F / nf, 'per_frame_decode_ms_scaled': pd[0] * F / len(frames3)}))
-    if args.out:
-        with open(args.out, 'w') as fh:
-            fh.write(text)
+    return report(lines, {'dist_kernel_ms': [d[0] for d in dist_ms], 'kernel_ms_final': rows[0][2][0], 'kernel_ms_traj': rows[1][2][0],
+                          'kernel_ms_4096': rows[2][2][0], 'frames': F, 'per_frame_launch_ms_scaled': pf[0] * F / nf,
+                          'per_frame_decode_ms_scaled': pd[0] * F / len(frames3)}, args.out)
 
 
 if __name__ == '__main__':

@@ -5,81 +5,31 @@ and in the same run; writes the table of profiles/mol_smiles_timing.md.
   python tools/bench_mol_smiles.py [--steps 1000] [--out FILE.md]
 
 (a) final prediction of the 128-graph headline batch, (b) its whole saved trajectory in ONE launch, (c) the synthetic batch of sparse
-aromatic graphs of tools/bench_mol_kekule.py, which all have a Kekulé structure and therefore a text, (d) the longest serial walk: a
+aromatic graphs of tools/mol_bench.py, which all have a Kekulé structure and therefore a text, (d) the longest serial walk: a
 chain of PG_MOL_MAX_ATOMS carbons with 99 ring closures open at once per graph.  Kernel times are HIP events around the launch alone
-(outputs allocated before), warm, median of repeats, exactly as tools/bench_mol_screen.py and tools/bench_mol_kekule.py take theirs;
-wall times are a host clock around a call that ends in a device synchronise.  The reverse step they are held against is the sampling
-call of this run divided by its steps.  A record, not a pass/fail: the kernel is new, there is nothing to regress against."""
-import argparse
-import json
-import os
-import statistics
-import sys
-import time
-
-import torch
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
-from bench import ligphore_workload  # noqa: E402
-from bench_mol_kekule import kekule_kernel_ms, onehot_result, sparse_aromatic_graphs  # noqa: E402
-from bench_mol_screen import kernel_ms, wall_ms  # noqa: E402
-from phoregen_amd import hip, molecule as M  # noqa: E402
-from phoregen_amd.config import default_model_config  # noqa: E402
-from phoregen_amd.models.diffusion import PhoreDiff  # noqa: E402
-from phoregen_amd.weights import init_deterministic_  # noqa: E402
+(outputs allocated before), warm, median of repeats, as tools/mol_bench.py takes them; wall times are a host clock around a call
+that ends in a device synchronise.  The reverse step they are held against is the sampling call of this run divided by its steps.
+A record, not a pass/fail: the kernel is new, there is nothing to regress against."""
+from mol_bench import (fmt, headline_run, label_chain_graphs, onehot_result, parser, relaunch_ms, report, sparse_aromatic_graphs,
+                       wall_ms)      # first: puts the repository root on sys.path
+from bench_mol_kekule import kekule_kernel_ms
+from bench_mol_screen import kernel_ms
+from phoregen_amd import hip, molecule as M
 
 
 def smiles_kernel_ms(sm, repeats, warmup=3):
     """Median / min / max of `repeats` event-timed pg_mol_smiles launches over all frames of a Smiles' screen, after `warmup`."""
     sc, kk = sm.screen, sm.kekule
     F, B = sc.status.shape
-    out = {k: torch.empty_like(getattr(sm, k)) for k in ('status', 'counts', 'text', 'length', 'atom_rank')}
     lib, table = hip.lib(), M._smiles_table(sc.cls.device)
-
-    def go():
-        M._launch_smiles(lib, sc, kk, B, F, max(sc.num_atoms), table, sm.capacity, out)
-    for _ in range(warmup):
-        go()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(repeats):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        go()
-        e1.record()
-        e1.synchronize()
-        ts.append(e0.elapsed_time(e1))
-    assert all(torch.equal(out[k], getattr(sm, k)) for k in out)
-    return statistics.median(ts), min(ts), max(ts)
+    return relaunch_ms(sm, ('status', 'counts', 'text', 'length', 'atom_rank'),
+                       lambda out: M._launch_smiles(lib, sc, kk, B, F, max(sc.num_atoms), table, sm.capacity, out), repeats, warmup)
 
 
-def label_chain_graphs(graphs, n, closures=M.SMILES_MAX_LABEL):
-    """A chain of n carbons with atom 0 also bonded to atoms 2 .. 2 + closures - 1."""
-    bonds = {(i, i + 1): 1 for i in range(n - 1)}
-    bonds.update({(0, i): 1 for i in range(2, 2 + closures)})
-    return [([1] * n, bonds)] * graphs
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--steps', type=int, default=1000, help='reverse steps of the sampled trajectory (frames = steps + 1)')
-    ap.add_argument('--graphs', type=int, default=128)
-    ap.add_argument('--out', type=str, default=None)
-    args = ap.parse_args()
+def main(argv=None):
+    args = parser().parse_args(argv)
     dev = 'cuda'
-    model = init_deterministic_(PhoreDiff(default_model_config(), 'zinc_300'), 0).eval().to(dev)
-    w = ligphore_workload(args.graphs)
-    sample = lambda steps, traj: model.sample_batch(w['h_phore'], w['pos_phore'], w['phore_norm'], w['batch_phore'], w['num_atoms'],   # noqa: E731
-                                                    torch.zeros(args.graphs, 3), rng='device', seed=1, num_steps=steps, return_traj=traj)
-    sample(5, False)                                                   # warm: code objects, plan, packed weights
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    res = sample(args.steps, True)
-    torch.cuda.synchronize()
-    t_sample = time.perf_counter() - t0
-    step_ms = t_sample * 1e3 / args.steps
+    _, _, res, t_sample, step_ms = headline_run(args.graphs, args.steps)
 
     def census(sm):
         c = dict(zip(M.SMILES_COUNTS, sm.counts.reshape(-1, len(M.SMILES_COUNTS)).sum(0).tolist()))
@@ -118,7 +68,6 @@ def main():
         a, b, c, sms = case(syn, 'final', M.screen(syn), 20, 3)
         rows.append((label, a, b, c, census(sms), None))
 
-    fmt = lambda t: '%.3f (%.3f - %.3f)' % t[:3]   # noqa: E731
     lines = ['| case | `pg_mol_screen` kernel ms, median (min - max) | `pg_mol_kekule` kernel ms | `pg_mol_smiles` kernel ms | smiles / screen | census | `smiles()` wall ms |',
              '|---|---|---|---|---|---|---|']
     lines += ['| %s | %s | %s | %s | %.1f x | %s | %s |' % (label, fmt(a), fmt(b), fmt(c), c[0] / a[0], cen, fmt(wl) if wl else '-')
@@ -132,14 +81,9 @@ def main():
               '',
               'Final frame, %d graphs (deterministic noise weights, so the molecules are noise): %d pass the screen, %d have a text; graphs per '
               'bit: %s.' % (args.graphs, int(sc.valid.sum()), int(sm.ok.sum()), ', '.join('%s %d' % kv for kv in flags.items()))]
-    text = '\n'.join(lines) + '\n'
-    print(text)
-    print(json.dumps({'screen_ms_final': ks[0], 'kekule_ms_final': kr[0], 'smiles_ms_final': sr[0], 'screen_ms_traj': kst[0],
-                      'kekule_ms_traj': krt[0], 'smiles_ms_traj': srt[0], 'frames': F, 'smiles_ms_sparse': rows[2][3][0],
-                      'smiles_ms_chain': rows[3][3][0], 'step_ms': step_ms}))
-    if args.out:
-        with open(args.out, 'w') as fh:
-            fh.write(text)
+    return report(lines, {'screen_ms_final': ks[0], 'kekule_ms_final': kr[0], 'smiles_ms_final': sr[0], 'screen_ms_traj': kst[0],
+                          'kekule_ms_traj': krt[0], 'smiles_ms_traj': srt[0], 'frames': F, 'smiles_ms_sparse': rows[2][3][0],
+                          'smiles_ms_chain': rows[3][3][0], 'step_ms': step_ms}, args.out)
 
 
 if __name__ == '__main__':

@@ -5,88 +5,39 @@ the screen and the plain SMILES kernel on the same inputs and in the same run; w
   python tools/bench_mol_stereo.py [--steps 1000] [--out FILE.md]
 
 (a) final prediction of the 128-graph headline batch, (b) its whole saved trajectory in ONE launch.  Kernel times are HIP events
-around the launch alone (outputs allocated before), warm, median of repeats, exactly as tools/bench_mol_screen.py and
-tools/bench_mol_smiles.py take theirs; wall times are a host clock around a call that ends in a device synchronise.  The reverse step
-they are held against is the sampling call of this run divided by its steps.  A record, not a pass/fail: the kernels are new, there
-is nothing to regress against and no target was set in advance."""
-import argparse
-import json
-import os
-import statistics
-import sys
-import time
-
-import torch
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, 'tools'))
-from bench import ligphore_workload  # noqa: E402
-from bench_mol_screen import kernel_ms, wall_ms  # noqa: E402
-from bench_mol_smiles import smiles_kernel_ms  # noqa: E402
-from phoregen_amd import hip, molecule as M  # noqa: E402
-from phoregen_amd.config import default_model_config  # noqa: E402
-from phoregen_amd.models.diffusion import PhoreDiff  # noqa: E402
-from phoregen_amd.weights import init_deterministic_  # noqa: E402
-
-
-def _timed(go, repeats, warmup):
-    for _ in range(warmup):
-        go()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(repeats):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        go()
-        e1.record()
-        e1.synchronize()
-        ts.append(e0.elapsed_time(e1))
-    return statistics.median(ts), min(ts), max(ts)
+around the launch alone (outputs allocated before), warm, median of repeats, as tools/mol_bench.py takes them; wall times are a
+host clock around a call that ends in a device synchronise.  The reverse step they are held against is the sampling call of this run
+divided by its steps.  A record, not a pass/fail: the kernels are new, there is nothing to regress against and no target was set in
+advance."""
+from mol_bench import fmt, headline_run, parser, relaunch_ms, report, wall_ms      # first: puts the repository root on sys.path
+from bench_mol_screen import kernel_ms
+from bench_mol_smiles import smiles_kernel_ms
+from phoregen_amd import hip, molecule as M
 
 
 def stereo_kernel_ms(st, pos, pos_fs, repeats, warmup=3):
     """Median / min / max of `repeats` event-timed pg_mol_stereo launches over all frames of a Stereo's screen, after `warmup`."""
     sc = st.screen
     F, B = sc.status.shape
-    names = ('status', 'counts', 'atom_parity', 'atom_label', 'bond_stereo', 'bond_label', 'stereo_key')
-    out = {k: torch.empty_like(getattr(st, k)) for k in names}
     lib = hip.lib()
-    t = _timed(lambda: M._launch_stereo(lib, pos, pos_fs, sc, st.kekule, st.rings, st.keys, B, F, max(sc.num_atoms), st.limits, out), repeats, warmup)
-    assert all(torch.equal(out[k], getattr(st, k)) for k in names)
-    return t
+    return relaunch_ms(st, ('status', 'counts', 'atom_parity', 'atom_label', 'bond_stereo', 'bond_label', 'stereo_key'),
+                       lambda out: M._launch_stereo(lib, pos, pos_fs, sc, st.kekule, st.rings, st.keys, B, F, max(sc.num_atoms), st.limits, out),
+                       repeats, warmup)
 
 
 def smiles_stereo_kernel_ms(sm, repeats, warmup=3):
     """The same of pg_mol_smiles_stereo for a Smiles written with stereo=."""
     sc = sm.screen
     F, B = sc.status.shape
-    names = ('status', 'counts', 'text', 'length', 'atom_rank', 'stereo_counts')
-    out = {k: torch.empty_like(getattr(sm, k)) for k in names}
     lib, table = hip.lib(), M._smiles_table(sc.cls.device)
-    t = _timed(lambda: M._launch_smiles(lib, sc, sm.kekule, B, F, max(sc.num_atoms), table, sm.capacity, out, sm.stereo), repeats, warmup)
-    assert all(torch.equal(out[k], getattr(sm, k)) for k in names)
-    return t
+    return relaunch_ms(sm, ('status', 'counts', 'text', 'length', 'atom_rank', 'stereo_counts'),
+                       lambda out: M._launch_smiles(lib, sc, sm.kekule, B, F, max(sc.num_atoms), table, sm.capacity, out, sm.stereo),
+                       repeats, warmup)
 
 
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--steps', type=int, default=1000, help='reverse steps of the sampled trajectory (frames = steps + 1)')
-    ap.add_argument('--graphs', type=int, default=128)
-    ap.add_argument('--out', type=str, default=None)
-    args = ap.parse_args()
-    dev = 'cuda'
-    model = init_deterministic_(PhoreDiff(default_model_config(), 'zinc_300'), 0).eval().to(dev)
-    w = ligphore_workload(args.graphs)
-    sample = lambda steps, traj: model.sample_batch(w['h_phore'], w['pos_phore'], w['phore_norm'], w['batch_phore'], w['num_atoms'],   # noqa: E731
-                                                    torch.zeros(args.graphs, 3), rng='device', seed=1, num_steps=steps, return_traj=traj)
-    sample(5, False)                                                   # warm: code objects, plan, packed weights
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    res = sample(args.steps, True)
-    torch.cuda.synchronize()
-    t_sample = time.perf_counter() - t0
-    step_ms = t_sample * 1e3 / args.steps
+def main(argv=None):
+    args = parser().parse_args(argv)
+    _, _, res, t_sample, step_ms = headline_run(args.graphs, args.steps)
 
     def census(st, sm):
         c = dict(zip(M.STEREO_COUNTS, st.counts.reshape(-1, len(M.STEREO_COUNTS)).sum(0).tolist()))
@@ -118,7 +69,6 @@ def main():
     w_st_t = wall_ms(lambda: M.stereo(res, frames='traj', screen=stt.screen, kekule=stt.kekule, rings=stt.rings, keys=stt.keys), 5)
     rows.append(('(b) trajectory, %d frames x %d graphs, ONE launch' % (F, args.graphs), *b[:4], census(stt, b[5]), w_st_t))
 
-    fmt = lambda t: '%.3f (%.3f - %.3f)' % t[:3]   # noqa: E731
     lines = ['| case | `pg_mol_screen` kernel ms, median (min - max) | `pg_mol_smiles` kernel ms | `pg_mol_stereo` kernel ms | '
              '`pg_mol_smiles_stereo` kernel ms | stereo / screen | census | `stereo()` wall ms |', '|---|---|---|---|---|---|---|---|']
     lines += ['| %s | %s | %s | %s | %s | %.1f x | %s | %s |' % (label, fmt(k), fmt(p), fmt(s), fmt(i), s[0] / k[0], cen, fmt(wl))
@@ -133,14 +83,9 @@ def main():
               '',
               'Final frame, %d graphs (deterministic noise weights, so the molecules are noise): graphs per bit: %s.'
               % (args.graphs, ', '.join('%s %d' % kv for kv in flags.items()))]
-    text = '\n'.join(lines) + '\n'
-    print(text)
-    print(json.dumps({'screen_ms_final': a[0][0], 'smiles_ms_final': a[1][0], 'stereo_ms_final': a[2][0], 'smiles_stereo_ms_final': a[3][0],
-                      'screen_ms_traj': b[0][0], 'smiles_ms_traj': b[1][0], 'stereo_ms_traj': b[2][0], 'smiles_stereo_ms_traj': b[3][0],
-                      'frames': F, 'step_ms': step_ms}))
-    if args.out:
-        with open(args.out, 'w') as fh:
-            fh.write(text)
+    return report(lines, {'screen_ms_final': a[0][0], 'smiles_ms_final': a[1][0], 'stereo_ms_final': a[2][0], 'smiles_stereo_ms_final': a[3][0],
+                          'screen_ms_traj': b[0][0], 'smiles_ms_traj': b[1][0], 'stereo_ms_traj': b[2][0], 'smiles_stereo_ms_traj': b[3][0],
+                          'frames': F, 'step_ms': step_ms}, args.out)
 
 
 if __name__ == '__main__':

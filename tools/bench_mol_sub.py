@@ -6,28 +6,15 @@ profiles/mol_sub_timing.md.
 
 Two batches of the headline shape (128 graphs, the workload's atom counts) against tables of P = 1, 16 and 256 patterns -- (a) the
 final prediction of the sampler with the deterministic noise weights, whose graphs are close to cliques, so that every root runs
-into the work bound: the worst case; (b) molecule-like graphs made up here (a random tree of degree at most 4 with a few ring
+into the work bound: the worst case; (b) tools/mol_bench.py's molecule-like graphs (a random tree of degree at most 4 with a few ring
 closures per graph, mostly carbon, mostly single bonds), where nothing is cut short.  The tables: the 6-cycle of any atoms alone;
 the paths of 2 .. 16 any-atoms and the 6-cycle; those sixteen repeated sixteen times under other names.  Kernel times are HIP events
 around the launch alone (table and outputs on the device before), warm, median of repeats; next to them the wall time of
 `substructure()` with the screen, the rings and the Kekulé form handed in.  There is no target: the numbers are recorded, not gated."""
-import argparse
-import json
-import os
-import statistics
-import sys
-import time
-
-import numpy as np
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
-from bench import ligphore_workload  # noqa: E402
-from phoregen_amd import hip, molecule as M, substructure as S  # noqa: E402
-from phoregen_amd.config import default_model_config  # noqa: E402
-from phoregen_amd.models.diffusion import PhoreDiff  # noqa: E402
-from phoregen_amd.weights import init_deterministic_  # noqa: E402
+from mol_bench import event_ms, headline_run, molecule_like, parser, report, wall_ms      # first: puts the repository root on sys.path
+from phoregen_amd import hip, molecule as M, substructure as S
 
 
 def pattern_lists():
@@ -35,42 +22,6 @@ def pattern_lists():
     sixteen = [{'name': 'path%d' % n, 'atoms': [{}] * n, 'bonds': [{'a': i, 'b': i + 1} for i in range(n - 1)]} for n in range(2, 17)] + [cycle]
     many = [dict(p, name='%s_%d' % (p['name'], r)) for r in range(16) for p in sixteen]
     return {1: [cycle], 16: sixteen, 256: many}
-
-
-def molecule_like(num_atoms, dev, seed=1):
-    """A sampler-shaped result with one-hot scores: per graph a random tree of degree <= 4 plus up to three ring closures."""
-    from phoregen_amd.plan import make_edge_data
-    rng = np.random.default_rng(seed)
-    nodes, edges = [], []
-    for n in num_atoms:
-        h = n * (n - 1) // 2
-        cls = rng.choice([1, 1, 1, 1, 1, 2, 2, 3, 3, 7, 8], n)
-        et, degree = np.zeros(h, dtype=np.int64), [0] * n
-        row = lambda a, b: a * n - a * (a + 1) // 2 + (b - a - 1)   # noqa: E731
-        for v in range(1, n):
-            u = int(rng.integers(max(0, v - 6), v))
-            while degree[u] >= 4:
-                u = int(rng.integers(0, v))
-            et[row(u, v)] = int(rng.choice([1, 1, 1, 1, 2, 4]))
-            degree[u] += 1
-            degree[v] += 1
-        for _ in range(3):
-            a, b = sorted(int(x) for x in rng.choice(n, 2, replace=False)) if n > 1 else (0, 0)
-            if a != b and et[row(a, b)] == 0 and degree[a] < 4 and degree[b] < 4:
-                et[row(a, b)] = 1
-                degree[a] += 1
-                degree[b] += 1
-        node = torch.zeros(n, 12)
-        node[torch.arange(n), torch.from_numpy(cls)] = 1.0
-        edge = torch.zeros(2 * h, 6)
-        edge[torch.arange(2 * h), torch.from_numpy(np.concatenate([et, et]))] = 1.0
-        nodes.append(node)
-        edges.append(edge)
-    na = torch.tensor(num_atoms, dtype=torch.long)
-    ei, eb = make_edge_data(na)
-    pos = torch.from_numpy(rng.normal(0, 3, (int(na.sum()), 3)).astype(np.float32))
-    return {'pred': [torch.cat(nodes).to(dev), pos.to(dev), torch.cat(edges).to(dev)], 'traj': [None, None, None],
-            'lig_info': [na.to(dev), torch.repeat_interleave(torch.arange(len(num_atoms)), na).to(dev), ei.to(dev), eb.to(dev)]}
 
 
 def kernel_ms(sc, rg, kek, patterns, max_steps, repeats, warmup=3):
@@ -84,50 +35,16 @@ def kernel_ms(sc, rg, kek, patterns, max_steps, repeats, warmup=3):
                atom_mask=torch.empty(F, B, P, 2, dtype=torch.int64, device=dev), first=torch.empty(F, B, P, S.MAX_ATOMS, dtype=torch.int16, device=dev),
                status=torch.empty(F, B, P, dtype=torch.int32, device=dev))
     lib = hip.lib()
-
-    def go():
-        S._launch_sub(lib, sc, rg, kek, B, F, max(sc.num_atoms), table, host, P, max_steps, out)
-    for _ in range(warmup):
-        go()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(repeats):
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        go()
-        e1.record()
-        e1.synchronize()
-        ts.append(e0.elapsed_time(e1))
-    return (statistics.median(ts), min(ts), max(ts)), out
+    return event_ms(lambda: S._launch_sub(lib, sc, rg, kek, B, F, max(sc.num_atoms), table, host, P, max_steps, out), repeats, warmup), out
 
 
-def wall_ms(fn, repeats, warmup=1):
-    for _ in range(warmup):
-        fn()
-    ts = []
-    for _ in range(repeats):
-        torch.cuda.synchronize()
-        t0 = time.perf_counter()
-        fn()
-        torch.cuda.synchronize()
-        ts.append((time.perf_counter() - t0) * 1e3)
-    return statistics.median(ts), min(ts), max(ts)
-
-
-def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument('--steps', type=int, default=1000, help='reverse steps of the sampler')
-    ap.add_argument('--graphs', type=int, default=128)
+def main(argv=None):
+    ap = parser(steps_help='reverse steps of the sampler')
     ap.add_argument('--max_steps', type=int, default=S.DEFAULT_STEPS)
     ap.add_argument('--repeats', type=int, default=30)
-    ap.add_argument('--out', type=str, default=None)
-    args = ap.parse_args()
+    args = ap.parse_args(argv)
     dev = 'cuda'
-    model = init_deterministic_(PhoreDiff(default_model_config(), 'zinc_300'), 0).eval().to(dev)
-    w = ligphore_workload(args.graphs)
-    res = model.sample_batch(w['h_phore'], w['pos_phore'], w['phore_norm'], w['batch_phore'], w['num_atoms'], torch.zeros(args.graphs, 3),
-                             rng='device', seed=1, num_steps=args.steps)
-    torch.cuda.synchronize()
+    _, w, res, _, _ = headline_run(args.graphs, args.steps, warm=False)      # the trajectory is kept, as sample_batch does by default
     lines, record = [], {}
     for tag, title, batch in (('a', '(a) the sampler\'s final prediction, noise weights', res),
                               ('b', '(b) molecule-like graphs', molecule_like([int(n) for n in w['num_atoms'].tolist()], dev))):
@@ -148,12 +65,7 @@ def main():
         lines += ['', 'The batch: %d graphs, %d atom rows, %d kept atoms, %d bonds, %d valid graphs; max_steps %d.' %
                   (args.graphs, sc.cls.size(1), int(sc.counts[0, :, 0].sum()), int(sc.counts[0, :, 1].sum()), int(sc.valid.sum()), args.max_steps), '']
     lines += ['(a) was sampled with %d reverse steps.' % args.steps]
-    text = '\n'.join(lines) + '\n'
-    print(text)
-    print(json.dumps(record))
-    if args.out:
-        with open(args.out, 'w') as fh:
-            fh.write(text)
+    return report(lines, record, args.out)
 
 
 if __name__ == '__main__':
