@@ -54,7 +54,8 @@ int pg_debug_order_point_fence_free(int on);
 enum {
   PG_OP_RECORD = 0, PG_OP_WAIT = 1, PG_OP_GEMM = 2, PG_OP_SEG_ATTN = 3, PG_OP_EMBED_CTX = 4, PG_OP_EMBED_BOND = 5, PG_OP_KNN_CTX = 6,
   PG_OP_LIG_NORMALS = 7, PG_OP_EDGE_GATE = 8, PG_OP_KNN_GROUP_BY_KIND = 9, PG_OP_BOND_SMEAR = 10, PG_OP_ATTN_FOLD_QUERY = 11,
-  PG_OP_ATTN_UNFOLD_VALUE = 12, PG_OP_APPLY_DX = 13, PG_OP_LAYER_GEOM = 14, PG_OP_ROWS_LINEAR = 15, PG_OP_ATOM_COUNT = 16
+  PG_OP_ATTN_UNFOLD_VALUE = 12, PG_OP_APPLY_DX = 13, PG_OP_LAYER_GEOM = 14, PG_OP_ROWS_LINEAR = 15, PG_OP_ATOM_COUNT = 16,
+  PG_OP_EMBED_BOND_E16 = 17
 };
 #define PG_PROGRAM_LANES 4
 #define PG_LAUNCH_MAX_ARGS 12
@@ -122,6 +123,8 @@ int pg_gemm(const PgGemm* p, void* stream);
  * (csrc/gemm_stream.hip), so that the tests can hold the two against each other (a product with row windows, `tile_rows`, has no tiled
  * form and stays on the streaming kernel) */
 int pg_debug_gemm_streaming(int on);
+/* which kernel pg_gemm launches for *p under the current setting of the hook: 1 the streaming kernel, 0 the tiled one (host arithmetic) */
+int pg_gemm_is_streaming(const PgGemm* p);
 
 /* ---- graph topology of one batch ------------------------------------------------------------
  * Built once per batch by the host mirror (phoregen_amd/plan.py); constant over the 1000 steps. */
@@ -157,7 +160,13 @@ int pg_embed_ctx(const PgTopo* t, const float* h_node_pert /*[n_lig,12]*/, const
                                         as soon as its types are drawn, the coordinates when its positions are: phoregen_amd/engine.py) */
 int pg_embed_bond(const PgTopo* t, const float* h_edge_pert /*[n_bond,6], caller's order (t->edge_ref)*/, const int* bond_graph,
                   const int64_t* time_step, const float* W_edge /*[118,6]*/, const float* t_offset,
-                  const float* t_coeff, float* h_bond /*[n_bond,128]*/, void* stream);
+                  const float* t_coeff, float* h_bond /*[n_bond,128], 16-byte aligned (PG_ERR_ARG otherwise)*/, void* stream);
+/* pg_embed_bond with a second, optional output: e16[e] = [ h_edge_pert of internal edge e (6) | the 10 time-smearing values of its graph ],
+ * the 16 numbers a row of h_bond is linear in (the very floats of h_bond[e, 118:128]).  Layer 0's bond-row products run over e16 with
+ * composed weights (phoregen_amd/packing.py: l0_compose).  e16 == NULL: pg_embed_bond.  h_bond and e16 must be 16-byte aligned */
+int pg_embed_bond_e16(const PgTopo* t, const float* h_edge_pert, const int* bond_graph, const int64_t* time_step, const float* W_edge,
+                      const float* t_offset, const float* t_coeff, float* h_bond /*[n_bond,128]*/, float* e16 /*[n_bond,16] or NULL*/,
+                      void* stream);
 
 /* ---- neighbour search (torch_cluster.knn_graph via uni_denoiser.py:355 and common.py:301) ----
  * pg_knn_ctx: k nearest other ctx nodes of the same graph -> nbr[n_ctx,k] (ascending distance, index

@@ -265,6 +265,10 @@ int launch_gemm_stream(const PgGemm* p, hipStream_t st);
 static int g_gemm_stream = 1;      // 0: tiled kernel only (tests: the two kernels against each other)
 extern "C" int pg_debug_gemm_streaming(int on) { const int old = g_gemm_stream; g_gemm_stream = on; return old; }
 
+extern "C" int pg_gemm_is_streaming(const PgGemm* p) {
+  return p && (p->tile_rows || (g_gemm_stream && pg::gemm_stream_eligible(p))) ? 1 : 0;
+}
+
 extern "C" int pg_gemm(const PgGemm* p, void* stream) {
   if (!p || !p->X || !p->W || !p->Y || p->M < 0 || p->N <= 0) { pg::set_error("pg_gemm: bad arguments"); return PG_ERR_ARG; }
   if (p->M == 0) return PG_OK;
@@ -297,8 +301,9 @@ extern "C" int pg_gemm(const PgGemm* p, void* stream) {
     }
     return pg::launch_gemm_stream(p, (hipStream_t)stream);
   }
-  // K = 128 (+ 20) / K = 20 products with a plain epilogue or LayerNorm-on-load: the streaming kernel (LDS-DMA tiles, no vector-ALU
-  // work on the memory path; gemm_stream.hip); everything else (row subsets, odd K, two gathered operands): the tiled kernel
+  // K = 128 (+ 20) products with a plain epilogue or LayerNorm-on-load, and the register-operand forms K = 20, K = 16 and K = 16 + 20:
+  // the streaming kernel (LDS-DMA tiles or rows straight into registers, no vector-ALU work on the memory path; gemm_stream.hip);
+  // everything else (fewer than 64 rows, row subsets, other K, two gathered operands): the tiled kernel
   if (g_gemm_stream && pg::gemm_stream_eligible(p)) return pg::launch_gemm_stream(p, (hipStream_t)stream);
   const int row_blocks = (p->M + pg::BM - 1) / pg::BM;
   dim3 grid((p->N + pg::BN - 1) / pg::BN, row_blocks < 65535 ? row_blocks : 65535);

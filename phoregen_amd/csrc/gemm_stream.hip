@@ -21,6 +21,8 @@
 // the only younger vector-memory operations of a wave at that point are the tile's 32 stores (more would be harmless, fewer
 // would let the wait pass early; tests/test_host_cpu.py cross-compiles this file and checks 32 buffer_store_dword per tile
 // body and no scratch in every variant).
+// Register-operand forms (K1 = 16 and / or K2 = 20, no K = 128 part: no LDS, no DMA, no barrier): the lane's 8 / 10 values of a row come
+// straight from HBM by buffer loads one tile ahead (layer 0's bond rows as their 16 embedding inputs; the bond-length smearing).
 // v_mfma_f32_32x32x2_f32: A lane (l31 = row, kh = k), B lane (l31 = column, kh = k), D reg r = row 8(r>>2) + 4 kh + (r&3).
 // The k order inside a chunk of eight is free: step s (0..3) of chunk c uses k = 8c + 4 kh + s on both operands, so a lane's
 // four values of a chunk are one 16-byte slot.
@@ -36,7 +38,7 @@ typedef int i2v __attribute__((ext_vector_type(2)));
 constexpr int ST_BM = 64;                       // rows per tile
 constexpr int ST_STAGE = ST_BM * 128 * 4;       // 32 KB
 
-template <int NW /* waves: 32 output columns each */, int NADD /* 0 | 1: rows add1[idx1[r]] | 2: rows add1[r] */, int K1 /* 128 | 0 */,
+template <int NW /* waves: 32 output columns each */, int NADD /* 0 | 1: rows add1[idx1[r]] | 2: rows add1[r] */, int K1 /* 128 | 16 | 0 */,
           int K2 /* 0 | 20 */, bool LN /* LayerNorm(128) + ReLU on the X rows (K1 = 128, NW = 4) */,
           bool SSP = false /* shifted softplus on the result (the heads' first layers) */,
           bool WIN = false /* row windows: tile t starts at row p.tile_rows[t] (K1 = 128, K2 = 0, NADD = 0) */>
@@ -48,9 +50,11 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void gemm_stream_kernel(P
   const int colw = blockIdx.y * (NW * 32) + 32 * wave;                 // the wave's first output column
   const int col = colw + l31;
 
+  constexpr bool DMA = K1 == 128;               // X through the LDS; K1 = 16: X is a register operand (below)
+  static_assert((K1 == 128 || K1 == 16 || K1 == 0) && (K2 == 20 || K2 == 0) && K1 + K2 > 0, "K1 128 | 16 | 0, K2 20 | 0");
   // ---- the wave's W slice: 64 registers for the whole kernel ----
-  float Wr[K1 ? 64 : 1];
-  if constexpr (K1 > 0) {
+  float Wr[DMA ? 64 : 1];
+  if constexpr (DMA) {
     const float* wrow = p.W + (size_t)col * p.ldw + 4 * kh;
 #pragma unroll
     for (int c = 0; c < 16; ++c) {
@@ -81,6 +85,27 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void gemm_stream_kernel(P
       for (int e = 0; e < 4; ++e) { x[b][e] = __builtin_bit_cast(float, (int)v0[e]); x[b][4 + e] = __builtin_bit_cast(float, (int)v1[e]); }
       x[b][8] = __builtin_bit_cast(float, (int)v2[0]);
       x[b][9] = __builtin_bit_cast(float, (int)v2[1]);
+    }
+  };
+  // K1 = 16 (layer 0's bond rows as their 16 embedding inputs, alone or in front of the 20 smearing columns of X2): X is a register
+  // operand too -- the lane's eight values of a row (k = 8 kh + s), two 16-byte loads one tile ahead, same split for the weights
+  float W1r[K1 == 16 ? 8 : 1];
+  float xra[2][8], xrb[2][8];               // as xa / xb
+  const unsigned ldxrb = K1 == 16 ? (unsigned)p.ldx * 4u : 0u;
+  const __amdgpu_buffer_rsrc_t descXr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(K1 == 16 ? p.X : nullptr), 0, (unsigned)p.M * ldxrb, 0x00020000);
+  const unsigned voffXr = (unsigned)l31 * ldxrb + 32u * kh;
+  if constexpr (K1 == 16) {
+#pragma unroll
+    for (int s1 = 0; s1 < 8; ++s1) W1r[s1] = p.W[(size_t)col * p.ldw + 8 * kh + s1];
+  }
+  auto load_xr = [&](unsigned row0, float (&x)[2][8]) {
+#pragma unroll
+    for (int b = 0; b < 2; ++b) {
+      const unsigned so = (row0 + 32u * b) * ldxrb;
+      const i4v v0 = __builtin_amdgcn_raw_buffer_load_b128(descXr, voffXr, so, 0);
+      const i4v v1 = __builtin_amdgcn_raw_buffer_load_b128(descXr, voffXr + 16u, so, 0);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) { x[b][e] = __builtin_bit_cast(float, (int)v0[e]); x[b][4 + e] = __builtin_bit_cast(float, (int)v1[e]); }
     }
   };
   const float bias = p.bias ? p.bias[col] : 0.f;
@@ -179,11 +204,12 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void gemm_stream_kernel(P
   };
 
   // ---- prologue: first tile's DMA and gathers ----
+  if constexpr (K1 == 16) load_xr(tile_row0(tile), xra);
   if constexpr (K2 > 0) load_x2(tile_row0(tile), xa);
   // row windows: first rows of this tile and of the next, carried round the loop (each is loaded one tile before the DMA that uses it)
   unsigned wrow = 0, wrow_next = 0;
   if constexpr (WIN) { wrow = win_row0(tile); wrow_next = win_row0(tile + tile_step); }
-  if constexpr (K1 > 0) dma_tile(WIN ? wrow : tile_row0(tile), 0);
+  if constexpr (DMA) dma_tile(WIN ? wrow : tile_row0(tile), 0);
   if constexpr (NADD == 1) { i4v ix[8]; load_idx(descI1, tile_row0(tile), ix); gather(descA1, ld1b, ix, g1); }
   if constexpr (NADD == 2) gather_plain(tile_row0(tile), g1);
 
@@ -191,7 +217,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void gemm_stream_kernel(P
     constexpr unsigned stage = decltype(stage_c)::value;
     constexpr bool first = decltype(first_c)::value;
     // this tile's DMA has landed (own pieces: counted wait; everybody's: barrier); the other stage is no longer read
-    if constexpr (K1 > 0) {
+    if constexpr (DMA) {
       if constexpr (first) asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
       else asm volatile("s_waitcnt vmcnt(32)\n\ts_barrier" ::: "memory");
     }
@@ -202,10 +228,11 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void gemm_stream_kernel(P
     // the wait the compiler puts in front of their use (it cannot see the DMA) finds the DMA long since landed
     i4v ix1[8];
     if constexpr (NADD == 1) load_idx(descI1, tile_row0(next), ix1);
+    if constexpr (K1 == 16) load_xr(tile_row0(next), stage ? xra : xrb);
     if constexpr (K2 > 0) load_x2(tile_row0(next), xn);
     unsigned wrow_after = 0;
     if constexpr (WIN) wrow_after = win_row0(next + tile_step);
-    if constexpr (K1 > 0) dma_tile(WIN ? wrow_next : tile_row0(next), stage ^ 1u);   // past the last tile: the clamped last tile once more, never consumed
+    if constexpr (DMA) dma_tile(WIN ? wrow_next : tile_row0(next), stage ^ 1u);   // past the last tile: the clamped last tile once more, never consumed
 
     if constexpr (LN) {
       // normalise the landed tile in place: 4 threads per row, each its 128-byte piece row, read in k order (slot q ^ sw holds
@@ -257,6 +284,14 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void gemm_stream_kernel(P
       acc[1] = biasv;
     }
 
+    if constexpr (K1 == 16) {
+      float (&xrc)[2][8] = stage ? xrb : xra;
+#pragma unroll
+      for (int s1 = 0; s1 < 8; ++s1) {
+        acc[0] = mfma32(xrc[0][s1], W1r[s1], acc[0]);
+        acc[1] = mfma32(xrc[1][s1], W1r[s1], acc[1]);
+      }
+    }
     if constexpr (K2 > 0) {
 #pragma unroll
       for (int s2 = 0; s2 < 10; ++s2) {
@@ -264,7 +299,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void gemm_stream_kernel(P
         acc[1] = mfma32(xc[1][s2], W2r[s2], acc[1]);
       }
     }
-    if constexpr (K1 > 0) {
+    if constexpr (DMA) {
       // operands one k-group ahead of their MFMAs (the compiler otherwise reads them right in front of the use)
       auto frag = [&](int c, int b) {
         return *reinterpret_cast<const f4*>(st_lds + rd[c & 3] + (stage * ST_STAGE + b * 16384u + (c >> 2) * 1024u));
@@ -324,7 +359,7 @@ __global__ __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) void gemm_stream_kernel(P
 template <int NW, int NADD, int K1, int K2, bool LN = false, bool SSP = false, bool WIN = false>
 static int launch_stream_t(const PgGemm* p, hipStream_t st) {
   const void* k = reinterpret_cast<const void*>(gemm_stream_kernel<NW, NADD, K1, K2, LN, SSP, WIN>);
-  const size_t lds = K1 ? 2 * ST_STAGE + (LN ? 1024 : 0) : 0;
+  const size_t lds = K1 == 128 ? 2 * ST_STAGE + (LN ? 1024 : 0) : 0;
   if (lds) if (int rc = reserve_lds(k, lds, "pg_gemm(stream)")) return rc;
   const int n_tiles = (p->M + ST_BM - 1) / ST_BM;      // (row windows: M = 64 x windows)
   const int n_cb = p->N / (NW * 32);
@@ -335,13 +370,14 @@ static int launch_stream_t(const PgGemm* p, hipStream_t st) {
   return check_launch("pg_gemm(stream)");
 }
 
-// eligible: K = 128 from X (optionally + 20 from X2), or K = 20 alone; no row subset / activation; N a multiple of 128; at most
+// eligible: K = 128 from X (optionally + 20 from X2); K = 20 alone; K = 16 from X, alone or + 20 from X2 (register operands);
+// no row subset / activation; N a multiple of 128; at most
 // one added operand (rows add1[idx1[r]] with the operand's row count, or rows add1[r]); 16-byte aligned rows; everything
 // addressable with 32-bit byte offsets; at least one full tile of rows.  LayerNorm-on-load: K = 128, N = 128, no added operand
 // (the second layer of the query MLPs); out_scale only there.  Shifted softplus: K = 128, N = 128, bias only (the heads)
 bool gemm_stream_eligible(const PgGemm* p) {
-  const bool k128 = p->K1 == 128 && (p->K2 == 0 || p->K2 == 20), k20 = p->K1 == 20 && p->K2 == 0;
-  if (!(k128 || k20) || p->rows || (p->N & 127) || p->M < ST_BM) return false;
+  const bool k128 = p->K1 == 128 && (p->K2 == 0 || p->K2 == 20), k20 = p->K1 == 20 && p->K2 == 0, k16 = p->K1 == 16 && (p->K2 == 0 || p->K2 == 20);
+  if (!(k128 || k20 || k16) || p->rows || (p->N & 127) || p->M < ST_BM) return false;
   if (p->act == 1) { if (p->K1 != 128 || p->K2 || p->N != 128 || p->ln_gamma || p->add1 || p->add2 || p->out_scale != 1.0f) return false; }
   else if (p->act != 0) return false;
   if (p->ln_gamma) { if (p->K1 != 128 || p->K2 || p->N != 128 || p->add1 || p->add2) return false; }
@@ -390,6 +426,7 @@ int launch_gemm_stream(const PgGemm* p, hipStream_t st) {
     q.X2 = p->X; q.ldx2 = p->ldx; q.K2 = 20; q.K1 = 0;
     return launch_stream_k<0, 20>(&q, st);
   }
+  if (p->K1 == 16) return p->K2 ? launch_stream_k<16, 20>(p, st) : launch_stream_k<16, 0>(p, st);
   return p->K2 ? launch_stream_k<128, 20>(p, st) : launch_stream_k<128, 0>(p, st);
 }
 

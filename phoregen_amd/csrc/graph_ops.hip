@@ -82,23 +82,49 @@ __global__ void embed_ctx_kernel(PgTopo t, const float* h_node, const float* pos
   }
 }
 
-__global__ void embed_bond_kernel(int n_bond, const int* edge_ref, const float* h_edge, const int* bond_graph,
-                                  const int64_t* time_step, const float* W_edge, const float* t_off, const float* t_coeff,
-                                  float* h_bond) {
-  const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const size_t e = idx >> 7;
-  const int c = idx & 127;
-  if (e >= (size_t)n_bond) return;
-  float v;
-  if (c < 118) {
-    v = 0.f;
-    const size_t er = edge_ref ? (size_t)edge_ref[e] : e;        // the caller's row of internal edge e
+// One thread per four channels of a row (16-byte stores), a workgroup of 8 x 32 threads walks EB_ROWS rows with its W_edge rows in
+// registers.  Per element the arithmetic is what one thread per element did (v += h_edge[k] * W[c][k] in k order; time_smear of the
+// row's graph): the lanes of channel groups 29 .. 31 evaluate the row's ten exponentials, once per row.
+// e16 (optional): [h_edge of the internal edge (6) | the ten smearing values] -- the lanes that hold a 16-byte piece of it store it
+constexpr int EB_ROWS = 128;
+
+__global__ __launch_bounds__(256) void embed_bond_kernel(int n_bond, const int* edge_ref, const float* h_edge, const int* bond_graph,
+                                                         const int64_t* time_step, const float* W_edge, const float* t_off,
+                                                         const float* t_coeff, float* h_bond, float* e16) {
+  const int cg = threadIdx.x & 31, c0 = 4 * cg;
+  float W[4][6];
 #pragma unroll
-    for (int k = 0; k < 6; ++k) v += h_edge[er * 6 + k] * W_edge[c * 6 + k];
-  } else {
-    v = time_smear((float)time_step[bond_graph[e]], t_off, t_coeff, c - 118);
+  for (int j = 0; j < 4; ++j)
+#pragma unroll
+    for (int k = 0; k < 6; ++k) W[j][k] = c0 + j < 118 ? W_edge[(c0 + j) * 6 + k] : 0.f;
+  const int e_end = min(n_bond, ((int)blockIdx.x + 1) * EB_ROWS);
+  for (int e = blockIdx.x * EB_ROWS + (threadIdx.x >> 5); e < e_end; e += 8) {
+    const size_t er = edge_ref ? (size_t)edge_ref[e] : (size_t)e;      // the caller's row of internal edge e
+    float h[6];
+#pragma unroll
+    for (int k = 0; k < 6; ++k) h[k] = h_edge[er * 6 + k];
+    f4 o;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      float v = 0.f;
+#pragma unroll
+      for (int k = 0; k < 6; ++k) v += h[k] * W[j][k];
+      o[j] = v;
+    }
+    if (cg >= 29) {
+      const float t = (float)time_step[bond_graph[e]];
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (c0 + j >= 118) o[j] = time_smear(t, t_off, t_coeff, c0 + j - 118);
+    }
+    *reinterpret_cast<f4*>(h_bond + (size_t)e * 128 + c0) = o;
+    if (e16 && cg >= 28) {
+      f4 piece = o;                                    // groups 30, 31: smearing values 2 .. 5, 6 .. 9
+      if (cg == 28) piece = (f4){h[0], h[1], h[2], h[3]};
+      if (cg == 29) piece = (f4){h[4], h[5], o[2], o[3]};
+      *reinterpret_cast<f4*>(e16 + (size_t)e * 16 + 4 * (cg - 28)) = piece;
+    }
   }
-  h_bond[e * 128 + c] = v;
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -482,13 +508,18 @@ extern "C" int pg_embed_ctx(const PgTopo* t, const float* h_node_pert, const flo
   return check_launch("pg_embed_ctx");
 }
 
+extern "C" int pg_embed_bond_e16(const PgTopo* t, const float* h_edge_pert, const int* bond_graph, const int64_t* time_step,
+                                 const float* W_edge, const float* t_off, const float* t_coeff, float* h_bond, float* e16, void* stream) {
+  if (t->n_bond == 0) return PG_OK;
+  if (((size_t)h_bond & 15) || ((size_t)e16 & 15)) { set_error("pg_embed_bond: h_bond and e16 must be 16-byte aligned"); return PG_ERR_ARG; }
+  hipLaunchKernelGGL(embed_bond_kernel, dim3((t->n_bond + EB_ROWS - 1) / EB_ROWS), dim3(256), 0, (hipStream_t)stream, t->n_bond,
+                     t->edge_ref, h_edge_pert, bond_graph, time_step, W_edge, t_off, t_coeff, h_bond, e16);
+  return check_launch("pg_embed_bond");
+}
+
 extern "C" int pg_embed_bond(const PgTopo* t, const float* h_edge_pert, const int* bond_graph, const int64_t* time_step,
                              const float* W_edge, const float* t_off, const float* t_coeff, float* h_bond, void* stream) {
-  const long n = (long)t->n_bond * 128;
-  if (n == 0) return PG_OK;
-  hipLaunchKernelGGL(embed_bond_kernel, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, t->n_bond, t->edge_ref,
-                     h_edge_pert, bond_graph, time_step, W_edge, t_off, t_coeff, h_bond);
-  return check_launch("pg_embed_bond");
+  return pg_embed_bond_e16(t, h_edge_pert, bond_graph, time_step, W_edge, t_off, t_coeff, h_bond, nullptr, stream);
 }
 
 // wave_knn holds KNN_MAXC candidates per lane: a graph with more context nodes would silently lose its far candidates

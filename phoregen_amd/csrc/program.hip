@@ -49,6 +49,7 @@ int n_args_of(int op) {
     case PG_OP_SEG_ATTN: return 2;
     case PG_OP_EMBED_CTX: return 12;
     case PG_OP_EMBED_BOND: return 8;
+    case PG_OP_EMBED_BOND_E16: return 9;
     case PG_OP_KNN_CTX: return 5;
     case PG_OP_LIG_NORMALS: return 5;
     case PG_OP_EDGE_GATE: return 12;
@@ -72,6 +73,8 @@ int run_one(const PgLaunch& L, void* s) {
       return pg_embed_ctx(TOPO(0), CFP(1), CFP(2), PTR(3, const int64_t*), CFP(4), CFP(5), CFP(6), CFP(7), CFP(8), CIP(9), FP(10),
                           FP(11), s);
     case PG_OP_EMBED_BOND: return pg_embed_bond(TOPO(0), CFP(1), CIP(2), PTR(3, const int64_t*), CFP(4), CFP(5), CFP(6), FP(7), s);
+    case PG_OP_EMBED_BOND_E16:
+      return pg_embed_bond_e16(TOPO(0), CFP(1), CIP(2), PTR(3, const int64_t*), CFP(4), CFP(5), CFP(6), FP(7), FP(8), s);
     case PG_OP_KNN_CTX: return pg_knn_ctx(TOPO(0), CFP(1), INT(2), IP(3), IP(4), s);
     case PG_OP_LIG_NORMALS: return pg_lig_normals(TOPO(0), CFP(1), CFP(2), CIP(3), FP(4), s);
     case PG_OP_EDGE_GATE:

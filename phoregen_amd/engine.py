@@ -90,6 +90,13 @@ class Engine:
         # 2: lane 0 also waits for what it reads alone (the first of the three Y2 launches; the first-layer blocks in front of P).
         # A plan of fewer than 64 context rows has no windows
         self.lig_windows = o['lig_windows'] if plan.lig_windows is not None else 0
+        # layer 0's bond rows are the embedding of 16 numbers per row (6 bond-type values, 10 time-smearing values): an engine that embeds
+        # them itself keeps those beside h_bond (`ws.e16`, pg_embed_bond_e16) and runs layer 0's three bond-row products over them with
+        # composed weights (packing.l0_compose), K = 16 / 16 + 20 instead of 128 / 128 + 20.  Not the denoiser-only entry: its caller hands
+        # in h_bond
+        self.l0_compact = bool(o['l0_compact']) and full and not phore_only
+        if self.l0_compact and not hasattr(pack.layers[0].TB, 'W_hbg36'):
+            raise ValueError('phoregen_amd: l0_compact needs the composed layer-0 weights of the sampler pack (ModelPack(..., detach=True))')
         self._lane = 0
         self._n_points = 0       # order points of this engine's launch lists
         self._points = {}        # ... their events in the Python runner (created at first use)
@@ -132,6 +139,7 @@ class Engine:
         w.h_in = _f(n, 128, device=d)
         w.x = [_f(n, 3, device=d), _f(n, 3, device=d)]
         w.hb = [_f(E, 128, device=d), _f(E, 128, device=d)]
+        w.e16 = _f(E, 16, device=d) if self.l0_compact else None     # [h_edge | time smearing] of the embedded bond rows (layer 0)
         w.nbr = torch.zeros(n, k, dtype=torch.int32, device=d)
         w.deg = torch.zeros(n, dtype=torch.int32, device=d)
         w.ew, w.nrm, w.G = _f(n, k, device=d), _f(n, 3, device=d), _f(E, 20, device=d)
@@ -366,8 +374,12 @@ class Engine:
     # ------------------------------------------------------------------ one denoiser forward
     def _embed_bond(self, prog, in_t):
         w, p, pk = self.ws, self.plan, self.pack
-        self._call(prog, self.lib.pg_embed_bond, p.topo_ref, w.in_h_edge.data_ptr(), p.bond_graph.data_ptr(), in_t.data_ptr(),
-                   pk.W_edge_emb.data_ptr(), pk.t_off.data_ptr(), pk.t_coeff.data_ptr(), w.hb[0].data_ptr())
+        args = (p.topo_ref, w.in_h_edge.data_ptr(), p.bond_graph.data_ptr(), in_t.data_ptr(), pk.W_edge_emb.data_ptr(), pk.t_off.data_ptr(),
+                pk.t_coeff.data_ptr(), w.hb[0].data_ptr())
+        if self.l0_compact:
+            self._call(prog, self.lib.pg_embed_bond_e16, *args, w.e16.data_ptr())
+        else:
+            self._call(prog, self.lib.pg_embed_bond, *args)
 
     def _embed_ctx(self, prog, in_t, features=True, coords=True):
         w, p, pk = self.ws, self.plan, self.pack
@@ -432,10 +444,10 @@ class Engine:
         y1_done = self._record(prog, 2)
         self._query_gemm(prog, L0.NE, w.Y1, 0, both, 3)
         self._wait(prog, 2, hb_done)
-        self._triplet_queries(prog, L0, w.hb[0], w.Y1)
+        self._triplet_queries(prog, L0, w.hb[0], w.Y1, l0=True)
         self._lane = 3
         self._wait(prog, 3, y1_done)
-        self._bond_node_rows(prog, L0, w.hb[0], w.Y1)
+        self._bond_node_rows(prog, L0, w.hb[0], w.Y1, l0=True)
         self._node_attention(prog, hip.SEG_BOND_NODE, L0.NB, w.Y1, 5 * 128, w.x[0], lig, out=w.aggB, csrc=w.CsB2, buf=2)
         self._lane = 0
         return prog
@@ -461,14 +473,27 @@ class Engine:
         self._gemm(prog, h_in, 128, L.W_node1[:640], Y1[:, :640], n, 640, bias=L.b_node1[:640])
         self._gemm(prog, h_in, 128, L.W_node1[640:], Y1[:, 640:], n, 1280, bias=L.b_node1[640:], lig_only=True)
 
-    def _triplet_queries(self, prog, L, hb_in, Y1):
+    def _l0_rows(self, l0, hb_in, W, W16):
+        """(X, K1, W) of a bond-row product: layer 0 of an engine that embedded the rows (`l0_compact`) reads them as their 16 embedding
+        inputs with the composed weight, every other product reads the 128 channels."""
+        return (self.ws.e16, 16, W16) if (l0 and self.l0_compact) else (hb_in, 128, W)
+
+    def _triplet_rows(self, prog, L, hb_in, Y1, staged, l0=False):
         w, p, E = self.ws, self.plan, self.plan.n_bond
-        self._gemm(prog, hb_in, 128, L.TB.W_q_hb, w.qhid, E, 128, add1=Y1[:, 14 * 128:15 * 128], idx1=p.bond_dst)
+        X, K, W = self._l0_rows(l0, hb_in, L.TB.W_hbg, L.TB.W_hbg36 if l0 and self.l0_compact else None)
+        self._gemm(prog, X, K, W, w.P, E, 256, X2=w.G, K2=20, add1=Y1[:, 10 * 128:12 * 128], idx1=p.bond_src,
+                   **({} if staged else dict(add2=Y1[:, 12 * 128:14 * 128], idx2=p.bond_dst)))
+
+    def _triplet_queries(self, prog, L, hb_in, Y1, l0=False):
+        w, p, E = self.ws, self.plan, self.plan.n_bond
+        X, K, W = self._l0_rows(l0, hb_in, L.TB.W_q_hb, L.TB.W_q_hb16 if l0 and self.l0_compact else None)
+        self._gemm(prog, X, K, W, w.qhid, E, 128, add1=Y1[:, 14 * 128:15 * 128], idx1=p.bond_dst)
         self._gemm(prog, w.qhid, 128, L.TB.W2q, w.qT, E, 128, bias=L.TB.b2q, ln=(L.TB.q_ln_g, L.TB.q_ln_b), scale=HEAD_SCALE)
 
-    def _bond_node_rows(self, prog, L, hb_in, Y1):
+    def _bond_node_rows(self, prog, L, hb_in, Y1, l0=False):
         w, p, E = self.ws, self.plan, self.plan.n_bond
-        self._gemm(prog, hb_in, 128, L.NB.W_hb, w.CsB2, E, 256, add1=Y1[:, 7 * 128:9 * 128], idx1=p.bond_src)
+        X, K, W = self._l0_rows(l0, hb_in, L.NB.W_hb, L.NB.W_hb16 if l0 and self.l0_compact else None)
+        self._gemm(prog, X, K, W, w.CsB2, E, 256, add1=Y1[:, 7 * 128:9 * 128], idx1=p.bond_src)
 
     def _denoiser_program(self, prog, lig, both, heads=None, pre_join=None, step_ahead=False):
         """uni_denoiser.py:396-430: knn graph + gate once, then the layers.  State starts in slot 0."""
@@ -527,8 +552,8 @@ class Engine:
             w.dxe2 = torch.zeros_like(w.dxe)
 
         first_layer_gemm = lambda L_, h_in, Y1_: self._first_layer_gemm(prog, L_, h_in, Y1_)
-        triplet_queries = lambda L_, hb_in, Y1_: self._triplet_queries(prog, L_, hb_in, Y1_)
-        bond_node_rows = lambda L_, hb_in, Y1_: self._bond_node_rows(prog, L_, hb_in, Y1_)
+        triplet_queries = lambda L_, hb_in, Y1_, l0=False: self._triplet_queries(prog, L_, hb_in, Y1_, l0)
+        bond_node_rows = lambda L_, hb_in, Y1_, l0=False: self._bond_node_rows(prog, L_, hb_in, Y1_, l0)
         assert not step_ahead or (ahead and staged)
 
         for li, L in enumerate(pk.layers):
@@ -582,9 +607,7 @@ class Engine:
             # same target j, so in the staged form that half rides on the segment's own row Q[j->i] instead (one gathered operand
             # per product); without a staged queue P carries both halves and the generic kernel runs
             self._lane = 0
-            self._gemm(prog, hbc, 128, L.TB.W_hbg, w.P, E, 256, X2=w.G, K2=20,
-                       add1=Y1c[:, 10 * 128:12 * 128], idx1=p.bond_src,
-                       **({} if staged else dict(add2=Y1c[:, 12 * 128:14 * 128], idx2=p.bond_dst)))
+            self._triplet_rows(prog, L, hbc, Y1c, staged, li == 0)
             # the per-segment constant of the triplet MLPs as rows: Wg2 . smear(d_ji) + (target half)[j].  Small batches: behind P on
             # lane 0 (a 25 us product costs less there than the two cross-lane hops around it on a side lane)
             q_lane = 0 if chain_q else 2
@@ -595,7 +618,7 @@ class Engine:
                     self._sync(prog, 0, (2,))          # lane 0 (the triplet kernel) waits for the Q rows, not for all of lane 2
             if not pre:
                 self._lane = 3                                                          # triplet queries
-                triplet_queries(L, hbc, Y1c)
+                triplet_queries(L, hbc, Y1c, li == 0)
                 q3_done = self._record(prog, 3)
             self._lane = 0
             if not pre:                            # (pre: lane 3 carries the bond-node attention, which lin_node waits for)
@@ -644,7 +667,7 @@ class Engine:
             #  updates, see below)
             self._lane = 3 if v2 else 2            # (v2: lane 3, so that lin_node on lane 1 waits on lane 3 and never on lane 2)
             if not pre:
-                bond_node_rows(L, hbc, Y1c)
+                bond_node_rows(L, hbc, Y1c, li == 0)
                 self._node_attention(prog, hip.SEG_BOND_NODE, L.NB, Y1c, 5 * 128, xc, lig, out=w.aggB, csrc=w.CsB2, buf=1)
                 if v2:
                     bn_done = self._record(prog, 3)

@@ -83,7 +83,8 @@ OP_RECORD, OP_WAIT = 0, 1
 # entry point -> PG_OP_* (include/phoregen_hip.h): what a launch list handed to pg_program_create may hold
 PROGRAM_OPS = {'pg_gemm': 2, 'pg_seg_attn': 3, 'pg_embed_ctx': 4, 'pg_embed_bond': 5, 'pg_knn_ctx': 6, 'pg_lig_normals': 7,
                'pg_edge_gate': 8, 'pg_knn_group_by_kind': 9, 'pg_bond_smear': 10, 'pg_attn_fold_query': 11,
-               'pg_attn_unfold_value': 12, 'pg_apply_dx': 13, 'pg_layer_geom': 14, 'pg_rows_linear': 15, 'pg_atom_count': 16}
+               'pg_attn_unfold_value': 12, 'pg_apply_dx': 13, 'pg_layer_geom': 14, 'pg_rows_linear': 15, 'pg_atom_count': 16,
+               'pg_embed_bond_e16': 17}
 
 SEG_KNN_NODE, SEG_KNN_POS, SEG_BOND_NODE, SEG_BOND_POS, SEG_TRIPLET, SEG_PHORE = range(6)
 ACT_NONE, ACT_SSP, ACT_RELU = 0, 1, 2
@@ -156,8 +157,10 @@ _PROTOS = {
     'pg_debug_force_generic_seg': (C.c_int, [C.c_int]),
     'pg_gemm': (C.c_int, [C.POINTER(PgGemm), C.c_void_p]),
     'pg_debug_gemm_streaming': (C.c_int, [C.c_int]),
+    'pg_gemm_is_streaming': (C.c_int, [C.POINTER(PgGemm)]),
     'pg_embed_ctx': (C.c_int, [C.POINTER(PgTopo)] + [c_fp] * 11 + [C.c_void_p]),
     'pg_embed_bond': (C.c_int, [C.POINTER(PgTopo)] + [c_fp] * 7 + [C.c_void_p]),
+    'pg_embed_bond_e16': (C.c_int, [C.POINTER(PgTopo)] + [c_fp] * 8 + [C.c_void_p]),
     'pg_knn_ctx': (C.c_int, [C.POINTER(PgTopo), c_fp, C.c_int, c_ip, c_ip, C.c_void_p]),
     'pg_lig_normals': (C.c_int, [C.POINTER(PgTopo), c_fp, c_fp, c_ip, c_fp, C.c_void_p]),
     'pg_lig_nn3': (C.c_int, [C.POINTER(PgTopo), c_fp, c_ip, C.c_void_p]),

@@ -37,6 +37,9 @@ DEFAULTS = dict(
                           # of the three Y2 launches in front of the bond-pos rows, the first-layer blocks in front of P (128 graphs 18.44 / 18.46 /
                           # 17.91 ms with 0 / 1 / 2: the split launches pay only with the finer waits; profiles/r08_lig_windows_ab.md)
     tri_grid=-1,          # persistent workgroups of the staged triplet kernel (-1: by batch size)
+    l0_compact=True,      # layer 0's bond-row products (triplet rows P, bond-node rows, triplet query rows) over the 16 embedding inputs of a bond
+                          # row with composed weights (K = 16 / 16 + 20) instead of its 128 channels; False: K = 128 like every later layer
+                          # (profiles/r10_l0_compact_ab.md)
     dgrad_mm=True,        # training: input gradients through the library GEMM
     rows_sum=True,        # training: pg_bond_rows_sum instead of atomic index_add_
     tri_onepass=True,     # training: one-pass triplet / node adjoints fed by the forward's softmax weights
@@ -57,7 +60,7 @@ _tri = lambda v: {'0': 'never', '1': 'auto', '2': 'always'}[v]
 _flag = lambda v: v != '0'
 _ENV = {
     'PG_STREAMS': ('streams', _flag),
-    'PG_LAYER_AHEAD': ('layer_ahead', _flag), 'PG_AHEAD_V2': ('ahead_v2', _tri), 'PG_AHEAD_V2_BELOW': ('ahead_v2_below', int), 'PG_TRI_GRID': ('tri_grid', int), 'PG_POS_TILED': ('pos_tiled', _tri), 'PG_POS_TILED_BELOW': ('pos_tiled_below', int), 'PG_C_PROGRAM': ('c_program', _flag), 'PG_STEP_AHEAD': ('step_ahead', _flag), 'PG_CHAIN_Q_FROM': ('chain_q_from', int), 'PG_TRI_SPLIT': ('tri_split', _flag), 'PG_TUNE_GRID': ('tune_grid', _flag), 'PG_GEOM_SPLIT': ('geom_split', _tri), 'PG_LIG_WINDOWS': ('lig_windows', int),
+    'PG_LAYER_AHEAD': ('layer_ahead', _flag), 'PG_AHEAD_V2': ('ahead_v2', _tri), 'PG_AHEAD_V2_BELOW': ('ahead_v2_below', int), 'PG_TRI_GRID': ('tri_grid', int), 'PG_POS_TILED': ('pos_tiled', _tri), 'PG_POS_TILED_BELOW': ('pos_tiled_below', int), 'PG_C_PROGRAM': ('c_program', _flag), 'PG_STEP_AHEAD': ('step_ahead', _flag), 'PG_CHAIN_Q_FROM': ('chain_q_from', int), 'PG_TRI_SPLIT': ('tri_split', _flag), 'PG_TUNE_GRID': ('tune_grid', _flag), 'PG_GEOM_SPLIT': ('geom_split', _tri), 'PG_LIG_WINDOWS': ('lig_windows', int), 'PG_L0_COMPACT': ('l0_compact', _flag),
     'PG_DGRAD_MM': ('dgrad_mm', _flag),
     'PG_ROWS_SUM': ('rows_sum', _flag), 'PG_TRI_ONEPASS': ('tri_onepass', _flag), 'PG_WIDE_GEMM': ('wide_gemm', _flag), 'PG_BWD_GRID': ('bwd_grid', int), 'PG_BWD_SPLIT': ('bwd_split', lambda v: {'0': 'none', '1': 'knn', '2': 'all'}[v]), 'PG_BWD_ATOM_SORT': ('bwd_atom_sort', _flag),
     'PG_TRI_BWD_FORM': ('tri_bwd_form', int), 'PG_TRI_BWD_GRID': ('tri_bwd_grid', int), 'PG_PH_ONEPASS': ('ph_onepass', _flag),

@@ -316,6 +316,15 @@ def pack_gate(sd, p='denoiser.edge_pred_layer'):
                 b3=float(m['b2'].reshape(-1)[0]))
 
 
+def l0_compose(W, W_edge, extra=None):
+    """Layer 0's bond rows are the embedding h_bond0 = [W_edge . h_edge (118) | time smearing (10)]: a product h_bond0 . W^T over them is
+    [h_edge | smearing] . W16^T with W16 = [W[:, :118] @ W_edge | W[:, 118:128]]  ([N, 16]; exact in real arithmetic for any h_edge).
+    `W` is the packed first-layer weight, so the sign and centring folds of _kv_mlp ride along; `extra`: further columns of W kept as they
+    are (the 20 bond-length columns of the triplet rows -> [N, 36]).  Composed in float64, rounded once to fp32."""
+    W16 = torch.cat([W[:, :118].double() @ W_edge.double(), W[:, 118:128].double()] + ([extra.double()] if extra is not None else []), -1)
+    return W16.to(W.dtype).contiguous()
+
+
 class ModelPack:
     """All kernel-layout weights of a PhoreDiff state_dict (tensors must already be on the GPU)."""
 
@@ -334,6 +343,11 @@ class ModelPack:
         c = lambda k: sd[k].contiguous()
         self.W_node_emb, self.W_edge_emb = c('node_embedder.weight'), c('edge_embedder.weight')
         self.t_off, self.t_coeff = c('time_emb.0.offset'), c('time_emb.0.coeff')
+        if detach:          # the sampler's layer 0 reads its bond rows as their 16 embedding inputs (Engine, options.l0_compact)
+            L0 = self.layers[0]
+            L0.NB.W_hb16 = l0_compose(L0.NB.W_hb, self.W_edge_emb)
+            L0.TB.W_q_hb16 = l0_compose(L0.TB.W_q_hb, self.W_edge_emb)
+            L0.TB.W_hbg36 = l0_compose(L0.TB.W_hbg[:, :128], self.W_edge_emb, extra=L0.TB.W_hbg[:, 128:148])
         self.W_pe, self.b_pe = c('phore_embedding.weight'), c('phore_embedding.bias')
         self.v0 = (c('v_inference.0.weight'), c('v_inference.0.bias'), c('v_inference.2.weight'), c('v_inference.2.bias'))
         self.b0 = (c('bond_inference.0.weight'), c('bond_inference.0.bias'), c('bond_inference.2.weight'),

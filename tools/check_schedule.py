@@ -133,6 +133,8 @@ def access_of(name, args, buf):
             rd(a[2]), rd(a[8]), wr(a[11])
     elif name == 'pg_embed_bond':
         rd(a[1]), rd(a[3]), wr(a[7])
+    elif name == 'pg_embed_bond_e16':
+        rd(a[1]), rd(a[3]), wr(a[7]), wr(a[8])
     elif name == 'pg_knn_ctx':
         rd(a[1]), wr(a[3]), wr(a[4])
     elif name == 'pg_edge_gate':
