@@ -157,12 +157,14 @@ def bond_case(name, mean=0.3, seed=2):
 
 
 @functools.lru_cache(maxsize=None)
-def tri_case(name, mean=0.3, seed=3):
-    plan = make_plan(TRI_SIZES[name])
+def tri_case(name, mean=0.3, seed=3, sizes=None):
+    """sizes: the batch of a case that is not one of TRI_SIZES (tests/seg_attn_grad_cases.py)."""
+    sizes = sizes or TRI_SIZES[name]
+    plan = make_plan(sizes)
     t = topo_of(plan)
     g = _gen(seed)
     nb = t.n_bond
-    c = NS(name=name, sizes=TRI_SIZES[name], x=_positions(t, g))
+    c = NS(name=name, sizes=sizes, x=_positions(t, g))
     c.Csrc = torch.cat([_rows(nb, g, mean), _rows(nb, g, mean)], 1)            # one [n_bond, 256] tensor: P_k | P_v
     c.Csrc_k, c.Csrc_v = c.Csrc[:, :128], c.Csrc[:, 128:]
     d = (c.x[t.bond_dst] - c.x[t.bond_src]).norm(dim=-1)

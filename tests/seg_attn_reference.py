@@ -13,6 +13,9 @@ Beside every output the functions return its per-element SCALE: the same contrac
 ReLU output z = relu(hidden + b' sigma) counted as |hidden| + |b'| sigma (that, not z, is what a rounding error of z is relative to:
 an element whose rows all sit at the kink is as uncertain as its pre-activations).  Errors are judged as |error| / scale.
 
+Everything is plain differentiable torch: tests/seg_attn_grad_cases.py runs it under autograd for the adjoint tests, and takes the
+LayerNorm+ReLU pre-activations h + b' sigma of every row through `pre` (`_report`) to keep its inputs off the ReLU kink.
+
 `variant` names one deliberate mistake (VARIANTS); tests/test_seg_attn_host.py shows that every one of them lies far outside the
 tolerances, i.e. that the tolerances would catch it in a kernel."""
 import math
@@ -60,13 +63,28 @@ def unfold_value(S, swn, W2v, b2v, dtype=torch.float64, S_scale=None):
     return out.reshape(-1, 128), sc.reshape(-1, 128)
 
 
+def pre_activation(h, bp):
+    """The LayerNorm+ReLU pre-activation h + b' sigma, its scale |h| + |b'| sigma, and sigma."""
+    var = (h * h).mean(-1) + 1e-5
+    sigma = var.sqrt()
+    return h + bp * sigma[..., None], h.abs() + bp.abs() * sigma[..., None], sigma
+
+
 def _ln_relu(h, bp, variant):
     if variant == 'mean_subtracted':
         h = h - h.mean(-1, keepdim=True)
-    var = (h * h).mean(-1) + 1e-5
-    sigma = var.sqrt()
-    z = torch.relu(h + bp * sigma[..., None])
-    return z, 1.0 / sigma, h.abs() + bp.abs() * sigma[..., None]
+    pre, scale, sigma = pre_activation(h, bp)
+    return torch.relu(pre), 1.0 / sigma, scale
+
+
+def _report(pre, seg, crow, valid, hk, hv, bk, bv):
+    """pre (a list or a callable, or None) receives one entry per group of segments: the pre-activations of both MLP paths [segments,
+    rows, 128], their scales, the segments' ids (rows of Cdst), the rows of Csrc every row reads and the rows that take part."""
+    if pre is not None:
+        with torch.no_grad():
+            (pk, sk, gk), (pv, sv, gv) = pre_activation(hk, bk), pre_activation(hv, bv)
+            (pre if callable(pre) else pre.append)(NS(seg=seg, crow=crow, valid=valid, pre=dict(k=pk, v=pv), scale=dict(k=sk, v=sv),
+                                                      sigma=dict(k=gk, v=gv)))
 
 
 def _attend(hk, valid, gate, U, bk, variant):
@@ -125,7 +143,7 @@ def _cast(c, names, dtype):
     return NS(**{k: (getattr(c, k).to(dtype) if getattr(c, k, None) is not None else None) for k in names})
 
 
-def node_attn(c, t, mode, ids, Wf_k=None, Wf_v=None, dtype=torch.float64, variant='', U=None):
+def node_attn(c, t, mode, ids, Wf_k=None, Wf_v=None, dtype=torch.float64, variant='', U=None, pre=None):
     """One sub-layer over the target nodes `ids` (ctx ids, any order).  c: the case's tensors (tests/seg_attn_cases.py), t: its
     topology (long tensors).  U None: folded from c.q and c.W2k.  Returns per listed target (rows in the order of ids):
     U, S, swn, out (node-update modes), dx (position modes, WITHOUT the accumulate term), the training record and the scales."""
@@ -202,6 +220,7 @@ def node_attn(c, t, mode, ids, Wf_k=None, Wf_v=None, dtype=torch.float64, varian
             else:
                 d = rel.norm(dim=-1)
             hk, hv = hk + d[..., None] * Wf_k[:, 0], hv + d[..., None] * Wf_v[:, 0]
+        _report(pre, seg, crow, valid, hk, hv, f.bk, f.bv)
         a = _attend(hk, valid, gate, U_all[sel], f.bk, variant)
         res.rows[sel] = R
         res.valid[sel, :R] = a.valid
@@ -221,7 +240,7 @@ def t_deg(c, seg):
 
 
 # ---- triplet ---------------------------------------------------------------------------------------------------------------------
-def triplet(c, t, dtype=torch.float64, variant='', staged=True):
+def triplet(c, t, dtype=torch.float64, variant='', staged=True, U=None, pre=None):
     """Every bond edge j -> i of the batch (rows of the results = internal bond ids).  staged: Cdst_k / Cdst_v given explicitly and the
     query folded from q; else Cdst = G . Wg2.  Returns U, S, swn (the training form's outputs), out = resid + W2v . S + b2v [not empty],
     aw [n_bond, max_nlig, 16] (softmax weights by ATOM k, zero for i and j) and the scales."""
@@ -229,7 +248,10 @@ def triplet(c, t, dtype=torch.float64, variant='', staged=True):
                   'Wf_k', 'Wf_v'), dtype)
     nb, dev = t.bond_src.numel(), t.bond_src.device
     z = lambda *s: torch.zeros(*s, dtype=dtype, device=dev)
-    U, U_scale = fold_query(f.q, f.W2k, dtype)
+    if U is None:
+        U, U_scale = fold_query(f.q, f.W2k, dtype)
+    else:
+        U, U_scale = U.to(dtype), U.to(dtype).abs()
     if staged:
         Ck, Cv = f.Cdst_k, f.Cdst_v
     else:
@@ -260,6 +282,7 @@ def triplet(c, t, dtype=torch.float64, variant='', staged=True):
             feat = torch.cat([theta[..., None], torch.sin(ang), torch.cos(ang), z(n - 1, n, 1)], -1)
             hk = torch.where(use, f.Csrc_k[crow], z(1)) + Ck[seg][:, None, :] + feat @ f.Wf_k.T
             hv = torch.where(use, f.Csrc_v[crow], z(1)) + Cv[seg][:, None, :] + feat @ f.Wf_v.T
+            _report(pre, seg, crow, valid, hk, hv, f.bk, f.bv)
             a = _attend(hk, valid, torch.ones(n - 1, n, dtype=dtype, device=dev), U[seg], f.bk, variant)
             res.S[seg], res.S_scale[seg], res.swn[seg] = _node_finish(a, hv, f.bv, variant)
             res.aw[seg, :n] = a.aw
